@@ -10,12 +10,20 @@ rank 0.  The blob itself never crosses PCIe; the host does wait for the shard (`
 580-byte D2H of the ok word) BEFORE it issues the collective, because torch enqueues collectives on a stream of its own and one
 that waits there for a whole batch blocks the hardware queue it shares with a caller stream.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step) and the roofline
+of the timed steps.  A plain run does only that: set-up, warm-up, the --steps timed steps, the outputs of the last step when
+--dump-outputs DIR asks for them, the line.  With --full the line also holds
   value_one_caller / value_host_buffers   one blocking caller, HBM-resident and PCIe-inclusive (outside the timed region)
   roofline      dominant kernel (chosen by kernel-alone durations of an un-overlapped profiling step), HBM bytes,
                 and roofline.int_mad: the integer multiply-add roofline this path is actually bound by
   cpu_baseline  the C restatement of the reference algorithm (oracle/bls_oracle.c) on the host cores, with legs for
                 the other BASELINE configs; BLST itself if the box has a libblst.
+  aux / multi_gpu   the side measurements of the other BASELINE configs (one GPU / N > 1)
+  roofline.int_mad.ceiling   measured again by tools/ubench_fp2chain.bin (a plain run quotes the committed figure)
+
+--dump-outputs DIR: after the timed steps, DIR/verdict.npy (float64, shape (1,)): the verdict batchVerify returned to its caller
+for the LAST timed step, 1.0 = valid batch.  The inputs (tuples, rnd chain) are fixed by the arguments, so two builds can be
+compared output for output.
 """
 import argparse
 import ctypes
@@ -161,6 +169,13 @@ def dist_info(world, backend, ctl, dev):
             "distinct_devices": len(set(objs)), "all_on_device0_test_hook": os.environ.get("BENCH_ALL_ON_DEVICE0") == "1"}
 
 
+def dump_outputs(path, verdict):
+    """--dump-outputs: what the last timed step returned to its caller, as float64 .npy files (one batchVerify: its verdict)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "verdict.npy"), np.array([1.0 if verdict else 0.0], dtype=np.float64))
+
+
 def next_rnd(rnd):
     """secureRandomBytes of the next step: re-hashed before every iteration as benchmarks/bls_signature.nim:269-275 does."""
     return hashlib.sha256(rnd).digest()
@@ -203,6 +218,10 @@ class ShardedRun:
         self.stage_acc = {}
         self.fv_busy = [False] * inflight
         self.rnd_of_slot = [None] * inflight
+        # verdict the caller received per step of the last run_steps call (rank 0 of the sharded path: the merged verdict)
+        self.verdicts = {}
+        self.step_of_slot = [None] * inflight
+        self.fv_step = [None] * inflight
 
     def close(self):
         for c in self.caches + self.fv_caches:
@@ -232,12 +251,16 @@ class ShardedRun:
         if not self.fv_busy[slot]:
             return True
         self.fv_busy[slot] = False
-        return self.fv_caches[slot].finalverify_wait()
+        res = self.fv_caches[slot].finalverify_wait()
+        self.verdicts[self.fv_step[slot]] = res
+        return res
 
     def collect(self, slot, record):
         c, st = self.caches[slot], self.streams[slot]
+        step = self.step_of_slot[slot]
         if not self.sharded_path:
             res = c.wait()
+            self.verdicts[step] = res
         elif self.exchange["mode"] == "device":
             # The bench SYNCHRONISES on the shard (shard_wait: a host wait + 580-byte D2H) before it issues the collective: torch
             # enqueues collectives on a stream of its own, and a collective that had to wait there for a whole batch would block the
@@ -252,12 +275,14 @@ class ShardedRun:
             if self.rank == 0:
                 self.fv_caches[slot].finalverify_blobs_submit(self.gathered[slot].data_ptr(), self.world, 640, st.cuda_stream)
                 self.fv_busy[slot] = True
+                self.fv_step[slot] = step
         else:
             state, okf = c.shard_wait()
             blobs = self.all_gather_host(state + bytes([1 if okf else 0]) + bytes(7))
             res = True
             if self.rank == 0:
                 res = all(b[576] == 1 for b in blobs) and self.fv_caches[slot].finalverify_shards([b[:576] for b in blobs])
+                self.verdicts[step] = res
         if record:
             self.record_timings(c)
         return res
@@ -272,6 +297,7 @@ class ShardedRun:
         ok = True
         inflight, caches = self.inflight, self.caches
         busy = [False] * inflight
+        self.verdicts = {}
         for it in range(k):
             slot = it % inflight
             if busy[slot]:
@@ -280,6 +306,7 @@ class ShardedRun:
             after = caches[(slot - 1) % inflight] if (inflight > 1 and self.n >= 32768) else None
             rnd = next_rnd(rnd)
             self.submit(slot, after, rnd)
+            self.step_of_slot[slot] = it
             busy[slot] = True
         for j in range(inflight):
             slot = (k + j) % inflight
@@ -309,7 +336,9 @@ class ShardedRun:
             finally:
                 free.put(slot)
         with ThreadPoolExecutor(max_workers=self.inflight) as pool:
-            return all(pool.map(one, rnds)), rnd
+            res = list(pool.map(one, rnds))
+        self.verdicts = dict(enumerate(res))
+        return all(res), rnd
 
     def reset_after_transport_error(self):
         torch.cuda.synchronize()
@@ -435,7 +464,14 @@ def main():
     ap.add_argument("--no-ceiling", action="store_true", help="do not run tools/ubench_fp2chain.bin before the timed region")
     ap.add_argument("--exchange", choices=["device", "host"], default=os.environ.get("BENCH_EXCHANGE", "device"),
                     help="N > 1: all_gather of device-resident shard blobs (RCCL, no host round trip) or of host bytes")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline: the multiply-add ceiling, the one-caller rows, the aux / multi-GPU rows "
+                         "and the CPU baseline (the --no-* switches above pick from these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(spawn_ranks(a))                 # this process never touches the GPU: the ranks are its children
@@ -473,7 +509,7 @@ def main():
         sys.stderr.write("bench.py: the library was built WITHOUT the instruction-alignment post-pass (%s); numbers from it are not the product's. "
                          "Rebuild (nim-blscurve_amd/build.sh -f) or set BLS_NO_ALIGN=1 to measure it on purpose.\n" % binfo)
         sys.exit(2)
-    ceiling_live = measure_ceiling() if (rank == 0 and not a.no_ceiling) else None
+    ceiling_live = measure_ceiling() if (rank == 0 and a.full and not a.no_ceiling) else None
     dinfo = dist_info(world, backend, ctl, dev) if sharded_path else None
     if dinfo and world > 1 and not dinfo["all_on_device0_test_hook"] and dinfo["distinct_devices"] != world:
         # a real N-GPU run whose ranks landed on fewer than N devices would report a scaling curve of one GPU: fail loudly instead
@@ -486,13 +522,16 @@ def main():
     inflight, streams, caches, d_sets = run.inflight, run.streams, run.caches, run.d_sets
     n_total, nthreads, lo, hi, throughput_mode = run.n_total, run.nthreads, run.lo, run.hi, run.throughput_mode
     rnd = hashlib.sha256(b"Mr F was here").digest()
-    cache = m.BatchedBLSVerifierCache.init(max_sets=n, numThreads=nthreads, device=local)      # the one blocking caller: latency mode
+    # the one blocking caller of the --full rows: latency mode
+    cache = m.BatchedBLSVerifierCache.init(max_sets=n, numThreads=nthreads, device=local) if a.full else None
     if os.environ.get("BENCH_TEST_DIE_RANK") == str(rank) and world > 1:
         # TEST HOOK (tests/test_gpu_bench_multirank.py): this rank dies after its set-up, the others are left inside the first
         # exchange - spawn_ranks must notice, end them and exit non-zero
         os._exit(3)
     dt = run.timed(a.steps, a.warmup)
     exchange, stage_acc, gen_s = run.exchange, run.stage_acc, run.gen_s
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, run.verdicts[a.steps - 1])
 
     out = None
     if rank == 0:
@@ -501,8 +540,8 @@ def main():
         stage_ms = {k: v for k, v in all_ms.items() if not k.startswith("k_")}
         timed_kernel_ms = {k: v for k, v in all_ms.items() if k.startswith("k_") and k in KERNEL_BYTES}
         timed_kernel_ms.update({KERNEL_OF_STAGE[k]: v for k, v in stage_ms.items() if k in KERNEL_OF_STAGE})
-        # ---- outside the timed region: ONE caller, un-overlapped (kernel-alone durations, single-caller rate, PCIe-inclusive rate)
-        if a.no_one_caller:
+        # ---- outside the timed region (--full): ONE caller, un-overlapped (kernel-alone durations, single-caller rate, PCIe-inclusive rate)
+        if a.no_one_caller or not a.full:
             one = {"kernel_alone_ms": {**timed_kernel_ms, "k_sig_bucket": stage_ms.get("sig_mul_sum", 0.0)}, "tail_ms_alone": {}, "value_one_caller": None,
                    "ms_one_caller": None}
         else:
@@ -600,10 +639,10 @@ def main():
                              "context (fork streams: its stages overlap)" % inflight,
             "input_gen_s": round(gen_s, 1),
         }
-        if not a.no_aux and world == 1 and not a.force_dist:
+        if a.full and not a.no_aux and world == 1 and not a.force_dist:
             out["aux"] = aux_rows(m, cache, dev)
-    # ---- N > 1, outside the timed region: the other multi-GPU rows (every rank takes part)
-    if world > 1 and not a.no_aux:
+    # ---- N > 1, outside the timed region (--full): the other multi-GPU rows (every rank takes part)
+    if a.full and world > 1 and not a.no_aux:
         run.close()
         del run, caches, d_sets
         torch.cuda.synchronize()
@@ -632,7 +671,7 @@ def main():
         if rank == 0:
             out["multi_gpu"] = multi
     if rank == 0:
-        if not a.no_cpu and world == 1 and not a.force_dist:                # the CPU baseline is timed at N = 1 only
+        if a.full and not a.no_cpu and world == 1 and not a.force_dist:     # the CPU baseline is timed at N = 1 only
             import c_oracle as co      # the CPU restatement: this leg only
             out["cpu_baseline"] = cpu_baseline(co, a.cpu_sample, rnd)
             out["speedup_vs_cpu_port"] = out["value"] / out["cpu_baseline"]["value"]

@@ -1,6 +1,6 @@
 # The evidence under profiles/ (round tag $TAG, default r04).  On the GPU box: bash tools/collect_profiles.sh
 R=$GRAFT_REPO_ROOT; TAG=${TAG:-r05}; O=$R/gpurun_out/$TAG; rm -rf $O; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu --no-aux --no-one-caller"
+B="python3 $R/bench.py --full --no-cpu --no-aux --no-one-caller"
 # kernel-trace statistics: the default bench command (3 chained batches in flight), the same kernels alone (one throughput-mode
 # caller), one latency-mode caller, and the aux configs (MSM 2^20, fastAggregateVerify 32768, 4096-tuple batch)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats3 -o s3 -- $B --steps 5 --warmup 1 > $O/stats3.log 2>&1
@@ -22,5 +22,5 @@ python3 $R/tools/summarize_pmc.py $O/pmc_summary.json $O/pmc_fetch $O/pmc_write 
 python3 $R/tools/summarize_pmc.py $O/pmc_summary_msm.json $O/pmc_fetch_aux $O/pmc_write_aux $O/pmc_sq_aux $O/pmc_sq2_aux >> $O/pmc_summary.log 2>&1
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*agent_info.csv" -delete; find $O -name "*counter_collection.csv" -delete
 # the plain bench line of the same build
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
 du -sh $O; find $O -type f | head -40; tail -c 300 $O/stats3.log

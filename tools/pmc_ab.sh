@@ -2,7 +2,7 @@
 # usage (GPU box): bash tools/pmc_ab.sh OUTDIR name1 name2 ...      -> OUTDIR/<name>.json + a table on stdout
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; shift; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 # a variant is selected with MI355_BLS_LIB (nim-blscurve_amd/__init__.py): the shipped library is never overwritten
-P="$R/bench.py --no-cpu --no-aux --no-one-caller --steps 2 --warmup 1 --inflight 1 --ctx-mode throughput"
+P="$R/bench.py --full --no-cpu --no-aux --no-one-caller --steps 2 --warmup 1 --inflight 1 --ctx-mode throughput"
 for v in "$@"; do
   export MI355_BLS_LIB=$R/nim-blscurve_amd/variants/$v.so
   rm -rf /tmp/pmc_$v; mkdir -p /tmp/pmc_$v

@@ -1,6 +1,6 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/trace; rm -rf $O; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 for k in 2 3; do
-rocprofv3 --kernel-trace --output-format csv -d $O/t$k -o t -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu --no-aux --inflight $k > $O/log$k.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/t$k -o t -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu --no-aux --inflight $k > $O/log$k.txt 2>&1
 python3 - <<PY
 import csv
 rows=list(csv.DictReader(open("$O/t$k/t_kernel_trace.csv")))
