@@ -730,7 +730,7 @@ BLS_HDN fp fp_inv(const fp& a) {
 // 4-bit sliding-window schedule is unrolled into the code and the table of odd powers lives in registers (v60 .. v171) instead of the scratch memory
 // fp_pow_sched indexes it in; 172 VGPRs and no AGPRs, so the two-waves-per-SIMD kernels keep their occupancy.  Contract: |a| < 8 p, limbs of at most two
 // units (asserted by the host tracker below); result as fp_mul's: canonical limbs, |r| < 2 p.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_POW_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
 #include "../build/pow_asm.inc"
 // Expanded in place at every call site (a few per kernel), not an out-of-line function: the statement clobbers v0 .. v171, half of which the
 // calling convention makes a callee preserve - as a function it saved them in AGPRs, and in the unified register file of a 256-register kernel

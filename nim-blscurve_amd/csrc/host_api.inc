@@ -13,18 +13,16 @@ struct msm_ws {
     uint8_t* d_sc = nullptr;
     uint32_t* pts_int = nullptr;
     uint32_t *hist = nullptr, *offs = nullptr, *cursor = nullptr, *sorted = nullptr, *order = nullptr, *chist = nullptr, *winout = nullptr, *out = nullptr, *part = nullptr, *shist = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_bucketed = nullptr, ev_join = nullptr, ev_g[4] = {nullptr, nullptr, nullptr, nullptr}, ev_tail[3] = {nullptr, nullptr, nullptr};
-    hipStream_t gs3 = nullptr;        // a third window group's stream (MI355_BLS_MSM_CUTS experiments; the context's main and side streams carry the first two)
+    hipEvent_t ev_fork = nullptr, ev_bucketed = nullptr, ev_g[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
     uint4 *buckets = nullptr, *segout = nullptr;
 };
 static void msm_free(msm_ws* m) {
     void* b[] = {m->d_pts, m->d_sc, m->pts_int, m->hist, m->offs, m->cursor, m->sorted, m->order, m->chist, m->winout, m->out, m->buckets, m->segout, m->part, m->shist};
     for (void* x : b)
         if (x) (void)hipFree(x);
-    hipEvent_t ev[] = {m->ev_fork, m->ev_bucketed, m->ev_join, m->ev_g[0], m->ev_g[1], m->ev_g[2], m->ev_g[3], m->ev_tail[0], m->ev_tail[1], m->ev_tail[2]};
+    hipEvent_t ev[] = {m->ev_fork, m->ev_bucketed, m->ev_g[0], m->ev_g[1], m->ev_tail[0], m->ev_tail[1]};
     for (hipEvent_t e : ev)
         if (e) (void)hipEventDestroy(e);
-    if (m->gs3) (void)hipStreamDestroy(m->gs3);
     *m = msm_ws();
 }
 
@@ -124,7 +122,7 @@ constexpr size_t SIG_WIDE_MIN = 40000;       // from here 8-bit digits (2048 ext
 static bool ensure_side(mi355_bls_ctx* c) {
     if (c->side && c->side2) return true;
     int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || exp_env("MI355_BLS_SIDE_NORMAL_PRIO")) least = greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
     for (hipStream_t* sp : {&c->side, &c->side2}) {
         if (*sp) continue;
         if (hipStreamCreateWithPriority(sp, hipStreamNonBlocking, greatest) != hipSuccess) {
@@ -352,49 +350,45 @@ static int io_reserve(mi355_bls_ctx* c, size_t n) {
 // Latency mode: how many messages / pairs the lane-team engine (16 lanes each, csrc/teamvm.hpp) takes before one lane each is the faster form.
 // The engine spends ~4 x the instructions of the one-lane kernels per item (sixteen lanes run the same ~700-instruction round for one product
 // each), so it wins exactly while the chip has SIMDs to spare: `slots` = one wave per SIMD = 4 x slots items per 0.63 ms (clearing) / 0.33 ms
-// (lines), against 2.9 ms / 1.9 ms per round of one-lane waves whatever their number.  Measured crossovers: tests/gpu_probe_team.py.
+// (lines), against 2.9 ms / 1.9 ms per round of one-lane waves whatever their number.  Measured crossovers: profiles/r06_ab/team_sweep.txt.
 constexpr uint32_t TEAM_CLEAR_ITEMS_PER_SLOT = 11, TEAM_LINES_ITEMS_PER_SLOT = 18;
-static inline uint32_t team_clear_max(const mi355_bls_ctx* c) {
-    const char* e = exp_env("MI355_BLS_TEAM_CLEAR_MAX");
-    return e ? (uint32_t)atoi(e) : c->slots * TEAM_CLEAR_ITEMS_PER_SLOT;
-}
-static inline uint32_t team_lines_max(const mi355_bls_ctx* c) {
-    const char* e = exp_env("MI355_BLS_TEAM_LINES_MAX");
-    return e ? (uint32_t)atoi(e) : c->slots * TEAM_LINES_ITEMS_PER_SLOT;
+static inline uint32_t team_clear_max(const mi355_bls_ctx* c) { return c->slots * TEAM_CLEAR_ITEMS_PER_SLOT; }
+static inline uint32_t team_lines_max(const mi355_bls_ctx* c) { return c->slots * TEAM_LINES_ITEMS_PER_SLOT; }
+// Which executor of the lane-team engine takes `count` items, the same ladder for clearing and Miller lines:
+//   ROWS   the row executor (four waves per item) while the grid stays well inside one wave per SIMD;
+//   ROWS2  the same at two workgroups per CU up to twice that: 240 sets 3.10 -> 2.72 ms, 400 3.15 -> 3.01, 448 3.16 -> 3.10
+//          (profiles/r06_ab/ab_rows2.txt);
+//   SPREAD one wave (four items) per SIMD while the waves fit the chip's slots;
+//   WIDE   the plain grid beyond.
+enum team_form { TEAM_ROWS, TEAM_ROWS2, TEAM_SPREAD, TEAM_WIDE };
+static team_form team_form_for(const mi355_bls_ctx* c, uint32_t count) {
+    const uint32_t rows_max = (c->slots - c->slots / 8) / 4;
+    if (count <= rows_max) return TEAM_ROWS;
+    if (count <= 2 * rows_max) return TEAM_ROWS2;
+    return (count + 3) / 4 <= c->slots ? TEAM_SPREAD : TEAM_WIDE;
 }
 // cofactor clearing of n32 mapped point pairs on the lane-team engine (16 lanes per message), then the (all but always idle) pass that
 // recomputes a message whose incomplete additions met an exceptional case
-// the ROW executor (four waves per item) while the grid stays well inside one wave per SIMD
-static uint32_t team_rows_max(const mi355_bls_ctx* c) {
-    static const bool off = exp_env("MI355_BLS_NO_ROWVM") != nullptr;
-    return off ? 0u : (c->slots - c->slots / 8) / 4;
-}
 static void launch_team_clear(mi355_bls_ctx* c, uint32_t n32, hipStream_t st) {
     const uint32_t waves = (n32 + 3) / 4;
-    static const bool rows2 = exp_env("MI355_BLS_NO_ROWVM2") == nullptr;          // two workgroups per CU: 240 sets 3.10 -> 2.72 ms, 400 3.15 -> 3.01, 448 3.16 -> 3.10 (profiles/r06_ab/ab_rows2.txt)
-    if (n32 <= team_rows_max(c)) k_team_clear_rows<<<n32, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);
-    else if (rows2 && n32 <= 2 * team_rows_max(c)) k_team_clear_rows2<<<n32, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);
-    else if (waves <= c->slots) k_team_clear_spread<<<waves, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);       // one wave per SIMD (see the kernel)
-    else k_team_clear<<<waves, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);
+    switch (team_form_for(c, n32)) {
+        case TEAM_ROWS: k_team_clear_rows<<<n32, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
+        case TEAM_ROWS2: k_team_clear_rows2<<<n32, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
+        case TEAM_SPREAD: k_team_clear_spread<<<waves, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;      // one wave per SIMD (see the kernel)
+        case TEAM_WIDE: k_team_clear<<<waves, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
+    }
     k_clear_fix<<<(n32 + WAVE - 1) / WAVE, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);
 }
 // 320-byte records -> d_M: the two mapped points of every message (two lanes per message)
 static void launch_hash_map(mi355_bls_ctx* c, const uint8_t* d_sets, uint32_t n32, hipStream_t st) {
     const uint32_t waves = (2 * n32 + WAVE - 1) / WAVE;
-    static const bool no_rows = exp_env("MI355_BLS_HASH_MAP_NO_ROWS") != nullptr;
-    if (c->coop && (2 * n32 + 3) / 4 <= c->slots - c->slots / 8 && !no_rows) k_hash_map_rows<<<(2 * n32 + 3) / 4, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride);      // a pair per row (room left for the fork streams' waves: a second round would double the time)
+    if (c->coop && (2 * n32 + 3) / 4 <= c->slots - c->slots / 8) k_hash_map_rows<<<(2 * n32 + 3) / 4, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride);      // a pair per row (room left for the fork streams' waves: a second round would double the time)
     else if (c->coop && waves <= c->slots) k_hash_map_spread<<<waves, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride);      // one wave per SIMD
     else k_hash_map<<<waves, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride);
 }
 // d_M (two mapped points per message) -> d_H = H(m_i)
 static void launch_hash_clear(mi355_bls_ctx* c, uint32_t n32, hipStream_t st) {
     if (c->coop && n32 <= team_clear_max(c)) launch_team_clear(c, n32, st);
-#if defined(BLS_CLEAR_TWO_WAVE)
-    else if (!exp_env("MI355_BLS_CLEAR_ONE_WAVE") && c->mstride * 16 * 24 < ((size_t)1 << 32) && c->stride * 16 * 24 < ((size_t)1 << 32)) {
-        k_hash_clear2<<<(n32 + WAVE - 1) / WAVE, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride, c->d_lines, reinterpret_cast<uint4*>(c->d_pktab));       // experiment: two waves per SIMD
-        k_clear_fix<<<(n32 + WAVE - 1) / WAVE, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);
-    }
-#endif
     else k_hash_clear<<<(n32 + WAVE - 1) / WAVE, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride, c->d_lines);
 }
 
@@ -526,18 +520,18 @@ static void host_combine_chain(const uint8_t rnd[32], size_t n, uint64_t* out) {
 // k_tail for this context: latency mode takes the form with the cyclotomic squarings on row arithmetic (five waves), throughput mode the engine's three
 template <class... A>
 static inline void launch_k_tail(const mi355_bls_ctx* c, hipStream_t st, A... a) {
-    static const bool no_cyc = exp_env("MI355_BLS_NO_ROWCYC") != nullptr;
-    if (c->coop && !no_cyc) k_tail_rows<<<1, K_TAIL_THREADS, 0, st>>>(a...);
+    if (c->coop) k_tail_rows<<<1, K_TAIL_THREADS, 0, st>>>(a...);
     else k_tail<<<1, TAIL_THREADS, 0, st>>>(a...);
 }
 // pairs first .. first + count - 1 on the lane-team engine
 static void launch_lines_at(mi355_bls_ctx* c, uint32_t first, uint32_t count, hipStream_t st) {
     const uint32_t waves = (count + 3) / 4;
-    static const bool rows2 = exp_env("MI355_BLS_NO_ROWVM2") == nullptr;          // two workgroups per CU: 240 sets 3.10 -> 2.72 ms, 400 3.15 -> 3.01, 448 3.16 -> 3.10 (profiles/r06_ab/ab_rows2.txt)
-    if (count <= team_rows_max(c)) k_team_lines_rows<<<count, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines);
-    else if (rows2 && count <= 2 * team_rows_max(c)) k_team_lines_rows2<<<count, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines);
-    else if (waves <= c->slots) k_team_lines_spread<<<waves, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines);
-    else k_team_lines<<<waves, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines);
+    switch (team_form_for(c, count)) {
+        case TEAM_ROWS: k_team_lines_rows<<<count, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+        case TEAM_ROWS2: k_team_lines_rows2<<<count, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+        case TEAM_SPREAD: k_team_lines_spread<<<waves, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+        case TEAM_WIDE: k_team_lines<<<waves, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+    }
 }
 static void launch_lines(mi355_bls_ctx* c, uint32_t npairs, uint32_t extra, hipStream_t st) {
     if (c->coop && npairs <= team_lines_max(c)) {
@@ -916,34 +910,14 @@ static int verify_common(mi355_bls_ctx* c, const uint8_t* d_sets, const uint8_t*
     return verify_wait(c);
 }
 
-// where a batch submitted with `after` starts: behind that batch's hashing and public-key multiplications (ev[3]).
-// MI355_BLS_CHAIN_EV = hm | clear | pk | sig | lines | lp moves the point (experiments: tools/abn.sh).
-static hipEvent_t chain_event(mi355_bls_ctx* a) {
-    static const int which = [] {
-        const char* e = exp_env("MI355_BLS_CHAIN_EV");
-        if (!e) return 2;
-        const char* names[] = {"hm", "clear", "pk", "sig", "lines", "lp"};
-        for (int i = 0; i < 6; i++)
-            if (!strcmp(e, names[i])) return i;
-        return 2;
-    }();
-    switch (which) {
-        case 0: return a->ev_hm;
-        case 1: return a->ev[2];
-        case 3: return a->ev[4];
-        case 4: return a->ev[5];
-        case 5: return a->ev_lp;
-        default: return a->ev[3];
-    }
-}
 extern "C" int mi355_bls_batch_submit_device(mi355_bls_ctx* c, const void* d_sets, size_t n, const uint8_t rnd[32], void* stream, mi355_bls_ctx* after) {
     if (after && after != c && after->wide_recorded) {
-        // software pipelining: this batch starts when `after`'s batch has finished hashing and its public-key multiplications (the best of the
+        // software pipelining: this batch starts when `after`'s batch has finished hashing and its public-key multiplications (ev[3]; the best of the
         // stage boundaries tried: 13.3 ms per batch against 13.7 one stage earlier and 17 one later), so the batches in flight sit
         // at different stages and the serial tail of one always runs beside whole-chip kernels of another (batches that
         // start together stay in phase: their tails coincide and leave the chip idle)
         HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, chain_event(after), 0));
+        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, after->ev[3], 0));
     }
     return verify_enqueue(c, (const uint8_t*)d_sets, nullptr, n, rnd, 0, (hipStream_t)stream);
 }
@@ -1594,21 +1568,11 @@ extern "C" int mi355_bls_fast_aggregate_verify(mi355_bls_ctx* c, const void* pks
 // ------------------------------------------------------------------------------------------
 // blst_p1s_mult_pippenger / blst_p2s_mult_pippenger replacement (host side)
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t MSM_SEG = 16;
 // buckets per running-sum segment of k_pip_segred.  Rounds 3-4 used 8 from 2^12 buckets per window on (shorter running sums while the
 // segments still fill the chip); since the bucket kernel became the assembly loop (round 5) the reductions are what the MSM waits for and
 // 16-bucket segments - half as many segment lanes competing with the other window group's bucket kernel - are ahead again at 2^20 points:
-// 4.63 - 4.68 ms against 4.75 - 4.81, two in flight 3.77 - 3.80 against 3.88 - 4.03 (profiles/r05_ab/msm_knobs.txt).  MI355_BLS_MSM_SEG
-// (4, 8, 16) overrides it in experiment builds (tools/msm_env.sh).
-static uint32_t msm_seg_len(uint32_t cbk) {
-    static const uint32_t forced = [] {
-        const char* e = exp_env("MI355_BLS_MSM_SEG");
-        uint32_t v = e ? (uint32_t)atoi(e) : 0;
-        return (v == 4 || v == 8 || v == 16) ? v : 0u;
-    }();
-    if (forced && (1u << cbk) >= forced) return forced;
-    return MSM_SEG;
-}
+// 4.63 - 4.68 ms against 4.75 - 4.81, two in flight 3.77 - 3.80 against 3.88 - 4.03 (profiles/r05_ab/msm_knobs.txt).
+constexpr uint32_t MSM_SEG = 16;
 
 // Window plan for npoints x nbits: about log2(n) - 3 bits per window (signed digits: 2^(c-1) buckets), widths balanced.
 static pip_win pip_plan(size_t npoints, size_t nbits) {
@@ -1678,13 +1642,10 @@ static int msm_reserve(mi355_bls_ctx* c, msm_ws* m, size_t n, const pip_win& W, 
 #undef MALLOC
     HIPCHK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&m->ev_bucketed, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
-    for (int g = 0; g < 2; g++) HIPCHK(hipEventCreateWithFlags(&m->ev_g[g], hipEventDisableTiming));
-    for (int g = 0; g < 3; g++) HIPCHK(hipEventCreateWithFlags(&m->ev_tail[g], hipEventDisableTiming));
-#ifdef BLS_EXPERIMENTS
-    for (int g = 2; g < 4; g++) HIPCHK(hipEventCreateWithFlags(&m->ev_g[g], hipEventDisableTiming));      // a third window group (MI355_BLS_MSM_CUTS)
-    HIPCHK(hipStreamCreateWithFlags(&m->gs3, hipStreamNonBlocking));
-#endif
+    for (int g = 0; g < 2; g++) {
+        HIPCHK(hipEventCreateWithFlags(&m->ev_g[g], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&m->ev_tail[g], hipEventDisableTiming));
+    }
     m->cap_n = cb;
     m->cap_total = ct;
     return 0;
@@ -1699,14 +1660,12 @@ static int msm_enqueue(mi355_bls_ctx* c, msm_ws* m, const void* d_points, size_t
     pip_win W = pip_plan(npoints, nbits);
     int rc = msm_reserve(c, m, npoints, W, AFFB);
     if (rc) return rc;
-    uint32_t n = (uint32_t)npoints, nw = W.nwin, total = nw << W.cbk, seg = msm_seg_len(W.cbk), segs_per_win = (1u << W.cbk) / seg,      // shorter running sums once they still fill the chip
+    uint32_t n = (uint32_t)npoints, nw = W.nwin, total = nw << W.cbk, seg = MSM_SEG, segs_per_win = (1u << W.cbk) / seg,
              nseg = nw * segs_per_win;
     const uint8_t* pts = (const uint8_t*)d_points;
     const uint8_t* sc = (const uint8_t*)d_scalars;
     uint32_t nbp = (n + WAVE - 1) / WAVE;
     uint32_t nsplit = segs_per_win >= 1024 ? 16 : (segs_per_win >= 128 ? 4 : 1);
-    static const bool row_tail_off = exp_env("MI355_BLS_MSM_NO_ROWTAIL") != nullptr;            // experiment builds: the one-lane window sums of rounds 1 - 5
-    const bool row_tail = sizeof(F) == sizeof(fp) && !row_tail_off;
     // One group of windows = the whole pipeline on a range of windows [w0, w1): sort -> buckets -> segment sums -> window sums.
     const bool lds_sort = W.cbk <= PIP_SORT_MAX_CBK && W.cbk >= 10 && n >= (1u << 15);        // counters of a window in LDS (large inputs)
     auto count_sort = [&](uint32_t w0, uint32_t w1, hipStream_t s) {
@@ -1734,16 +1693,13 @@ static int msm_enqueue(mi355_bls_ctx* c, msm_ws* m, const void* d_points, size_t
         uint32_t g0 = w0 << W.cbk, gc = (w1 - w0) << W.cbk;
         k_pip_bucket<F><<<(gc + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->pts_int, m->sorted, m->offs, m->hist, m->order, n, W.cbk, total, g0, gc, m->buckets);
     };
-    auto reduce_group = [&](uint32_t w0, uint32_t w1, hipStream_t s, uint32_t g, bool last) -> int {
+    auto reduce_group = [&](uint32_t w0, uint32_t w1, hipStream_t s, uint32_t g) {
         uint32_t t0 = w0 * segs_per_win, tc = (w1 - w0) * segs_per_win;
         // G1: 4 or 2 lanes per segment (lane teams) while the team waves stay well inside the chip's 1024 one-per-SIMD wave slots (<= 960 waves: a
         // kernel of exactly 1024 such waves finds a few SIMDs taken by the other group's reduction and runs a second round for the stragglers).
         // profiles/r04_ab/msm_team.txt: 2^14 points 2.70 -> 2.29 ms, 2^16 2.56 -> 2.28, 2^18 3.28 -> 3.10 (two lanes); 2^20 would need 1024 waves per
-        // group and measured 5.2 - 5.4 ms against 5.1 - 5.2: one lane per segment there.  MI355_BLS_MSM_TEAM = 1 / 2 / 4 forces a size.
-        static const int team_forced = exp_env("MI355_BLS_MSM_TEAM") ? atoi(exp_env("MI355_BLS_MSM_TEAM")) : 0;
-        static const int team_last = exp_env("MI355_BLS_MSM_TEAM_LAST") ? atoi(exp_env("MI355_BLS_MSM_TEAM_LAST")) : 0;
-        int team = sizeof(F) != sizeof(fp) ? 1 : (team_forced > 0 ? team_forced : ((size_t)tc * 4 <= 61440 ? 4 : ((size_t)tc * 2 <= 61440 ? 2 : 1)));
-        if (last && team_last > 0 && sizeof(F) == sizeof(fp)) team = team_last;
+        // group and measured 5.2 - 5.4 ms against 5.1 - 5.2: one lane per segment there.
+        const int team = sizeof(F) != sizeof(fp) ? 1 : ((size_t)tc * 4 <= 61440 ? 4 : ((size_t)tc * 2 <= 61440 ? 2 : 1));
         if (team == 4) k_pip_segred_team<4><<<(tc * 4 + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->buckets, total, W.cbk, seg, nseg, t0, tc, m->segout);
         else if (team == 2) k_pip_segred_team<2><<<(tc * 2 + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->buckets, total, W.cbk, seg, nseg, t0, tc, m->segout);
         else k_pip_segred<F><<<(tc + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->buckets, total, W.cbk, seg, nseg, t0, tc, m->segout);
@@ -1751,15 +1707,13 @@ static int msm_enqueue(mi355_bls_ctx* c, msm_ws* m, const void* d_points, size_t
         if constexpr (sizeof(F) == sizeof(fp)) {
             // G1: the parts' sums and ONE Horner walk over the group's windows on the row arithmetic, continuing the walk of the group above (it runs
             // on another stream: ev_tail[g - 1]); the last group writes the result.  No per-window doubling chains, no k_pip_final.
-            if (row_tail) {
-                if (g) HIPCHK(hipStreamWaitEvent(s, m->ev_tail[g - 1], 0));
-                uint32_t waves = w1 - w0 < 16 ? w1 - w0 : 16;
-                k_pip_rowtail<<<1, waves * WAVE, 0, s>>>(m->part, nsplit, W, w0, w1, g ? m->winout + 48 * (g - 1) : nullptr, m->winout + 48 * g, m->out);
-                HIPCHK(hipEventRecord(m->ev_tail[g], s));
-                return 0;
-            }
+            if (g) HIPCHK(hipStreamWaitEvent(s, m->ev_tail[g - 1], 0));
+            uint32_t waves = w1 - w0 < 16 ? w1 - w0 : 16;
+            k_pip_rowtail<<<1, waves * WAVE, 0, s>>>(m->part, nsplit, W, w0, w1, g ? m->winout + 48 * (g - 1) : nullptr, m->winout + 48 * g, m->out);
+            HIPCHK(hipEventRecord(m->ev_tail[g], s));
+        } else {
+            k_pip_winsum<F><<<w1 - w0, WAVE, 0, s>>>(m->part, nsplit, W, w0, m->winout);      // G2: window sums, then k_pip_final's Horner walk
         }
-        k_pip_winsum<F><<<w1 - w0, WAVE, 0, s>>>(m->part, nsplit, W, w0, m->winout);
         return 0;
     };
     HIPCHK(hipMemsetAsync(m->hist, 0, (size_t)total * 4, st));
@@ -1772,51 +1726,33 @@ static int msm_enqueue(mi355_bls_ctx* c, msm_ws* m, const void* d_points, size_t
     // accumulation of the low group and only the short chains of the low windows are left at the end.  More groups lose more
     // in the bucket kernels' tails than they hide.  Large inputs only: a small MSM is latency-bound in every stage.
     const bool split = allow_split && nw >= 4 && (size_t)n * nw >= ((size_t)1 << 22) && ensure_side(c);
-    // Groups [cut[g + 1], cut[g]) from the high windows down: two halves.  MI355_BLS_MSM_CUTS="a" or "a,b" (window indices, descending)
-    // moves the cut or makes three groups for experiments (tools/msm_cuts.sh).  Measured at 2^20 x 255 bits, 16 windows
+    // Groups [cut[g + 1], cut[g]) from the high windows down: two halves.  Measured at 2^20 x 255 bits, 16 windows
     // (profiles/r04_ab/msm_cuts.txt): cuts 5 .. 10 are within the noise of 8; three groups (10,4 / 11,5 / 12,6 / 9,3), whose last
     // group's exposed reduction is shorter, are 1 - 3 % SLOWER alone and 10 % slower with two MSMs in flight - every extra group's
     // bucket kernel has its own tail and shares the chip with one more reduction.
-    uint32_t cut[5] = {nw, 0, 0, 0, 0}, ngroups = 1;
-    if (split) {
-        static const char* e = exp_env("MI355_BLS_MSM_CUTS");
-        uint32_t a = nw / 2, b = 0;
-        if (e) {
-            a = (uint32_t)atoi(e);
-            const char* q = strchr(e, ',');
-            b = q ? (uint32_t)atoi(q + 1) : 0;
-            if (a == 0 || a >= nw || b >= a) { a = nw / 2; b = 0; }
-        }
-        cut[1] = a;
-        ngroups = 2;
-        if (b) { cut[2] = b; ngroups = 3; }
-    }
+    const uint32_t ngroups = split ? 2 : 1, cut[3] = {nw, split ? nw / 2 : 0, 0};
     // group g runs on its own stream, its bucket kernel behind the bucket kernel of group g - 1: the (latency-bound, few-wave)
     // reduction of a group is dispatched before the next group's bucket kernel and runs beside it.  (Both bucket kernels enqueued at
     // once, the second on a lowest-priority stream so that its waves would only fill the tail of the first - 26 % of a bucket
     // kernel's wave slots idle on average, profiles/r03_pmc_summary_msm.json - was measured 3 % SLOWER: the 512-register reduction
     // waves of the first group then wait for whole SIMDs that the second group's 256-register waves keep half full.)
-    hipStream_t gs[3] = {st, c->side, m->gs3};
+    hipStream_t gs[2] = {st, c->side};
     count_sort(0, nw, st);
     for (uint32_t g = 0; g < ngroups; g++) order_group(cut[g + 1], cut[g], g, st);
     if (timed) HIPCHK(hipEventRecord(c->ev[1], st));
-    if (ngroups > 2) {                                                   // the third stream starts behind everything enqueued so far
-        HIPCHK(hipEventRecord(m->ev_join, st));
-        HIPCHK(hipStreamWaitEvent(gs[2], m->ev_join, 0));
-    }
     for (uint32_t g = 0; g < ngroups; g++) {
         if (g) HIPCHK(hipStreamWaitEvent(gs[g], m->ev_g[g - 1], 0));
         bucket_group(cut[g + 1], cut[g], gs[g]);
         HIPCHK(hipEventRecord(m->ev_g[g], gs[g]));
         if (g == 0 && timed) HIPCHK(hipEventRecord(c->ev[2], st));
-        if (int rc2 = reduce_group(cut[g + 1], cut[g], gs[g], g, g + 1 == ngroups)) return rc2;
+        if (int rc2 = reduce_group(cut[g + 1], cut[g], gs[g], g)) return rc2;
         if (g == 0 && timed) HIPCHK(hipEventRecord(c->ev[3], st));
     }
     for (uint32_t g = 1; g < ngroups; g++) {
         HIPCHK(hipEventRecord(m->ev_g[g], gs[g]));
         HIPCHK(hipStreamWaitEvent(st, m->ev_g[g], 0));
     }
-    if (!(row_tail && sizeof(F) == sizeof(fp))) k_pip_final<F><<<1, WAVE, 0, st>>>(m->winout, nw, m->out);
+    if constexpr (sizeof(F) != sizeof(fp)) k_pip_final<F><<<1, WAVE, 0, st>>>(m->winout, nw, m->out);
     if (timed) HIPCHK(hipEventRecord(c->ev[4], st));
     HIPCHK(hipGetLastError());
     return 0;

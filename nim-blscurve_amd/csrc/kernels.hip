@@ -54,15 +54,6 @@ thread_local std::string g_err;
 
 constexpr int WAVE = 64;
 
-// Experiment knobs of the measurement scripts under tools/ (MI355_BLS_CHAIN_EV, MI355_BLS_MSM_SEG / _TEAM / _CUTS) exist only in builds
-// made with -DBLS_EXPERIMENTS; the product reads two environment variables, both documented in the header: MI355_BLS_NO_ENV and
-// MI355_BLS_DEVICE.
-#ifdef BLS_EXPERIMENTS
-inline const char* exp_env(const char* name) { return getenv(name); }
-#else
-inline const char* exp_env(const char*) { return nullptr; }
-#endif
-
 struct dst_t {
     uint8_t b[64];
     uint32_t len;
@@ -414,7 +405,7 @@ struct g2_park_lds {
 // context's line store, unused until k_lines; other streams only touch columns >= n of it).  A lane that met an exceptional case of the
 // incomplete addition formulas (a Z that turned out zero: operand at infinity, P == +-Q) comes back flagged and is recomputed here with the
 // complete compiled formulas - never taken for hash outputs, exercised by mi355_bls_debug_g2_clear_cofactor.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_CLEAR_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
 #include "../build/clear_asm.inc"
 __device__ __forceinline__ uint32_t clear_asm(const uint4* M, uint32_t mstride16, uint4* H, uint32_t stride16, uint4* scratch, uint32_t sstride16, uint32_t i, uint32_t lds) {
     uint32_t flag;
@@ -431,7 +422,7 @@ __global__ void __launch_bounds__(WAVE) k_hash_clear(const uint4* __restrict__ M
 #else
     g2_park_regs park;               // host pass of the translation unit: kernels are parsed, never run
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_CLEAR_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
     if (scratch && mstride * 16 * 24 < ((size_t)1 << 32) && stride * 16 * 24 < ((size_t)1 << 32)) {      // wave-uniform: the loop's row arithmetic is 32-bit
         const uint32_t flag = clear_asm(M, (uint32_t)(mstride * 16), H, (uint32_t)(stride * 16), scratch, (uint32_t)(stride * 16), i, (uint32_t)(uintptr_t)park.base);
         if (flag) {                     // complete formulas for this lane (the out-of-line compact form)
@@ -444,33 +435,6 @@ __global__ void __launch_bounds__(WAVE) k_hash_clear(const uint4* __restrict__ M
     g2_jac q0 = soa_ld_g2(M, mstride, 2 * (size_t)i), q1 = soa_ld_g2(M, mstride, 2 * (size_t)i + 1);
     soa_st_g2(H, stride, i, clear_cofactor_g2_with(jac_add(q0, q1), park, mul_inplace{}));
 }
-#if defined(BLS_CLEAR_TWO_WAVE)
-// EXPERIMENT (round 6, review item 4; builds made with -DBLS_CLEAR_TWO_WAVE only): the same generated kernel body for 256 registers and two
-// waves per SIMD (tools/gen_clear_asm.py --two-wave): no AGPRs, no LDS - what the one-wave form parks there travels through a wave-private block of
-// global memory (252 rows of 256 bytes) and a third scratch column; the doubling loop touches neither.  A flagged lane leaves Z = 0 for
-// k_clear_fix (the complete formulas need the whole register file).  `scratch` (the context's line store): three per-lane columns, rows 0 .. 71;
-// `wave_blocks`: k_pkmul's table buffer, idle while the hashing runs (the line store's columns >= n belong to the extra pairs' lines, which a
-// latency-mode call writes on the fork stream at the same time).
-#if defined(__HIP_DEVICE_COMPILE__)
-#include "../build/clear2_asm.inc"
-#endif
-__global__ void __launch_bounds__(WAVE, 2) k_hash_clear2(const uint4* __restrict__ M, size_t mstride, uint32_t n, uint4* __restrict__ H, size_t stride, uint4* __restrict__ scratch,
-                                                          uint4* __restrict__ wave_blocks) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint4* wblock = wave_blocks + (size_t)blockIdx.x * (252 * 256 / 16);
-    uint32_t flag;
-    asm volatile(BLS_CLEAR2_ASM_BODY
-                 : "=v"(flag)
-                 : "s"(M), "s"((uint32_t)(mstride * 16)), "s"(H), "s"((uint32_t)(stride * 16)), "s"(scratch), "s"((uint32_t)(stride * 16)), "v"(i), "s"(0u), "s"(wblock)
-                 : BLS_CLEAR2_ASM_CLOBBERS);
-    if (flag) {                                   // mark for k_clear_fix: Z = 0
-        soa_st2(H, stride, 4, i, fp2_zero());
-    }
-#endif
-}
-#endif
 // test entry (mi355_bls_debug_g2_clear_cofactor): pairs of blst_p2 images -> the SoA layout k_hash_map leaves its mapped points in
 __global__ void __launch_bounds__(WAVE) k_debug_to_soa(const uint32_t* __restrict__ in, uint32_t npoints, uint4* __restrict__ M, size_t mstride) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -785,7 +749,7 @@ k_team_lines_rows2(const uint4* __restrict__ P, const uint4* __restrict__ H, uin
 // per lane (the compiled kernel indexed a table in scratch memory: 16 % of its cycles waiting), a window's entry gathered before the window's four
 // doublings.  A lane whose addition met Z3 == 0 (possible only for a
 // key outside G1) is flagged and recomputed below with the complete formulas.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_PKMUL_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
 #include "../build/pkmul_asm.inc"
 __device__ __forceinline__ uint32_t pkmul_asm(uint64_t r, uint8_t* table, uint32_t off16, uint4* P, uint32_t pstride16, uint32_t lds) {
     uint32_t flag;
@@ -801,7 +765,7 @@ __device__ __forceinline__ void pkmul_body(const uint8_t* __restrict__ sets, uin
     g1_aff pk = ld_g1a_blst(w);
     const bool inf = aff_is_inf(pk);
     if (inf) atomicOr(flags, 1u);        // BLST_PK_IS_INFINITY -> update() false
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_PKMUL_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
     if (table) {                                                     // the context's table buffer (MI355_BLS_PKTAB_BYTES per set)
         __shared__ bls_u32x4 key_slot[BLS_LDS_SLOT];
         if (inf) {
@@ -836,7 +800,7 @@ k_pkmul_spread(const uint8_t* __restrict__ sets, uint32_t n, const uint64_t* __r
 // fixed VGPR blocks, Q and the P-side factors in AGPRs, four multiplier subroutines that read fixed operand slots, the 24 line stores of a
 // step issued from the result registers and never waited for.  The compiled prologue (P-side factors, Q in homogeneous form) hands its
 // ten Fp values over through five LDS slots.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_LINES_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
 #include "../build/lines_asm.inc"
 __device__ __forceinline__ void lines_asm(uint4* lines, uint32_t stride16, uint32_t off16, uint32_t skip, uint32_t lds_a, uint32_t lds_b) {
     asm volatile(BLS_LINES_ASM_BODY : : "s"(lines), "s"(stride16), "v"(off16), "v"(skip), "s"(lds_a), "s"(lds_b) : BLS_LINES_ASM_CLOBBERS);
@@ -849,7 +813,7 @@ __global__ void __launch_bounds__(WAVE) k_lines(const uint4* __restrict__ P, con
     i += first;
     g1_jac p = soa_ld_g1(P, stride, i);
     g2_jac q = soa_ld_g2(H, stride, i);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_LINES_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
     if (stride * 16 * 24 < ((size_t)1 << 32)) {      // wave-uniform: the loop's row arithmetic is 32-bit (24 rows of a step < 4 GiB: up to 11 M pairs per context)
         __shared__ bls_u32x4 hand_over[4 * BLS_LDS_SLOT];
         const bool skip = jac_is_inf(p) | jac_is_inf(q);
@@ -886,7 +850,7 @@ __global__ void __launch_bounds__(WAVE) k_lines(const uint4* __restrict__ P, con
 // build/lineprod_asm.inc by build.sh): f <- line_0, then f <- f * line_j for j = 1 .. rounds - 1 with fp12_mul_by_line_lazy's schoolbook
 // product (two six-term Montgomery dot products per coefficient), every value in a fixed register, no scratch, no LDS, no calls;
 // lanes whose pair index is past npairs sit out (exec) and keep f = 1.  The statement ends with f stored in st_fp12_int's layout.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_LINEPROD_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
 #include "../build/lineprod_asm.inc"
 __device__ __forceinline__ void lineprod_asm(const uint4* step_base, uint32_t stride16, uint32_t npairs, uint32_t first, uint32_t rounds, uint32_t* out,
                                              uint32_t lds_buf) {
@@ -902,7 +866,7 @@ __global__ void __launch_bounds__(WAVE) k_lineprod(const uint4* __restrict__ lin
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ bls_u32x4 line_slots[4 * BLS_LDS_SLOT];              // 28 KB: with the 7 KB hand-over slot 35 of the 40 KB a wave may use
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_LINEPROD_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
     if (per_lane == 1) {                              // wave-uniform; 2 = the compiled per-lane path below (byte offsets beyond 32 bits)
         uint32_t rounds = 0;
         if (first < npairs) {
@@ -1714,7 +1678,7 @@ __global__ void __launch_bounds__(WAVE) k_pip_convert(const uint8_t* __restrict_
 // addition expanded in place on fixed registers (no calls, no operand copies), the NEXT point's record gathered while the current addition
 // runs, 230 VGPRs = two waves per SIMD as before.  A lane whose bucket met an exceptional case (addend == +- accumulator, a point at
 // infinity: ZZ3 = 0 or the record's flag) comes back flagged and recomputes its bucket with the complete compiled formulas below.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_MSM_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
 #include "../build/msm_asm.inc"
 __device__ __forceinline__ uint32_t msm_bucket_asm(const uint32_t* pts, const uint32_t* srt, uint32_t cnt, uint4* buckets, uint32_t ostride16, uint32_t off16) {
     uint32_t flag;
@@ -1734,7 +1698,7 @@ __global__ void __launch_bounds__(WAVE, sizeof(F) == sizeof(fp) ? 2 : 1) k_pip_b
     uint32_t g = g0 + (order ? order[g0 + t] : t);
     uint32_t w = g >> cbk, cnt = hist[g], off = offs[g];
     const uint32_t* srt = sorted + (size_t)w * n + off;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BLS_MSM_NOASM)
+#if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (sizeof(F) == sizeof(fp)) {
         if (!msm_bucket_asm(pts, srt, cnt, buckets, total * 16u, g * 16u)) return;        // stored by the loop; flagged lanes fall through to the complete formulas
     }
