@@ -333,7 +333,8 @@ int mi355_bls_combine(mi355_bls_ctx* ctx, const uint8_t rnd[32], const void* pks
  * with messages of arbitrary length: message i = msgs[msg_offsets[i] .. msg_offsets[i+1]) (n + 1 offsets).
  * pks: n x 96 B, sig: 192 B, host memory.  n == 0 -> 0; infinity public key -> 0.  The proofs of possession
  * must have been checked by the caller, as for the reference's two-argument overloads.  Any n: inputs beyond the
- * context's capacity are processed in slices. */
+ * context's capacity are processed in slices.  A single message must fit the context's staging buffer (max_sets * 320 - 104
+ * bytes), else MI355_BLS_ERR_CAPACITY. */
 int mi355_bls_aggregate_verify(mi355_bls_ctx* ctx, const void* pks, const uint8_t* msgs, const uint32_t* msg_offsets, size_t n,
                                const void* sig);
 /* the same with the signature as an AggregateSignature (blst_p2, Jacobian, 288 B): finish(signature: AggregateSignature),

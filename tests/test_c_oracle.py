@@ -171,3 +171,51 @@ def test_aggregate_verify_restatement():
     sig = o.g2_to_blst_affine(o.aggregate_g2([o.sign(sk, t) for (pk, sk), t in zip(keys, texts)]))
     pkb = [o.g1_to_blst_affine(pk) for pk, sk in keys]
     assert co.aggregate_verify(pkb, texts, sig) is True and co.aggregate_verify(pkb, [b"x"] + texts[1:], sig) is False
+
+
+def test_hash_to_g2_over_message_lengths_vs_python():
+    """tests/golden/aggv_varlen.json rests on the restatement's hash-to-G2 at lengths the KAT fixtures do not hold: one message of every
+    residue 0 .. 63 mod 64 (short and long ones in turn) and the long lengths of tests/util.py varlen_case, against the Python oracle."""
+    from util import VARLEN_LONG, ctr_bytes
+    lens = [r + 64 * (r % 4) for r in range(64)] + [1000, 4095, 4096, 4097, VARLEN_LONG]
+    assert {n % 64 for n in lens[:64]} == set(range(64)) and {8, 73, 16, 81} <= set(lens)
+    data = ctr_bytes(b"c_oracle", VARLEN_LONG)
+    for n in lens:
+        msg = data[:n]
+        assert co.hash_to_g2(msg, o.DST_SIG) == o.g2_to_blst_affine(o.hash_to_g2(msg, o.DST_SIG)), n
+
+
+def test_aggregate_verify_varlen_wave_vs_python():
+    """The `wave` case of tests/golden/aggv_varlen.json (65 messages, every residue mod 64): the fixture's aggregate signature is the sum of the
+    Python oracle's signatures, its verdicts are the Python oracle's pairing check (valid: GT = 1; a defect: the pairs it changes no longer cancel)."""
+    from util import varlen_case, varlen_defect
+    sks, msgs = varlen_case("wave")
+    fx = {c["n"]: c for c in golden("aggv_varlen")["cases"] if c["name"] == "wave"}
+    pks = [co.sk_to_pk(sk) for sk in sks]
+    P = [o.g1_from_blst_affine(p) for p in pks]
+    assert P[:3] == [o.sk_to_pk(sk) for sk in sks[:3]]
+    H = [o.hash_to_g2(x) for x in msgs]
+    sigs = [co.sign(sk, x) for sk, x in zip(sks, msgs)]
+    for i in (0, 7, 64):                                         # 1 000 bytes, the empty message, 4 096 bytes
+        assert o.g2_from_blst_affine(sigs[i]) == o.g2_mul(H[i], sks[i])
+
+    def gt_of(pairs):
+        return o.final_exp(o.miller_loop(pairs))
+    for n in (63, 64, 65):
+        c = fx[n]
+        agg = co.g2_sum(b"".join(sigs[:n]))
+        assert agg.hex() == c["aggsig"]
+        ok, gt = co.aggregate_verify(pks[:n], msgs[:n], agg, gt=True)
+        assert ok is True and gt.hex() == c["valid"]["gt"] and fp12_from_bytes(gt) == o.F12_ONE
+    S = o.g2_from_blst_affine(bytes.fromhex(fx[65]["aggsig"]))
+    assert S == o.aggregate_g2([o.g2_from_blst_affine(s) for s in sigs])
+    assert gt_of(list(zip(P, H)) + [(o.g1_neg(o.G1_GEN), S)]) == o.F12_ONE
+    for d in fx[65]["defects"]:
+        bad = varlen_defect(msgs, d)
+        # the valid product is 1, so the defective one is prod e(pk_i, H(bad_i)) / e(pk_i, H(m_i)) over the messages that changed
+        moved = [i for i in range(65) if bad[i] != msgs[i]]
+        assert 1 <= len(moved) <= 2
+        ratio = gt_of([(P[i], o.hash_to_g2(bad[i])) for i in moved] + [(o.g1_neg(P[i]), H[i]) for i in moved])
+        assert ratio != o.F12_ONE, d
+        ok, gt = co.aggregate_verify(pks, bad, bytes.fromhex(fx[65]["aggsig"]), gt=True)
+        assert ok is False and gt.hex() == d["gt"], d

@@ -124,3 +124,101 @@ def test_hash_one_against_rfc9380_and_oracle(m):
     for msg, dst in ((b"abc", rfc), (bytes(range(32)), o.DST_SIG), (bytes(range(48)), pop), (b"x" * 200, o.DST_SIG), (bytes(32), pop)):
         assert h(msg, dst) == o.hash_to_g2(msg, dst)
     cache.close()
+
+
+# ---- k_hash_one over message and DST lengths (mi355_bls_debug_hash_to_g2 against the C restatement; a spread against the Python oracle too)
+SWEEP_MSG_LENS = list(range(192)) + [255, 256, 257, 4031, 4032, 4033, 4095, 4096]
+SWEEP_DST_LENS = list(range(1, 65))
+
+
+def _hook(m, cache):
+    import ctypes
+    from util import g2_jac_to_affine
+    out = ctypes.create_string_buffer(288)
+
+    def h(msg, dst):
+        assert m._check(m.lib().mi355_bls_debug_hash_to_g2(cache._h, msg, len(msg), dst, len(dst), out)) == 0
+        return o.g2_to_blst_affine(g2_jac_to_affine(out.raw))
+    return h
+
+
+def test_hash_one_over_message_lengths(m):
+    """Every message length 0 .. 191 (three cycles of the residues mod 64: with the 43-byte DST the SHA-256 padding edges sit at residues 8, 9,
+    16, 17), the lengths around 256, around 4 032 (= 63 * 64: the edges of the last block that fits) and the limit 4 096 (a full d_msg)."""
+    import c_oracle as co
+    from util import ctr_bytes
+    cache = m.BatchedBLSVerifierCache.init(max_sets=64)
+    h = _hook(m, cache)
+    assert {n % 64 for n in SWEEP_MSG_LENS[:192]} == set(range(64)) and all(r + 64 * k in SWEEP_MSG_LENS for r in (8, 9, 16, 17) for k in range(3))
+    data = ctr_bytes(b"hash_one", 4096)
+    py = {0, 8, 9, 16, 17, 32, 72, 81, 137, 144, 191, 256, 4032, 4096}
+    for n in SWEEP_MSG_LENS:
+        msg = data[4096 - n:] if n else b""                 # a different window for every length
+        got = h(msg, o.DST_SIG)
+        assert got == co.hash_to_g2(msg, o.DST_SIG), n
+        if n in py:
+            assert got == o.g2_to_blst_affine(o.hash_to_g2(msg, o.DST_SIG)), n
+    cache.close()
+
+
+def test_hash_one_over_dst_lengths(m):
+    """DST lengths 1 .. 64 with a 32-byte message (the prepared-constants path from 28 bytes on, the byte-wise absorber below: both sides of the
+    switch are in the range) and with a 33-byte one (the absorber throughout)."""
+    import c_oracle as co
+    from util import ctr_bytes
+    cache = m.BatchedBLSVerifierCache.init(max_sets=64)
+    h = _hook(m, cache)
+    assert 27 in SWEEP_DST_LENS and 28 in SWEEP_DST_LENS
+    tag = ctr_bytes(b"dst", 64)
+    msg = ctr_bytes(b"dst_msg", 33)
+    py = {1, 27, 28, 43, 55, 64}
+    for dn in SWEEP_DST_LENS:
+        for x in (msg[:32], msg):
+            got = h(x, tag[:dn])
+            assert got == co.hash_to_g2(x, tag[:dn]), (dn, len(x))
+            if dn in py:
+                assert got == o.g2_to_blst_affine(o.hash_to_g2(x, tag[:dn])), (dn, len(x))
+    cache.close()
+
+
+def test_hash_one_refuses_lengths_beyond_its_limits(m):
+    import ctypes
+    cache = m.BatchedBLSVerifierCache.init(max_sets=64)
+    out = ctypes.create_string_buffer(288)
+    f = m.lib().mi355_bls_debug_hash_to_g2
+    ERR_ARG = -3
+    assert f(cache._h, bytes(32), 32, bytes(65), 0, out) == ERR_ARG
+    assert f(cache._h, bytes(32), 32, bytes(65), 65, out) == ERR_ARG
+    assert f(cache._h, bytes(4097), 4097, o.DST_SIG, len(o.DST_SIG), out) == ERR_ARG
+    assert f(cache._h, bytes(4096), 4096, o.DST_SIG, len(o.DST_SIG), out) == 0
+    with pytest.raises(m.BlsGpuError):
+        m._check(f(cache._h, bytes(4097), 4097, o.DST_SIG, len(o.DST_SIG), out))
+    cache.close()
+
+
+def test_messages_at_the_4096_byte_limit_through_the_entry_points(m, cache):
+    """fastAggregateVerify and verifyAggregate with messages of 4 095 and 4 096 bytes: the message fills d_msg up to the byte where the signature is
+    staged (d_msg + 4096) - a valid signature verifies, the scalar-plus-one signature does not; 4 097 bytes are refused by all three entry points."""
+    import c_oracle as co
+    from util import ctr_bytes
+    sks = [int.from_bytes(hashlib.sha256(b"lim" + bytes([i])).digest(), "little") % o.R or 1 for i in range(5)]
+    pks = b"".join(co.sk_to_pk(sk) for sk in sks)
+    agg = m.aggregateAll(cache, pks)
+    data = ctr_bytes(b"limit", 4097)
+    for n in (4095, 4096):
+        msg = data[:n]
+        hm = co.hash_to_g2(msg, o.DST_SIG)
+        sig, bad = co.g2_mul(hm, sum(sks) % o.R), co.g2_mul(hm, (sum(sks) + 1) % o.R)
+        assert co.fast_aggregate_verify(pks, msg, sig) is True and co.fast_aggregate_verify(pks, msg, bad) is False
+        assert m.fastAggregateVerify(cache, pks, msg, sig) is True, n
+        assert m.fastAggregateVerify(cache, pks, msg, bad) is False, n
+        assert m.fastAggregateVerify(cache, pks, msg[:-1] + bytes([msg[-1] ^ 1]), sig) is False, n       # the last byte before the staged signature
+        assert m.verifyAggregate(cache, agg, msg, sig) is True, n
+        assert m.verifyAggregate(cache, agg, msg, bad) is False, n
+    sig = co.g2_mul(co.hash_to_g2(data, o.DST_SIG), sum(sks) % o.R)
+    for call in (lambda: m.fastAggregateVerify(cache, pks, data, sig), lambda: m.verifyAggregate(cache, agg, data, sig),
+                 lambda: m.fastAggregateVerifyMulti([cache], pks, data, sig)):
+        with pytest.raises(m.BlsGpuError) as e:
+            call()
+        assert "error -3" in str(e.value)
+    assert m.fastAggregateVerify(cache, pks, data[:4096], co.g2_mul(co.hash_to_g2(data[:4096], o.DST_SIG), sum(sks) % o.R)) is True     # the context still works

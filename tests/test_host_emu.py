@@ -48,10 +48,61 @@ def test_inversion_by_division_steps_equals_fermat(emu):
 
 
 def test_sha256(emu):
+    """the streaming SHA-256 at every length 0 .. 200: three times round the padding edges (55 | 56 and 63 | 64 bytes in the last block)"""
     rng = random.Random(1)
-    for n in [0, 1, 31, 32, 55, 56, 63, 64, 65, 119, 120, 128, 200]:
+    for n in range(201):
         m = bytes(rng.randrange(256) for _ in range(n))
-        assert call(emu, "emu_sha256", m, n, outlen=32) == hashlib.sha256(m).digest()
+        assert call(emu, "emu_sha256", m, n, outlen=32) == hashlib.sha256(m).digest(), n
+
+
+def _u_bytes(u):
+    return b"".join(o.fp_to_mont_bytes(c) for c in (u[0][0], u[0][1], u[1][0], u[1][1]))
+
+
+def test_hash_to_field_over_message_lengths(emu):
+    """hash_to_field_fp2x2 (the byte-wise absorber of k_hash_var and k_hash_one) against the oracle for every message length 0 .. 191 under the
+    scheme's DST: with its 43 bytes the first hash's padding edges sit at len mod 64 in {8, 9, 16, 17}."""
+    rng = random.Random(6)
+    data = bytes(rng.getrandbits(8) for _ in range(191))
+    for n in range(192):
+        msg = data[191 - n:]
+        assert call(emu, "emu_hash_to_field", msg, n, o.DST_SIG, len(o.DST_SIG), outlen=192) == _u_bytes(o.hash_to_field_fp2(msg, o.DST_SIG, 2)), n
+
+
+def test_hash_to_field_over_dst_lengths(emu):
+    """DST lengths 1 .. 100 at message lengths 32 and 33: the generic absorber against the oracle; the prepared-constants form for 32-byte messages
+    agrees wherever it reports valid - exactly 28 .. 83 - and returns 0 outside."""
+    rng = random.Random(7)
+    tag = bytes(rng.getrandbits(8) for _ in range(100))
+    m33 = bytes(rng.getrandbits(8) for _ in range(33))
+    valid = []
+    for dn in range(1, 101):
+        dst = tag[:dn]
+        for msg in (m33[:32], m33):
+            assert call(emu, "emu_hash_to_field", msg, len(msg), dst, dn, outlen=192) == _u_bytes(o.hash_to_field_fp2(msg, dst, 2)), (dn, len(msg))
+        a = buf(192)
+        if emu.emu_hash_to_field_msg32(m33[:32], dst, dn, a) == 1:
+            valid.append(dn)
+            assert a.raw == _u_bytes(o.hash_to_field_fp2(m33[:32], dst, 2)), dn
+    assert valid == list(range(28, 84))
+
+
+def test_sswu_edge_inputs(emu):
+    """The SSWU map at its one exceptional input u = 0 (tv1 = Z^2 u^4 + Z u^2 = 0: x1 = B / (Z A), the fp2_select in sswu_g2_with) and at inputs
+    whose sign needs the imaginary part (sgn0 with a zero real part), against the oracle.  tv1 = Z u^2 (Z u^2 + 1) vanishes only for u = 0 or
+    u^2 = -1/Z, and -1/Z is not a square in Fp2: u = 0 is the only exceptional input."""
+    Z = o.SSWU_Z
+    minus_inv_z = o.f2neg(o.f2inv(Z))
+    assert o.f2mul(minus_inv_z, Z) == (o.P - 1, 0)
+    assert not o.f2_is_square(minus_inv_z) and o.f2sqrt(minus_inv_z) is None
+    us = [(0, 0), (1, 0), (0, 1), (o.P - 1, 0), (0, o.P - 1), (o.P - 1, o.P - 1), (2, 3), (5, 0)]
+    assert sum(1 for u in us if u[0] == 0 and u[1] != 0) >= 2 and {o.f2sgn0(u) for u in us if u[0] == 0 and u[1] != 0} == {0, 1}
+    for u in us:
+        zu2 = o.f2mul(Z, o.f2sqr(u))
+        exceptional = o.f2_is_zero(o.f2add(o.f2sqr(zu2), zu2))
+        assert exceptional == (u == (0, 0))
+        q = call(emu, "emu_sswu", o.fp_to_mont_bytes(u[0]) + o.fp_to_mont_bytes(u[1]), outlen=288)
+        assert g2_jac_to_affine(q) == o.sswu_g2(u), u
 
 
 def test_hash_to_g2_stages(emu):

@@ -1,5 +1,6 @@
 """Shared helpers for tests: fixture loading and canonicalisation of projective outputs."""
 import ctypes
+import hashlib
 import json
 import os
 
@@ -129,3 +130,173 @@ def apply_defect(rec, d):
         rec[320 * i + 128:320 * i + 320] = bytes(192)
     else:
         raise ValueError(d["kind"])
+
+
+# ---- variable-length aggregateVerify inputs: tests/golden/gen_aggv_varlen.py (fixture) and tests/test_gpu_aggv_varlen.py (device) build the
+# same keys and messages from this rule.  Every byte is SHA-256 in counter mode over a fixed label (no `random`: the two sides cannot drift).
+VARLEN_LABEL = b"nim-blscurve_amd/aggv_varlen/v1"
+VARLEN_CASES = ("one", "wave", "mixed", "wide", "long")
+VARLEN_PREFIXES = {"one": (1,), "wave": (63, 64, 65), "mixed": (1000,), "wide": (4097,), "long": (40,)}      # the sizes a case is verified at
+VARLEN_RUN32 = (301, 581)           # `mixed`: messages [301, 581) are all 32 bytes long, between two far ones
+VARLEN_LONG = 20000                 # `long`: eight messages of this length
+# with the scheme's 43-byte DST, Z_pad | msg | 0x0100 | 0x00 | DST | len is len(msg) + 111 bytes: the 0x80 byte and the 8-byte bit count
+# fall at the end of one block / into the next one at len(msg) mod 64 in {8, 9, 16, 17}
+VARLEN_PAD_EDGES = [b + d for d in (0, 64, 128) for b in (8, 9, 16, 17)]
+VARLEN_REQUIRED = [0, 1, 31, 32, 33] + VARLEN_PAD_EDGES + [1000, 4095, 4096, 4097]
+VARLEN_SHORT_MAX, VARLEN_FAR_MIN = 191, 320      # a "short" length is <= 191, a "far" one >= 320: neighbours of different kinds differ by > 2 SHA blocks
+
+
+def ctr_bytes(tag, n):
+    """n bytes: SHA256(label | tag | LE64(0)) | SHA256(label | tag | LE64(1)) | ..."""
+    out = bytearray()
+    i = 0
+    while len(out) < n:
+        out += hashlib.sha256(VARLEN_LABEL + b"|" + tag + b"|" + i.to_bytes(8, "little")).digest()
+        i += 1
+    return bytes(out[:n])
+
+
+def _alternate(far, short, n):
+    """far, short, far, short, ... (n lengths; both lists are consumed in order)"""
+    out = []
+    for i in range(n):
+        out.append(far.pop(0) if i % 2 == 0 else short.pop(0))
+    assert not far and not short, (len(far), len(short))
+    return out
+
+
+def _fill(kind, count, first):
+    """`count` lengths of one kind walking the residues from `first`: short = r, r + 64, r + 128 in turn; far = r + 64 k, k = 5 .. 15 in turn"""
+    out = []
+    for j in range(count):
+        r = (first + j) % 64
+        out.append(r + 64 * (j % 3) if kind == "short" else r + 64 * (5 + j % 11))
+    return out
+
+
+def varlen_lengths(name):
+    """The message lengths of a case.  Lanes alternate between far (>= 320) and short (<= 191) lengths, so adjacent lanes of a wave differ by
+    more than a SHA block (outside `mixed`'s run of 32-byte messages).
+
+    `mixed` and `wide` hold every length of VARLEN_REQUIRED and every residue mod 64.  `wave` cannot: its 64-message prefix has room for each
+    residue once, and 8 / 72 / 136 (or 0 / 4096) share one.  It takes each residue exactly once in its first 64 messages - the padding edges
+    8, 9, 16, 17 themselves, 0, 1, 31, 32, 33, 1000 and 4095 - and 4096 as the lone lane of its second block."""
+    if name == "one":
+        return [17]
+    if name == "wave":
+        short_req, far_req = [0, 1, 31, 32, 33, 8, 9, 16, 17], [1000, 4095]
+        taken = {x % 64 for x in short_req + far_req}
+        rest = [r for r in range(64) if r not in taken]                  # 53 residues: 23 short, 30 far
+        short = [r + 64 * (j % 3) for j, r in enumerate(rest[:23])]
+        far = [r + 64 * (5 + j % 11) for j, r in enumerate(rest[23:])]
+        short = short[:3] + short_req + short[3:]                        # the zero-length message away from lane 63
+        L = _alternate(far_req + far, short, 64) + [4096]
+    elif name in ("mixed", "wide"):
+        n = VARLEN_PREFIXES[name][0]
+        short_req = [x for x in VARLEN_REQUIRED if x <= VARLEN_SHORT_MAX]
+        far_req = [x for x in VARLEN_REQUIRED if x >= VARLEN_FAR_MIN]
+        if name == "mixed":
+            a, b = VARLEN_RUN32
+            head = _alternate(far_req + _fill("far", (a + 1) // 2 - len(far_req), 0),
+                              _fill("short", 3, 40) + short_req + _fill("short", a // 2 - 3 - len(short_req), 2), a)
+            m = n - b
+            tail = _alternate(_fill("far", (m + 1) // 2, 11), _fill("short", m // 2, 23), m)
+            L = head + [32] * (b - a) + tail
+        else:
+            nf, ns = (n + 1) // 2, n // 2
+            L = _alternate(far_req + _fill("far", nf - len(far_req), 0), _fill("short", 3, 40) + short_req + _fill("short", ns - 3 - len(short_req), 2), n)
+    elif name == "long":
+        # eight messages of 20 000 bytes between short ones, and the three around the one-message limit
+        short = _fill("short", 20, 5)
+        far = [VARLEN_LONG, 4096, VARLEN_LONG, 1000, VARLEN_LONG, VARLEN_LONG, 4095] + [VARLEN_LONG, 4097, 333] + [VARLEN_LONG] * 3 + _fill("far", 7, 50)
+        L = _alternate(far, short, 40)
+        assert L.count(VARLEN_LONG) == 8
+    else:
+        raise ValueError(name)
+    n = len(L)
+    assert n == max(VARLEN_PREFIXES[name])
+    run = range(*VARLEN_RUN32) if name == "mixed" else range(0)
+    for i in range(n - 1):                                              # adjacent lanes: more than one SHA block apart
+        if i // 64 == (i + 1) // 64 and not (i in run and i + 1 in run):
+            assert abs(L[i] - L[i + 1]) > 64, (name, i, L[i], L[i + 1])
+    if n >= 64:
+        assert {x % 64 for x in L[:64]} == set(range(64)) or name != "wave"
+        assert {x % 64 for x in L} == set(range(64)), name
+        need = VARLEN_REQUIRED if name != "wave" else [0, 1, 31, 32, 33, 8, 9, 16, 17, 1000, 4095, 4096]
+        assert all(x in L for x in need), (name, [x for x in need if x not in L])
+        assert any(x != 32 for x in L) and 32 in L
+    if name == "mixed":
+        assert all(L[i] == 32 for i in run) and len(run) >= 256 and all(L[i] != 32 or i in run or L.count(32) > len(run) for i in range(n))
+    return L
+
+
+def varlen_case(name):
+    """-> (sks, msgs): secret keys (ints below the group order, as bench.secret_key masks them) and messages of varlen_lengths(name)."""
+    L = varlen_lengths(name)
+    tag = name.encode()
+    sks = []
+    for i in range(len(L)):
+        sk = bytearray(ctr_bytes(b"sk|" + tag + b"|%d" % i, 32))
+        sk[31] &= 0x3f
+        sk[0] |= 1
+        sks.append(int.from_bytes(sk, "little"))
+    msgs = [ctr_bytes(b"msg|" + tag + b"|%d" % i, n) for i, n in enumerate(L)]
+    return sks, msgs
+
+
+# ---- aggregate_verify_impl's greedy cut (csrc/host_api.inc), restated: a slice takes pairs while it holds fewer than `cap` of them and
+# 4 + sum(96 + 4 + len) stays within cap * 320 staged bytes; a slice whose messages are all 32 bytes long takes the batch path's hashing kernels,
+# any other k_hash_var.  tests/test_aggv_plan_mirror.py ties this to the source.
+AGGV_PAIR_BYTES = 96 + 4
+AGGV_SET_BYTES = 320
+
+
+def aggv_slice_plan(lengths, cap):
+    """-> [(a, b, cut, all32)]: slice [a, b), cut = "pairs" | "bytes" | "end", or None where one message does not fit (MI355_BLS_ERR_CAPACITY)"""
+    budget = cap * AGGV_SET_BYTES
+    n, a, plan = len(lengths), 0, []
+    while a < n:
+        b, used = a, 4
+        cut = "end"
+        while b < n:
+            if b - a >= cap:
+                cut = "pairs"
+                break
+            add = AGGV_PAIR_BYTES + lengths[b]
+            if used + add > budget:
+                cut = "bytes"
+                break
+            used += add
+            b += 1
+        if b == a:
+            return None
+        plan.append((a, b, cut, all(x == 32 for x in lengths[a:b])))
+        a = b
+    return plan
+
+
+def aggv_one_slice_cap(lengths):
+    """the smallest context that takes the whole input in one slice"""
+    need = 4 + sum(AGGV_PAIR_BYTES + x for x in lengths)
+    return max(len(lengths), -(-need // AGGV_SET_BYTES))
+
+
+def varlen_defect(msgs, d):
+    """A defect of tests/golden/aggv_varlen.json applied to the list of messages -> a new list."""
+    out = list(msgs)
+    i = d["index"]
+    if d["kind"] == "shift":                                  # the first byte of message i + 1 moves to the end of message i: same bytes, one offset differs
+        out[i], out[i + 1] = out[i] + out[i + 1][:1], out[i + 1][1:]
+        assert b"".join(out) == b"".join(msgs)
+    elif d["kind"] == "trail":                                # one byte appended (0x00, or the SHA padding byte 0x80)
+        out[i] = out[i] + bytes([d["byte"]])
+    elif d["kind"] == "flip":                                 # the lowest bit of the last byte of a long message
+        assert len(out[i]) >= 4096
+        out[i] = out[i][:-1] + bytes([out[i][-1] ^ 1])
+    elif d["kind"] == "swap":                                 # two messages of different lengths change places
+        j = d["other"]
+        assert len(out[i]) != len(out[j])
+        out[i], out[j] = out[j], out[i]
+    else:
+        raise ValueError(d["kind"])
+    return out
