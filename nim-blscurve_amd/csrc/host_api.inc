@@ -2,6 +2,9 @@
 // of batches larger than a workspace, the multi-device drivers, the Pippenger host side.  Included by kernels.hip (same translation
 // unit: the kernels it launches live in that file's anonymous namespace); not a stand-alone source.
 #pragma once
+#include "plan.hpp"      // which kernel, what grid, which stream: every size decision of this file
+using plan::SIG_SLOTS_MAX;
+static_assert(plan::WAVE == (uint32_t)WAVE && plan::N_LINES == (uint32_t)N_LINES, "plan.hpp restates the wave size and the Miller loop's step count");
 
 // ------------------------------------------------------------------------------------------
 // Context
@@ -107,9 +110,7 @@ struct mi355_bls_ctx {
     msm_ws* msm2 = nullptr;          // a second one: combine runs its G1 and its G2 Pippenger side by side
 };
 
-constexpr uint32_t SIG_SLOTS_MAX = 2048;     // 8 windows x 256 digits
 constexpr size_t PKTAB_BYTES = 8 * 5 * 64;   // per set: 8 table entries x (X, Y, Z, Z^2, Z^3) x 64 bytes (tools/gen_pkmul_asm.py LANE_BYTES)
-constexpr size_t SIG_WIDE_MIN = 40000;       // from here 8-bit digits (2048 extra pairs, 8 additions per tuple) beat 4-bit ones (256, 15)
 
 // The context's two fork streams (latency-mode batches, fastAggregateVerify's key sum, the window groups of a large MSM, combine's second
 // Pippenger), created with the context.  They get the device's HIGHEST stream priority: HIP spreads the streams of one priority over
@@ -347,49 +348,30 @@ static int io_reserve(mi355_bls_ctx* c, size_t n) {
     return 0;
 }
 
-// Latency mode: how many messages / pairs the lane-team engine (16 lanes each, csrc/teamvm.hpp) takes before one lane each is the faster form.
-// The engine spends ~4 x the instructions of the one-lane kernels per item (sixteen lanes run the same ~700-instruction round for one product
-// each), so it wins exactly while the chip has SIMDs to spare: `slots` = one wave per SIMD = 4 x slots items per 0.63 ms (clearing) / 0.33 ms
-// (lines), against 2.9 ms / 1.9 ms per round of one-lane waves whatever their number.  Measured crossovers: profiles/r06_ab/team_sweep.txt.
-constexpr uint32_t TEAM_CLEAR_ITEMS_PER_SLOT = 11, TEAM_LINES_ITEMS_PER_SLOT = 18;
-static inline uint32_t team_clear_max(const mi355_bls_ctx* c) { return c->slots * TEAM_CLEAR_ITEMS_PER_SLOT; }
-static inline uint32_t team_lines_max(const mi355_bls_ctx* c) { return c->slots * TEAM_LINES_ITEMS_PER_SLOT; }
-// Which executor of the lane-team engine takes `count` items, the same ladder for clearing and Miller lines:
-//   ROWS   the row executor (four waves per item) while the grid stays well inside one wave per SIMD;
-//   ROWS2  the same at two workgroups per CU up to twice that: 240 sets 3.10 -> 2.72 ms, 400 3.15 -> 3.01, 448 3.16 -> 3.10
-//          (profiles/r06_ab/ab_rows2.txt);
-//   SPREAD one wave (four items) per SIMD while the waves fit the chip's slots;
-//   WIDE   the plain grid beyond.
-enum team_form { TEAM_ROWS, TEAM_ROWS2, TEAM_SPREAD, TEAM_WIDE };
-static team_form team_form_for(const mi355_bls_ctx* c, uint32_t count) {
-    const uint32_t rows_max = (c->slots - c->slots / 8) / 4;
-    if (count <= rows_max) return TEAM_ROWS;
-    if (count <= 2 * rows_max) return TEAM_ROWS2;
-    return (count + 3) / 4 <= c->slots ? TEAM_SPREAD : TEAM_WIDE;
-}
-// cofactor clearing of n32 mapped point pairs on the lane-team engine (16 lanes per message), then the (all but always idle) pass that
-// recomputes a message whose incomplete additions met an exceptional case
-static void launch_team_clear(mi355_bls_ctx* c, uint32_t n32, hipStream_t st) {
-    const uint32_t waves = (n32 + 3) / 4;
-    switch (team_form_for(c, n32)) {
-        case TEAM_ROWS: k_team_clear_rows<<<n32, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
-        case TEAM_ROWS2: k_team_clear_rows2<<<n32, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
-        case TEAM_SPREAD: k_team_clear_spread<<<waves, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;      // one wave per SIMD (see the kernel)
-        case TEAM_WIDE: k_team_clear<<<waves, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
-    }
-    k_clear_fix<<<(n32 + WAVE - 1) / WAVE, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);
-}
 // 320-byte records -> d_M: the two mapped points of every message (two lanes per message)
 static void launch_hash_map(mi355_bls_ctx* c, const uint8_t* d_sets, uint32_t n32, hipStream_t st) {
-    const uint32_t waves = (2 * n32 + WAVE - 1) / WAVE;
-    if (c->coop && (2 * n32 + 3) / 4 <= c->slots - c->slots / 8) k_hash_map_rows<<<(2 * n32 + 3) / 4, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride);      // a pair per row (room left for the fork streams' waves: a second round would double the time)
-    else if (c->coop && waves <= c->slots) k_hash_map_spread<<<waves, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride);      // one wave per SIMD
-    else k_hash_map<<<waves, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride);
+    const plan::hash_map_plan p = plan::hash_map_for(c->slots, c->coop, n32);
+    switch (p.form) {
+        case plan::HASH_MAP_ROWS: k_hash_map_rows<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride); break;
+        case plan::HASH_MAP_SPREAD: k_hash_map_spread<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride); break;
+        case plan::HASH_MAP_PLAIN: k_hash_map<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride); break;
+    }
 }
-// d_M (two mapped points per message) -> d_H = H(m_i)
+// d_M (two mapped points per message) -> d_H = H(m_i): the engine, then the (all but always idle) pass that recomputes a message whose
+// incomplete additions met an exceptional case; or k_hash_clear
 static void launch_hash_clear(mi355_bls_ctx* c, uint32_t n32, hipStream_t st) {
-    if (c->coop && n32 <= team_clear_max(c)) launch_team_clear(c, n32, st);
-    else k_hash_clear<<<(n32 + WAVE - 1) / WAVE, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride, c->d_lines);
+    const plan::stage p = plan::clear_for(c->slots, c->coop, n32);
+    if (p.team) {
+        switch (p.form) {       // the lane-team engine (16 lanes per message, csrc/teamvm.hpp)
+            case plan::TEAM_ROWS: k_team_clear_rows<<<p.grid, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
+            case plan::TEAM_ROWS2: k_team_clear_rows2<<<p.grid, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
+            case plan::TEAM_SPREAD: k_team_clear_spread<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;      // one wave per SIMD (see the kernel)
+            case plan::TEAM_WIDE: k_team_clear<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
+        }
+        k_clear_fix<<<plan::waves_for(n32), WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);
+    } else {
+        k_hash_clear<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride, c->d_lines);
+    }
 }
 
 // TEST HOOK: out[i] = clear_cofactor(q0_i + q1_i) for n pairs of blst_p2 images in HOST memory, through the kernels of the batch path themselves
@@ -512,69 +494,45 @@ static void host_combine_chain(const uint8_t rnd[32], size_t n, uint64_t* out) {
     }
 }
 
-// Miller lines of pairs 0 .. npairs-1 (the last `extra` of them are the bucket pairs of the signature side): the
-// 8-lanes-per-pair kernel while that does not take more waves than the chip has slots.  Whole-chip batches in latency mode
-// (coop): the tuple pairs fill the chip exactly, so the few extra pairs would be a second round of waves that takes as long as
-// the first (2.2 ms at 3 % occupancy); with 8 lanes per pair they take ~1 ms instead.  In throughput mode (several batches
-// in flight) that second round overlaps other batches' kernels and one lane per pair is the cheaper form.
 // k_tail for this context: latency mode takes the form with the cyclotomic squarings on row arithmetic (five waves), throughput mode the engine's three
 template <class... A>
 static inline void launch_k_tail(const mi355_bls_ctx* c, hipStream_t st, A... a) {
     if (c->coop) k_tail_rows<<<1, K_TAIL_THREADS, 0, st>>>(a...);
     else k_tail<<<1, TAIL_THREADS, 0, st>>>(a...);
 }
-// pairs first .. first + count - 1 on the lane-team engine
-static void launch_lines_at(mi355_bls_ctx* c, uint32_t first, uint32_t count, hipStream_t st) {
-    const uint32_t waves = (count + 3) / 4;
-    switch (team_form_for(c, count)) {
-        case TEAM_ROWS: k_team_lines_rows<<<count, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
-        case TEAM_ROWS2: k_team_lines_rows2<<<count, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
-        case TEAM_SPREAD: k_team_lines_spread<<<waves, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
-        case TEAM_WIDE: k_team_lines<<<waves, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+// the Miller lines of pairs first .. first + count - 1 as `t` says: on the lane-team engine or one lane each (k_lines)
+static void launch_lines_at(mi355_bls_ctx* c, const plan::stage& t, uint32_t first, uint32_t count, hipStream_t st) {
+    if (!t.team) {
+        k_lines<<<t.grid, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines);
+        return;
+    }
+    switch (t.form) {
+        case plan::TEAM_ROWS: k_team_lines_rows<<<t.grid, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+        case plan::TEAM_ROWS2: k_team_lines_rows2<<<t.grid, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+        case plan::TEAM_SPREAD: k_team_lines_spread<<<t.grid, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+        case plan::TEAM_WIDE: k_team_lines<<<t.grid, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
     }
 }
-static void launch_lines(mi355_bls_ctx* c, uint32_t npairs, uint32_t extra, hipStream_t st) {
-    if (c->coop && npairs <= team_lines_max(c)) {
-        launch_lines_at(c, 0, npairs, st);
-    } else if (c->coop && extra && extra < npairs && extra <= team_lines_max(c) &&
-               (npairs + WAVE - 1) / WAVE > c->slots * (((npairs - extra + WAVE - 1) / WAVE + c->slots - 1) / c->slots)) {
-        // the extra pairs would start one more round of waves: a team of lanes each instead
-        uint32_t main_pairs = npairs - extra;
-        k_lines<<<(main_pairs + WAVE - 1) / WAVE, WAVE, 0, st>>>(c->d_P, c->d_H, 0, main_pairs, c->stride, c->d_lines);
-        launch_lines_at(c, main_pairs, extra, st);
-    } else {
-        k_lines<<<(npairs + WAVE - 1) / WAVE, WAVE, 0, st>>>(c->d_P, c->d_H, 0, npairs, c->stride, c->d_lines);
-    }
+// pairs 0 .. main_pairs - 1, then the extra pairs behind them where the plan gives them a form of their own (plan.hpp lines_for)
+static void launch_lines(mi355_bls_ctx* c, const plan::lines_plan& p, hipStream_t st) {
+    launch_lines_at(c, p.main, 0, p.main_pairs, st);
+    if (p.extra_pairs) launch_lines_at(c, p.extra, p.main_pairs, p.extra_pairs, st);
 }
 
 // The per-step products of the Miller lines of pairs 0 .. npairs-1 -> d_L (68 step products).  mid_ev: recorded between the wide
 // kernel and the fold of its partials.
 static int enqueue_line_products(mi355_bls_ctx* c, uint32_t npairs, hipStream_t st, hipEvent_t mid_ev) {
-    uint32_t nblk = c->slots / N_LINES;
-    if (nblk < 1) nblk = 1;
-    if (nblk > c->nblk_cap) nblk = c->nblk_cap;
-    uint32_t m = (npairs + WAVE * nblk - 1) / (WAVE * nblk);
-    if (m < 1) m = 1;
-    nblk = (npairs + WAVE * m - 1) / (WAVE * m);
-    // every lane hands its partial product over (64 x nblk per step).  Throughput mode: k_lineprod2's 68 waves fold them,
-    // 15 sequential Fp12 products per lane + one shuffle tree (least total work); latency mode: k_fold on the lane-cooperative
-    // engine, 64 per block and then the nblk block results (one caller, 65 536 tuples: 1.8 -> 0.35 ms)
-    // 1: the assembly loop (32-bit byte offsets inside one step's 24 planes); 2: the compiled loop
-    const int per_lane = (uint64_t)c->stride * 16 * 24 + (uint64_t)npairs * 16 < (1ull << 32) ? 1 : 2;
-    k_lineprod<<<dim3(N_LINES, nblk), WAVE, 0, st>>>(c->d_lines, npairs, c->stride, m, c->d_lpart, nblk, per_lane);
-    if (mid_ev) HIPCHK(hipEventRecord(mid_ev, st));
     c->fold_form = (c->coop || c->alone) ? 1 : 0;
+    const plan::lineprod_plan p = plan::lineprod_for(c->slots, c->nblk_cap, c->stride, npairs, c->fold_form != 0);
+    // every lane hands its partial product over (64 x nblk per step); what folds them: plan.hpp lineprod_for
+    k_lineprod<<<dim3(N_LINES, p.nblk), WAVE, 0, st>>>(c->d_lines, npairs, c->stride, p.m, c->d_lpart, p.nblk, p.per_lane);
+    if (mid_ev) HIPCHK(hipEventRecord(mid_ev, st));
     if (c->fold_form) {
-        size_t first_last = (size_t)(nblk - 1) * WAVE * m;             // lanes past the last pair hold 1: not folded
-        uint32_t live = (nblk - 1) * WAVE + (npairs - first_last < WAVE ? (uint32_t)(npairs - first_last) : WAVE);
-        uint32_t per = 1;                                              // two levels of about sqrt(live) dependent products each
-        while (per * per < live) per++;
-        uint32_t nb1 = (live + per - 1) / per;
         uint32_t* mid = c->d_lpart + (size_t)N_LINES * c->nblk_cap * WAVE * F12W;
-        k_fold<<<dim3(N_LINES, nb1), TAIL_THREADS, 0, st>>>(c->d_lpart, nblk * WAVE, per, live - (nb1 - 1) * per, nb1 > 1 ? mid : c->d_L);
-        if (nb1 > 1) k_fold<<<dim3(N_LINES, 1), TAIL_THREADS, 0, st>>>(mid, nb1, nb1, nb1, c->d_L);
+        k_fold<<<dim3(N_LINES, p.nb1), TAIL_THREADS, 0, st>>>(c->d_lpart, p.nblk * WAVE, p.per, p.live - (p.nb1 - 1) * p.per, p.nb1 > 1 ? mid : c->d_L);
+        if (p.nb1 > 1) k_fold<<<dim3(N_LINES, 1), TAIL_THREADS, 0, st>>>(mid, p.nb1, p.nb1, p.nb1, c->d_L);
     } else {
-        k_lineprod2<<<N_LINES, WAVE, 0, st>>>(c->d_lpart, nblk * WAVE, c->d_L);
+        k_lineprod2<<<N_LINES, WAVE, 0, st>>>(c->d_lpart, p.nblk * WAVE, c->d_L);
     }
     return 0;
 }
@@ -604,25 +562,25 @@ static int run_slice(mi355_bls_ctx* c, mi355_bls_ctx* p, const uint8_t* d_sets, 
 // Everything behind the blinding scalars (d_r[0 .. n) are ready on `st`): hashing, [r]PK, the signature side, Miller lines, line
 // products, the committed state of these n tuples in d_states slot 0.
 static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStream_t st) {
-    uint32_t n32 = (uint32_t)n;
-    uint32_t nb = (n32 + WAVE - 1) / WAVE;
+    const uint32_t n32 = (uint32_t)n;
     HIPCHK(hipEventRecord(c->ev[1], st));
-    const bool have_side = c->coop && ensure_side(c);
-    const bool fork = have_side && n32 <= 16 * c->slots;                // pk + signature side beside the hashing
-    // A whole-chip batch of ONE caller (latency mode): the signature side and the Miller lines of its extra pairs run on the side
-    // stream beside the hashing.  The tuple pairs then fill the chip's wave slots exactly once; behind them the extra pairs
+    const plan::slice_plan p = plan::slice_for(c->slots, c->coop, c->coop && ensure_side(c), n);
+    const uint32_t nb = p.nb, cw = p.cw, nwin = p.nwin, total = p.total;
+    // SIDE_FORK_SIG - a whole-chip batch of ONE caller (latency mode): the signature side and the Miller lines of its extra pairs run on the
+    // side stream beside the hashing.  The tuple pairs then fill the chip's wave slots exactly once; behind them the extra pairs
     // would be a second round of waves (or ~1 ms of the 8-lanes-per-pair kernel).  Throughput mode keeps everything on the
     // caller's stream: with several batches in flight the nearly empty second round overlaps other batches' kernels, and
     // folding the 2048 bucket sums further (to 64 per-bit sums, or to one sum per window) so that fewer extra pairs remain was
     // measured SLOWER per pipelined batch (+0.5 ms and +2.5 ms: the fold is a chain of small dependent kernels on the batch's
     // critical path, the 2048 extra pairs are 3 % more of two embarrassingly parallel kernels).
-    const bool fork_sig = !fork && have_side;
-    // Round 6: a small batch's [r]PK runs on a fork stream of its OWN, beside the signature side instead of in front of it (they do not
+    // SIDE_FORK - round 6: a small batch's [r]PK runs on a fork stream of its OWN, beside the signature side instead of in front of it (they do not
     // depend on each other; in a row they outlasted the hashing they were meant to hide in: 0.75 + 0.8 ms against 0.9 + 0.66), and the
     // Miller lines of the extra pairs follow the signature side on its stream, so that the tuple pairs alone - at 4 096 sets exactly one
     // engine wave per SIMD - are what the caller's stream still has to walk.
-    hipStream_t sd = fork ? (c->side2 ? c->side2 : c->side) : st;       // [r]PK
-    hipStream_t ss = (fork || fork_sig) ? c->side : st;                 // signature side
+    const bool fork = p.side == plan::SIDE_FORK, fork_sig = p.side == plan::SIDE_FORK_SIG;
+    const auto stream_of = [&](plan::stream_role r) { return r == plan::STREAM_CALLER ? st : r == plan::STREAM_SIDE2 && c->side2 ? c->side2 : c->side; };
+    hipStream_t sd = stream_of(p.pk_stream);                            // [r]PK
+    hipStream_t ss = stream_of(p.sig_stream);                           // signature side
     if (fork || fork_sig) HIPCHK(hipStreamWaitEvent(c->side, c->ev[1], 0));
     if (fork && sd != c->side) HIPCHK(hipStreamWaitEvent(sd, c->ev[1], 0));
     // ---- hashing (caller's stream)
@@ -631,13 +589,12 @@ static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStrea
     launch_hash_clear(c, n32, st);
     HIPCHK(hipEventRecord(c->ev[2], st));
     // ---- [r]PK
-    if (c->coop && nb <= c->slots) k_pkmul_spread<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, c->d_P, c->stride, c->d_flags, c->d_pktab);      // one wave per SIMD
+    if (p.pkmul_spread) k_pkmul_spread<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, c->d_P, c->stride, c->d_flags, c->d_pktab);      // one wave per SIMD
     else k_pkmul<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, c->d_P, c->stride, c->d_flags, c->d_pktab);
     HIPCHK(hipEventRecord(c->ev[3], sd));
     // ---- signature side as a bucket fold: sig_slots extra Miller pairs n .. n + sig_slots - 1 (every batch size: for a
     // handful of tuples the 256 nearly empty buckets are still cheaper than one 64-bit G2 multiplication per tuple, which is a
     // 3 ms chain of doublings when nothing hides its latency)
-    uint32_t cw = n >= SIG_WIDE_MIN ? 8 : 4, nwin = 64 / cw, total = nwin << cw;
     {
         msm_win W{nwin, cw, 0};
         uint32_t *hist = c->d_sig_hist, *offs = hist + SIG_SLOTS_MAX, *cursor = offs + SIG_SLOTS_MAX;
@@ -647,45 +604,25 @@ static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStrea
         k_msm_hist<<<dim3(nb, nwin), WAVE, 0, ss>>>(reinterpret_cast<const uint8_t*>(c->d_r), 8, n32, W, cw, hist);
         k_msm_scan<<<nwin, WAVE, 0, ss>>>(hist, cw, offs, cursor);
         k_msm_scatter<<<dim3(nb, nwin), WAVE, 0, ss>>>(reinterpret_cast<const uint8_t*>(c->d_r), 8, n32, W, cw, cursor, c->d_sig_sorted);
-        uint32_t per = n32 >> cw, lshift = 0;                          // expected entries per bucket; ~16 per lane
-        const uint32_t per_lane_min = c->coop ? 16u : 64u;      // throughput mode: fewer, longer lanes (the fold of a bucket's lanes is pure overhead)
-        while (lshift < 6 && (per >> (lshift + 1)) >= per_lane_min) lshift++;
-        // small batches leave most of the chip idle: more lanes per bucket (down to ~2 entries per lane) shorten the kernel
-        while (lshift < 6 && ((total << (lshift + 1)) <= 16 * c->slots) && (per >> (lshift + 1)) >= 2) lshift++;
-        k_sig_bucket<<<((total << lshift) + WAVE - 1) / WAVE, WAVE, 0, ss>>>(c->d_sig_pts, c->d_sig_sorted, offs, hist, n32, cw, lshift, total,
-                                                                             c->d_sig_consts + (cw == 8 ? (size_t)SIG_SLOTS_MAX * G1W : 0), c->d_H, c->d_P,
-                                                                             c->stride, (size_t)n32);
+        k_sig_bucket<<<p.bucket_grid, WAVE, 0, ss>>>(c->d_sig_pts, c->d_sig_sorted, offs, hist, n32, cw, p.lshift, total,
+                                                     c->d_sig_consts + (cw == 8 ? (size_t)SIG_SLOTS_MAX * G1W : 0), c->d_H, c->d_P, c->stride, (size_t)n32);
         c->sig_c = cw;
         c->sig_slots = total;
         c->agg_valid = false;
     }
     // ---- Miller lines and their products per step
     uint32_t npairs = n32 + total;
-    if (fork_sig) {
-        // the extra pairs' walk on the lane-team engine (round 6): 512 waves for 0.35 ms instead of 32 one-lane waves for 1.9 ms - the signature side is
-        // out of the way 1.4 ms earlier and no longer displaces the waves of [r]PK behind the hashing (one blocking 65 536-set call: 12.7 -> 12.0 ms)
-        if (total <= team_lines_max(c)) launch_lines_at(c, n32, total, ss);
-        else k_lines<<<(total + WAVE - 1) / WAVE, WAVE, 0, ss>>>(c->d_P, c->d_H, n32, total, c->stride, c->d_lines);
-        HIPCHK(hipEventRecord(c->ev[4], ss));
-        HIPCHK(hipEventRecord(c->ev_l0, st));
-        launch_lines(c, n32, 0, st);
-        HIPCHK(hipStreamWaitEvent(st, c->ev[4], 0));                    // join
-    } else if (fork && total <= team_lines_max(c)) {
-        launch_lines_at(c, n32, total, ss);                             // the extra pairs' lines: on the signature side's stream, beside the hashing
-        HIPCHK(hipEventRecord(c->ev[4], ss));
+    // the extra pairs' walk on the signature side's stream, beside the hashing (round 6, on the lane-team engine: 512 waves for 0.35 ms instead of 32
+    // one-lane waves for 1.9 ms - the signature side is out of the way 1.4 ms earlier and no longer displaces the waves of [r]PK behind the hashing)
+    if (p.extra_apart) launch_lines_at(c, p.extra_lines, n32, total, ss);
+    HIPCHK(hipEventRecord(c->ev[4], ss));
+    if (fork) {
         HIPCHK(hipStreamWaitEvent(st, c->ev[4], 0));                    // join: the signature side ...
         HIPCHK(hipStreamWaitEvent(st, c->ev[3], 0));                    // ... and [r]PK
-        HIPCHK(hipEventRecord(c->ev_l0, st));
-        launch_lines(c, n32, 0, st);
-    } else {
-        HIPCHK(hipEventRecord(c->ev[4], ss));
-        if (fork) {
-            HIPCHK(hipStreamWaitEvent(st, c->ev[4], 0));                // join
-            HIPCHK(hipStreamWaitEvent(st, c->ev[3], 0));
-        }
-        HIPCHK(hipEventRecord(c->ev_l0, st));
-        launch_lines(c, npairs, total, st);
     }
+    HIPCHK(hipEventRecord(c->ev_l0, st));
+    launch_lines(c, p.lines, st);                                       // the tuple pairs, and the extra pairs where they did not run apart
+    if (fork_sig) HIPCHK(hipStreamWaitEvent(st, c->ev[4], 0));          // join behind the tuple pairs' lines
     HIPCHK(hipEventRecord(c->ev[5], st));
     {
         int rcp = enqueue_line_products(c, npairs, st, c->ev_lp);
@@ -700,12 +637,6 @@ static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStrea
     c->have_gt = false;
     c->gt_is_fv = false;
     return 0;
-}
-
-// chunk of the parallel_chunks partition (parallel_chunks.nim:42-66) that tuple t of n_total falls into, B chunks
-static inline uint32_t chunk_of_tuple(size_t n_total, uint32_t B, size_t t) {
-    size_t base = n_total / B, rem = n_total % B, cut = (base + 1) * rem;
-    return (uint32_t)(t < cut ? t / (base + 1) : rem + (t - cut) / base);
 }
 
 // the internal workspaces of pipelined slices: same device, same capacity, throughput mode (no fork streams: the slices overlap each other)
@@ -768,12 +699,12 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
         c->h_r.resize(n);
         host_serial_chain(rnd, n, c->h_r.data());
     }
-    const size_t nslices = (n + c->cap - 1) / c->cap;
+    const size_t nslices = plan::shard_nslices(n, c->cap);
     c->alone = nslices == 1 && g_in_flight.load(std::memory_order_relaxed) == 0;       // slices of one call overlap each other: throughput form
     if (nslices == 1) {
         const uint8_t* d = src_dev ? src_dev : c->d_sets;
         if (!src_dev) HIPCHK(hipMemcpyAsync(c->d_sets, src_host, n * 320, hipMemcpyHostToDevice, st));
-        uint32_t c_lo = serial ? 0 : chunk_of_tuple(n_total, nchunks, tuple_base), c_hi = serial ? 1 : chunk_of_tuple(n_total, nchunks, tuple_base + n - 1) + 1;
+        uint32_t c_lo = serial ? 0 : plan::chunk_of_tuple(n_total, nchunks, tuple_base), c_hi = serial ? 1 : plan::chunk_of_tuple(n_total, nchunks, tuple_base + n - 1) + 1;
         return run_slice(c, c, d, n_total, nchunks, c_lo, c_hi - c_lo, tuple_base, n, serial, 0, 0, st, nullptr);
     }
     // ---- several slices: pipelined over the workspaces of this context and of up to two lanes, each on its own stream.  Slice i starts
@@ -783,7 +714,7 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
     // slice's k_blind left: ev_blind), and each workspace's own stream.  Every workspace keeps the running product of ITS slices in
     // slot 1 of its d_states; at the end the lanes' products are copied over and multiplied in (an Fp12 product commutes).  The last
     // slice always runs in this context's own workspace, so fetch_stage(0..3) shows it as before.
-    int nl = nslices >= 3 ? 3 : 2;                            // workspaces used, this context's included
+    int nl = plan::shard_workspaces(nslices);                 // workspaces used, this context's included
     {
         int have = ensure_lanes(c, nl - 1);
         if (have < 0) return have;
@@ -802,10 +733,10 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
     mi355_bls_ctx* prev = nullptr;
     size_t done = 0;
     for (uint32_t slice = 0; done < n; slice++) {
-        size_t left = nslices - slice, cnt = (n - done + left - 1) / left;          // balanced: never a sliver at the end
+        size_t cnt = plan::shard_slice_count(n, done, nslices, slice);              // balanced: never a sliver at the end
         size_t t0 = tuple_base + done;
-        uint32_t c_lo = serial ? 0 : chunk_of_tuple(n_total, nchunks, t0), c_hi = serial ? 1 : chunk_of_tuple(n_total, nchunks, t0 + cnt - 1) + 1;
-        const int L = (int)((nslices - 1 - slice) % (size_t)nl);                    // the last slice on this context's own workspace
+        uint32_t c_lo = serial ? 0 : plan::chunk_of_tuple(n_total, nchunks, t0), c_hi = serial ? 1 : plan::chunk_of_tuple(n_total, nchunks, t0 + cnt - 1) + 1;
+        const int L = plan::shard_workspace_of(nslices, slice, nl);                 // the last slice on this context's own workspace
         mi355_bls_ctx* x = L ? c->lane[L - 1] : c;
         hipStream_t sx = L ? c->lane_st[L - 1] : st;
         if (slice) {
@@ -1469,7 +1400,7 @@ static int fav_run(mi355_bls_ctx* c, const void* d_pks, size_t n, const uint8_t*
     if (sd != st) HIPCHK(hipStreamWaitEvent(st, c->ev[1], 0));
     k_fav_setup<<<1, 1, 0, st>>>(c->d_agg1, reinterpret_cast<const uint32_t*>(c->d_msg + 4096), c->d_H, c->d_P, c->stride, c->d_flags);
     HIPCHK(hipEventRecord(c->ev[2], st));
-    launch_lines(c, 2, 0, st);
+    launch_lines(c, plan::lines_for(c->slots, c->coop, 2, 0), st);
     HIPCHK(hipEventRecord(c->ev[3], st));
     k_lineprod<<<dim3(N_LINES, 1), WAVE, 0, st>>>(c->d_lines, 2, c->stride, 1, c->d_lpart, 1, 0);
     k_lineprod2<<<N_LINES, WAVE, 0, st>>>(c->d_lpart, 1, c->d_L);
@@ -2108,8 +2039,7 @@ static int aggv_slice(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* msgs,
     if (total) HIPCHK(hipMemcpyAsync(d_msgs, msgs, total, hipMemcpyHostToDevice, st));
     uint32_t n32 = (uint32_t)n, nb = (n32 + WAVE - 1) / WAVE, npairs = n32 + (with_sig ? 1u : 0u), nb1 = (npairs + WAVE - 1) / WAVE;
     HIPCHK(hipEventRecord(c->ev[0], st));
-    bool all32 = c->xmd.valid;                      // every message 32 bytes long (signing roots): the batch path's hashing kernels
-    for (size_t i = 0; i < n && all32; i++) all32 = offs[i + 1] - offs[i] == 32;
+    const bool all32 = c->xmd.valid && plan::aggv_all32(offs, n);       // every message 32 bytes long (signing roots): the batch path's hashing kernels
     if (all32) {
         // k_hash_map reads the message at offset 96 of a 320-byte record: the 32-byte messages are spread to that layout on the device
         // side of the staging buffer (keys | offsets | messages are packed at its start; the records go to d_comp)
@@ -2122,7 +2052,7 @@ static int aggv_slice(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* msgs,
     HIPCHK(hipEventRecord(c->ev[1], st));
     k_aggv_setup<<<nb1, WAVE, 0, st>>>(d_pk, n32, with_sig ? 1 : 0, reinterpret_cast<const uint32_t*>(c->d_msg + 4096), c->d_H, c->d_P, c->stride, c->d_flags);
     HIPCHK(hipEventRecord(c->ev[2], st));
-    launch_lines(c, npairs, 0, st);
+    launch_lines(c, plan::lines_for(c->slots, c->coop, npairs, 0), st);
     HIPCHK(hipEventRecord(c->ev[3], st));
     {
         int rcp = enqueue_line_products(c, npairs, st, nullptr);
@@ -2152,20 +2082,12 @@ static int aggregate_verify_impl(mi355_bls_ctx* c, const void* pks, const uint8_
     } else {
         HIPCHK(hipMemcpyAsync(c->d_msg + 4096, sig, 192, hipMemcpyHostToDevice, st));
     }
-    const size_t budget = c->cap * 320;
     std::vector<uint32_t> offs;
     size_t a = 0;
     uint32_t slice = 0;
     bool single = true;
     while (a < n) {
-        // greedy slice [a, b): at most cap pairs, staged bytes within d_sets
-        size_t b = a, bytes = 4;
-        while (b < n && b - a < c->cap) {
-            size_t add = 96 + 4 + (msg_offsets[b + 1] - msg_offsets[b]);
-            if (bytes + add > budget) break;
-            bytes += add;
-            b++;
-        }
+        const size_t b = plan::aggv_cut(msg_offsets, n, a, c->cap);      // greedy slice [a, b): at most cap pairs, staged bytes within d_sets
         if (b == a) {
             g_err = "one message does not fit the context's staging buffer";
             return MI355_BLS_ERR_CAPACITY;

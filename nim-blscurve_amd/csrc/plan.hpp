@@ -1,0 +1,214 @@
+// The host layer's launch plans: which kernel, what grid, which stream a stage of a call takes, as plain integer functions of the
+// context's numbers (wave slots, capacity, mode) and the call's size.  host_api.inc asks for a plan and launches what it says; the CPU
+// tests call the same functions through tests/host_emu/plan.cpp.  No device type, no context: numbers in, small structs out.
+#ifndef BLS_PLAN_HPP
+#define BLS_PLAN_HPP
+#include <cstddef>
+#include <cstdint>
+
+namespace plan {
+
+constexpr uint32_t WAVE = 64;                // lanes of a wavefront: the workgroup of every one-lane-per-item kernel
+constexpr uint32_t N_LINES = 68;             // steps of the Miller loop (pairing.hpp)
+constexpr uint32_t SIG_SLOTS_MAX = 2048;     // 8 windows x 256 digits: the most extra pairs a slice has
+static_assert(((64u / 8) << 8) == SIG_SLOTS_MAX, "the buckets of the 8-bit digits");
+constexpr size_t SIG_WIDE_MIN = 40000;       // from here 8-bit digits (2048 extra pairs, 8 additions per tuple) beat 4-bit ones (256, 15)
+constexpr uint32_t FORK_ITEMS_PER_SLOT = 16; // [r]PK and the signature side on the two fork streams up to 16 sets per slot, the signature side's stream alone beyond
+
+// Latency mode: how many messages / pairs the lane-team engine (16 lanes each, csrc/teamvm.hpp) takes before one lane each is the faster form.
+// The engine spends ~4 x the instructions of the one-lane kernels per item (sixteen lanes run the same ~700-instruction round for one product
+// each), so it wins exactly while the device has SIMDs to spare: `slots` = one wave per SIMD = 4 x slots items per 0.63 ms (clearing) / 0.33 ms
+// (lines), against 2.9 ms / 1.9 ms per round of one-lane waves whatever their number.  Measured crossovers: profiles/r06_ab/team_sweep.txt.
+constexpr uint32_t TEAM_CLEAR_ITEMS_PER_SLOT = 11, TEAM_LINES_ITEMS_PER_SLOT = 18;
+inline uint32_t team_clear_max(uint32_t slots) { return slots * TEAM_CLEAR_ITEMS_PER_SLOT; }
+inline uint32_t team_lines_max(uint32_t slots) { return slots * TEAM_LINES_ITEMS_PER_SLOT; }
+
+// waves of a kernel that gives every item one lane
+inline uint32_t waves_for(uint32_t count) { return (count + WAVE - 1) / WAVE; }
+
+// Which executor of the lane-team engine takes `count` items, the same ladder for clearing and Miller lines:
+//   ROWS   the row executor (four waves per item) while the grid stays well inside one wave per SIMD;
+//   ROWS2  the same at two workgroups per CU up to twice that: 240 sets 3.10 -> 2.72 ms, 400 3.15 -> 3.01, 448 3.16 -> 3.10
+//          (profiles/r06_ab/ab_rows2.txt);
+//   SPREAD one wave (four items) per SIMD while the waves fit the device's slots;
+//   WIDE   the plain grid beyond.
+enum team_form { TEAM_ROWS, TEAM_ROWS2, TEAM_SPREAD, TEAM_WIDE };
+inline uint32_t team_rows_max(uint32_t slots) { return (slots - slots / 8) / 4; }      // room left for the fork streams' waves
+inline team_form team_form_for(uint32_t slots, uint32_t count) {
+    const uint32_t rows_max = team_rows_max(slots);
+    if (count <= rows_max) return TEAM_ROWS;
+    if (count <= 2 * rows_max) return TEAM_ROWS2;
+    return (count + 3) / 4 <= slots ? TEAM_SPREAD : TEAM_WIDE;
+}
+
+// A stage that the engine (`team`: in `form`, `grid` workgroups of 256 lanes for the row forms, of one wave otherwise) or the one-lane
+// kernel (`grid` waves) takes.
+struct stage {
+    bool team;
+    team_form form;
+    uint32_t grid;
+};
+inline stage team_stage(uint32_t slots, uint32_t count) {
+    const team_form f = team_form_for(slots, count);
+    return {true, f, f == TEAM_ROWS || f == TEAM_ROWS2 ? count : (count + 3) / 4};
+}
+inline stage one_lane_stage(uint32_t count) { return {false, TEAM_WIDE, waves_for(count)}; }
+
+// 320-byte records -> the two mapped points of every message (two lanes per message)
+enum hash_map_form { HASH_MAP_ROWS, HASH_MAP_SPREAD, HASH_MAP_PLAIN };
+struct hash_map_plan {
+    hash_map_form form;
+    uint32_t grid;
+};
+inline hash_map_plan hash_map_for(uint32_t slots, bool coop, uint32_t n32) {
+    const uint32_t waves = (2 * n32 + WAVE - 1) / WAVE;
+    if (coop && (2 * n32 + 3) / 4 <= slots - slots / 8) return {HASH_MAP_ROWS, (2 * n32 + 3) / 4};      // a pair per row (room left for the fork streams' waves: a second round would double the time)
+    if (coop && waves <= slots) return {HASH_MAP_SPREAD, waves};                                         // one wave per SIMD
+    return {HASH_MAP_PLAIN, waves};
+}
+
+// cofactor clearing of n32 mapped point pairs: the engine (then k_clear_fix) or k_hash_clear
+inline stage clear_for(uint32_t slots, bool coop, uint32_t n32) {
+    return coop && n32 <= team_clear_max(slots) ? team_stage(slots, n32) : one_lane_stage(n32);
+}
+
+// Miller lines of pairs 0 .. npairs-1 (the last `extra` of them are the bucket pairs of the signature side): the engine while that does
+// not take more waves than the device has slots.  Whole-device batches in latency mode (coop): the tuple pairs fill the device exactly, so the
+// few extra pairs would be a second round of waves that takes as long as the first (2.2 ms at 3 % occupancy); on the engine they take
+// ~1 ms instead.  In throughput mode (several batches in flight) that second round overlaps other batches' kernels and one lane per
+// pair is the cheaper form.
+// -> pairs [0, main_pairs) as `main` says, then pairs [main_pairs, main_pairs + extra_pairs) on the engine as `extra` says (none: extra_pairs = 0)
+struct lines_plan {
+    uint32_t main_pairs;
+    stage main;
+    uint32_t extra_pairs;
+    stage extra;
+};
+inline lines_plan lines_for(uint32_t slots, bool coop, uint32_t npairs, uint32_t extra) {
+    if (coop && npairs <= team_lines_max(slots)) return {npairs, team_stage(slots, npairs), 0, {}};
+    if (coop && extra && extra < npairs && extra <= team_lines_max(slots) &&
+        (npairs + WAVE - 1) / WAVE > slots * (((npairs - extra + WAVE - 1) / WAVE + slots - 1) / slots)) {
+        // the extra pairs would start one more round of waves: a team of lanes each instead
+        const uint32_t main_pairs = npairs - extra;
+        return {main_pairs, one_lane_stage(main_pairs), extra, team_stage(slots, extra)};
+    }
+    return {npairs, one_lane_stage(npairs), 0, {}};
+}
+
+// One batch slice of n sets (what run_pairs follows).  The three producers of Miller pairs are independent until the lines: hashing,
+// [r]PK and the signature side (bucket fold).
+//   SIDE_NONE      everything on the caller's stream (throughput mode, or no fork stream could be created);
+//   SIDE_FORK      a small batch in latency mode: [r]PK on a fork stream of its own, the signature side on the other, beside the hashing;
+//   SIDE_FORK_SIG  a whole-device batch of one caller: only the signature side (and its extra pairs' lines) beside the hashing.
+enum side_mode { SIDE_NONE, SIDE_FORK, SIDE_FORK_SIG };
+enum stream_role { STREAM_CALLER, STREAM_SIDE, STREAM_SIDE2 };
+struct slice_plan {
+    uint32_t nb;                       // waves of the one-lane-per-set kernels ([r]PK, the signature side's conversion, histogram, scatter)
+    hash_map_plan hash_map;
+    stage clear;
+    bool pkmul_spread;                 // k_pkmul_spread (one wave per SIMD) | k_pkmul
+    side_mode side;
+    stream_role pk_stream, sig_stream; // [r]PK; the signature side (and the extra pairs' lines where they run apart)
+    uint32_t cw, nwin, total;          // the signature side's digit width, its windows, its buckets = the extra Miller pairs
+    uint32_t lshift, bucket_grid;      // k_sig_bucket: 2^lshift lanes per bucket
+    bool extra_apart;                  // the extra pairs' lines follow the signature side on its stream; the caller's stream walks the tuple pairs alone
+    stage extra_lines;                 //   their form there
+    lines_plan lines;                  // the caller's stream: the tuple pairs (extra_apart) or all n + total pairs
+};
+inline slice_plan slice_for(uint32_t slots, bool coop, bool have_side, size_t n) {
+    slice_plan p{};
+    const uint32_t n32 = (uint32_t)n;
+    p.nb = waves_for(n32);
+    const bool fork = have_side && n32 <= FORK_ITEMS_PER_SLOT * slots;      // pk + signature side beside the hashing
+    const bool fork_sig = !fork && have_side;
+    p.side = fork ? SIDE_FORK : fork_sig ? SIDE_FORK_SIG : SIDE_NONE;
+    p.pk_stream = fork ? STREAM_SIDE2 : STREAM_CALLER;
+    p.sig_stream = (fork || fork_sig) ? STREAM_SIDE : STREAM_CALLER;
+    p.hash_map = hash_map_for(slots, coop, n32);
+    p.clear = clear_for(slots, coop, n32);
+    p.pkmul_spread = coop && p.nb <= slots;
+    // the signature side as a bucket fold: `total` extra Miller pairs n .. n + total - 1 (every batch size: for a handful of tuples the
+    // 256 nearly empty buckets are still cheaper than one 64-bit G2 multiplication per tuple)
+    p.cw = n >= SIG_WIDE_MIN ? 8 : 4, p.nwin = 64 / p.cw, p.total = p.nwin << p.cw;
+    uint32_t per = n32 >> p.cw, lshift = 0;                     // expected entries per bucket; ~16 per lane
+    const uint32_t per_lane_min = coop ? 16u : 64u;             // throughput mode: fewer, longer lanes (the fold of a bucket's lanes is pure overhead)
+    while (lshift < 6 && (per >> (lshift + 1)) >= per_lane_min) lshift++;
+    // small batches leave most of the device idle: more lanes per bucket (down to ~2 entries per lane) shorten the kernel
+    while (lshift < 6 && ((p.total << (lshift + 1)) <= 16 * slots) && (per >> (lshift + 1)) >= 2) lshift++;
+    p.lshift = lshift;
+    p.bucket_grid = ((p.total << lshift) + WAVE - 1) / WAVE;
+    // the extra pairs' walk beside the hashing, on the engine where they fit it (one blocking 65 536-set call: 12.7 -> 12.0 ms); a forked
+    // small batch whose extra pairs do not fit the engine leaves them to the caller's stream
+    p.extra_apart = fork_sig || (fork && p.total <= team_lines_max(slots));
+    p.extra_lines = p.total <= team_lines_max(slots) ? team_stage(slots, p.total) : one_lane_stage(p.total);
+    p.lines = p.extra_apart ? lines_for(slots, coop, n32, 0) : lines_for(slots, coop, n32 + p.total, p.total);
+    return p;
+}
+
+// The per-step products of the Miller lines of pairs 0 .. npairs-1: k_lineprod's grid (N_LINES x nblk, m pairs per lane), then the fold of
+// the 64 x nblk partial products per step.  `fold` (latency mode, or a call alone on the device): k_fold on the lane-cooperative engine,
+// two levels of about sqrt(live) dependent products each - nb1 blocks of `per`, then the nb1 block results (one caller, 65 536 tuples:
+// 1.8 -> 0.35 ms); otherwise k_lineprod2's 68 waves, 15 sequential Fp12 products per lane + one shuffle tree (least total work).
+struct lineprod_plan {
+    uint32_t nblk, m;
+    int per_lane;                      // 1: the assembly loop (32-bit byte offsets inside one step's 24 planes); 2: the compiled loop
+    uint32_t live, per, nb1;           // fold only
+};
+inline lineprod_plan lineprod_for(uint32_t slots, uint32_t nblk_cap, uint32_t stride, uint32_t npairs, bool fold) {
+    lineprod_plan p{};
+    uint32_t nblk = slots / N_LINES;
+    if (nblk < 1) nblk = 1;
+    if (nblk > nblk_cap) nblk = nblk_cap;
+    uint32_t m = (npairs + WAVE * nblk - 1) / (WAVE * nblk);
+    if (m < 1) m = 1;
+    nblk = (npairs + WAVE * m - 1) / (WAVE * m);
+    p.nblk = nblk, p.m = m;
+    p.per_lane = (uint64_t)stride * 16 * 24 + (uint64_t)npairs * 16 < (1ull << 32) ? 1 : 2;
+    if (fold) {
+        size_t first_last = (size_t)(nblk - 1) * WAVE * m;             // lanes past the last pair hold 1: not folded
+        p.live = (nblk - 1) * WAVE + (npairs - first_last < WAVE ? (uint32_t)(npairs - first_last) : WAVE);
+        p.per = 1;
+        while (p.per * p.per < p.live) p.per++;
+        p.nb1 = (p.live + p.per - 1) / p.per;
+    }
+    return p;
+}
+
+// aggregateVerify's greedy slice [a, b): at most cap pairs, and the staged bytes (n + 1 offsets | per pair a 96-byte key and the message)
+// within the cap * 320 bytes of the staging buffer.  b == a: the message at `a` alone does not fit.
+inline size_t aggv_cut(const uint32_t* msg_offsets, size_t n, size_t a, size_t cap) {
+    const size_t budget = cap * 320;
+    size_t b = a, bytes = 4;
+    while (b < n && b - a < cap) {
+        size_t add = 96 + 4 + (msg_offsets[b + 1] - msg_offsets[b]);
+        if (bytes + add > budget) break;
+        bytes += add;
+        b++;
+    }
+    return b;
+}
+// every message of the slice 32 bytes long (signing roots): the batch path's hashing kernels can take it
+inline bool aggv_all32(const uint32_t* offs, size_t n) {
+    bool all32 = true;
+    for (size_t i = 0; i < n && all32; i++) all32 = offs[i + 1] - offs[i] == 32;
+    return all32;
+}
+
+// A shard of n tuples on a workspace of `cap`: ceil(n / cap) balanced slices (never a sliver at the end), pipelined over up to three
+// workspaces - slice i of nslices on workspace (nslices - 1 - i) mod nl, so that the last slice runs on workspace 0, the caller's own.
+inline size_t shard_nslices(size_t n, size_t cap) { return (n + cap - 1) / cap; }
+inline int shard_workspaces(size_t nslices) { return nslices >= 3 ? 3 : 2; }
+inline size_t shard_slice_count(size_t n, size_t done, size_t nslices, uint32_t slice) {
+    size_t left = nslices - slice;
+    return (n - done + left - 1) / left;
+}
+inline int shard_workspace_of(size_t nslices, uint32_t slice, int nl) { return (int)((nslices - 1 - slice) % (size_t)nl); }
+
+// chunk of the parallel_chunks partition (parallel_chunks.nim:42-66) that tuple t of n_total falls into, B chunks
+inline uint32_t chunk_of_tuple(size_t n_total, uint32_t B, size_t t) {
+    size_t base = n_total / B, rem = n_total % B, cut = (base + 1) * rem;
+    return (uint32_t)(t < cut ? t / (base + 1) : rem + (t - cut) / base);
+}
+
+}  // namespace plan
+#endif

@@ -1,5 +1,5 @@
-"""The Python restatement of aggregate_verify_impl's slicing (tests/util.py aggv_slice_plan) against the lines of csrc/host_api.inc it restates, and
-the plans tests/test_gpu_aggv_varlen.py relies on: a bound moved in the product without the mirror fails here, instead of leaving the GPU test to
+"""aggregateVerify's slicing as the product's own code decides it (csrc/plan.hpp aggv_cut / aggv_all32, through tests/util.py aggv_slice_plan), pinned
+by literal plans, and the plans tests/test_gpu_aggv_varlen.py relies on: a bound moved in the product fails here, instead of leaving the GPU test to
 pass without the byte-budget cut or without slices on both hashing paths.  Also the rule of tests/util.py varlen_case and its fixture."""
 import hashlib
 import os
@@ -9,40 +9,17 @@ from util import (VARLEN_CASES, VARLEN_LONG, VARLEN_PAD_EDGES, VARLEN_PREFIXES, 
                   golden, varlen_case, varlen_defect, varlen_lengths)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "nim-blscurve_amd", "csrc", "host_api.inc")
 
 
-def _norm(s):
-    return re.sub(r"\s+", " ", s)
-
-
-def _function(src, head):
-    a = src.index(head)
-    return _norm(src[a:src.index("\n}\n", a)])
-
-
-def test_slicing_matches_the_product():
-    src = open(SRC).read()
-    f = _function(src, "static int aggregate_verify_impl(")
-    assert "const size_t budget = c->cap * 320;" in f
-    assert "size_t b = a, bytes = 4;" in f
-    assert "while (b < n && b - a < c->cap) {" in f
-    assert "size_t add = 96 + 4 + (msg_offsets[b + 1] - msg_offsets[b]);" in f
-    assert "if (bytes + add > budget) break;" in f
-    assert "if (b == a) {" in f and "return MI355_BLS_ERR_CAPACITY;" in f
-    assert "for (size_t i = a; i <= b; i++) offs[i - a] = msg_offsets[i] - msg_offsets[a];" in f
-    assert "aggv_slice(c, (const uint8_t*)pks + 96 * a, msgs + msg_offsets[a], offs.data(), b - a, last, single, st);" in f
-    assert "c->cap = max_sets;" in src and "ALLOC(c->d_sets, max_sets * 320);" in src
-    s = _function(src, "static int aggv_slice(")
-    # the staged layout the budget counts: keys | n + 1 offsets | messages; all32 decided per slice, from the slice's own offsets
-    assert "uint32_t* d_off = reinterpret_cast<uint32_t*>(c->d_sets + n * 96);" in s
-    assert "uint8_t* d_msgs = c->d_sets + n * 96 + (n + 1) * 4;" in s
-    assert "bool all32 = c->xmd.valid;" in s
-    assert "for (size_t i = 0; i < n && all32; i++) all32 = offs[i + 1] - offs[i] == 32;" in s
-    assert "k_aggv_records<<<nb, WAVE, 0, st>>>(d_msgs, n32, c->d_comp);" in s
-    assert "k_hash_var<<<nb, WAVE, 0, st>>>(d_msgs, d_off, n32, c->dst, c->d_H, c->stride);" in s
-    hdr = _norm(open(os.path.join(ROOT, "include", "blscurve_mi355x.h")).read().replace("\n * ", " "))
+def test_one_message_limit():
+    """what the header promises is what the compiled cut does: a lone message of cap * 320 - 104 bytes fits, one byte more is refused"""
+    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "blscurve_mi355x.h")).read().replace("\n * ", " "))
     assert "A single message must fit the context's staging buffer (max_sets * 320 - 104 bytes), else MI355_BLS_ERR_CAPACITY." in hdr
+    for cap in (1, 2, 64, 1000, 65536):
+        limit = cap * 320 - 104
+        assert aggv_slice_plan([limit], cap) == [(0, 1, "end", False)] and aggv_slice_plan([limit + 1], cap) is None
+        assert aggv_slice_plan([0, limit, 0], cap) == [(0, 1, "bytes" if cap > 1 else "pairs", False), (1, 2, "bytes" if cap > 1 else "pairs", False), (2, 3, "end", False)]
+        assert aggv_one_slice_cap([limit]) == cap and aggv_one_slice_cap([limit + 1]) == cap + 1
 
 
 def test_restated_cut():

@@ -1,8 +1,10 @@
 """Shared helpers for tests: fixture loading and canonicalisation of projective outputs."""
 import ctypes
 import hashlib
+import itertools
 import json
 import os
+import subprocess
 
 import bls12381_py as o
 
@@ -72,48 +74,92 @@ def fp12_to_bytes(a):
     return b"".join(o.fp_to_mont_bytes(c[0]) + o.fp_to_mont_bytes(c[1]) for c in t)
 
 
-# ---- the latency-mode plan of one blocking batch call (csrc/host_api.inc), restated for the tests that must sit on its boundaries.
-# S = the context's wave slots (4 x CU count).  test_latency_plan_mirror.py reads these constants and bounds out of host_api.inc.
-TEAM_CLEAR_ITEMS_PER_SLOT = 11      # the lane-team engine clears up to 11 S messages, k_hash_clear beyond (launch_hash_clear)
-TEAM_LINES_ITEMS_PER_SLOT = 18      # the engine walks up to 18 S pairs' Miller lines, k_lines beyond (launch_lines)
-SIG_WIDE_MIN = 40000                # the signature side's 8-bit digits (2048 extra pairs) from here, 4-bit ones (256) below
-FORK_ITEMS_PER_SLOT = 16            # run_pairs: `fork` up to 16 S sets, `fork_sig` beyond
-WAVE = 64
+# ---- the host layer's launch plans.  csrc/plan.hpp decides which kernel, grid and stream every stage of a call takes; it is plain C++, and
+# tests/host_emu/plan.cpp compiles it for the host.  The tests that must sit on the plan's boundaries ask that library, i.e. the product's own
+# code, where they are: nothing below restates a rule.  S = the context's wave slots (4 x CU count).
+_PLAN = None
+_PLAN_CONSTANTS = ("WAVE", "N_LINES", "SIG_SLOTS_MAX", "SIG_WIDE_MIN", "FORK_ITEMS_PER_SLOT", "TEAM_CLEAR_ITEMS_PER_SLOT", "TEAM_LINES_ITEMS_PER_SLOT")
+TEAM_FORMS = ("rows", "rows2", "spread", "wide")
+_STAGE = ("team", "form", "grid")
+_LINES = ("main_pairs",) + tuple("main_" + f for f in _STAGE) + ("extra_pairs",) + tuple("extra_" + f for f in _STAGE)
+_SLICE = (("nb", "hash_map", "hash_map_grid") + tuple("clear_" + f for f in _STAGE) + ("pkmul_spread", "side", "pk_stream", "sig_stream", "cw", "nwin",
+          "total", "lshift", "bucket_grid", "extra_apart") + tuple("extra_lines_" + f for f in _STAGE) + tuple("lines_" + f for f in _LINES))
+_LINEPROD = ("nblk", "m", "per_lane", "live", "per", "nb1")
+
+
+def plan_lib():
+    """csrc/plan.hpp as a ctypes library (built on first use, well under a second)"""
+    global _PLAN
+    if _PLAN is None:
+        here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emu")
+        subprocess.check_call([os.path.join(here, "build_plan.sh")])
+        L = ctypes.CDLL(os.path.join(here, "_build", "libplan.so"))
+        u32, sz, i, out = ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)
+        for name, res, args in (("plan_constants", None, (out,)), ("plan_team_rows_max", u32, (u32,)), ("plan_team_lines_max", u32, (u32,)),
+                                ("plan_team_form", u32, (u32, u32)), ("plan_lines", None, (u32, i, u32, u32, out)),
+                                ("plan_slice", None, (u32, i, i, sz, out)), ("plan_lineprod", None, (u32, u32, u32, u32, i, out)),
+                                ("plan_aggv_cut", sz, (out, sz, sz, sz)), ("plan_aggv_all32", i, (out, sz)), ("plan_shard_nslices", sz, (sz, sz)),
+                                ("plan_shard_workspaces", i, (sz,)), ("plan_shard_slice_count", sz, (sz, sz, sz, u32)),
+                                ("plan_shard_workspace_of", i, (sz, u32, i)), ("plan_chunk_of_tuple", u32, (sz, u32, sz))):
+            getattr(L, name).restype, getattr(L, name).argtypes = res, args
+        _PLAN = L
+    return _PLAN
+
+
+def _plan_call(fn, fields, *args):
+    """fn(*args, out) -> {field: word}"""
+    out = (ctypes.c_uint32 * len(fields))()
+    getattr(plan_lib(), fn)(*args, out)
+    return dict(zip(fields, out))
+
+
+def __getattr__(name):
+    """the plan's constants (TEAM_CLEAR_ITEMS_PER_SLOT, SIG_WIDE_MIN, ...), read from the compiled plan"""
+    if name in _PLAN_CONSTANTS:
+        return _plan_call("plan_constants", _PLAN_CONSTANTS)[name]
+    raise AttributeError(name)
+
+
+def slice_plan(n, S, coop=True, have_side=True):
+    """plan.hpp slice_for: everything run_pairs follows for a slice of n sets"""
+    return _plan_call("plan_slice", _SLICE, S, int(coop), int(have_side), n)
+
+
+def lines_plan(npairs, extra, S, coop=True):
+    """plan.hpp lines_for"""
+    return _plan_call("plan_lines", _LINES, S, int(coop), npairs, extra)
+
+
+def lineprod_plan(S, nblk_cap, stride, npairs, fold):
+    """plan.hpp lineprod_for"""
+    return _plan_call("plan_lineprod", _LINEPROD, S, nblk_cap, stride, npairs, int(fold))
 
 
 def rows_max(S):
-    """team_form_for: the row executor's bound (room left for the fork streams' waves)"""
-    return (S - S // 8) // 4
+    """the row executor's bound"""
+    return plan_lib().plan_team_rows_max(S)
 
 
 def team_form(count, S):
-    """team_form_for: which form of an engine kernel (clearing or Miller lines) takes `count` items"""
-    if count <= rows_max(S):
-        return "rows"
-    if count <= 2 * rows_max(S):
-        return "rows2"
-    return "spread" if (count + 3) // 4 <= S else "wide"
+    """which form of an engine kernel (clearing or Miller lines) takes `count` items"""
+    return TEAM_FORMS[plan_lib().plan_team_form(S, count)]
+
+
+def _stage_name(p, stage):
+    return "team_" + TEAM_FORMS[p[stage + "_form"]] if p[stage + "_team"] else "one_lane"
 
 
 def latency_plan(n, S):
-    """The executors a latency-mode (cooperative) context with side streams picks for a blocking call of n sets."""
-    if (2 * n + 3) // 4 <= S - S // 8:
-        hash_map = "rows"                                     # k_hash_map_rows
-    elif (2 * n + WAVE - 1) // WAVE <= S:
-        hash_map = "spread"                                   # k_hash_map_spread
-    else:
-        hash_map = "plain"                                    # k_hash_map
-    clear = "team_" + team_form(n, S) if n <= TEAM_CLEAR_ITEMS_PER_SLOT * S else "one_lane"      # ... + k_clear_fix | k_hash_clear
-    lines = "team_" + team_form(n, S) if n <= TEAM_LINES_ITEMS_PER_SLOT * S else "one_lane"      # the tuple pairs' lines | k_lines
-    side = "fork" if n <= FORK_ITEMS_PER_SLOT * S else "fork_sig"
-    extra = 2048 if n >= SIG_WIDE_MIN else 256
-    return {"hash_map": hash_map, "clear": clear, "side": side, "lines": lines, "extra_pairs": extra}
+    """The executors a latency-mode (cooperative) context with side streams picks for a blocking call of n sets (`lines`: of the tuple pairs)."""
+    p = slice_plan(n, S)
+    return {"hash_map": ("rows", "spread", "plain")[p["hash_map"]], "clear": _stage_name(p, "clear"), "side": ("none", "fork", "fork_sig")[p["side"]],
+            "lines": _stage_name(p, "lines_main"), "extra_pairs": p["total"]}
 
 
 def latency_hand_overs(S):
-    """(stage, t): the plan changes `stage`'s executor between t and t + 1 sets - the hand-overs of the 4 S .. 32 S range."""
-    return [("clear", 4 * S), ("clear", TEAM_CLEAR_ITEMS_PER_SLOT * S), ("side", FORK_ITEMS_PER_SLOT * S),
-            ("lines", 4 * S), ("lines", TEAM_LINES_ITEMS_PER_SLOT * S), ("hash_map", 32 * S)]
+    """(stage, t): the plan changes `stage`'s executor between t and t + 1 sets - the hand-overs of the 4 S .. 32 S range, stage by stage."""
+    plans = [latency_plan(n, S) for n in range(4 * S, 32 * S + 2)]
+    return [(stage, 4 * S + i) for stage in ("clear", "side", "lines", "hash_map") for i in range(len(plans) - 1) if plans[i][stage] != plans[i + 1][stage]]
 
 
 def apply_defect(rec, d):
@@ -244,41 +290,39 @@ def varlen_case(name):
     return sks, msgs
 
 
-# ---- aggregate_verify_impl's greedy cut (csrc/host_api.inc), restated: a slice takes pairs while it holds fewer than `cap` of them and
-# 4 + sum(96 + 4 + len) stays within cap * 320 staged bytes; a slice whose messages are all 32 bytes long takes the batch path's hashing kernels,
-# any other k_hash_var.  tests/test_aggv_plan_mirror.py ties this to the source.
-AGGV_PAIR_BYTES = 96 + 4
-AGGV_SET_BYTES = 320
+# ---- aggregateVerify's greedy cut (plan.hpp aggv_cut, aggv_all32): a slice takes pairs while it holds fewer than `cap` of them and the staged
+# bytes stay within the context's buffer; a slice whose messages are all 32 bytes long takes the batch path's hashing kernels, any other k_hash_var.
+def _offsets(lengths):
+    return (ctypes.c_uint32 * (len(lengths) + 1))(*itertools.accumulate(lengths, initial=0))
 
 
 def aggv_slice_plan(lengths, cap):
     """-> [(a, b, cut, all32)]: slice [a, b), cut = "pairs" | "bytes" | "end", or None where one message does not fit (MI355_BLS_ERR_CAPACITY)"""
-    budget = cap * AGGV_SET_BYTES
-    n, a, plan = len(lengths), 0, []
+    L, n, offs = plan_lib(), len(lengths), _offsets(lengths)
+    a, plan = 0, []
     while a < n:
-        b, used = a, 4
-        cut = "end"
-        while b < n:
-            if b - a >= cap:
-                cut = "pairs"
-                break
-            add = AGGV_PAIR_BYTES + lengths[b]
-            if used + add > budget:
-                cut = "bytes"
-                break
-            used += add
-            b += 1
+        b = L.plan_aggv_cut(offs, n, a, cap)
         if b == a:
             return None
-        plan.append((a, b, cut, all(x == 32 for x in lengths[a:b])))
+        cut = "end" if b == n else "pairs" if b - a >= cap else "bytes"
+        plan.append((a, b, cut, bool(L.plan_aggv_all32(ctypes.cast(ctypes.byref(offs, 4 * a), ctypes.POINTER(ctypes.c_uint32)), b - a))))
         a = b
     return plan
 
 
 def aggv_one_slice_cap(lengths):
-    """the smallest context that takes the whole input in one slice"""
-    need = 4 + sum(AGGV_PAIR_BYTES + x for x in lengths)
-    return max(len(lengths), -(-need // AGGV_SET_BYTES))
+    """the smallest context that takes the whole input in one slice (the cut is monotone in cap: bisection)"""
+    L, n, offs = plan_lib(), len(lengths), _offsets(lengths)
+    lo = hi = max(n, 1)
+    while L.plan_aggv_cut(offs, n, 0, hi) != n:
+        lo, hi = hi + 1, 2 * hi
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if L.plan_aggv_cut(offs, n, 0, mid) == n:
+            hi = mid
+        else:
+            lo = mid + 1
+    return hi
 
 
 def varlen_defect(msgs, d):
