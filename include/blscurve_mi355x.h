@@ -131,6 +131,22 @@ int mi355_bls_batch_verify_many(mi355_bls_ctx* ctx, const void* sets, const size
 int mi355_bls_batch_verify_many_device(mi355_bls_ctx* ctx, const void* d_sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
                                        void* stream);
 
+/* Per-set verdicts in one device pass: verdicts[i] = verify(pk_i, msg_i, sig_i) (bls_sig_min_pubkey.nim:108-125 ->
+ * coreVerifyNoGroupCheck, blst_min_pubkey_sig_core.nim:269-297) for every 320-byte SignatureSet record of the input - what a host does
+ * set by set after a batch has failed, to find the culprits.  No blinding and no random bytes: verdict i depends on set i alone, not on
+ * n, on its position, on the other sets or on num_threads; nothing is sticky.  Infinity rules as BLST's: an infinity public key gives 0;
+ * an infinity signature contributes no pair (0 for a valid key).  Preconditions as the reference's: points decoded and group-checked.
+ * Any n (larger inputs run in slices).  Returns 1 when every set verified, 0 otherwise (n == 0: 0, nothing written), negative on a
+ * runtime failure.  verdicts: n bytes, host memory.  Synchronous. */
+int mi355_bls_verify_each(mi355_bls_ctx* ctx, const void* sets, size_t n, uint8_t verdicts[]);
+int mi355_bls_verify_each_device(mi355_bls_ctx* ctx, const void* d_sets, size_t n, uint8_t verdicts[], void* stream);
+/* batchVerify first (mi355_bls_batch_verify with rnd); if it passes: 1 and every verdict 1, no per-set pass.  If it fails: one
+ * mi355_bls_verify_each pass, returns 0 with the per-set verdicts.
+ * COST: a passing call is the batch pass alone.  A failing call costs the batch pass PLUS the per-set pass, whose time does not depend on
+ * how many sets are bad: at 65 536 sets 12.7 ms + 72.3 ms (profiles/verify_each_bench.json; one device call per set: 141 s). */
+int mi355_bls_batch_verify_locate(mi355_bls_ctx* ctx, const void* sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[]);
+int mi355_bls_batch_verify_locate_device(mi355_bls_ctx* ctx, const void* d_sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[], void* stream);
+
 /* Multi-GPU sharding (replaces processSingleChunk + merge, bls_batch_verifier.nim:326-369).
  * The global batch of n_total sets is cut into B = min(n_total, num_threads) chunks by
  * parallel_chunks (parallel_chunks.nim:42-66); this call processes chunks [chunk_lo, chunk_hi),
@@ -398,6 +414,10 @@ int mi355_bls_debug_hash_to_g2(mi355_bls_ctx* ctx, const uint8_t* msg, size_t ms
  * host time in microseconds, counted from the start of the last mi355_bls_batch_verify_multi* call of this thread, at which each
  * device's shard was handed to its stream (the start skew between devices); returns the number of devices recorded. */
 int mi355_bls_debug_fail_next_enqueue(mi355_bls_ctx* ctx);
+/* mi355_bls_verify_each with the value of every set: gt_out gets n x 576 B, final_exp(f_i) as a blst_fp12 image (what
+ * mi355_bls_fetch_stage(4) is to the batch paths).  debug_verify_each_passes: per-set passes this context has made so far. */
+int mi355_bls_debug_verify_each_gt(mi355_bls_ctx* ctx, const void* sets, size_t n, uint8_t verdicts[], uint8_t* gt_out);
+int mi355_bls_debug_verify_each_passes(mi355_bls_ctx* ctx);
 size_t mi355_bls_debug_multi_enqueue_us(float* out, size_t cap);
 /* Batches submitted and not yet waited for, over all contexts of the process: what the library looks at when it chooses between the
  * low-latency and the least-work fold of the line products (a batch enqueued while this is zero has the chip to itself).  The tests

@@ -59,6 +59,12 @@ def lib():
         L.mi355_bls_batch_wait.argtypes = [vp]
         L.mi355_bls_batch_verify_many.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_char_p]
         L.mi355_bls_batch_verify_many_device.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_char_p, vp]
+        L.mi355_bls_verify_each.argtypes = [vp, vp, sz, ctypes.c_char_p]
+        L.mi355_bls_verify_each_device.argtypes = [vp, vp, sz, ctypes.c_char_p, vp]
+        L.mi355_bls_batch_verify_locate.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p]
+        L.mi355_bls_batch_verify_locate_device.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp]
+        L.mi355_bls_debug_verify_each_gt.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p]
+        L.mi355_bls_debug_verify_each_passes.argtypes = [vp]
         L.mi355_bls_batch_shard_device.argtypes = [vp, vp, sz, u32, u32, ctypes.c_char_p, vp, ctypes.c_char_p, ctypes.POINTER(i32)]
         L.mi355_bls_batch_shard_submit_device.argtypes = [vp, vp, sz, u32, u32, ctypes.c_char_p, vp, vp]
         L.mi355_bls_batch_shard_wait.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i32)]
@@ -350,6 +356,67 @@ def batchVerifyMany_device(cache, d_ptr, counts, secureRandomBytes_list, stream=
     out = ctypes.create_string_buffer(k)
     _check(lib().mi355_bls_batch_verify_many_device(cache._h, d_ptr, carr, rnds, k, out, stream))
     return [bool(v) for v in out.raw]
+
+
+def verifyEach(cache, input_):
+    """verify(publicKey, message, signature) (bls_sig_min_pubkey.nim:108-125) for every set of the input in one device pass
+    (mi355_bls_verify_each): -> [bool], one per set; no random bytes, set i's verdict depends on set i alone.  Empty input -> []."""
+    rec = _as_records(input_)
+    n = len(rec) // SIGSET_BYTES
+    if n == 0:
+        return []
+    out = ctypes.create_string_buffer(n)
+    _check(lib().mi355_bls_verify_each(cache._h, rec, n, out))
+    return [v == 1 for v in out.raw]
+
+
+def verifyEach_device(cache, d_ptr, n, stream=0):
+    """Same with the n records in device memory."""
+    if n == 0:
+        return []
+    out = ctypes.create_string_buffer(n)
+    _check(lib().mi355_bls_verify_each_device(cache._h, d_ptr, n, out, stream))
+    return [v == 1 for v in out.raw]
+
+
+def verifyEachValues(cache, input_):
+    """Test hook (mi355_bls_debug_verify_each_gt): -> ([bool], [576-byte blst_fp12 image of final_exp(f_i)])."""
+    rec = _as_records(input_)
+    n = len(rec) // SIGSET_BYTES
+    if n == 0:
+        return [], []
+    out, gt = ctypes.create_string_buffer(n), ctypes.create_string_buffer(n * 576)
+    _check(lib().mi355_bls_debug_verify_each_gt(cache._h, rec, n, out, gt))
+    raw = gt.raw                      # one copy: .raw copies the whole buffer at every access
+    return [v == 1 for v in out.raw], [raw[576 * i:576 * i + 576] for i in range(n)]
+
+
+def verifyEachPasses(cache):
+    """per-set passes the cache's context has made (test hook)"""
+    return _check(lib().mi355_bls_debug_verify_each_passes(cache._h))
+
+
+def batchVerifyLocate(cache, input_, secureRandomBytes):
+    """batchVerify first; a failing batch gets one verifyEach pass (mi355_bls_batch_verify_locate).
+    -> (ok, [bool] per set): (True, all True) for a passing batch, (False, the per-set verdicts) otherwise; empty input -> (False, [])."""
+    rec = _as_records(input_)
+    n = len(rec) // SIGSET_BYTES
+    rnd = _rnd32(secureRandomBytes)
+    if n == 0:
+        return False, []
+    out = ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_batch_verify_locate(cache._h, rec, n, rnd, out))
+    return bool(ok), [v == 1 for v in out.raw]
+
+
+def batchVerifyLocate_device(cache, d_ptr, n, secureRandomBytes, stream=0):
+    """Same with the n records in device memory."""
+    rnd = _rnd32(secureRandomBytes)
+    if n == 0:
+        return False, []
+    out = ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_batch_verify_locate_device(cache._h, d_ptr, n, rnd, out, stream))
+    return bool(ok), [v == 1 for v in out.raw]
 
 
 def batchVerifySerial(cache, input_, secureRandomBytes):

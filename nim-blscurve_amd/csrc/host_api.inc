@@ -108,6 +108,14 @@ struct mi355_bls_ctx {
     std::vector<uint32_t> av_offs;
     bool av_failed = false;
     msm_ws* msm2 = nullptr;          // a second one: combine runs its G1 and its G2 Pippenger side by side
+    // per-set verification (mi355_bls_verify_each): one verdict byte per set of the call, and the values of the debug hook; grown on demand
+    uint8_t* d_each_v = nullptr;
+    uint32_t* d_each_gt = nullptr;
+    size_t each_cap_v = 0, each_cap_gt = 0;
+    uint4 *d_each_H = nullptr, *d_each_P = nullptr, *d_each_lines = nullptr;      // pairs of a slice: 2 x cap, made at the first per-set call
+    uint32_t* d_each_work = nullptr; // the engine form's step values and results, one block per workgroup
+    size_t each_stride = 0;
+    int each_passes = 0;             // per-set passes made on this context (mi355_bls_debug_verify_each_passes)
 };
 
 constexpr size_t PKTAB_BYTES = 8 * 5 * 64;   // per set: 8 table entries x (X, Y, Z, Z^2, Z^3) x 64 bytes (tools/gen_pkmul_asm.py LANE_BYTES)
@@ -189,7 +197,7 @@ extern "C" void mi355_bls_ctx_destroy(mi355_bls_ctx* c) {
     if (c->ev_sl0) (void)hipEventDestroy(c->ev_sl0);
     for (auto& e : c->ev_blind)
         if (e) (void)hipEventDestroy(e);
-    void* bufs[] = {c->d_sets, c->d_rnd, c->d_r, c->d_H, c->d_M, c->d_P, c->d_lines, c->d_pktab, c->d_sig_pts, c->d_sig_sorted, c->d_sig_hist, c->d_sig_consts, c->d_agg, c->d_agg1, c->d_msg, c->d_comp, c->d_status, c->d_lpart, c->d_L, c->d_states, c->d_gt, c->d_gt_fv, c->d_carry, c->d_blob, c->d_flags, c->d_export};
+    void* bufs[] = {c->d_sets, c->d_rnd, c->d_r, c->d_H, c->d_M, c->d_P, c->d_lines, c->d_pktab, c->d_sig_pts, c->d_sig_sorted, c->d_sig_hist, c->d_sig_consts, c->d_agg, c->d_agg1, c->d_msg, c->d_comp, c->d_status, c->d_lpart, c->d_L, c->d_states, c->d_gt, c->d_gt_fv, c->d_carry, c->d_blob, c->d_flags, c->d_export, c->d_each_v, c->d_each_gt, c->d_each_H, c->d_each_P, c->d_each_lines, c->d_each_work};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (c->h_flags) (void)hipHostFree(c->h_flags);
@@ -867,6 +875,125 @@ static int verify_host(mi355_bls_ctx* c, const void* sets, size_t n, const uint8
 
 extern "C" int mi355_bls_batch_verify(mi355_bls_ctx* c, const void* sets, size_t n, const uint8_t rnd[32]) { return verify_host(c, sets, n, rnd, 0); }
 extern "C" int mi355_bls_batch_verify_serial(mi355_bls_ctx* c, const void* sets, size_t n, const uint8_t rnd[32]) { return verify_host(c, sets, n, rnd, 1); }
+
+// ------------------------------------------------------------------------------------------
+// Per-set verdicts: verify (bls_sig_min_pubkey.nim:108-125 -> coreVerifyNoGroupCheck, core :269-297) applied to every set of the input in
+// one device pass.  No blinding, no random bytes: verdict i is a function of set i alone.  Any n: slices of at most max_sets sets
+// follow each other on the caller's stream (hashing, pair setup, Miller lines of the 2 m pairs in a pair store of the path's own, the
+// per-set tail in the form plan::each_for names); the verdict bytes of all slices collect in d_each_v and come back in one copy.
+// ------------------------------------------------------------------------------------------
+static int each_reserve(mi355_bls_ctx* c, size_t n, bool want_gt) {
+    if (n > c->each_cap_v) {
+        if (c->d_each_v) (void)hipFree(c->d_each_v);
+        c->d_each_v = nullptr, c->each_cap_v = 0;
+        HIPCHK(hipMalloc((void**)&c->d_each_v, n + n / 4));
+        c->each_cap_v = n + n / 4;
+    }
+    if (!c->each_stride) {
+        const size_t st = plan::each_stride(c->cap);
+        HIPCHK(hipMalloc((void**)&c->d_each_H, st * 6 * 64));
+        HIPCHK(hipMalloc((void**)&c->d_each_P, st * 3 * 64));
+        HIPCHK(hipMalloc((void**)&c->d_each_lines, st * 6 * 64 * (size_t)N_LINES));
+        HIPCHK(hipMalloc((void**)&c->d_each_work, (size_t)plan::each_engine_grid_max(c->slots) * EACH_WORK_WORDS * 4));
+        c->each_stride = st;         // last: a failed allocation leaves the path unarmed (the buffers made so far are freed with the context)
+    }
+    if (want_gt && n > c->each_cap_gt) {
+        if (c->d_each_gt) (void)hipFree(c->d_each_gt);
+        c->d_each_gt = nullptr, c->each_cap_gt = 0;
+        HIPCHK(hipMalloc((void**)&c->d_each_gt, n * 576));
+        c->each_cap_gt = n;
+    }
+    return 0;
+}
+static int each_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, size_t n, uint8_t verdicts[], uint8_t* gt_out, hipStream_t st) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;                      // nothing verified, nothing written
+    if (!verdicts || (!d_src && !h_src)) return MI355_BLS_ERR_ARG;
+    if (c->pending) {
+        g_err = "a batch submitted on this context has not been waited for";
+        return MI355_BLS_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    int rc = each_reserve(c, n, gt_out != nullptr);
+    if (rc) return rc;
+    const size_t slice_max = plan::each_slice_max(c->cap), nslices = plan::each_nslices(n, slice_max);
+    // the stage launchers read the pair buffers from the context: this call's are the per-set path's own (2 x cap pairs)
+    struct pair_store {
+        mi355_bls_ctx* c;
+        uint4 *H, *P, *lines;
+        size_t stride;
+        ~pair_store() { c->d_H = H, c->d_P = P, c->d_lines = lines, c->stride = stride; }
+    } keep{c, c->d_H, c->d_P, c->d_lines, c->stride};
+    c->d_H = c->d_each_H, c->d_P = c->d_each_P, c->d_lines = c->d_each_lines, c->stride = c->each_stride;
+    HIPCHK(hipEventRecord(c->ev[0], st));
+    size_t done = 0;
+    for (uint32_t sl = 0; sl < nslices; sl++) {
+        const size_t m = plan::each_slice_count(n, done, nslices, sl);
+        const uint32_t m32 = (uint32_t)m;
+        const uint8_t* src = d_src ? d_src + done * 320 : c->d_sets;
+        if (!d_src) HIPCHK(hipMemcpyAsync(c->d_sets, h_src + done * 320, m * 320, hipMemcpyHostToDevice, st));      // behind the last slice's kernels on the same stream
+        const plan::each_plan p = plan::each_for(c->slots, c->coop, m32);
+        launch_hash_map(c, src, m32, st);                                  // H(msg_i) -> pair slot i, in the forms the batch path takes for m messages
+        launch_hash_clear(c, m32, st);
+        k_each_setup<<<p.setup_grid, WAVE, 0, st>>>(src, m32, c->d_H, c->d_P, c->stride);
+        launch_lines(c, p.lines, st);
+        uint8_t* dv = c->d_each_v + done;
+        uint32_t* dg = gt_out ? c->d_each_gt + done * 144 : nullptr;
+        if (!p.tail_engine) k_each_tail<<<p.tail_grid, WAVE, 0, st>>>(c->d_lines, c->stride, m32, src, dv, dg);
+        else if (c->coop) k_each_engine_rows<<<p.tail_grid, K_TAIL_THREADS, 0, st>>>(c->d_lines, c->stride, m32, src, dv, dg, c->d_each_work);
+        else k_each_engine<<<p.tail_grid, TAIL_THREADS, 0, st>>>(c->d_lines, c->stride, m32, src, dv, dg, c->d_each_work);
+        done += m;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev[1], st));
+    HIPCHK(hipMemcpyAsync(verdicts, c->d_each_v, n, hipMemcpyDeviceToHost, st));
+    if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, c->d_each_gt, n * 576, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->each_passes++;
+    c->last_n = 0;                             // d_H / d_P hold this call's pairs, not a batch's stages
+    c->sig_slots = 0;
+    c->agg_valid = false;
+    c->have_gt = false;
+    rc = collect_timings(c, 1);
+    if (rc) return rc;
+    int all = 1;
+    for (size_t i = 0; i < n; i++) all &= verdicts[i] == 1;
+    return all;
+}
+extern "C" int mi355_bls_verify_each(mi355_bls_ctx* c, const void* sets, size_t n, uint8_t verdicts[]) {
+    return each_run(c, nullptr, (const uint8_t*)sets, n, verdicts, nullptr, nullptr);
+}
+extern "C" int mi355_bls_verify_each_device(mi355_bls_ctx* c, const void* d_sets, size_t n, uint8_t verdicts[], void* stream) {
+    return each_run(c, (const uint8_t*)d_sets, nullptr, n, verdicts, nullptr, (hipStream_t)stream);
+}
+// TEST HOOKS: the same pass with the 576-byte value of every set (what mi355_bls_fetch_stage(4) is to the batch paths); the number of
+// per-set passes this context has made
+extern "C" int mi355_bls_debug_verify_each_gt(mi355_bls_ctx* c, const void* sets, size_t n, uint8_t verdicts[], uint8_t* gt_out) {
+    if (!gt_out) return MI355_BLS_ERR_ARG;
+    return each_run(c, nullptr, (const uint8_t*)sets, n, verdicts, gt_out, nullptr);
+}
+extern "C" int mi355_bls_debug_verify_each_passes(mi355_bls_ctx* c) { return c ? c->each_passes : MI355_BLS_ERR_ARG; }
+
+// batchVerify first; only a failing batch pays for the per-set pass
+static int locate_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, size_t n, const uint8_t rnd[32], uint8_t verdicts[], hipStream_t st) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!verdicts || (!d_src && !h_src)) return MI355_BLS_ERR_ARG;
+    int rc = verify_common(c, d_src, h_src, n, rnd, 0, st);
+    if (rc < 0) return rc;
+    if (rc == 1) {
+        std::memset(verdicts, 1, n);
+        return 1;
+    }
+    rc = each_run(c, d_src, h_src, n, verdicts, nullptr, st);
+    return rc < 0 ? rc : 0;
+}
+extern "C" int mi355_bls_batch_verify_locate(mi355_bls_ctx* c, const void* sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[]) {
+    return locate_run(c, nullptr, (const uint8_t*)sets, n, rnd, verdicts, nullptr);
+}
+extern "C" int mi355_bls_batch_verify_locate_device(mi355_bls_ctx* c, const void* d_sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[], void* stream) {
+    return locate_run(c, (const uint8_t*)d_sets, nullptr, n, rnd, verdicts, (hipStream_t)stream);
+}
 
 // ------------------------------------------------------------------------------------------
 // Many independent batches in ONE device pass.  A host that verifies many SMALL batches (a few thousand sets each: one per block or

@@ -32,6 +32,7 @@
 #include "deser.hpp"
 #include "h2c.hpp"
 #include "pairing.hpp"
+#include "vereach.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -2130,6 +2131,82 @@ __global__ void __launch_bounds__(WAVE) k_aggv_setup(const uint8_t* __restrict__
         soa_st_g1(P, stride, n, g1_jac{fp_from_const(k::G1_X), fp_from_const(k::G1_NEG_Y), fp_one()});
         soa_st_g2(H, stride, n, jac_from_aff(ld_g2a_blst(sig)));
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-set verification of many sets (mi355_bls_verify_each; verify, bls_sig_min_pubkey.nim:108-125, for every set of a batch): the
+// arithmetic is csrc/vereach.hpp.  A slice of m sets uses 2 m pairs of the line store: pair i = (pk_i, H(msg_i)), unblinded, H where
+// the hashing kernels leave it; pair m + i = (-G1, sig_i).  Pairs with an operand at infinity get line_one() lines from the line kernels.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(WAVE) k_each_setup(const uint8_t* __restrict__ sets, uint32_t m, uint4* __restrict__ H, uint4* __restrict__ P, size_t stride) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(sets + (size_t)i * 320);
+    soa_st_g1(P, stride, i, jac_from_aff(ld_g1a_blst(w)));
+    soa_st_g1(P, stride, (size_t)m + i, g1_jac{fp_from_const(k::G1_X), fp_from_const(k::G1_NEG_Y), fp_one()});
+    soa_st_g2(H, stride, (size_t)m + i, jac_from_aff(ld_g2a_blst(w + 32)));
+}
+// One lane per set: the two-pair Horner over the 68 steps, the final exponentiation, the comparison with one.  verdicts[i] = 0 / 1;
+// gt (may be null: the debug hook) gets the 576-byte blst_fp12 image of the value.  One wave per SIMD: the Fp12 working set of the tower
+// functions wants the whole register file (registers / scratch of the build: the library's .kmeta.json).
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_each_tail(const uint4* __restrict__ lines, size_t stride, uint32_t m, const uint8_t* __restrict__ sets, uint8_t* __restrict__ verdicts, uint32_t* __restrict__ gt) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const auto line_of = [&](int s, size_t j) {
+        const uint4* b = lines + (size_t)s * 24 * stride;
+        return line_t{soa_ld2(b, stride, 0, j), soa_ld2(b, stride, 2, j), soa_ld2(b, stride, 4, j)};
+    };
+    const bool pk_inf = aff_is_inf(ld_g1a_blst(reinterpret_cast<const uint32_t*>(sets + (size_t)i * 320)));
+    const vereach_out o = vereach_set([&](int s) { return line_of(s, i); }, [&](int s) { return line_of(s, (size_t)m + i); }, pk_inf);
+    verdicts[i] = o.ok ? 1 : 0;
+    if (gt) {
+        uint32_t* g = gt + (size_t)i * 144;
+        const fp2* c[6] = {&o.value.c0.a0, &o.value.c0.a1, &o.value.c0.a2, &o.value.c1.a0, &o.value.c1.a1, &o.value.c1.a2};
+        for (int t = 0; t < 6; t++) {
+            st_fp_blst(g + 24 * t, c[t]->c0);
+            st_fp_blst(g + 24 * t + 12, c[t]->c1);
+        }
+    }
+}
+// The same per set on the lane-cooperative Fp12 engine (tail_body: the Horner over 68 step values and the final exponentiation of k_tail /
+// k_tail_rows, unchanged), for calls too small to give every SIMD a wave of the one-lane form: a workgroup takes sets blockIdx.x,
+// blockIdx.x + gridDim.x, ...  Per set, wave 0 first forms the 68 step values La_s * Lb_s (one sparse line product per lane: the multipliers'
+// hand-over slot is indexed by lane, so only one wave of a workgroup may use it) into the workgroup's block of `work`
+// (EACH_WORK_WORDS words: 68 step values | Miller value | final value | verdict word), then the engine walks them.
+constexpr uint32_t EACH_WORK_STATE = N_LINES * F12W, EACH_WORK_GT = EACH_WORK_STATE + 144, EACH_WORK_V = EACH_WORK_GT + 144, EACH_WORK_WORDS = EACH_WORK_V + 16;
+template <bool ROWS>
+__device__ __forceinline__ void each_engine_body(const uint4* __restrict__ lines, size_t stride, uint32_t m, const uint8_t* __restrict__ sets,
+                                                 uint8_t* __restrict__ verdicts, uint32_t* __restrict__ gt, uint32_t* __restrict__ work) {
+    uint32_t* W = work + (size_t)blockIdx.x * EACH_WORK_WORDS;
+    for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) {                 // workgroup-uniform
+        if (threadIdx.x < WAVE) {
+            for (uint32_t s = threadIdx.x; s < (uint32_t)N_LINES; s += WAVE) {
+                const uint4* b = lines + (size_t)s * 24 * stride;
+                const line_t la{soa_ld2(b, stride, 0, i), soa_ld2(b, stride, 2, i), soa_ld2(b, stride, 4, i)};
+                const size_t j = (size_t)m + i;
+                const line_t lb{soa_ld2(b, stride, 0, j), soa_ld2(b, stride, 2, j), soa_ld2(b, stride, 4, j)};
+                st_fp12_int(W + (size_t)s * F12W, fp12_reduce(fp12_mul_by_line(fp12_from_line(la), lb)));
+            }
+        }
+        __syncthreads();
+        tail_body<ROWS>(W, W + EACH_WORK_STATE, 1, 3, W + EACH_WORK_GT, W + EACH_WORK_V, 144, 0);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const bool pk_inf = aff_is_inf(ld_g1a_blst(reinterpret_cast<const uint32_t*>(sets + (size_t)i * 320)));
+            verdicts[i] = (W[EACH_WORK_V] == 1u && !pk_inf) ? 1 : 0;
+        }
+        if (gt && threadIdx.x < 144) gt[(size_t)i * 144 + threadIdx.x] = W[EACH_WORK_GT + threadIdx.x];
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(TAIL_THREADS) k_each_engine(const uint4* __restrict__ lines, size_t stride, uint32_t m, const uint8_t* __restrict__ sets,
+                                                              uint8_t* __restrict__ verdicts, uint32_t* __restrict__ gt, uint32_t* __restrict__ work) {
+    each_engine_body<false>(lines, stride, m, sets, verdicts, gt, work);
+}
+__global__ void __launch_bounds__(K_TAIL_THREADS) k_each_engine_rows(const uint4* __restrict__ lines, size_t stride, uint32_t m, const uint8_t* __restrict__ sets,
+                                                                     uint8_t* __restrict__ verdicts, uint32_t* __restrict__ gt, uint32_t* __restrict__ work) {
+    each_engine_body<true>(lines, stride, m, sets, verdicts, gt, work);
 }
 
 // ------------------------------------------------------------------------------------------

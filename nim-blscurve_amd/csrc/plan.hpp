@@ -204,6 +204,37 @@ inline size_t shard_slice_count(size_t n, size_t done, size_t nslices, uint32_t 
 }
 inline int shard_workspace_of(size_t nslices, uint32_t slice, int nl) { return (int)((nslices - 1 - slice) % (size_t)nl); }
 
+// Per-set verification (mi355_bls_verify_each): n sets in balanced slices of at most `cap` sets.  A slice of m sets puts 2 m pairs through
+// a line store of its own (2 cap pairs, made at the first such call): pair i = (pk_i, H(msg_i)), pair m + i = (-G1, sig_i), so a call of
+// cap sets is ONE slice.  Hashing and Miller lines take the forms the batch path takes for the same counts (clear_for on m messages,
+// lines_for on 2 m pairs: the lane-team engine up to each_team_clear_max / each_team_lines_max sets in latency mode, one lane per item
+// beyond).  The tail - Horner, final exponentiation, comparison - has two forms: the lane-cooperative Fp12 engine, a workgroup per set and
+// each_engine_grid workgroups at a time (two per CU: 66 KB of LDS each), in latency mode up to each_engine_max sets; one lane per set
+// (k_each_tail) beyond and in throughput mode.  Measured around every hand-over: profiles/verify_each_sweep.txt.
+constexpr uint32_t EACH_ENGINE_SETS_PER_SLOT = 7;      // 4.4 ms per S sets on the engine against the lane form's flat 36 ms: level near 8 S
+inline size_t each_slice_max(size_t cap) { return cap; }
+inline size_t each_stride(size_t cap) { return ((2 * cap + 63) / 64) * 64; }
+inline size_t each_nslices(size_t n, size_t slice_max) { return shard_nslices(n, slice_max); }
+inline size_t each_slice_count(size_t n, size_t done, size_t nslices, uint32_t slice) { return shard_slice_count(n, done, nslices, slice); }
+inline uint32_t each_team_clear_max(uint32_t slots) { return team_clear_max(slots); }
+inline uint32_t each_team_lines_max(uint32_t slots) { return team_lines_max(slots) / 2; }
+inline uint32_t each_engine_max(uint32_t slots) { return slots * EACH_ENGINE_SETS_PER_SLOT; }
+inline uint32_t each_engine_grid_max(uint32_t slots) { return slots / 2 ? slots / 2 : 1; }
+struct each_plan {
+    uint32_t setup_grid;               // k_each_setup: one lane per set
+    lines_plan lines;                  // all 2 m pairs in one form
+    bool tail_engine;                  // k_each_engine(_rows): tail_grid workgroups, each walks sets i, i + tail_grid, ... | k_each_tail: tail_grid waves
+    uint32_t tail_grid;
+};
+inline each_plan each_for(uint32_t slots, bool coop, uint32_t m) {
+    each_plan p{};
+    p.setup_grid = waves_for(m);
+    p.lines = lines_for(slots, coop, 2 * m, 0);
+    p.tail_engine = coop && m <= each_engine_max(slots);
+    p.tail_grid = p.tail_engine ? (m < each_engine_grid_max(slots) ? m : each_engine_grid_max(slots)) : waves_for(m);
+    return p;
+}
+
 // chunk of the parallel_chunks partition (parallel_chunks.nim:42-66) that tuple t of n_total falls into, B chunks
 inline uint32_t chunk_of_tuple(size_t n_total, uint32_t B, size_t t) {
     size_t base = n_total / B, rem = n_total % B, cut = (base + 1) * rem;
