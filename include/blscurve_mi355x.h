@@ -235,6 +235,42 @@ int mi355_bls_fast_aggregate_verify_device(mi355_bls_ctx* ctx, const void* d_pks
  * (blst_p1_add_or_double), which runs the one pairing check.  pks: n x 96 B in host memory. */
 int mi355_bls_fast_aggregate_verify_multi(mi355_bls_ctx* const ctxs[], size_t ngpu, const void* pks, size_t n, const uint8_t* msg,
                                           size_t msg_len, const void* sig);
+/* fastAggregateVerify for MANY sets: the key aggregation of every set in ONE device pass.  In the batch verifier's workload (attestations,
+ * sync-committee messages) a set's public key is not on the wire: it is aggregateAll (blst_min_pubkey_sig_core.nim:179-195; the first step
+ * of fastAggregateVerify, bls_sig_min_pubkey.nim:234-258) over a committee.  These calls take k key lists at once and leave k ordinary
+ * 320-byte SignatureSet records (aggregate key | message | signature) in device memory, which every batch and per-set entry point takes
+ * unchanged.
+ *   keys      n_table x 96-byte blst_p1_affine images: the key table (e.g. the validator registry, kept resident on the device)
+ *   idx       NULL: list s is keys [offsets[s], offsets[s+1]) of the table itself (offsets[k] <= n_table);
+ *             else: list s is keys idx[offsets[s]] .. idx[offsets[s+1] - 1] of the table (offsets[k] = the length of idx; repeats allowed)
+ *   offsets   k + 1 entries in HOST memory (also in the _device forms), non-decreasing; an empty list is allowed
+ *   msgs32    k x 32 bytes, sigs192: k x 192-byte blst_p2_affine images, packed, one per list
+ *   status    k bytes, host memory: 0 ok, 1 empty list, 2 the aggregate is the point at infinity, 3 an index was >= n_table (it is never
+ *             dereferenced; 3 wins over 1 and 2).  The record of a list whose status is not 0 carries the infinity key (96 zero bytes), for
+ *             which every verifier answers 0.
+ * An affine infinity image among the keys adds nothing, as in mi355_bls_g1_aggregate (fromBytes never yields one).  Device pointers are
+ * 4-byte aligned.  Preconditions as the reference's: keys decoded and group-checked, proofs of possession verified by the caller.
+ * Any k and any list lengths up to 2^32 - 2 keys in all; nothing here is bounded by max_sets (the verification passes slice as always).
+ * aggregate_sets:  returns 1 when every status is 0, else 0; k == 0: 0, nothing written.  MI355_BLS_ERR_ARG for decreasing offsets,
+ *                  offsets[k] > n_table without idx, NULL pointers.  The _device form enqueues on `stream` and synchronises it once, for
+ *                  the status bytes; d_out_records: k x 320 bytes of device memory.
+ * fast_aggregate_verify_each:   out[s] = fastAggregateVerify(keys of list s, msg_s, sig_s) for every s (an empty list: 0,
+ *                  bls_sig_min_pubkey.nim:251-253) - the aggregation, then the mi355_bls_verify_each pass on the records.  Returns 1 iff all are 1.
+ * batch_fast_aggregate_verify:  batchVerify (mi355_bls_batch_verify with rnd) over the sets (aggregateAll(keys_s), msg_s, sig_s); if any
+ *                  status is not 0 the result is 0 and no verification pass is run. */
+int mi355_bls_aggregate_sets(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                             const void* msgs32, const void* sigs192, void* out_records, uint8_t* status);
+int mi355_bls_aggregate_sets_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                    const void* d_msgs32, const void* d_sigs192, void* d_out_records, uint8_t* status, void* stream);
+int mi355_bls_fast_aggregate_verify_each(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                         const void* msgs32, const void* sigs192, uint8_t* out);
+int mi355_bls_fast_aggregate_verify_each_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                                size_t k, const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream);
+int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                          const void* msgs32, const void* sigs192, const uint8_t rnd[32]);
+int mi355_bls_batch_fast_aggregate_verify_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                                 size_t k, const void* d_msgs32, const void* d_sigs192, const uint8_t rnd[32], void* stream);
+
 /* coreVerifyNoGroupCheck on an AggregatePublicKey the caller already holds (core :269-297): agg_p1 = blst_p1 (Jacobian, 144 B), e.g.
  * mi355_bls_p1s_add of the per-rank mi355_bls_g1_aggregate_device partial sums of a key-sharded fastAggregateVerify (one process per
  * GPU).  Aggregate at infinity -> 0. */

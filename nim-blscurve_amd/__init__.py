@@ -100,6 +100,13 @@ def lib():
         L.mi355_bls_fast_aggregate_verify_device.argtypes = [vp, vp, sz, ctypes.c_char_p, sz, ctypes.c_char_p, vp]
         L.mi355_bls_fast_aggregate_verify_multi.argtypes = [ctypes.POINTER(vp), sz, vp, sz, ctypes.c_char_p, sz, ctypes.c_char_p]
         L.mi355_bls_verify_aggregate.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.c_char_p]
+        pu32, psz = ctypes.POINTER(u32), ctypes.POINTER(sz)
+        L.mi355_bls_aggregate_sets.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp, vp]
+        L.mi355_bls_aggregate_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp, vp]
+        L.mi355_bls_fast_aggregate_verify_each.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp]
+        L.mi355_bls_fast_aggregate_verify_each_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
+        L.mi355_bls_batch_fast_aggregate_verify.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, ctypes.c_char_p]
+        L.mi355_bls_batch_fast_aggregate_verify_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, ctypes.c_char_p, vp]
         L.mi355_bls_p1s_mult_pippenger_scratch_sizeof.argtypes = [sz]
         L.mi355_bls_p1s_mult_pippenger_scratch_sizeof.restype = sz
         L.mi355_bls_p1s_mult_pippenger.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), sz, ctypes.POINTER(vp), sz]
@@ -495,6 +502,110 @@ def fastAggregateVerifyMulti(caches, publicKeys, message, signature):
         return False
     arr = (ctypes.c_void_p * len(caches))(*[c._h for c in caches])
     return bool(_check(lib().mi355_bls_fast_aggregate_verify_multi(arr, len(caches), buf, n, bytes(message), len(message), bytes(signature))))
+
+
+AGG_OK, AGG_EMPTY, AGG_INFINITY, AGG_BAD_INDEX = 0, 1, 2, 3      # status bytes of aggregateSets
+
+
+def _join(x, unit, what):
+    b = bytes(x) if isinstance(x, (bytes, bytearray, memoryview)) else b"".join(bytes(e) for e in x)
+    if len(b) % unit:
+        raise ValueError("%s: a multiple of %d bytes" % (what, unit))
+    return b
+
+
+def _key_lists(keys, messages, signatures):
+    """The key lists of the aggregateSets family -> (key table bytes, n_table, idx array or None, offsets array, k, messages, signatures).
+    keys: a list of key lists (each a list of 96-byte blst_p1_affine images, or their concatenation) - they are laid end to end and no index
+    array is sent - or a tuple (table, idx, offsets): table = the 96-byte keys, idx = None or a sequence of table indices, offsets = k + 1
+    non-decreasing positions (into idx, or into the table when idx is None)."""
+    if isinstance(keys, tuple):
+        table, idx, offsets = keys
+        table = _join(table, 96, "key table")
+        offsets = [int(x) for x in offsets]
+        if idx is not None:
+            idx = [int(x) for x in idx]
+            if any(x < 0 or x >= 1 << 32 for x in idx):
+                raise ValueError("indices are 32-bit unsigned")
+            if offsets and offsets[-1] != len(idx):
+                raise ValueError("offsets[k] is the length of the index array")
+    else:
+        lists = [_join(x, 96, "public keys") for x in keys]
+        table, idx, offsets = b"".join(lists), None, [0]
+        for x in lists:
+            offsets.append(offsets[-1] + len(x) // 96)
+    if not offsets or any(x < 0 for x in offsets):
+        raise ValueError("offsets: k + 1 non-negative positions")
+    k = len(offsets) - 1
+    ms, sg = _join(messages, 32, "messages"), _join(signatures, 192, "signatures")
+    if len(ms) != 32 * k or len(sg) != 192 * k:
+        raise ValueError("one 32-byte message and one 192-byte signature per key list")
+    iarr = (ctypes.c_uint32 * max(len(idx), 1))(*idx) if idx is not None else None
+    return table, len(table) // 96, iarr, (ctypes.c_size_t * (k + 1))(*offsets), k, ms, sg
+
+
+def aggregateSets(cache, keys, messages, signatures):
+    """aggregateAll (blst_min_pubkey_sig_core.nim:179-195) for every key list in one device pass (mi355_bls_aggregate_sets); keys as
+    _key_lists takes them.  -> (all_ok, k x 320-byte SignatureSet records with the aggregate keys, k status bytes: 0 ok, 1 empty list,
+    2 aggregate at infinity, 3 index out of range; a record whose status is not 0 carries the infinity key)."""
+    table, n_table, idx, offs, k, ms, sg = _key_lists(keys, messages, signatures)
+    if k == 0:
+        return False, b"", b""
+    out, st = ctypes.create_string_buffer(320 * k), ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_aggregate_sets(cache._h, table or b"\0", n_table, idx, offs, k, ms, sg, out, st))
+    return bool(ok), out.raw, st.raw
+
+
+def aggregateSets_device(cache, d_keys, n_table, d_idx, offsets, d_msgs, d_sigs, d_out, stream=0):
+    """Same with the key table, the indices (0 / None: none), messages, signatures and the output records in device memory (raw pointers);
+    offsets stay on the host.  -> (all_ok, status bytes)."""
+    k = len(offsets) - 1
+    if k <= 0:
+        return False, b""
+    st = ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_aggregate_sets_device(cache._h, d_keys, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k, d_msgs, d_sigs,
+                                                      d_out, st, stream))
+    return bool(ok), st.raw
+
+
+def fastAggregateVerifyEach(cache, keys, messages, signatures):
+    """fastAggregateVerify (bls_sig_min_pubkey.nim:234-258) for every (key list, message, signature) in one device pass
+    (mi355_bls_fast_aggregate_verify_each): -> [bool], one per list; an empty list gives False."""
+    table, n_table, idx, offs, k, ms, sg = _key_lists(keys, messages, signatures)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_fast_aggregate_verify_each(cache._h, table or b"\0", n_table, idx, offs, k, ms, sg, out))
+    return [v == 1 for v in out.raw]
+
+
+def fastAggregateVerifyEach_device(cache, d_keys, n_table, d_idx, offsets, d_msgs, d_sigs, stream=0):
+    k = len(offsets) - 1
+    if k <= 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_fast_aggregate_verify_each_device(cache._h, d_keys, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k, d_msgs,
+                                                              d_sigs, out, stream))
+    return [v == 1 for v in out.raw]
+
+
+def batchFastAggregateVerify(cache, keys, messages, signatures, secureRandomBytes):
+    """batchVerify over the sets (aggregateAll(keys_s), message_s, signature_s) (mi355_bls_batch_fast_aggregate_verify): False when a list
+    gives no key (empty, out-of-range index, aggregate at infinity) or the batch does not verify; no lists -> False."""
+    rnd = _rnd32(secureRandomBytes)
+    table, n_table, idx, offs, k, ms, sg = _key_lists(keys, messages, signatures)
+    if k == 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_fast_aggregate_verify(cache._h, table or b"\0", n_table, idx, offs, k, ms, sg, rnd)))
+
+
+def batchFastAggregateVerify_device(cache, d_keys, n_table, d_idx, offsets, d_msgs, d_sigs, secureRandomBytes, stream=0):
+    rnd = _rnd32(secureRandomBytes)
+    k = len(offsets) - 1
+    if k <= 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_fast_aggregate_verify_device(cache._h, d_keys, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k,
+                                                                          d_msgs, d_sigs, rnd, stream)))
 
 
 def verifyAggregate(cache, aggregate_p1, message, signature):

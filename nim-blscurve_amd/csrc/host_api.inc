@@ -116,6 +116,16 @@ struct mi355_bls_ctx {
     uint32_t* d_each_work = nullptr; // the engine form's step values and results, one block per workgroup
     size_t each_stride = 0;
     int each_passes = 0;             // per-set passes made on this context (mi355_bls_debug_verify_each_passes)
+    // per-set key aggregation (mi355_bls_aggregate_sets): sized by the call, grown on demand (agg_grow), never by max_sets
+    uint32_t* d_agg_part = nullptr;  // the plan's partials, G1W words each
+    uint32_t* d_agg_tab = nullptr;   // item table | final_of, as agg_tab holds them
+    uint32_t* d_agg_bad = nullptr;   // per segment: an index was out of range
+    uint8_t* d_agg_status = nullptr; // per segment: the status byte
+    uint8_t* d_agg_rec = nullptr;    // the records of the forms that verify them (and of the host form)
+    uint8_t* d_agg_in = nullptr;     // host inputs staged: keys | signatures | messages | indices
+    size_t agg_cap_part = 0, agg_cap_tab = 0, agg_cap_bad = 0, agg_cap_status = 0, agg_cap_rec = 0, agg_cap_in = 0;      // bytes
+    std::vector<uint32_t> agg_tab;   // the table of the call in flight: the async copy reads it
+    std::vector<uint8_t> agg_status_h;
 };
 
 constexpr size_t PKTAB_BYTES = 8 * 5 * 64;   // per set: 8 table entries x (X, Y, Z, Z^2, Z^3) x 64 bytes (tools/gen_pkmul_asm.py LANE_BYTES)
@@ -197,7 +207,7 @@ extern "C" void mi355_bls_ctx_destroy(mi355_bls_ctx* c) {
     if (c->ev_sl0) (void)hipEventDestroy(c->ev_sl0);
     for (auto& e : c->ev_blind)
         if (e) (void)hipEventDestroy(e);
-    void* bufs[] = {c->d_sets, c->d_rnd, c->d_r, c->d_H, c->d_M, c->d_P, c->d_lines, c->d_pktab, c->d_sig_pts, c->d_sig_sorted, c->d_sig_hist, c->d_sig_consts, c->d_agg, c->d_agg1, c->d_msg, c->d_comp, c->d_status, c->d_lpart, c->d_L, c->d_states, c->d_gt, c->d_gt_fv, c->d_carry, c->d_blob, c->d_flags, c->d_export, c->d_each_v, c->d_each_gt, c->d_each_H, c->d_each_P, c->d_each_lines, c->d_each_work};
+    void* bufs[] = {c->d_sets, c->d_rnd, c->d_r, c->d_H, c->d_M, c->d_P, c->d_lines, c->d_pktab, c->d_sig_pts, c->d_sig_sorted, c->d_sig_hist, c->d_sig_consts, c->d_agg, c->d_agg1, c->d_msg, c->d_comp, c->d_status, c->d_lpart, c->d_L, c->d_states, c->d_gt, c->d_gt_fv, c->d_carry, c->d_blob, c->d_flags, c->d_export, c->d_each_v, c->d_each_gt, c->d_each_H, c->d_each_P, c->d_each_lines, c->d_each_work, c->d_agg_part, c->d_agg_tab, c->d_agg_bad, c->d_agg_status, c->d_agg_rec, c->d_agg_in};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (c->h_flags) (void)hipHostFree(c->h_flags);
@@ -993,6 +1003,178 @@ extern "C" int mi355_bls_batch_verify_locate(mi355_bls_ctx* c, const void* sets,
 }
 extern "C" int mi355_bls_batch_verify_locate_device(mi355_bls_ctx* c, const void* d_sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[], void* stream) {
     return locate_run(c, (const uint8_t*)d_sets, nullptr, n, rnd, verdicts, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-set key aggregation: aggregateAll (blst_min_pubkey_sig_core.nim:179-195) for the key list of every set of a batch in one device pass,
+// the step fastAggregateVerify (bls_sig_min_pubkey.nim:234-258) runs in front of its pairing.  k key lists in CSR form (list s = positions
+// [offsets[s], offsets[s + 1]) of the key sequence; the sequence is the key table itself, or - with an index array - table entries picked by
+// index, so a validator key table can stay on the device) become k ordinary 320-byte SignatureSet records in device memory, which the batch
+// and the per-set paths take unchanged.  The host lays the segmented sum out (plan.hpp aggsets_fill: levels of items of up to AGG_C
+// operands, no item across two lists) and sends the table with one copy; a kernel per level and k_aggsets_finish follow on the caller's stream.
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(plan::agg_item) == 16, "k_aggsets_l0 / k_aggsets_ln load an item as one uint4");
+static int agg_grow(void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return 0;
+    if (*p) (void)hipFree(*p);           // every entry point that used it has drained its stream before returning
+    *p = nullptr, *cap = 0;
+    const size_t want = bytes + bytes / 4;
+    HIPCHK(hipMalloc(p, want));
+    *cap = want;
+    return 0;
+}
+static bool agg_offsets_ok(const size_t* offsets, size_t k) {
+    for (size_t s = 0; s < k; s++)
+        if (offsets[s + 1] < offsets[s]) return false;
+    return true;
+}
+// device addresses of a call's inputs
+struct agg_in {
+    const uint8_t* keys;
+    const uint32_t* idx;
+    const uint8_t *msgs, *sigs;
+};
+// aggregation of k > 0 lists enqueued on st: records at d_out, status bytes in c->d_agg_status
+static int aggsets_enqueue(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, uint8_t* d_out, hipStream_t st) {
+    if (!in.keys || !in.msgs || !in.sigs || !offsets || !d_out) return MI355_BLS_ERR_ARG;
+    if (((uintptr_t)in.keys | (uintptr_t)in.msgs | (uintptr_t)in.sigs | (uintptr_t)in.idx | (uintptr_t)d_out) & 3) {
+        g_err = "aggregate_sets: keys, messages, signatures, indices and records must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (c->pending) {
+        g_err = "a batch submitted on this context has not been waited for";
+        return MI355_BLS_ERR_ARG;
+    }
+    const plan::aggsets_plan p = k < plan::AGG_NONE ? plan::aggsets_measure(offsets, k) : plan::aggsets_plan{};
+    if (!p.ok) {
+        g_err = "aggregate_sets: offsets decrease, or more than 2^32 - 2 keys or lists";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (!in.idx && offsets[k] > n_table) {
+        g_err = "aggregate_sets: offsets[k] exceeds the number of keys";
+        return MI355_BLS_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    c->agg_tab.resize(p.items * 4 + k);
+    plan::aggsets_fill(p, offsets, k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), c->agg_tab.data() + p.items * 4);
+    int rc = agg_grow((void**)&c->d_agg_part, &c->agg_cap_part, (p.items ? p.items : 1) * (size_t)G1W * 4);
+    if (!rc) rc = agg_grow((void**)&c->d_agg_tab, &c->agg_cap_tab, c->agg_tab.size() * 4);
+    if (!rc) rc = agg_grow((void**)&c->d_agg_bad, &c->agg_cap_bad, k * 4);
+    if (!rc) rc = agg_grow((void**)&c->d_agg_status, &c->agg_cap_status, k);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, k * 4, st));
+    HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), c->agg_tab.size() * 4, hipMemcpyHostToDevice, st));
+    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab);
+    for (uint32_t l = 0; l < p.levels; l++) {
+        const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
+        if (l == 0) k_aggsets_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, in.keys, n_table, in.idx, c->d_agg_part, c->d_agg_bad);
+        else k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + p.level_first[l], cnt, c->d_agg_part);
+    }
+    k_aggsets_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(c->d_agg_tab + p.items * 4, (uint32_t)k, c->d_agg_part, c->d_agg_bad,
+                                                                   reinterpret_cast<const uint32_t*>(in.msgs), reinterpret_cast<const uint32_t*>(in.sigs),
+                                                                   reinterpret_cast<uint32_t*>(d_out), c->d_agg_status);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the status bytes back (the call's synchronisation): 1 when every list gave a key
+static int aggsets_status(mi355_bls_ctx* c, size_t k, uint8_t* status, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(status, c->d_agg_status, k, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int all = 1;
+    for (size_t s = 0; s < k; s++) all &= status[s] == 0;
+    return all;
+}
+// host inputs -> d_agg_in (keys | signatures | messages | indices: every part 4-byte aligned)
+static int agg_stage(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k, const void* msgs, const void* sigs,
+                     hipStream_t st, agg_in* out) {
+    if (!keys || !offsets || !msgs || !sigs || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
+    const size_t n_idx = idx ? offsets[k] : 0, kb = n_table * 96, sb = k * 192, mb = k * 32;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = agg_grow((void**)&c->d_agg_in, &c->agg_cap_in, kb + sb + mb + n_idx * 4 + 4);
+    if (rc) return rc;
+    uint8_t* d = c->d_agg_in;
+    if (kb) HIPCHK(hipMemcpyAsync(d, keys, kb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d + kb, sigs, sb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d + kb + sb, msgs, mb, hipMemcpyHostToDevice, st));
+    if (n_idx) HIPCHK(hipMemcpyAsync(d + kb + sb + mb, idx, n_idx * 4, hipMemcpyHostToDevice, st));
+    *out = agg_in{d, idx ? reinterpret_cast<const uint32_t*>(d + kb + sb + mb) : nullptr, d + kb + sb, d + kb};
+    return 0;
+}
+extern "C" int mi355_bls_aggregate_sets_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                               const void* d_msgs32, const void* d_sigs192, void* d_out_records, uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing aggregated, nothing written
+    if (!status) return MI355_BLS_ERR_ARG;
+    const agg_in in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192};
+    int rc = aggsets_enqueue(c, in, n_table, offsets, k, (uint8_t*)d_out_records, (hipStream_t)stream);
+    if (rc) return rc;
+    return aggsets_status(c, k, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_aggregate_sets(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                        const void* msgs32, const void* sigs192, void* out_records, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!out_records || !status) return MI355_BLS_ERR_ARG;
+    agg_in in;
+    int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
+    if (!rc) rc = agg_grow((void**)&c->d_agg_rec, &c->agg_cap_rec, k * 320);
+    if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out_records, c->d_agg_rec, k * 320, hipMemcpyDeviceToHost, nullptr));
+    return aggsets_status(c, k, status, nullptr);
+}
+// fastAggregateVerify (bls_sig_min_pubkey.nim:234-258) for every list: the records into the context's own buffer, then the per-set pass
+// on them.  A list without a key, with an out-of-range index or with the sum at infinity has the infinity key in its record: verdict 0.
+static int agg_each(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, uint8_t* out, hipStream_t st) {
+    int rc = agg_grow((void**)&c->d_agg_rec, &c->agg_cap_rec, k * 320);
+    if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, st);
+    if (rc) return rc;
+    return each_run(c, c->d_agg_rec, nullptr, k, out, nullptr, st);
+}
+extern "C" int mi355_bls_fast_aggregate_verify_each_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                                           size_t k, const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!out) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    return agg_each(c, agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, n_table, offsets, k, out, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_fast_aggregate_verify_each(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                                    const void* msgs32, const void* sigs192, uint8_t* out) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!out) return MI355_BLS_ERR_ARG;
+    agg_in in;
+    int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
+    if (rc) return rc;
+    return agg_each(c, in, n_table, offsets, k, out, nullptr);
+}
+// batchVerify over the sets (aggregateAll(keys_s), msg_s, sig_s): a list that gives no key (any status but 0) ends the call with 0 before
+// any verification pass - the reference's caller would not have obtained a SignatureSet for it.
+static int agg_batch(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, const uint8_t rnd[32], hipStream_t st) {
+    int rc = agg_grow((void**)&c->d_agg_rec, &c->agg_cap_rec, k * 320);
+    if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, st);
+    if (rc) return rc;
+    c->agg_status_h.resize(k);
+    rc = aggsets_status(c, k, c->agg_status_h.data(), st);
+    if (rc != 1) return rc;
+    return verify_common(c, c->d_agg_rec, nullptr, k, rnd, 0, st);
+}
+extern "C" int mi355_bls_batch_fast_aggregate_verify_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                                            size_t k, const void* d_msgs32, const void* d_sigs192, const uint8_t rnd[32], void* stream) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    return agg_batch(c, agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, n_table, offsets, k, rnd, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                                     const void* msgs32, const void* sigs192, const uint8_t rnd[32]) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    agg_in in;
+    int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
+    if (rc) return rc;
+    return agg_batch(c, in, n_table, offsets, k, rnd, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -33,6 +33,7 @@
 #include "h2c.hpp"
 #include "pairing.hpp"
 #include "vereach.hpp"
+#include "aggsets.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -2207,6 +2208,49 @@ __global__ void __launch_bounds__(TAIL_THREADS) k_each_engine(const uint4* __res
 __global__ void __launch_bounds__(K_TAIL_THREADS) k_each_engine_rows(const uint4* __restrict__ lines, size_t stride, uint32_t m, const uint8_t* __restrict__ sets,
                                                                      uint8_t* __restrict__ verdicts, uint32_t* __restrict__ gt, uint32_t* __restrict__ work) {
     each_engine_body<true>(lines, stride, m, sets, verdicts, gt, work);
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-set key aggregation (mi355_bls_aggregate_sets: aggregateAll, blst_min_pubkey_sig_core.nim:179-195, for the key list of every set of a
+// batch - the step in front of fastAggregateVerify's pairing, bls_sig_min_pubkey.nim:234-258): a segmented sum in levels of one-lane items.
+// The arithmetic is csrc/aggsets.hpp, the item tables are plan.hpp aggsets_fill's (an item = the four words src_first, count, dst, seg of
+// plan::agg_item, one 16-byte load).  Partials are internal G1 images (G1W words), partial i written by item i of the table.
+// ------------------------------------------------------------------------------------------
+// level 0, one lane per item: up to AGG_C keys (96-byte blst_p1_affine images; through idx into a table of n_table keys when idx != nullptr)
+// -> one partial.  An index that is not below n_table is not dereferenced: the lane sets the segment's status word and goes on.
+__global__ void __launch_bounds__(WAVE, 2) k_aggsets_l0(const uint4* __restrict__ items, uint32_t n_items, const uint8_t* __restrict__ keys, size_t n_table,
+                                                        const uint32_t* __restrict__ idx, uint32_t* __restrict__ part, uint32_t* __restrict__ seg_bad) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    const g1_jac acc = aggsets_l0_item(it.x, it.y, idx, n_table,
+                                       [&](size_t t) { return ld_g1a_blst(reinterpret_cast<const uint32_t*>(keys + t * 96)); },
+                                       [&]() { atomicOr(seg_bad + it.w, 1u); });
+    st_g1_int(part + (size_t)it.z * G1W, acc);
+}
+// a higher level, one lane per item: up to AGG_C partials of the level below -> one partial
+__global__ void __launch_bounds__(WAVE, 2) k_aggsets_ln(const uint4* __restrict__ items, uint32_t n_items, uint32_t* __restrict__ part) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    const g1_jac acc = aggsets_ln_item(it.x, it.y, [&](uint32_t j) { return ld_g1_int(part + (size_t)j * G1W); });
+    st_g1_int(part + (size_t)it.z * G1W, acc);
+}
+// one lane per segment: its last partial (final_of[s]; 0xffffffff: no key at all) to affine, the 320-byte SignatureSet record
+// pk96 | msg32 | sig192 from the packed k x 32 messages and k x 192 signatures (4-byte aligned), and the status byte (aggsets.hpp AGG_*)
+__global__ void __launch_bounds__(WAVE) k_aggsets_finish(const uint32_t* __restrict__ final_of, uint32_t k, const uint32_t* __restrict__ part,
+                                                         const uint32_t* __restrict__ seg_bad, const uint32_t* __restrict__ msgs, const uint32_t* __restrict__ sigs,
+                                                         uint32_t* __restrict__ records, uint8_t* __restrict__ status) {
+    uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= k) return;
+    const uint32_t f = final_of[s];
+    const bool empty = f == 0xffffffffu;
+    const aggsets_end e = aggsets_finish_item(empty, seg_bad[s] != 0, empty ? jac_inf<fp>() : ld_g1_int(part + (size_t)f * G1W));
+    uint32_t* r = records + (size_t)s * 80;
+    for (int i = 0; i < 24; i++) r[i] = e.pk[i];
+    for (int i = 0; i < 8; i++) r[24 + i] = msgs[(size_t)s * 8 + i];
+    for (int i = 0; i < 48; i++) r[32 + i] = sigs[(size_t)s * 48 + i];
+    status[s] = e.status;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -235,6 +235,72 @@ inline each_plan each_for(uint32_t slots, bool coop, uint32_t m) {
     return p;
 }
 
+// Per-set key aggregation (mi355_bls_aggregate_sets): k segments of keys in CSR form (segment s = keys [offsets[s], offsets[s + 1])) summed
+// in levels of one-lane items.  A level-0 item reads up to AGG_C consecutive keys of ONE segment and writes one Jacobian partial; an item of a
+// higher level reads up to AGG_C consecutive partials of one segment (all written by the level below) and writes one.  A segment leaves the
+// plan at the level that gives it a single partial, whose index is final_of[s] (AGG_NONE: the segment is empty and has no item at all), so
+// the levels number ceil(log_C(longest segment)), at least one, and the work is sum ceil(len / C) + k however the lengths are spread: 65 536
+// segments of one key are one level of 65 536 items, one segment of 2^20 keys is seven levels of 131 072, 16 384, ... 1 items.
+// Partials are numbered like the items that write them (item i of the table writes partial i: dst == its position), level after level, so
+// the partial buffer holds `items` points and nothing is overwritten while a later level still reads it.
+constexpr uint32_t AGG_C = 8;                // keys / partials per item: the "~8 points per lane" of the single-aggregate sum
+constexpr uint32_t AGG_MAX_LEVELS = 11;      // 8^11 > 2^32 keys
+constexpr uint32_t AGG_NONE = 0xffffffffu;
+static_assert(AGG_C >= 2, "a level must shrink a segment");
+struct agg_item {
+    uint32_t src_first, count, dst, seg;     // level 0: keys src_first .. + count of segment seg; above: partials; -> partial dst
+};
+struct aggsets_plan {
+    bool ok;                                 // false: more than 2^32 - 2 keys or items (the tables are 32-bit), or offsets that decrease
+    uint32_t levels;
+    size_t level_first[AGG_MAX_LEVELS + 1];  // items [level_first[l], level_first[l + 1]) are level l
+    size_t items;                            // = level_first[levels] = the partials the context's buffer must hold
+};
+inline size_t agg_ceil_div(size_t a) { return (a + AGG_C - 1) / AGG_C; }
+// pass 1: the levels and their sizes (offsets: k + 1 entries, non-decreasing)
+inline aggsets_plan aggsets_measure(const size_t* offsets, size_t k) {
+    aggsets_plan p{};
+    size_t per_level[AGG_MAX_LEVELS] = {};
+    for (size_t s = 0; s < k; s++) {
+        if (offsets[s + 1] < offsets[s]) return p;
+        size_t n = offsets[s + 1] - offsets[s];
+        if (offsets[s + 1] >= AGG_NONE) return p;
+        uint32_t l = 0;
+        while (n > 0) {                      // n things (keys, then partials) -> ceil(n / C) partials, until there is one
+            n = agg_ceil_div(n);
+            per_level[l++] += n;
+            if (l > p.levels) p.levels = l;
+            if (n == 1) break;
+        }
+    }
+    for (uint32_t l = 0; l < p.levels; l++) p.level_first[l + 1] = p.level_first[l] + per_level[l];
+    p.items = p.level_first[p.levels];
+    p.ok = p.items < AGG_NONE;
+    return p;
+}
+// pass 2: the item table (p.items entries) and final_of (k entries), one walk over the segments
+inline void aggsets_fill(const aggsets_plan& p, const size_t* offsets, size_t k, agg_item* items, uint32_t* final_of) {
+    size_t cur[AGG_MAX_LEVELS];
+    for (uint32_t l = 0; l < AGG_MAX_LEVELS; l++) cur[l] = l < p.levels ? p.level_first[l] : 0;
+    for (size_t s = 0; s < k; s++) {
+        size_t n = offsets[s + 1] - offsets[s], src = offsets[s];
+        final_of[s] = AGG_NONE;
+        for (uint32_t l = 0; n > 0; l++) {
+            const size_t m = agg_ceil_div(n), base = cur[l];
+            for (size_t j = 0; j < m; j++) {
+                const size_t left = n - j * AGG_C;
+                items[base + j] = agg_item{(uint32_t)(src + j * AGG_C), (uint32_t)(left < AGG_C ? left : AGG_C), (uint32_t)(base + j), (uint32_t)s};
+            }
+            cur[l] += m;
+            src = base, n = m;
+            if (m == 1) {
+                final_of[s] = (uint32_t)base;
+                break;
+            }
+        }
+    }
+}
+
 // chunk of the parallel_chunks partition (parallel_chunks.nim:42-66) that tuple t of n_total falls into, B chunks
 inline uint32_t chunk_of_tuple(size_t n_total, uint32_t B, size_t t) {
     size_t base = n_total / B, rem = n_total % B, cut = (base + 1) * rem;
