@@ -459,6 +459,10 @@ size_t mi355_bls_debug_multi_enqueue_us(float* out, size_t cap);
  * low-latency and the least-work fold of the line products (a batch enqueued while this is zero has the chip to itself).  The tests
  * check that submit / wait / destroy keep it balanced. */
 int mi355_bls_debug_batches_in_flight(void);
+/* Device buffers, events, streams and pinned host buffers the library owns at this moment, over all contexts of the process (the lanes of
+ * sliced calls and the lazily made workspaces included).  The tests check that destroying a context brings it back to where it was before
+ * the context was created, whatever the context was used for. */
+int mi355_bls_debug_live_resources(void);
 /* Which fold of the per-lane line products the LAST batch / shard call on this context enqueued: 1 = the low-latency form on the Fp12 engine
  * (k_fold: latency-mode contexts, and any call enqueued while no other batch of the process was in flight), 0 = the least-work form
  * (k_lineprod2: throughput-mode contexts with other batches in flight).  Same GT bytes either way; profiles and the bench line record it so

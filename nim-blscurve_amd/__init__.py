@@ -140,6 +140,8 @@ def lib():
         L.mi355_bls_p1s_add_device.argtypes = [vp, ctypes.c_char_p, vp, sz, sz, vp]
         L.mi355_bls_debug_fail_next_enqueue.argtypes = [vp]
         L.mi355_bls_debug_batches_in_flight.argtypes = []
+        L.mi355_bls_debug_live_resources.argtypes = []
+        L.mi355_bls_debug_live_resources.restype = i32
         L.mi355_bls_last_fold_form.argtypes = [vp]
         L.mi355_bls_debug_g2_clear_cofactor.argtypes = [vp, cp, sz, cp]
         L.mi355_bls_debug_hash_to_g2.argtypes = [vp, cp, sz, cp, sz, cp]

@@ -3,6 +3,7 @@
 // unit: the kernels it launches live in that file's anonymous namespace); not a stand-alone source.
 #pragma once
 #include "plan.hpp"      // which kernel, what grid, which stream: every size decision of this file
+#include "devres.hpp"    // the owners of device buffers, events, streams and pinned memory
 using plan::SIG_SLOTS_MAX;
 static_assert(plan::WAVE == (uint32_t)WAVE && plan::N_LINES == (uint32_t)N_LINES, "plan.hpp restates the wave size and the Miller loop's step count");
 
@@ -10,25 +11,21 @@ static_assert(plan::WAVE == (uint32_t)WAVE && plan::N_LINES == (uint32_t)N_LINES
 // Context
 // ------------------------------------------------------------------------------------------
 struct msm_ws {
-    size_t cap_n = 0;                 // capacity of d_pts in bytes
-    uint32_t cap_total = 0;
-    uint8_t* d_pts = nullptr;
-    uint8_t* d_sc = nullptr;
-    uint32_t* pts_int = nullptr;
-    uint32_t *hist = nullptr, *offs = nullptr, *cursor = nullptr, *sorted = nullptr, *order = nullptr, *chist = nullptr, *winout = nullptr, *out = nullptr, *part = nullptr, *shist = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_bucketed = nullptr, ev_g[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
-    uint4 *buckets = nullptr, *segout = nullptr;
+    dev_buf<uint8_t> d_pts, d_sc;     // d_pts.bytes is the point capacity; hist.bytes / 4 the bucket capacity (msm_reserve)
+    dev_buf<uint32_t> pts_int;
+    dev_buf<uint32_t> hist, offs, cursor, sorted, order, chist, winout, out, part, shist;
+    dev_event ev_fork, ev_bucketed, ev_g[2], ev_tail[2];
+    dev_buf<uint4> buckets, segout;
 };
-static void msm_free(msm_ws* m) {
-    void* b[] = {m->d_pts, m->d_sc, m->pts_int, m->hist, m->offs, m->cursor, m->sorted, m->order, m->chist, m->winout, m->out, m->buckets, m->segout, m->part, m->shist};
-    for (void* x : b)
-        if (x) (void)hipFree(x);
-    hipEvent_t ev[] = {m->ev_fork, m->ev_bucketed, m->ev_g[0], m->ev_g[1], m->ev_tail[0], m->ev_tail[1]};
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    *m = msm_ws();
-}
 
+// the buffers Miller pairs live in, as the stage launchers take them: a view, it owns nothing
+struct pair_store {
+    uint4 *H, *P, *lines;
+    size_t stride;
+};
+
+// Ownership: the members own (csrc/devres.hpp) and go with the context; views and raw pointers handed to launchers do not.  A routine that
+// grows buffers builds the new ones in locals and swaps them in, so a failure leaves the context as it was.
 struct mi355_bls_ctx {
     int device = 0;
     size_t cap = 0;          // sets the pipeline workspace holds at once (larger batches are sliced)
@@ -37,64 +34,64 @@ struct mi355_bls_ctx {
     uint32_t num_threads = 4096;
     uint32_t nblk_cap = 64;
     // device buffers
-    uint8_t* d_sets = nullptr;       // staging for host-pointer calls
-    uint8_t* d_rnd = nullptr;
-    uint64_t* d_r = nullptr;
-    uint4* d_H = nullptr;
-    uint4* d_M = nullptr;            // the two mapped points per message before cofactor clearing (2 x cap Jacobian slots)
+    dev_buf<uint8_t> d_sets;         // staging for host-pointer calls
+    dev_buf<uint8_t> d_rnd;
+    dev_buf<uint64_t> d_r;
+    dev_buf<uint4> d_H;
+    dev_buf<uint4> d_M;              // the two mapped points per message before cofactor clearing (2 x cap Jacobian slots)
     size_t mstride = 0;
-    uint4* d_P = nullptr;
-    uint4* d_lines = nullptr;
-    uint8_t* d_pktab = nullptr;      // k_pkmul's window tables: 8 multiples of the key with Z^2, Z^3 per set (PKTAB_BYTES each)
+    dev_buf<uint4> d_P;
+    dev_buf<uint4> d_lines;
+    dev_buf<uint8_t> d_pktab;        // k_pkmul's window tables: 8 multiples of the key with Z^2, Z^3 per set (PKTAB_BYTES each)
     // bucket fold of the signatures (batches of >= SIG_BUCKET_MIN tuples)
-    uint32_t* d_sig_pts = nullptr;   // signatures in the device representation, cap x 4 x FPW words
-    uint32_t* d_sig_sorted = nullptr;// counting sort by digit: nwin x cap tuple indices
-    uint32_t* d_sig_hist = nullptr;  // 3 x SIG_SLOTS_MAX: histogram, offsets, cursors
-    uint32_t* d_sig_consts = nullptr;// -[d 2^(cw)]G1 for the window widths c = 4 and c = 8
+    dev_buf<uint32_t> d_sig_pts;     // signatures in the device representation, cap x 4 x FPW words
+    dev_buf<uint32_t> d_sig_sorted;  // counting sort by digit: nwin x cap tuple indices
+    dev_buf<uint32_t> d_sig_hist;    // 3 x SIG_SLOTS_MAX: histogram, offsets, cursors
+    dev_buf<uint32_t> d_sig_consts;  // -[d 2^(cw)]G1 for the window widths c = 4 and c = 8
     uint32_t sig_c = 0, sig_slots = 0; // window width / bucket slots of the last batch (0: per-tuple multiplications)
     bool agg_valid = false;
-    uint32_t* d_agg = nullptr;
-    uint32_t* d_agg1 = nullptr;      // G1 aggregate (blst_p1 image)
-    uint8_t* d_msg = nullptr;        // message (<= 4096 B) + signature staging
-    uint8_t* d_comp = nullptr;       // compressed wire-format staging: cap x (48 + 32 + 96) bytes
-    uint8_t* d_status = nullptr;     // per-tuple deserialisation status
-    hipEvent_t ev_deser0 = nullptr, ev_deser1 = nullptr;
+    dev_buf<uint32_t> d_agg;
+    dev_buf<uint32_t> d_agg1;        // G1 aggregate (blst_p1 image)
+    dev_buf<uint8_t> d_msg;          // message (<= 4096 B) + signature staging
+    dev_buf<uint8_t> d_comp;         // compressed wire-format staging: cap x (48 + 32 + 96) bytes
+    dev_buf<uint8_t> d_status;       // per-tuple deserialisation status
+    dev_event ev_deser0, ev_deser1;
     float deser_ms = 0.f;
-    uint32_t* d_lpart = nullptr;
-    uint32_t* d_L = nullptr;
-    uint32_t* d_states = nullptr;    // up to 64 committed states (slot 0 = own)
-    uint32_t* d_gt = nullptr;
-    uint32_t* d_blob = nullptr;      // shard state + ok word for the device-resident exchange (MI355_BLS_BLOB_BYTES)
+    dev_buf<uint32_t> d_lpart;
+    dev_buf<uint32_t> d_L;
+    dev_buf<uint32_t> d_states;      // up to 64 committed states (slot 0 = own)
+    dev_buf<uint32_t> d_gt;
+    dev_buf<uint32_t> d_blob;        // shard state + ok word for the device-resident exchange (MI355_BLS_BLOB_BYTES)
     uint32_t* d_blob_out = nullptr;  // where shard submits write the blob: d_blob, or a caller's device buffer (set_shard_blob_device)
     bool fv_pending = false;         // a finalverify_blobs submit has not been waited for
     hipStream_t fv_stream = nullptr;
-    uint32_t* d_flags = nullptr;     // [0] = update-failed flag, [1] = verdict, [2] = some tuple failed to deserialise / sign, [3] = verdict of finalverify_blobs
+    dev_buf<uint32_t> d_flags;       // [0] = update-failed flag, [1] = verdict, [2] = some tuple failed to deserialise / sign, [3] = verdict of finalverify_blobs
                                      // (a word and a GT buffer of its own: a blob merge may be in flight on another stream while this context takes the next shard)
-    uint32_t* d_gt_fv = nullptr;     // GT of the last finalverify_blobs
+    dev_buf<uint32_t> d_gt_fv;       // GT of the last finalverify_blobs
     bool gt_is_fv = false;           // fetch_stage(4): the last GT came from finalverify_blobs
-    uint32_t* d_carry = nullptr;     // 2 x 8 seed words: blinding-chain state of the chunk that a slice boundary cuts (capacity-free batches)
+    dev_buf<uint32_t> d_carry;       // 2 x 8 seed words: blinding-chain state of the chunk that a slice boundary cuts (capacity-free batches)
     bool fail_next_enqueue = false;  // test hook (mi355_bls_debug_fail_next_enqueue)
-    uint32_t* h_flags = nullptr;     // pinned host copy of d_flags[0..1] (asynchronous submit / wait)
+    pinned_words h_flags;            // pinned host copy of d_flags[0..1] (asynchronous submit / wait)
     bool pending = false;            // a submitted batch has not been waited for yet
     bool alone = false;              // this call was enqueued while no other batch of the process was in flight (see g_in_flight)
     int fold_form = -1;              // the fold the last call enqueued: 1 = k_fold (Fp12 engine), 0 = k_lineprod2 (mi355_bls_last_fold_form)
     bool coop = true;                // small batches: lane-cooperative kernels (latency) instead of one lane per item (throughput)
     bool wide_recorded = false;      // ev_lp (end of the whole-chip kernels) has been recorded at least once
-    hipStream_t pending_stream = nullptr;
-    hipStream_t side = nullptr;      // fork / join stream of latency-mode calls (independent stages beside each other)
-    hipStream_t side2 = nullptr;     // a second one: [r]PK of a small batch beside its signature side (both beside the hashing)
-    uint32_t* d_export = nullptr;
-    hipEvent_t ev[9] = {};
+    hipStream_t pending_stream = nullptr;      // the caller's: not owned
+    dev_stream side;                 // fork / join stream of latency-mode calls (independent stages beside each other)
+    dev_stream side2;                // a second one: [r]PK of a small batch beside its signature side (both beside the hashing)
+    dev_buf<uint32_t> d_export;
+    dev_event ev[9];
     // A batch larger than the workspace runs in slices; the slices of ONE call are pipelined over up to three workspaces - this
     // context's and two internal ones (lanes), created at the first sliced call, each on a stream of its own - like the batches of
     // three callers (run_shard).
-    mi355_bls_ctx* lane[2] = {nullptr, nullptr};
-    hipStream_t lane_st[2] = {nullptr, nullptr};
-    hipEvent_t lane_ev[2] = {nullptr, nullptr};
-    hipEvent_t ev_sl0 = nullptr, ev_blind[3] = {nullptr, nullptr, nullptr};
+    std::unique_ptr<mi355_bls_ctx> lane[2];
+    dev_stream lane_st[2];
+    dev_event lane_ev[2];
+    dev_event ev_sl0, ev_blind[3];
     bool is_lane = false;
-    hipEvent_t ev_hm = nullptr, ev_lp = nullptr;   // inside the hash stage (after k_hash_map) and the line-product stage (after k_lineprod)
-    hipEvent_t ev_s0 = nullptr, ev_l0 = nullptr;   // start of the signature side (on its stream) and of the tuple pairs' Miller lines: the stage timers of forked calls
+    dev_event ev_hm, ev_lp;       // inside the hash stage (after k_hash_map) and the line-product stage (after k_lineprod)
+    dev_event ev_s0, ev_l0;       // start of the signature side (on its stream) and of the tuple pairs' Miller lines: the stage timers of forked calls
     float ktimes[4] = {};         // k_hash_map, k_hash_clear, k_lineprod, k_lineprod2 of the last batch call
     uint32_t slots = 1024;        // wave slots at one wave per SIMD: 4 x CUs
     size_t last_n = 0;
@@ -103,30 +100,46 @@ struct mi355_bls_ctx {
     dst_t dst;
     xmd32_consts xmd;                // message-independent SHA-256 words of expand_message_xmd for this DST
     std::vector<uint64_t> h_r;       // host-computed scalar chains (serial blinding chain, combine)
-    msm_ws* msm = nullptr;           // lazily sized MSM workspace
+    msm_ws msm;                      // lazily sized MSM workspace
     std::vector<uint8_t> av_pks, av_msgs;      // streaming aggregateVerify (mi355_bls_aggv_*): the pairs collected so far
     std::vector<uint32_t> av_offs;
     bool av_failed = false;
-    msm_ws* msm2 = nullptr;          // a second one: combine runs its G1 and its G2 Pippenger side by side
+    msm_ws msm2;                     // a second one: combine runs its G1 and its G2 Pippenger side by side
     // per-set verification (mi355_bls_verify_each): one verdict byte per set of the call, and the values of the debug hook; grown on demand
-    uint8_t* d_each_v = nullptr;
-    uint32_t* d_each_gt = nullptr;
-    size_t each_cap_v = 0, each_cap_gt = 0;
-    uint4 *d_each_H = nullptr, *d_each_P = nullptr, *d_each_lines = nullptr;      // pairs of a slice: 2 x cap, made at the first per-set call
-    uint32_t* d_each_work = nullptr; // the engine form's step values and results, one block per workgroup
+    dev_buf<uint8_t> d_each_v;
+    dev_buf<uint32_t> d_each_gt;
+    dev_buf<uint4> d_each_H, d_each_P, d_each_lines;      // pairs of a slice: 2 x cap, made at the first per-set call
+    dev_buf<uint32_t> d_each_work;   // the engine form's step values and results, one block per workgroup
     size_t each_stride = 0;
     int each_passes = 0;             // per-set passes made on this context (mi355_bls_debug_verify_each_passes)
-    // per-set key aggregation (mi355_bls_aggregate_sets): sized by the call, grown on demand (agg_grow), never by max_sets
-    uint32_t* d_agg_part = nullptr;  // the plan's partials, G1W words each
-    uint32_t* d_agg_tab = nullptr;   // item table | final_of, as agg_tab holds them
-    uint32_t* d_agg_bad = nullptr;   // per segment: an index was out of range
-    uint8_t* d_agg_status = nullptr; // per segment: the status byte
-    uint8_t* d_agg_rec = nullptr;    // the records of the forms that verify them (and of the host form)
-    uint8_t* d_agg_in = nullptr;     // host inputs staged: keys | signatures | messages | indices
-    size_t agg_cap_part = 0, agg_cap_tab = 0, agg_cap_bad = 0, agg_cap_status = 0, agg_cap_rec = 0, agg_cap_in = 0;      // bytes
+    // per-set key aggregation (mi355_bls_aggregate_sets): sized by the call, grown on demand (reserve with a quarter of slack), never by max_sets
+    dev_buf<uint32_t> d_agg_part;    // the plan's partials, G1W words each
+    dev_buf<uint32_t> d_agg_tab;     // item table | final_of, as agg_tab holds them
+    dev_buf<uint32_t> d_agg_bad;     // per segment: an index was out of range
+    dev_buf<uint8_t> d_agg_status;   // per segment: the status byte
+    dev_buf<uint8_t> d_agg_rec;      // the records of the forms that verify them (and of the host form)
+    dev_buf<uint8_t> d_agg_in;       // host inputs staged: keys | signatures | messages | indices
     std::vector<uint32_t> agg_tab;   // the table of the call in flight: the async copy reads it
     std::vector<uint8_t> agg_status_h;
+
+    // the batch workspace's pair store (ctx_build makes it; it never changes) and the per-set path's (each_reserve)
+    pair_store batch_pairs() const { return {d_H, d_P, d_lines, stride}; }
+    pair_store each_pairs() const { return {d_each_H, d_each_P, d_each_lines, each_stride}; }
+    // the lanes' streams drain before anything they use goes; then the lanes; then the members, in reverse order
+    ~mi355_bls_ctx() {
+        (void)hipSetDevice(device);
+        for (int k = 0; k < 2; k++) {
+            if (lane_st[k]) (void)hipStreamSynchronize(lane_st[k]);
+            lane_st[k].reset();
+            lane[k].reset();
+        }
+    }
 };
+// one batch per context at a time: every entry point that enqueues on a context refuses while a submitted batch is unwaited
+static bool ctx_busy(const mi355_bls_ctx* c) {
+    if (c->pending) g_err = "a batch submitted on this context has not been waited for";
+    return c->pending;
+}
 
 constexpr size_t PKTAB_BYTES = 8 * 5 * 64;   // per set: 8 table entries x (X, Y, Z, Z^2, Z^3) x 64 bytes (tools/gen_pkmul_asm.py LANE_BYTES)
 
@@ -142,16 +155,8 @@ static bool ensure_side(mi355_bls_ctx* c) {
     if (c->side && c->side2) return true;
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
-    for (hipStream_t* sp : {&c->side, &c->side2}) {
-        if (*sp) continue;
-        if (hipStreamCreateWithPriority(sp, hipStreamNonBlocking, greatest) != hipSuccess) {
-            (void)hipGetLastError();
-            if (hipStreamCreateWithFlags(sp, hipStreamNonBlocking) != hipSuccess) {
-                (void)hipGetLastError();
-                *sp = nullptr;
-            }
-        }
-    }
+    for (dev_stream* sp : {&c->side, &c->side2})
+        if (!*sp) (void)sp->create(&greatest);
     return c->side != nullptr;         // side2 missing: [r]PK shares the first fork stream
 }
 
@@ -192,51 +197,16 @@ extern "C" int mi355_bls_last_fold_form(mi355_bls_ctx* c) { return c ? c->fold_f
 #define BLS_STR(x) BLS_STR2(x)
 extern "C" const char* mi355_bls_build_info(void) { return "aligned=" BLS_STR(BLS_BUILD_ALIGNED) " dpp_combine=off stamp=" BLS_BUILD_STAMP; }
 
+extern "C" int mi355_bls_debug_live_resources(void) { return g_live_resources.load(std::memory_order_relaxed); }
 extern "C" void mi355_bls_ctx_destroy(mi355_bls_ctx* c) {
     if (!c) return;
     if (c->pending) g_in_flight.fetch_sub(1, std::memory_order_relaxed);      // destroyed with a batch submitted and never waited for
-    (void)hipSetDevice(c->device);
-    for (int k = 0; k < 2; k++) {
-        if (c->lane_st[k]) {
-            (void)hipStreamSynchronize(c->lane_st[k]);
-            (void)hipStreamDestroy(c->lane_st[k]);
-        }
-        if (c->lane_ev[k]) (void)hipEventDestroy(c->lane_ev[k]);
-        if (c->lane[k]) mi355_bls_ctx_destroy(c->lane[k]);
-    }
-    if (c->ev_sl0) (void)hipEventDestroy(c->ev_sl0);
-    for (auto& e : c->ev_blind)
-        if (e) (void)hipEventDestroy(e);
-    void* bufs[] = {c->d_sets, c->d_rnd, c->d_r, c->d_H, c->d_M, c->d_P, c->d_lines, c->d_pktab, c->d_sig_pts, c->d_sig_sorted, c->d_sig_hist, c->d_sig_consts, c->d_agg, c->d_agg1, c->d_msg, c->d_comp, c->d_status, c->d_lpart, c->d_L, c->d_states, c->d_gt, c->d_gt_fv, c->d_carry, c->d_blob, c->d_flags, c->d_export, c->d_each_v, c->d_each_gt, c->d_each_H, c->d_each_P, c->d_each_lines, c->d_each_work, c->d_agg_part, c->d_agg_tab, c->d_agg_bad, c->d_agg_status, c->d_agg_rec, c->d_agg_in};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (c->h_flags) (void)hipHostFree(c->h_flags);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->side2) (void)hipStreamDestroy(c->side2);
-    for (auto& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_hm) (void)hipEventDestroy(c->ev_hm);
-    if (c->ev_lp) (void)hipEventDestroy(c->ev_lp);
-    if (c->ev_s0) (void)hipEventDestroy(c->ev_s0);
-    if (c->ev_l0) (void)hipEventDestroy(c->ev_l0);
-    if (c->ev_deser0) (void)hipEventDestroy(c->ev_deser0);
-    if (c->ev_deser1) (void)hipEventDestroy(c->ev_deser1);
-    if (c->msm2) {
-        msm_free(c->msm2);
-        delete c->msm2;
-    }
-    if (c->msm) {
-        msm_free(c->msm);
-        delete c->msm;
-    }
     delete c;
 }
 
 // everything of ctx_create that can fail after the context object exists: any failure destroys it (no leaked device buffers)
 static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     c->device = device;
-    c->msm = new msm_ws();
-    c->msm2 = new msm_ws();
     c->cap = max_sets;
     c->cap_io = max_sets;
     c->stride = ((max_sets + 1 + SIG_SLOTS_MAX + 63) / 64) * 64;          // tuple pairs + the extra pair(s) of the signature side
@@ -254,45 +224,42 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     if (nblk > 64) nblk = 64;
     if (nblk > nwaves) nblk = (uint32_t)nwaves;
     c->nblk_cap = nblk;
-#define ALLOC(p, bytes) HIPCHK(hipMalloc((void**)&(p), (bytes)))
-    ALLOC(c->d_sets, max_sets * 320);
-    ALLOC(c->d_rnd, 32);
-    ALLOC(c->d_r, c->stride * 8);
-    ALLOC(c->d_H, c->stride * 6 * 64);
     c->mstride = ((2 * max_sets + 63) / 64) * 64;
-    ALLOC(c->d_M, c->mstride * 6 * 64);
-    ALLOC(c->d_P, c->stride * 3 * 64);
-    ALLOC(c->d_lines, c->stride * 6 * 64 * (size_t)N_LINES);
-    ALLOC(c->d_pktab, max_sets * PKTAB_BYTES);
-    ALLOC(c->d_sig_pts, max_sets * 4 * FPW * 4);
-    ALLOC(c->d_sig_sorted, max_sets * 16 * 4);
-    ALLOC(c->d_sig_hist, 3 * SIG_SLOTS_MAX * 4);
-    ALLOC(c->d_sig_consts, 2 * SIG_SLOTS_MAX * G1W * 4);
-    ALLOC(c->d_agg, 288);
-    ALLOC(c->d_agg1, 144);
-    ALLOC(c->d_msg, 4096 + 192 + 64 + 288);      // message | affine signature | pad | Jacobian signature (AggregateSignature overloads)
-    ALLOC(c->d_comp, max_sets * 320);          // wire-format staging: keys (<= 96 B) | messages (32 B) | signatures (<= 192 B)
-    ALLOC(c->d_status, max_sets);
-    ALLOC(c->d_lpart, (size_t)N_LINES * (c->nblk_cap * (WAVE + 1) + 64) * F12W * 4);     // per-lane partial products of k_lineprod (+ k_fold's first-level results)
-    ALLOC(c->d_L, (size_t)N_LINES * F12W * 4);
-    ALLOC(c->d_states, 64 * 576);
-    ALLOC(c->d_gt, 576);
-    ALLOC(c->d_gt_fv, 576);
-    ALLOC(c->d_carry, 64);
-    ALLOC(c->d_blob, MI355_BLS_BLOB_BYTES);
+    int rc = 0;                                    // the first failure: nothing is created behind it
+    const auto alloc = [&rc](auto& buf, size_t bytes) { rc = rc ? rc : buf.alloc(bytes); };
+    alloc(c->d_sets, max_sets * 320);
+    alloc(c->d_rnd, 32);
+    alloc(c->d_r, c->stride * 8);
+    alloc(c->d_H, c->stride * 6 * 64);
+    alloc(c->d_M, c->mstride * 6 * 64);
+    alloc(c->d_P, c->stride * 3 * 64);
+    alloc(c->d_lines, c->stride * 6 * 64 * (size_t)N_LINES);
+    alloc(c->d_pktab, max_sets * PKTAB_BYTES);
+    alloc(c->d_sig_pts, max_sets * 4 * FPW * 4);
+    alloc(c->d_sig_sorted, max_sets * 16 * 4);
+    alloc(c->d_sig_hist, 3 * SIG_SLOTS_MAX * 4);
+    alloc(c->d_sig_consts, 2 * SIG_SLOTS_MAX * G1W * 4);
+    alloc(c->d_agg, 288);
+    alloc(c->d_agg1, 144);
+    alloc(c->d_msg, 4096 + 192 + 64 + 288);      // message | affine signature | pad | Jacobian signature (AggregateSignature overloads)
+    alloc(c->d_comp, max_sets * 320);          // wire-format staging: keys (<= 96 B) | messages (32 B) | signatures (<= 192 B)
+    alloc(c->d_status, max_sets);
+    alloc(c->d_lpart, (size_t)N_LINES * (c->nblk_cap * (WAVE + 1) + 64) * F12W * 4);     // per-lane partial products of k_lineprod (+ k_fold's first-level results)
+    alloc(c->d_L, (size_t)N_LINES * F12W * 4);
+    alloc(c->d_states, 64 * 576);
+    alloc(c->d_gt, 576);
+    alloc(c->d_gt_fv, 576);
+    alloc(c->d_carry, 64);
+    alloc(c->d_blob, MI355_BLS_BLOB_BYTES);
+    alloc(c->d_flags, 16);
+    alloc(c->d_export, c->stride * 288 + 2048 * 2 * G1W * 4);
+    if (rc) return rc;
     c->d_blob_out = c->d_blob;
-    ALLOC(c->d_flags, 16);
-    ALLOC(c->d_export, c->stride * 288 + 2048 * 2 * G1W * 4);
-#undef ALLOC
     (void)ensure_side(c);                          // the fork streams (a context without them still works: nothing forks)
-    HIPCHK(hipHostMalloc((void**)&c->h_flags, 1024, hipHostMallocDefault));    // words 0..3 flags, 4..11 staging copy of rnd, 16..159 shard state
-    for (auto& e : c->ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventCreate(&c->ev_hm));
-    HIPCHK(hipEventCreate(&c->ev_lp));
-    HIPCHK(hipEventCreate(&c->ev_s0));
-    HIPCHK(hipEventCreate(&c->ev_l0));
-    HIPCHK(hipEventCreate(&c->ev_deser0));
-    HIPCHK(hipEventCreate(&c->ev_deser1));
+    rc = c->h_flags.alloc(1024);                   // words 0..3 flags, 4..11 staging copy of rnd, 16..159 shard state
+    for (auto& e : c->ev) rc = rc ? rc : e.create();
+    for (dev_event* e : {&c->ev_hm, &c->ev_lp, &c->ev_s0, &c->ev_l0, &c->ev_deser0, &c->ev_deser1}) rc = rc ? rc : e->create();
+    if (rc) return rc;
     k_sig_consts<<<(256 + WAVE - 1) / WAVE, WAVE>>>(4, 256, c->d_sig_consts);
     k_sig_consts<<<(2048 + WAVE - 1) / WAVE, WAVE>>>(8, 2048, c->d_sig_consts + (size_t)SIG_SLOTS_MAX * G1W);
     HIPCHK(hipGetLastError());
@@ -310,15 +277,10 @@ extern "C" int mi355_bls_ctx_create(mi355_bls_ctx** out, int device, size_t max_
         return MI355_BLS_ERR_HIP;
     }
     HIPCHK(hipSetDevice(device));
-    auto* c = new mi355_bls_ctx();
-    int rc = ctx_build(c, device, max_sets);
-    if (rc) {
-        std::string keep = g_err;
-        mi355_bls_ctx_destroy(c);
-        g_err = keep;
-        return rc;
-    }
-    *out = c;
+    std::unique_ptr<mi355_bls_ctx> c(new mi355_bls_ctx());
+    int rc = ctx_build(c.get(), device, max_sets);
+    if (rc) return rc;                             // the context goes, with whatever it had got; g_err stays
+    *out = c.release();
     return 0;
 }
 
@@ -327,41 +289,26 @@ extern "C" int mi355_bls_ctx_create(mi355_bls_ctx** out, int device, size_t max_
 // point refuses an input for its size.  (The pipeline workspace itself stays at max_sets: larger batches are sliced, run_shard.)
 static int io_reserve(mi355_bls_ctx* c, size_t n) {
     if (n <= c->cap_io) return 0;
-    if (c->pending) {
-        g_err = "a batch submitted on this context has not been waited for";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     size_t want = n + n / 4;
     HIPCHK(hipSetDevice(c->device));
-    // the new buffers first: if one allocation fails the context keeps its old buffers and capacity (entry points that take
+    // the new buffers first, in locals: if one allocation fails the context keeps its old buffers and capacity (entry points that take
     // device-resident input never come through here and would otherwise launch on null pointers)
-    void* nb[4] = {nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[4] = {want * 320, want * 320, want, (want > c->stride ? want : c->stride) * 8};
-    for (int i = 0; i < 4; i++) {
-        hipError_t e = hipMalloc(&nb[i], bytes[i]);
-        if (e != hipSuccess) {
-            for (int j = 0; j < i; j++) (void)hipFree(nb[j]);
-            g_err = std::string("io_reserve: hipMalloc: ") + hipGetErrorString(e);
-            return MI355_BLS_ERR_HIP;
-        }
-    }
+    dev_buf<uint8_t> sets, comp, status;
+    dev_buf<uint64_t> r;
+    int rc = sets.alloc(want * 320);
+    if (!rc) rc = comp.alloc(want * 320);
+    if (!rc) rc = status.alloc(want);
+    if (!rc) rc = r.alloc((want > c->stride ? want : c->stride) * 8);
+    if (rc) return rc;
     // only this context's own work can still read the old buffers, and no call is pending (checked above; blocking calls return after
     // their stream has drained): the fork stream and the stream of the last call are waited for, never the whole device (other
     // contexts keep running)
     // (pending_stream is cleared by every wait: a handle kept from an earlier call may belong to a stream the host has destroyed since)
-    hipError_t se = c->side ? hipStreamSynchronize(c->side) : hipSuccess;
-    if (se == hipSuccess && c->side2) se = hipStreamSynchronize(c->side2);
-    if (se == hipSuccess && c->pending_stream) se = hipStreamSynchronize(c->pending_stream);
-    if (se != hipSuccess) {
-        for (int i = 0; i < 4; i++) (void)hipFree(nb[i]);
-        g_err = std::string("io_reserve: hipStreamSynchronize: ") + hipGetErrorString(se);
-        return MI355_BLS_ERR_HIP;
-    }
-    void** bufs[] = {(void**)&c->d_sets, (void**)&c->d_comp, (void**)&c->d_status, (void**)&c->d_r};
-    for (int i = 0; i < 4; i++) {
-        if (*bufs[i]) (void)hipFree(*bufs[i]);
-        *bufs[i] = nb[i];
-    }
+    if (c->side) HIPCHK(hipStreamSynchronize(c->side));
+    if (c->side2) HIPCHK(hipStreamSynchronize(c->side2));
+    if (c->pending_stream) HIPCHK(hipStreamSynchronize(c->pending_stream));
+    c->d_sets.swap(sets), c->d_comp.swap(comp), c->d_status.swap(status), c->d_r.swap(r);      // the old ones go with the locals
     c->cap_io = want;
     return 0;
 }
@@ -375,20 +322,20 @@ static void launch_hash_map(mi355_bls_ctx* c, const uint8_t* d_sets, uint32_t n3
         case plan::HASH_MAP_PLAIN: k_hash_map<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride); break;
     }
 }
-// d_M (two mapped points per message) -> d_H = H(m_i): the engine, then the (all but always idle) pass that recomputes a message whose
+// d_M (two mapped points per message) -> ps.H = H(m_i): the engine, then the (all but always idle) pass that recomputes a message whose
 // incomplete additions met an exceptional case; or k_hash_clear
-static void launch_hash_clear(mi355_bls_ctx* c, uint32_t n32, hipStream_t st) {
+static void launch_hash_clear(mi355_bls_ctx* c, const pair_store& ps, uint32_t n32, hipStream_t st) {
     const plan::stage p = plan::clear_for(c->slots, c->coop, n32);
     if (p.team) {
         switch (p.form) {       // the lane-team engine (16 lanes per message, csrc/teamvm.hpp)
-            case plan::TEAM_ROWS: k_team_clear_rows<<<p.grid, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
-            case plan::TEAM_ROWS2: k_team_clear_rows2<<<p.grid, 256, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
-            case plan::TEAM_SPREAD: k_team_clear_spread<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;      // one wave per SIMD (see the kernel)
-            case plan::TEAM_WIDE: k_team_clear<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride); break;
+            case plan::TEAM_ROWS: k_team_clear_rows<<<p.grid, 256, 0, st>>>(c->d_M, c->mstride, n32, ps.H, ps.stride); break;
+            case plan::TEAM_ROWS2: k_team_clear_rows2<<<p.grid, 256, 0, st>>>(c->d_M, c->mstride, n32, ps.H, ps.stride); break;
+            case plan::TEAM_SPREAD: k_team_clear_spread<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, ps.H, ps.stride); break;      // one wave per SIMD (see the kernel)
+            case plan::TEAM_WIDE: k_team_clear<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, ps.H, ps.stride); break;
         }
-        k_clear_fix<<<plan::waves_for(n32), WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride);
+        k_clear_fix<<<plan::waves_for(n32), WAVE, 0, st>>>(c->d_M, c->mstride, n32, ps.H, ps.stride);
     } else {
-        k_hash_clear<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, c->d_H, c->stride, c->d_lines);
+        k_hash_clear<<<p.grid, WAVE, 0, st>>>(c->d_M, c->mstride, n32, ps.H, ps.stride, ps.lines);
     }
 }
 
@@ -397,24 +344,18 @@ static void launch_hash_clear(mi355_bls_ctx* c, uint32_t n32, hipStream_t st) {
 // lets the tests put points through them that no hash produces
 extern "C" int mi355_bls_debug_g2_clear_cofactor(mi355_bls_ctx* c, const uint8_t* in_pairs, size_t n, uint8_t* out_p2) {
     if (!c || !in_pairs || !out_p2 || n == 0 || n > c->cap) return MI355_BLS_ERR_ARG;
-    if (c->pending) {
-        g_err = "a batch submitted on this context has not been waited for";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    uint32_t* d_in = nullptr;
-    HIPCHK(hipMalloc((void**)&d_in, n * 576));
-    hipError_t e = hipMemcpy(d_in, in_pairs, n * 576, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const uint32_t n32 = (uint32_t)n;
-        k_debug_to_soa<<<(2 * n32 + WAVE - 1) / WAVE, WAVE>>>(d_in, 2 * n32, c->d_M, c->mstride);
-        launch_hash_clear(c, n32, nullptr);                       // the kernels the batch path would launch for this context and size
-        k_export_g2<<<(n32 + 63) / 64, 64>>>(c->d_H, c->stride, n32, c->d_export);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_p2, c->d_export, n * 288, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    HIPCHK(e);
+    dev_buf<uint32_t> d_in;
+    if (int rc = d_in.alloc(n * 576)) return rc;
+    HIPCHK(hipMemcpy(d_in, in_pairs, n * 576, hipMemcpyHostToDevice));
+    const pair_store ps = c->batch_pairs();
+    const uint32_t n32 = (uint32_t)n;
+    k_debug_to_soa<<<(2 * n32 + WAVE - 1) / WAVE, WAVE>>>(d_in, 2 * n32, c->d_M, c->mstride);
+    launch_hash_clear(c, ps, n32, nullptr);                       // the kernels the batch path would launch for this context and size
+    k_export_g2<<<(n32 + 63) / 64, 64>>>(ps.H, ps.stride, n32, c->d_export);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out_p2, c->d_export, n * 288, hipMemcpyDeviceToHost));      // blocking: d_in is idle when it goes
     return 0;
 }
 
@@ -423,10 +364,7 @@ extern "C" int mi355_bls_debug_g2_clear_cofactor(mi355_bls_ctx* c, const uint8_t
 // tests hold the device against published hash-to-curve vectors, whose DST is not the signature scheme's.
 extern "C" int mi355_bls_debug_hash_to_g2(mi355_bls_ctx* c, const uint8_t* msg, size_t msg_len, const uint8_t* dst, size_t dst_len, uint8_t out_p2[288]) {
     if (!c || (!msg && msg_len) || !dst || dst_len == 0 || dst_len > 64 || msg_len > 4096 || !out_p2) return MI355_BLS_ERR_ARG;
-    if (c->pending) {
-        g_err = "a batch submitted on this context has not been waited for";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     dst_t d;
     std::memset(&d, 0, sizeof(d));
@@ -434,8 +372,9 @@ extern "C" int mi355_bls_debug_hash_to_g2(mi355_bls_ctx* c, const uint8_t* msg, 
     std::memcpy(d.b, dst, dst_len);
     const xmd32_consts xc = xmd32_precompute(d.b, d.len);
     if (msg_len) HIPCHK(hipMemcpy(c->d_msg, msg, msg_len, hipMemcpyHostToDevice));
-    k_hash_one<<<1, 256>>>(c->d_msg, (uint32_t)msg_len, d, xc, c->d_H, c->stride, 0);
-    k_export_g2<<<1, 64>>>(c->d_H, c->stride, 1, c->d_export);
+    const pair_store ps = c->batch_pairs();
+    k_hash_one<<<1, 256>>>(c->d_msg, (uint32_t)msg_len, d, xc, ps.H, ps.stride, 0);
+    k_export_g2<<<1, 64>>>(ps.H, ps.stride, 1, c->d_export);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out_p2, c->d_export, 288, hipMemcpyDeviceToHost));
     return 0;
@@ -513,37 +452,37 @@ static void host_combine_chain(const uint8_t rnd[32], size_t n, uint64_t* out) {
 }
 
 // k_tail for this context: latency mode takes the form with the cyclotomic squarings on row arithmetic (five waves), throughput mode the engine's three
-template <class... A>
-static inline void launch_k_tail(const mi355_bls_ctx* c, hipStream_t st, A... a) {
-    if (c->coop) k_tail_rows<<<1, K_TAIL_THREADS, 0, st>>>(a...);
-    else k_tail<<<1, TAIL_THREADS, 0, st>>>(a...);
+static inline void launch_k_tail(const mi355_bls_ctx* c, hipStream_t st, const uint32_t* L, uint32_t* states, uint32_t kk, int mode, uint32_t* gt_out,
+                                 uint32_t* verdict, uint32_t sstride, int blob) {
+    if (c->coop) k_tail_rows<<<1, K_TAIL_THREADS, 0, st>>>(L, states, kk, mode, gt_out, verdict, sstride, blob);
+    else k_tail<<<1, TAIL_THREADS, 0, st>>>(L, states, kk, mode, gt_out, verdict, sstride, blob);
 }
 // the Miller lines of pairs first .. first + count - 1 as `t` says: on the lane-team engine or one lane each (k_lines)
-static void launch_lines_at(mi355_bls_ctx* c, const plan::stage& t, uint32_t first, uint32_t count, hipStream_t st) {
+static void launch_lines_at(const pair_store& ps, const plan::stage& t, uint32_t first, uint32_t count, hipStream_t st) {
     if (!t.team) {
-        k_lines<<<t.grid, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines);
+        k_lines<<<t.grid, WAVE, 0, st>>>(ps.P, ps.H, first, count, ps.stride, ps.lines);
         return;
     }
     switch (t.form) {
-        case plan::TEAM_ROWS: k_team_lines_rows<<<t.grid, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
-        case plan::TEAM_ROWS2: k_team_lines_rows2<<<t.grid, 256, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
-        case plan::TEAM_SPREAD: k_team_lines_spread<<<t.grid, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
-        case plan::TEAM_WIDE: k_team_lines<<<t.grid, WAVE, 0, st>>>(c->d_P, c->d_H, first, count, c->stride, c->d_lines); break;
+        case plan::TEAM_ROWS: k_team_lines_rows<<<t.grid, 256, 0, st>>>(ps.P, ps.H, first, count, ps.stride, ps.lines); break;
+        case plan::TEAM_ROWS2: k_team_lines_rows2<<<t.grid, 256, 0, st>>>(ps.P, ps.H, first, count, ps.stride, ps.lines); break;
+        case plan::TEAM_SPREAD: k_team_lines_spread<<<t.grid, WAVE, 0, st>>>(ps.P, ps.H, first, count, ps.stride, ps.lines); break;
+        case plan::TEAM_WIDE: k_team_lines<<<t.grid, WAVE, 0, st>>>(ps.P, ps.H, first, count, ps.stride, ps.lines); break;
     }
 }
 // pairs 0 .. main_pairs - 1, then the extra pairs behind them where the plan gives them a form of their own (plan.hpp lines_for)
-static void launch_lines(mi355_bls_ctx* c, const plan::lines_plan& p, hipStream_t st) {
-    launch_lines_at(c, p.main, 0, p.main_pairs, st);
-    if (p.extra_pairs) launch_lines_at(c, p.extra, p.main_pairs, p.extra_pairs, st);
+static void launch_lines(const pair_store& ps, const plan::lines_plan& p, hipStream_t st) {
+    launch_lines_at(ps, p.main, 0, p.main_pairs, st);
+    if (p.extra_pairs) launch_lines_at(ps, p.extra, p.main_pairs, p.extra_pairs, st);
 }
 
 // The per-step products of the Miller lines of pairs 0 .. npairs-1 -> d_L (68 step products).  mid_ev: recorded between the wide
 // kernel and the fold of its partials.
-static int enqueue_line_products(mi355_bls_ctx* c, uint32_t npairs, hipStream_t st, hipEvent_t mid_ev) {
+static int enqueue_line_products(mi355_bls_ctx* c, const pair_store& ps, uint32_t npairs, hipStream_t st, hipEvent_t mid_ev) {
     c->fold_form = (c->coop || c->alone) ? 1 : 0;
-    const plan::lineprod_plan p = plan::lineprod_for(c->slots, c->nblk_cap, c->stride, npairs, c->fold_form != 0);
+    const plan::lineprod_plan p = plan::lineprod_for(c->slots, c->nblk_cap, ps.stride, npairs, c->fold_form != 0);
     // every lane hands its partial product over (64 x nblk per step); what folds them: plan.hpp lineprod_for
-    k_lineprod<<<dim3(N_LINES, p.nblk), WAVE, 0, st>>>(c->d_lines, npairs, c->stride, p.m, c->d_lpart, p.nblk, p.per_lane);
+    k_lineprod<<<dim3(N_LINES, p.nblk), WAVE, 0, st>>>(ps.lines, npairs, ps.stride, p.m, c->d_lpart, p.nblk, p.per_lane);
     if (mid_ev) HIPCHK(hipEventRecord(mid_ev, st));
     if (c->fold_form) {
         uint32_t* mid = c->d_lpart + (size_t)N_LINES * c->nblk_cap * WAVE * F12W;
@@ -581,6 +520,7 @@ static int run_slice(mi355_bls_ctx* c, mi355_bls_ctx* p, const uint8_t* d_sets, 
 // products, the committed state of these n tuples in d_states slot 0.
 static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStream_t st) {
     const uint32_t n32 = (uint32_t)n;
+    const pair_store ps = c->batch_pairs();
     HIPCHK(hipEventRecord(c->ev[1], st));
     const plan::slice_plan p = plan::slice_for(c->slots, c->coop, c->coop && ensure_side(c), n);
     const uint32_t nb = p.nb, cw = p.cw, nwin = p.nwin, total = p.total;
@@ -604,11 +544,11 @@ static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStrea
     // ---- hashing (caller's stream)
     launch_hash_map(c, d_sets, n32, st);
     HIPCHK(hipEventRecord(c->ev_hm, st));
-    launch_hash_clear(c, n32, st);
+    launch_hash_clear(c, ps, n32, st);
     HIPCHK(hipEventRecord(c->ev[2], st));
     // ---- [r]PK
-    if (p.pkmul_spread) k_pkmul_spread<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, c->d_P, c->stride, c->d_flags, c->d_pktab);      // one wave per SIMD
-    else k_pkmul<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, c->d_P, c->stride, c->d_flags, c->d_pktab);
+    if (p.pkmul_spread) k_pkmul_spread<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, ps.P, ps.stride, c->d_flags, c->d_pktab);      // one wave per SIMD
+    else k_pkmul<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, ps.P, ps.stride, c->d_flags, c->d_pktab);
     HIPCHK(hipEventRecord(c->ev[3], sd));
     // ---- signature side as a bucket fold: sig_slots extra Miller pairs n .. n + sig_slots - 1 (every batch size: for a
     // handful of tuples the 256 nearly empty buckets are still cheaper than one 64-bit G2 multiplication per tuple, which is a
@@ -619,11 +559,11 @@ static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStrea
         HIPCHK(hipEventRecord(c->ev_s0, ss));
         HIPCHK(hipMemsetAsync(hist, 0, (size_t)total * 4, ss));
         k_sig_convert<<<nb, WAVE, 0, ss>>>(d_sets, n32, c->d_sig_pts);
-        k_msm_hist<<<dim3(nb, nwin), WAVE, 0, ss>>>(reinterpret_cast<const uint8_t*>(c->d_r), 8, n32, W, cw, hist);
+        k_msm_hist<<<dim3(nb, nwin), WAVE, 0, ss>>>(reinterpret_cast<const uint8_t*>(c->d_r.p), 8, n32, W, cw, hist);
         k_msm_scan<<<nwin, WAVE, 0, ss>>>(hist, cw, offs, cursor);
-        k_msm_scatter<<<dim3(nb, nwin), WAVE, 0, ss>>>(reinterpret_cast<const uint8_t*>(c->d_r), 8, n32, W, cw, cursor, c->d_sig_sorted);
+        k_msm_scatter<<<dim3(nb, nwin), WAVE, 0, ss>>>(reinterpret_cast<const uint8_t*>(c->d_r.p), 8, n32, W, cw, cursor, c->d_sig_sorted);
         k_sig_bucket<<<p.bucket_grid, WAVE, 0, ss>>>(c->d_sig_pts, c->d_sig_sorted, offs, hist, n32, cw, p.lshift, total,
-                                                     c->d_sig_consts + (cw == 8 ? (size_t)SIG_SLOTS_MAX * G1W : 0), c->d_H, c->d_P, c->stride, (size_t)n32);
+                                                     c->d_sig_consts + (cw == 8 ? (size_t)SIG_SLOTS_MAX * G1W : 0), ps.H, ps.P, ps.stride, (size_t)n32);
         c->sig_c = cw;
         c->sig_slots = total;
         c->agg_valid = false;
@@ -632,18 +572,18 @@ static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStrea
     uint32_t npairs = n32 + total;
     // the extra pairs' walk on the signature side's stream, beside the hashing (round 6, on the lane-team engine: 512 waves for 0.35 ms instead of 32
     // one-lane waves for 1.9 ms - the signature side is out of the way 1.4 ms earlier and no longer displaces the waves of [r]PK behind the hashing)
-    if (p.extra_apart) launch_lines_at(c, p.extra_lines, n32, total, ss);
+    if (p.extra_apart) launch_lines_at(ps, p.extra_lines, n32, total, ss);
     HIPCHK(hipEventRecord(c->ev[4], ss));
     if (fork) {
         HIPCHK(hipStreamWaitEvent(st, c->ev[4], 0));                    // join: the signature side ...
         HIPCHK(hipStreamWaitEvent(st, c->ev[3], 0));                    // ... and [r]PK
     }
     HIPCHK(hipEventRecord(c->ev_l0, st));
-    launch_lines(c, p.lines, st);                                       // the tuple pairs, and the extra pairs where they did not run apart
+    launch_lines(ps, p.lines, st);                                       // the tuple pairs, and the extra pairs where they did not run apart
     if (fork_sig) HIPCHK(hipStreamWaitEvent(st, c->ev[4], 0));          // join behind the tuple pairs' lines
     HIPCHK(hipEventRecord(c->ev[5], st));
     {
-        int rcp = enqueue_line_products(c, npairs, st, c->ev_lp);
+        int rcp = enqueue_line_products(c, ps, npairs, st, c->ev_lp);
         if (rcp) return rcp;
     }
     c->wide_recorded = true;
@@ -662,34 +602,31 @@ static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStrea
 // and a lane that cannot be created (out of memory: a workspace is ~29 KB per set) is not an error - the slices then run on fewer
 // workspaces, down to this context's own (the serial slice loop of round 3).  Negative: the events every sliced call needs failed.
 static int ensure_lanes(mi355_bls_ctx* c, int want) {
-    if (!c->ev_sl0) HIPCHK(hipEventCreateWithFlags(&c->ev_sl0, hipEventDisableTiming));
-    for (auto& e : c->ev_blind)
-        if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (dev_event* e : {&c->ev_sl0, &c->ev_blind[0], &c->ev_blind[1], &c->ev_blind[2]})
+        if (!*e)
+            if (int rc = e->create(hipEventDisableTiming)) return rc;
     int have = 0;
     for (int k = 0; k < want && k < 2; k++) {
         if (c->lane[k]) {
             have = k + 1;
             continue;
         }
-        mi355_bls_ctx* x = nullptr;
-        hipStream_t s = nullptr;
-        hipEvent_t e = nullptr;
-        if (mi355_bls_ctx_create(&x, c->device, c->cap) != 0) x = nullptr;
-        if (x && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
-        if (x && s && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) e = nullptr;
-        if (!x || !s || !e) {
-            if (e) (void)hipEventDestroy(e);
-            if (s) (void)hipStreamDestroy(s);
-            if (x) mi355_bls_ctx_destroy(x);
+        mi355_bls_ctx* raw = nullptr;
+        dev_stream s;
+        dev_event e;
+        if (mi355_bls_ctx_create(&raw, c->device, c->cap) != 0) raw = nullptr;
+        std::unique_ptr<mi355_bls_ctx> x(raw);
+        if (!x || !s.create() || e.create(hipEventDisableTiming) != 0) {
+            x.reset();                              // what was made goes with the locals
             (void)hipGetLastError();                // an out-of-memory error is sticky until read
             (void)hipSetDevice(c->device);
             break;
         }
         x->is_lane = true;
         x->coop = false;
-        c->lane_st[k] = s;
-        c->lane_ev[k] = e;
-        c->lane[k] = x;
+        c->lane_st[k] = std::move(s);
+        c->lane_ev[k] = std::move(e);
+        c->lane[k] = std::move(x);
         have = k + 1;
     }
     return have;
@@ -740,7 +677,7 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
     }
     HIPCHK(hipEventRecord(c->ev_sl0, st));                     // rnd uploaded, flags cleared
     for (int k = 0; k < nl - 1; k++) {
-        mi355_bls_ctx* x = c->lane[k];
+        mi355_bls_ctx* x = c->lane[k].get();
         x->num_threads = c->num_threads;
         x->dst = c->dst;
         x->xmd = c->xmd;
@@ -755,7 +692,7 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
         size_t t0 = tuple_base + done;
         uint32_t c_lo = serial ? 0 : plan::chunk_of_tuple(n_total, nchunks, t0), c_hi = serial ? 1 : plan::chunk_of_tuple(n_total, nchunks, t0 + cnt - 1) + 1;
         const int L = plan::shard_workspace_of(nslices, slice, nl);                 // the last slice on this context's own workspace
-        mi355_bls_ctx* x = L ? c->lane[L - 1] : c;
+        mi355_bls_ctx* x = L ? c->lane[L - 1].get() : c;
         hipStream_t sx = L ? c->lane_st[L - 1] : st;
         if (slice) {
             if (!serial) HIPCHK(hipStreamWaitEvent(sx, c->ev_blind[(slice - 1) % 3], 0));       // the chain state this slice continues from
@@ -780,7 +717,7 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
     }
     for (int k = 0; k < nl - 1; k++) {
         if (!used[k + 1]) continue;
-        mi355_bls_ctx* x = c->lane[k];
+        mi355_bls_ctx* x = c->lane[k].get();
         HIPCHK(hipEventRecord(c->lane_ev[k], c->lane_st[k]));
         HIPCHK(hipStreamWaitEvent(st, c->lane_ev[k], 0));
         HIPCHK(hipMemcpyAsync(c->d_states + (size_t)(2 + k) * 144, x->d_states + 144, 576, hipMemcpyDeviceToDevice, st));
@@ -817,10 +754,7 @@ static int collect_timings(mi355_bls_ctx* c, int last_ev) {
 static int verify_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, const uint8_t* h_sets, size_t n, const uint8_t rnd[32], int serial, hipStream_t st) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if ((!d_sets && !h_sets) || n == 0) return MI355_BLS_ERR_ARG;
-    if (c->pending) {
-        g_err = "a batch submitted on this context has not been waited for";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     uint32_t B = (uint32_t)(n < c->num_threads ? n : c->num_threads);
     int rc = run_shard(c, d_sets, h_sets, n, B, 0, serial ? 1 : B, 0, n, serial, rnd, st);
     if (rc) return rc;
@@ -893,48 +827,31 @@ extern "C" int mi355_bls_batch_verify_serial(mi355_bls_ctx* c, const void* sets,
 // per-set tail in the form plan::each_for names); the verdict bytes of all slices collect in d_each_v and come back in one copy.
 // ------------------------------------------------------------------------------------------
 static int each_reserve(mi355_bls_ctx* c, size_t n, bool want_gt) {
-    if (n > c->each_cap_v) {
-        if (c->d_each_v) (void)hipFree(c->d_each_v);
-        c->d_each_v = nullptr, c->each_cap_v = 0;
-        HIPCHK(hipMalloc((void**)&c->d_each_v, n + n / 4));
-        c->each_cap_v = n + n / 4;
-    }
-    if (!c->each_stride) {
+    if (int rc = c->d_each_v.reserve(n, n / 4)) return rc;
+    if (!c->each_stride) {      // the pair store: all four buffers or none
         const size_t st = plan::each_stride(c->cap);
-        HIPCHK(hipMalloc((void**)&c->d_each_H, st * 6 * 64));
-        HIPCHK(hipMalloc((void**)&c->d_each_P, st * 3 * 64));
-        HIPCHK(hipMalloc((void**)&c->d_each_lines, st * 6 * 64 * (size_t)N_LINES));
-        HIPCHK(hipMalloc((void**)&c->d_each_work, (size_t)plan::each_engine_grid_max(c->slots) * EACH_WORK_WORDS * 4));
-        c->each_stride = st;         // last: a failed allocation leaves the path unarmed (the buffers made so far are freed with the context)
+        dev_buf<uint4> H, P, lines;
+        dev_buf<uint32_t> work;
+        int rc = H.alloc(st * 6 * 64);
+        if (!rc) rc = P.alloc(st * 3 * 64);
+        if (!rc) rc = lines.alloc(st * 6 * 64 * (size_t)N_LINES);
+        if (!rc) rc = work.alloc((size_t)plan::each_engine_grid_max(c->slots) * EACH_WORK_WORDS * 4);
+        if (rc) return rc;
+        c->d_each_H = std::move(H), c->d_each_P = std::move(P), c->d_each_lines = std::move(lines), c->d_each_work = std::move(work);
+        c->each_stride = st;
     }
-    if (want_gt && n > c->each_cap_gt) {
-        if (c->d_each_gt) (void)hipFree(c->d_each_gt);
-        c->d_each_gt = nullptr, c->each_cap_gt = 0;
-        HIPCHK(hipMalloc((void**)&c->d_each_gt, n * 576));
-        c->each_cap_gt = n;
-    }
-    return 0;
+    return want_gt ? c->d_each_gt.reserve(n * 576, 0) : 0;
 }
 static int each_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, size_t n, uint8_t verdicts[], uint8_t* gt_out, hipStream_t st) {
     if (!c) return MI355_BLS_ERR_ARG;
     if (n == 0) return 0;                      // nothing verified, nothing written
     if (!verdicts || (!d_src && !h_src)) return MI355_BLS_ERR_ARG;
-    if (c->pending) {
-        g_err = "a batch submitted on this context has not been waited for";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     int rc = each_reserve(c, n, gt_out != nullptr);
     if (rc) return rc;
     const size_t slice_max = plan::each_slice_max(c->cap), nslices = plan::each_nslices(n, slice_max);
-    // the stage launchers read the pair buffers from the context: this call's are the per-set path's own (2 x cap pairs)
-    struct pair_store {
-        mi355_bls_ctx* c;
-        uint4 *H, *P, *lines;
-        size_t stride;
-        ~pair_store() { c->d_H = H, c->d_P = P, c->d_lines = lines, c->stride = stride; }
-    } keep{c, c->d_H, c->d_P, c->d_lines, c->stride};
-    c->d_H = c->d_each_H, c->d_P = c->d_each_P, c->d_lines = c->d_each_lines, c->stride = c->each_stride;
+    const pair_store ps = c->each_pairs();       // the per-set path's own (2 x cap pairs): the batch workspace keeps what it holds
     HIPCHK(hipEventRecord(c->ev[0], st));
     size_t done = 0;
     for (uint32_t sl = 0; sl < nslices; sl++) {
@@ -944,14 +861,14 @@ static int each_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src
         if (!d_src) HIPCHK(hipMemcpyAsync(c->d_sets, h_src + done * 320, m * 320, hipMemcpyHostToDevice, st));      // behind the last slice's kernels on the same stream
         const plan::each_plan p = plan::each_for(c->slots, c->coop, m32);
         launch_hash_map(c, src, m32, st);                                  // H(msg_i) -> pair slot i, in the forms the batch path takes for m messages
-        launch_hash_clear(c, m32, st);
-        k_each_setup<<<p.setup_grid, WAVE, 0, st>>>(src, m32, c->d_H, c->d_P, c->stride);
-        launch_lines(c, p.lines, st);
+        launch_hash_clear(c, ps, m32, st);
+        k_each_setup<<<p.setup_grid, WAVE, 0, st>>>(src, m32, ps.H, ps.P, ps.stride);
+        launch_lines(ps, p.lines, st);
         uint8_t* dv = c->d_each_v + done;
         uint32_t* dg = gt_out ? c->d_each_gt + done * 144 : nullptr;
-        if (!p.tail_engine) k_each_tail<<<p.tail_grid, WAVE, 0, st>>>(c->d_lines, c->stride, m32, src, dv, dg);
-        else if (c->coop) k_each_engine_rows<<<p.tail_grid, K_TAIL_THREADS, 0, st>>>(c->d_lines, c->stride, m32, src, dv, dg, c->d_each_work);
-        else k_each_engine<<<p.tail_grid, TAIL_THREADS, 0, st>>>(c->d_lines, c->stride, m32, src, dv, dg, c->d_each_work);
+        if (!p.tail_engine) k_each_tail<<<p.tail_grid, WAVE, 0, st>>>(ps.lines, ps.stride, m32, src, dv, dg);
+        else if (c->coop) k_each_engine_rows<<<p.tail_grid, K_TAIL_THREADS, 0, st>>>(ps.lines, ps.stride, m32, src, dv, dg, c->d_each_work);
+        else k_each_engine<<<p.tail_grid, TAIL_THREADS, 0, st>>>(ps.lines, ps.stride, m32, src, dv, dg, c->d_each_work);
         done += m;
     }
     HIPCHK(hipGetLastError());
@@ -960,7 +877,7 @@ static int each_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src
     if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, c->d_each_gt, n * 576, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     c->each_passes++;
-    c->last_n = 0;                             // d_H / d_P hold this call's pairs, not a batch's stages
+    c->last_n = 0;                             // fetch_stage shows the last call, and this one left no batch stages
     c->sig_slots = 0;
     c->agg_valid = false;
     c->have_gt = false;
@@ -1014,15 +931,6 @@ extern "C" int mi355_bls_batch_verify_locate_device(mi355_bls_ctx* c, const void
 // operands, no item across two lists) and sends the table with one copy; a kernel per level and k_aggsets_finish follow on the caller's stream.
 // ------------------------------------------------------------------------------------------
 static_assert(sizeof(plan::agg_item) == 16, "k_aggsets_l0 / k_aggsets_ln load an item as one uint4");
-static int agg_grow(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return 0;
-    if (*p) (void)hipFree(*p);           // every entry point that used it has drained its stream before returning
-    *p = nullptr, *cap = 0;
-    const size_t want = bytes + bytes / 4;
-    HIPCHK(hipMalloc(p, want));
-    *cap = want;
-    return 0;
-}
 static bool agg_offsets_ok(const size_t* offsets, size_t k) {
     for (size_t s = 0; s < k; s++)
         if (offsets[s + 1] < offsets[s]) return false;
@@ -1041,10 +949,7 @@ static int aggsets_enqueue(mi355_bls_ctx* c, const agg_in& in, size_t n_table, c
         g_err = "aggregate_sets: keys, messages, signatures, indices and records must be 4-byte aligned";
         return MI355_BLS_ERR_ARG;
     }
-    if (c->pending) {
-        g_err = "a batch submitted on this context has not been waited for";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     const plan::aggsets_plan p = k < plan::AGG_NONE ? plan::aggsets_measure(offsets, k) : plan::aggsets_plan{};
     if (!p.ok) {
         g_err = "aggregate_sets: offsets decrease, or more than 2^32 - 2 keys or lists";
@@ -1057,14 +962,16 @@ static int aggsets_enqueue(mi355_bls_ctx* c, const agg_in& in, size_t n_table, c
     HIPCHK(hipSetDevice(c->device));
     c->agg_tab.resize(p.items * 4 + k);
     plan::aggsets_fill(p, offsets, k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), c->agg_tab.data() + p.items * 4);
-    int rc = agg_grow((void**)&c->d_agg_part, &c->agg_cap_part, (p.items ? p.items : 1) * (size_t)G1W * 4);
-    if (!rc) rc = agg_grow((void**)&c->d_agg_tab, &c->agg_cap_tab, c->agg_tab.size() * 4);
-    if (!rc) rc = agg_grow((void**)&c->d_agg_bad, &c->agg_cap_bad, k * 4);
-    if (!rc) rc = agg_grow((void**)&c->d_agg_status, &c->agg_cap_status, k);
+    // grown with a quarter of slack; every entry point that used the old buffers has drained its stream before returning
+    const size_t pb = (p.items ? p.items : 1) * (size_t)G1W * 4, tb = c->agg_tab.size() * 4;
+    int rc = c->d_agg_part.reserve(pb, pb / 4);
+    if (!rc) rc = c->d_agg_tab.reserve(tb, tb / 4);
+    if (!rc) rc = c->d_agg_bad.reserve(k * 4, k);
+    if (!rc) rc = c->d_agg_status.reserve(k, k / 4);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, k * 4, st));
     HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), c->agg_tab.size() * 4, hipMemcpyHostToDevice, st));
-    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab);
+    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
     for (uint32_t l = 0; l < p.levels; l++) {
         const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
         if (l == 0) k_aggsets_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, in.keys, n_table, in.idx, c->d_agg_part, c->d_agg_bad);
@@ -1088,9 +995,9 @@ static int aggsets_status(mi355_bls_ctx* c, size_t k, uint8_t* status, hipStream
 static int agg_stage(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k, const void* msgs, const void* sigs,
                      hipStream_t st, agg_in* out) {
     if (!keys || !offsets || !msgs || !sigs || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
-    const size_t n_idx = idx ? offsets[k] : 0, kb = n_table * 96, sb = k * 192, mb = k * 32;
+    const size_t n_idx = idx ? offsets[k] : 0, kb = n_table * 96, sb = k * 192, mb = k * 32, all = kb + sb + mb + n_idx * 4 + 4;
     HIPCHK(hipSetDevice(c->device));
-    int rc = agg_grow((void**)&c->d_agg_in, &c->agg_cap_in, kb + sb + mb + n_idx * 4 + 4);
+    int rc = c->d_agg_in.reserve(all, all / 4);
     if (rc) return rc;
     uint8_t* d = c->d_agg_in;
     if (kb) HIPCHK(hipMemcpyAsync(d, keys, kb, hipMemcpyHostToDevice, st));
@@ -1117,7 +1024,7 @@ extern "C" int mi355_bls_aggregate_sets(mi355_bls_ctx* c, const void* keys, size
     if (!out_records || !status) return MI355_BLS_ERR_ARG;
     agg_in in;
     int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
-    if (!rc) rc = agg_grow((void**)&c->d_agg_rec, &c->agg_cap_rec, k * 320);
+    if (!rc) rc = c->d_agg_rec.reserve(k * 320, k * 80);
     if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out_records, c->d_agg_rec, k * 320, hipMemcpyDeviceToHost, nullptr));
@@ -1126,7 +1033,7 @@ extern "C" int mi355_bls_aggregate_sets(mi355_bls_ctx* c, const void* keys, size
 // fastAggregateVerify (bls_sig_min_pubkey.nim:234-258) for every list: the records into the context's own buffer, then the per-set pass
 // on them.  A list without a key, with an out-of-range index or with the sum at infinity has the infinity key in its record: verdict 0.
 static int agg_each(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, uint8_t* out, hipStream_t st) {
-    int rc = agg_grow((void**)&c->d_agg_rec, &c->agg_cap_rec, k * 320);
+    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
     if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, st);
     if (rc) return rc;
     return each_run(c, c->d_agg_rec, nullptr, k, out, nullptr, st);
@@ -1152,7 +1059,7 @@ extern "C" int mi355_bls_fast_aggregate_verify_each(mi355_bls_ctx* c, const void
 // batchVerify over the sets (aggregateAll(keys_s), msg_s, sig_s): a list that gives no key (any status but 0) ends the call with 0 before
 // any verification pass - the reference's caller would not have obtained a SignatureSet for it.
 static int agg_batch(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, const uint8_t rnd[32], hipStream_t st) {
-    int rc = agg_grow((void**)&c->d_agg_rec, &c->agg_cap_rec, k * 320);
+    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
     if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, st);
     if (rc) return rc;
     c->agg_status_h.resize(k);
@@ -1190,10 +1097,7 @@ extern "C" int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* c, const voi
 static int verify_many(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
                        hipStream_t st) {
     if (!c || !counts || !rnds || !verdicts || (!d_src && !h_src)) return MI355_BLS_ERR_ARG;
-    if (c->pending) {
-        g_err = "a batch submitted on this context has not been waited for";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     size_t total = 0;
     for (size_t b = 0; b < k; b++) {
         verdicts[b] = 0;
@@ -1253,7 +1157,7 @@ static int verify_many(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_
         HIPCHK(hipEventRecord(c->ev[0], st));
         if (any_serial) HIPCHK(hipMemcpyAsync(c->d_r, c->h_r.data(), total * 8, hipMemcpyHostToDevice, st));      // serial batches' scalars (zeros elsewhere, overwritten below)
         if (lanes) {
-            many_meta* d_meta = reinterpret_cast<many_meta*>(c->d_comp);
+            many_meta* d_meta = reinterpret_cast<many_meta*>(c->d_comp.p);
             uint8_t* d_rr = c->d_comp + ((meta.size() * sizeof(many_meta) + 63) / 64) * 64;
             HIPCHK(hipMemcpyAsync(d_meta, meta.data(), meta.size() * sizeof(many_meta), hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(d_rr, rr.data(), rr.size(), hipMemcpyHostToDevice, st));
@@ -1307,10 +1211,7 @@ extern "C" int mi355_bls_batch_verify_many_device(mi355_bls_ctx* c, const void* 
 static int shard_enqueue(mi355_bls_ctx* c, const void* d_sets, const uint8_t* h_sets, size_t n_total, uint32_t chunk_lo, uint32_t chunk_hi, const uint8_t rnd[32],
                          hipStream_t st, mi355_bls_ctx* after) {
     if (!c || !rnd || n_total == 0 || (!d_sets && !h_sets)) return MI355_BLS_ERR_ARG;
-    if (c->pending) {
-        g_err = "a batch submitted on this context has not been waited for";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     uint32_t B = (uint32_t)(n_total < c->num_threads ? n_total : c->num_threads);
     if (chunk_hi > B) chunk_hi = B;
     if (chunk_lo >= chunk_hi) return MI355_BLS_ERR_ARG;
@@ -1454,10 +1355,7 @@ static int verify_multi(mi355_bls_ctx* const ctxs[], size_t ngpu, const uint8_t*
     struct plan_t { uint32_t lo, hi; size_t first, count; } plan[64];
     for (size_t g = 0; g < ngpu; g++) {
         if (!ctxs[g] || ctxs[g]->num_threads != ctxs[0]->num_threads) return MI355_BLS_ERR_ARG;
-        if (ctxs[g]->pending) {
-            g_err = "a batch submitted on this context has not been waited for";
-            return MI355_BLS_ERR_ARG;
-        }
+        if (ctx_busy(ctxs[g])) return MI355_BLS_ERR_ARG;
         mi355_bls_shard_plan(n, ctxs[0]->num_threads, (uint32_t)ngpu, (uint32_t)g, &plan[g].lo, &plan[g].hi, &plan[g].first, &plan[g].count);
         if (plan[g].count && !(d_sets && d_sets[g]) && !sets) return MI355_BLS_ERR_ARG;
     }
@@ -1693,6 +1591,7 @@ extern "C" int mi355_bls_g1_aggregate(mi355_bls_ctx* c, const void* pks, size_t 
 // beside the hash of the message in latency mode); d_pks == nullptr: the aggregate is already in d_agg1 (the multi-device form).
 static int fav_run(mi355_bls_ctx* c, const void* d_pks, size_t n, const uint8_t* msg, size_t msg_len, const void* sig, hipStream_t st) {
     HIPCHK(hipSetDevice(c->device));
+    const pair_store ps = c->batch_pairs();
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
     HIPCHK(hipMemcpyAsync(c->d_msg, msg, msg_len, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->d_msg + 4096, sig, 192, hipMemcpyHostToDevice, st));
@@ -1705,13 +1604,13 @@ static int fav_run(mi355_bls_ctx* c, const void* d_pks, size_t n, const uint8_t*
         if (rc) return rc;
     }
     HIPCHK(hipEventRecord(c->ev[1], sd));
-    k_hash_one<<<1, 256, 0, st>>>(c->d_msg, (uint32_t)msg_len, c->dst, c->xmd, c->d_H, c->stride, 0);
+    k_hash_one<<<1, 256, 0, st>>>(c->d_msg, (uint32_t)msg_len, c->dst, c->xmd, ps.H, ps.stride, 0);
     if (sd != st) HIPCHK(hipStreamWaitEvent(st, c->ev[1], 0));
-    k_fav_setup<<<1, 1, 0, st>>>(c->d_agg1, reinterpret_cast<const uint32_t*>(c->d_msg + 4096), c->d_H, c->d_P, c->stride, c->d_flags);
+    k_fav_setup<<<1, 1, 0, st>>>(c->d_agg1, reinterpret_cast<const uint32_t*>(c->d_msg + 4096), ps.H, ps.P, ps.stride, c->d_flags);
     HIPCHK(hipEventRecord(c->ev[2], st));
-    launch_lines(c, plan::lines_for(c->slots, c->coop, 2, 0), st);
+    launch_lines(ps, plan::lines_for(c->slots, c->coop, 2, 0), st);
     HIPCHK(hipEventRecord(c->ev[3], st));
-    k_lineprod<<<dim3(N_LINES, 1), WAVE, 0, st>>>(c->d_lines, 2, c->stride, 1, c->d_lpart, 1, 0);
+    k_lineprod<<<dim3(N_LINES, 1), WAVE, 0, st>>>(ps.lines, 2, ps.stride, 1, c->d_lpart, 1, 0);
     k_lineprod2<<<N_LINES, WAVE, 0, st>>>(c->d_lpart, 1, c->d_L);
     HIPCHK(hipEventRecord(c->ev[4], st));
     launch_k_tail(c, st, c->d_L, c->d_states, 1, 3, c->d_gt, c->d_flags + 1, 144, 0);
@@ -1846,48 +1745,35 @@ extern "C" size_t mi355_bls_p1s_mult_pippenger_scratch_sizeof(size_t npoints) {
 }
 
 // workspace for npoints points of `affb`-byte affine images (96: G1, 192: G2) under window plan W
-static int msm_reserve(mi355_bls_ctx* c, msm_ws* m, size_t n, const pip_win& W, size_t affb) {
-    (void)c;
-    uint32_t total = W.nwin << W.cbk;
+static int msm_reserve(msm_ws* m, size_t n, const pip_win& W, size_t affb) {
+    uint32_t total = W.nwin << W.cbk, cap_total = (uint32_t)(m->hist.bytes / 4);
     size_t pts_bytes = n * affb;
-    if (pts_bytes <= m->cap_n && total <= m->cap_total) return 0;
-    size_t cb = pts_bytes > m->cap_n ? pts_bytes : m->cap_n;
-    uint32_t ct = total > m->cap_total ? total : m->cap_total;
-    msm_free(m);
-#define MALLOC(p, bytes)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = hipMalloc((void**)&(p), (bytes));                                  \
-        if (e_ != hipSuccess) {                                                            \
-            g_err = std::string("hipMalloc " #p ": ") + hipGetErrorString(e_);             \
-            msm_free(m);                                                                   \
-            return MI355_BLS_ERR_HIP;                                                      \
-        }                                                                                  \
-    } while (0)
+    if (pts_bytes <= m->d_pts.bytes && total <= cap_total) return 0;
+    size_t cb = pts_bytes > m->d_pts.bytes ? pts_bytes : m->d_pts.bytes;
+    uint32_t ct = total > cap_total ? total : cap_total;
+    *m = msm_ws();                                       // everything goes first: a failed grow leaves an empty workspace
+    msm_ws w;
+    int rc = 0;                                          // the first failure: nothing is created behind it
+    const auto alloc = [&rc](auto& buf, size_t bytes) { rc = rc ? rc : buf.alloc(bytes); };
     size_t cn = cb / 96;                                 // point capacity counted in G1 points (a G2 point takes two)
-    MALLOC(m->d_pts, cb);
-    MALLOC(m->d_sc, cn * 32);
-    MALLOC(m->pts_int, cn * 2 * FPW * 4);
-    MALLOC(m->hist, (size_t)ct * 4);
-    MALLOC(m->offs, (size_t)ct * 4);
-    MALLOC(m->cursor, (size_t)ct * 4);
-    MALLOC(m->order, (size_t)ct * 4);
-    MALLOC(m->chist, 4 * 256 * 4);
-    MALLOC(m->shist, (size_t)ct * PIP_SLICES * 4);      // per-slice counters of the LDS counting sort
-    MALLOC(m->part, 64 * 16 * G2W * 4);                 // per window up to 16 partial sums
-    MALLOC(m->sorted, (size_t)cn * 64 * 4);          // up to 52 + 1 windows (nbits 256 at 5-bit windows)
-    MALLOC(m->buckets, (size_t)ct * 6 * 64);
-    MALLOC(m->segout, (size_t)(ct / 4 + 64) * 6 * 64);
-    MALLOC(m->winout, 64 * G2W * 4);
-    MALLOC(m->out, 288);
-#undef MALLOC
-    HIPCHK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&m->ev_bucketed, hipEventDisableTiming));
-    for (int g = 0; g < 2; g++) {
-        HIPCHK(hipEventCreateWithFlags(&m->ev_g[g], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&m->ev_tail[g], hipEventDisableTiming));
-    }
-    m->cap_n = cb;
-    m->cap_total = ct;
+    alloc(w.d_pts, cb);
+    alloc(w.d_sc, cn * 32);
+    alloc(w.pts_int, cn * 2 * FPW * 4);
+    alloc(w.hist, (size_t)ct * 4);
+    alloc(w.offs, (size_t)ct * 4);
+    alloc(w.cursor, (size_t)ct * 4);
+    alloc(w.order, (size_t)ct * 4);
+    alloc(w.chist, 4 * 256 * 4);
+    alloc(w.shist, (size_t)ct * PIP_SLICES * 4);      // per-slice counters of the LDS counting sort
+    alloc(w.part, 64 * 16 * G2W * 4);                 // per window up to 16 partial sums
+    alloc(w.sorted, (size_t)cn * 64 * 4);          // up to 52 + 1 windows (nbits 256 at 5-bit windows)
+    alloc(w.buckets, (size_t)ct * 6 * 64);
+    alloc(w.segout, (size_t)(ct / 4 + 64) * 6 * 64);
+    alloc(w.winout, 64 * G2W * 4);
+    alloc(w.out, 288);
+    for (dev_event* e : {&w.ev_fork, &w.ev_bucketed, &w.ev_g[0], &w.ev_tail[0], &w.ev_g[1], &w.ev_tail[1]}) rc = rc ? rc : e->create(hipEventDisableTiming);
+    if (rc) return rc;
+    *m = std::move(w);
     return 0;
 }
 
@@ -1898,7 +1784,7 @@ static int msm_enqueue(mi355_bls_ctx* c, msm_ws* m, const void* d_points, size_t
                        hipStream_t st, bool timed, bool allow_split) {
     constexpr size_t AFFB = sizeof(F) == sizeof(fp) ? 96 : 192;
     pip_win W = pip_plan(npoints, nbits);
-    int rc = msm_reserve(c, m, npoints, W, AFFB);
+    int rc = msm_reserve(m, npoints, W, AFFB);
     if (rc) return rc;
     uint32_t n = (uint32_t)npoints, nw = W.nwin, total = nw << W.cbk, seg = MSM_SEG, segs_per_win = (1u << W.cbk) / seg,
              nseg = nw * segs_per_win;
@@ -2010,9 +1896,9 @@ static int msm_run(mi355_bls_ctx* c, uint8_t* ret, const void* d_points, size_t 
     if (!d_points || !d_scalars) return MI355_BLS_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
-    int rc = msm_enqueue<F>(c, c->msm, d_points, npoints, d_scalars, sbytes, nbits, st, true, true);
+    int rc = msm_enqueue<F>(c, &c->msm, d_points, npoints, d_scalars, sbytes, nbits, st, true, true);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ret, c->msm->out, JACB, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ret, c->msm.out, JACB, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return collect_timings(c, 4);       // [0] sort, [1] bucket accumulation, [2] segment reduction, [3] window sums + doublings
 }
@@ -2031,11 +1917,11 @@ static int msm_host(mi355_bls_ctx* c, uint8_t* ret, const uint8_t* pts, size_t n
     constexpr size_t AFFB = sizeof(F) == sizeof(fp) ? 96 : 192;
     if (!c || nbits == 0 || nbits > 256 || npoints > (1u << 28)) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    int rc = msm_reserve(c, c->msm, npoints, pip_plan(npoints, nbits), AFFB);
+    int rc = msm_reserve(&c->msm, npoints, pip_plan(npoints, nbits), AFFB);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(c->msm->d_pts, pts, npoints * AFFB, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(c->msm->d_sc, scalars, npoints * sbytes, hipMemcpyHostToDevice, nullptr));
-    return msm_run<F>(c, ret, c->msm->d_pts, npoints, c->msm->d_sc, sbytes, nbits, nullptr);
+    HIPCHK(hipMemcpyAsync(c->msm.d_pts, pts, npoints * AFFB, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(c->msm.d_sc, scalars, npoints * sbytes, hipMemcpyHostToDevice, nullptr));
+    return msm_run<F>(c, ret, c->msm.d_pts, npoints, c->msm.d_sc, sbytes, nbits, nullptr);
 }
 
 // Same shape as blst_p1s_mult_pippenger incl. the NULL-terminated pointer-to-array convention
@@ -2310,16 +2196,16 @@ extern "C" int mi355_bls_combine(mi355_bls_ctx* c, const uint8_t rnd[32], const 
     hipStream_t s2 = ensure_side(c) ? c->side : st;
     HIPCHK(hipEventRecord(c->ev[0], st));
     if (s2 != st) HIPCHK(hipStreamWaitEvent(s2, c->ev[0], 0));            // the staged inputs
-    int rc = msm_enqueue<fp2>(c, c->msm2, d_sg, n, c->d_r, 8, 64, s2, false, false);
+    int rc = msm_enqueue<fp2>(c, &c->msm2, d_sg, n, c->d_r, 8, 64, s2, false, false);
     if (rc) return rc;
     HIPCHK(hipEventRecord(c->ev[2], s2));
-    rc = msm_enqueue<fp>(c, c->msm, d_pk, n, c->d_r, 8, 64, st, false, s2 == st);
+    rc = msm_enqueue<fp>(c, &c->msm, d_pk, n, c->d_r, 8, 64, st, false, s2 == st);
     if (rc) return rc;
     HIPCHK(hipEventRecord(c->ev[1], st));
     if (s2 != st) HIPCHK(hipStreamWaitEvent(st, c->ev[2], 0));
     // `finish` (to affine, core :172-177)
-    uint32_t* d_out = reinterpret_cast<uint32_t*>(c->d_msg);
-    k_finish_affine<<<1, 1, 0, st>>>(c->msm->out, c->msm2->out, d_out, d_out + 24);
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(c->d_msg.p);
+    k_finish_affine<<<1, 1, 0, st>>>(c->msm.out, c->msm2.out, d_out, d_out + 24);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[3], st));
     HIPCHK(hipMemcpyAsync(out_pk, d_out, 96, hipMemcpyDeviceToHost, st));
@@ -2340,6 +2226,7 @@ extern "C" int mi355_bls_combine(mi355_bls_ctx* c, const uint8_t rnd[32], const 
 // this slice.  Leaves the slice's committed state in d_states slot 0 (final: also runs the final exponentiation, one-slice calls).
 static int aggv_slice(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint32_t* offs, size_t n, bool with_sig, bool final, hipStream_t st) {
     size_t total = offs[n];
+    const pair_store ps = c->batch_pairs();
     uint8_t* d_pk = c->d_sets;
     uint32_t* d_off = reinterpret_cast<uint32_t*>(c->d_sets + n * 96);
     uint8_t* d_msgs = c->d_sets + n * 96 + (n + 1) * 4;
@@ -2354,17 +2241,17 @@ static int aggv_slice(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* msgs,
         // side of the staging buffer (keys | offsets | messages are packed at its start; the records go to d_comp)
         k_aggv_records<<<nb, WAVE, 0, st>>>(d_msgs, n32, c->d_comp);
         launch_hash_map(c, c->d_comp, n32, st);
-        launch_hash_clear(c, n32, st);
+        launch_hash_clear(c, ps, n32, st);
     } else {
-        k_hash_var<<<nb, WAVE, 0, st>>>(d_msgs, d_off, n32, c->dst, c->d_H, c->stride);
+        k_hash_var<<<nb, WAVE, 0, st>>>(d_msgs, d_off, n32, c->dst, ps.H, ps.stride);
     }
     HIPCHK(hipEventRecord(c->ev[1], st));
-    k_aggv_setup<<<nb1, WAVE, 0, st>>>(d_pk, n32, with_sig ? 1 : 0, reinterpret_cast<const uint32_t*>(c->d_msg + 4096), c->d_H, c->d_P, c->stride, c->d_flags);
+    k_aggv_setup<<<nb1, WAVE, 0, st>>>(d_pk, n32, with_sig ? 1 : 0, reinterpret_cast<const uint32_t*>(c->d_msg + 4096), ps.H, ps.P, ps.stride, c->d_flags);
     HIPCHK(hipEventRecord(c->ev[2], st));
-    launch_lines(c, plan::lines_for(c->slots, c->coop, npairs, 0), st);
+    launch_lines(ps, plan::lines_for(c->slots, c->coop, npairs, 0), st);
     HIPCHK(hipEventRecord(c->ev[3], st));
     {
-        int rcp = enqueue_line_products(c, npairs, st, nullptr);
+        int rcp = enqueue_line_products(c, ps, npairs, st, nullptr);
         if (rcp) return rcp;
     }
     HIPCHK(hipEventRecord(c->ev[4], st));
@@ -2530,9 +2417,9 @@ extern "C" int mi355_bls_p1s_mult_pippenger_partial_device(mi355_bls_ctx* c, voi
         return 0;
     }
     if (!d_points || !d_scalars) return MI355_BLS_ERR_ARG;
-    int rc = msm_enqueue<fp>(c, c->msm, d_points, npoints, d_scalars, 32, nbits, st, false, true);
+    int rc = msm_enqueue<fp>(c, &c->msm, d_points, npoints, d_scalars, 32, nbits, st, false, true);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(d_out_p1, c->msm->out, 144, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_out_p1, c->msm.out, 144, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
@@ -2568,20 +2455,20 @@ static int msm_multi(mi355_bls_ctx* const ctxs[], size_t ngpu, uint8_t* ret, con
         const void *dp = d_pts ? d_pts[g] : nullptr, *ds = d_sc ? d_sc[g] : nullptr;
         if (!dp || !ds) {
             if (!pts || !sc) { rc = MI355_BLS_ERR_ARG; break; }
-            rc = msm_reserve(c, c->msm, cnt, pip_plan(cnt, nbits), AFFB);
+            rc = msm_reserve(&c->msm, cnt, pip_plan(cnt, nbits), AFFB);
             if (rc) break;
-            if (hipMemcpyAsync(c->msm->d_pts, pts + off * AFFB, cnt * AFFB, hipMemcpyHostToDevice, nullptr) != hipSuccess ||
-                hipMemcpyAsync(c->msm->d_sc, sc + off * 32, cnt * 32, hipMemcpyHostToDevice, nullptr) != hipSuccess) {
+            if (hipMemcpyAsync(c->msm.d_pts, pts + off * AFFB, cnt * AFFB, hipMemcpyHostToDevice, nullptr) != hipSuccess ||
+                hipMemcpyAsync(c->msm.d_sc, sc + off * 32, cnt * 32, hipMemcpyHostToDevice, nullptr) != hipSuccess) {
                 g_err = "hipMemcpyAsync (MSM shard staging)";
                 rc = MI355_BLS_ERR_HIP;
                 break;
             }
-            dp = c->msm->d_pts;
-            ds = c->msm->d_sc;
+            dp = c->msm.d_pts;
+            ds = c->msm.d_sc;
         }
-        rc = msm_enqueue<F>(c, c->msm, dp, cnt, ds, 32, nbits, nullptr, false, true);
+        rc = msm_enqueue<F>(c, &c->msm, dp, cnt, ds, 32, nbits, nullptr, false, true);
         if (rc) break;
-        if (hipMemcpyAsync(c->h_flags + 160, c->msm->out, JACB, hipMemcpyDeviceToHost, nullptr) != hipSuccess) { g_err = "hipMemcpyAsync (MSM partial)"; rc = MI355_BLS_ERR_HIP; break; }
+        if (hipMemcpyAsync(c->h_flags + 160, c->msm.out, JACB, hipMemcpyDeviceToHost, nullptr) != hipSuccess) { g_err = "hipMemcpyAsync (MSM partial)"; rc = MI355_BLS_ERR_HIP; break; }
         live[g] = true;
     }
     std::vector<uint8_t> parts;

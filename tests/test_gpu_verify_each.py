@@ -202,3 +202,37 @@ def test_argument_validation(m, cache):
     with pytest.raises(ValueError):
         m.batchVerifyLocate(cache, bytes(640), bytes(31))
     assert m.verifyEach(cache, b"") == []
+
+
+def test_per_set_call_leaves_the_batch_workspace_intact(m):
+    """The per-set path runs in a pair store of its own: a batch's committed state survives a per-set call on the same context, fetch_stage
+    shows no batch stages behind it (the last call left none), and the same batch verifies again to the same GT bytes."""
+    import c_oracle as co
+    rnd = hashlib.sha256(b"each beside batch").digest()
+    rec = co.make_batch(8, seed=20262)
+    ok, st = co.batch_verify(rec, rnd, 4, stages=True)
+    assert ok
+    sets = with_bad([rec[320 * i:320 * i + 320] for i in range(8)], [3], 1)
+    c = m.BatchedBLSVerifierCache.init(max_sets=64, numThreads=4)
+    try:
+        assert m.batchVerifyParallel(c, rec, rnd) is True
+        gt, state = c.fetch(4, 576), c.fetch(5, 576)
+        assert gt == st["gt"]
+        assert o_affine_g2(c.fetch(1, 288 * 8)[:288]) == st["H"][:192]
+        assert m.verifyEach(c, b"".join(sets)) == [oracle_verdict(r) for r in sets] == [i != 3 for i in range(8)]
+        assert c.fetch(5, 576) == state                                               # the batch's committed state
+        assert c.fetch(0, 0) == b""                                                   # no tuples of a batch to show ...
+        for what, nbytes in ((1, 288 * 8), (2, 144 * 8), (4, 576)):                   # ... no pairs, and no GT of the last call
+            with pytest.raises(m.BlsGpuError):
+                c.fetch(what, nbytes)
+        assert m.batchVerifyParallel(c, rec, rnd) is True
+        assert c.fetch(4, 576) == gt and c.fetch(5, 576) == state
+        assert o_affine_g2(c.fetch(1, 288 * 8)[:288]) == st["H"][:192]
+    finally:
+        c.close()
+
+
+def o_affine_g2(jac288):
+    import bls12381_py as o
+    from util import g2_jac_to_affine
+    return o.g2_to_blst_affine(g2_jac_to_affine(jac288))
