@@ -172,6 +172,37 @@ void emu_g2_sum_xyzz(const uint8_t* pts, uint32_t n, uint8_t* out) {
 }
 void emu_g1_add(const uint8_t* a, const uint8_t* b, uint8_t* out) { g1_jac_store(out, jac_add(g1_jac_load(a), g1_jac_load(b))); }
 void emu_g2_add(const uint8_t* a, const uint8_t* b, uint8_t* out) { g2_jac_store(out, jac_add(g2_jac_load(a), g2_jac_load(b))); }
+// What the complete addition's branch test sees for a + b (the H and r of jac_add_body): bit 0 H = 0 mod p, bit 1 the limbs of H are all zero,
+// bits 2 and 3 the same for r.  A guard for test inputs: equal or opposite operands are the hard case only where bit 0 is set and bit 1 is not.
+int emu_g1_add_probe(const uint8_t* a, const uint8_t* b) {
+    g1_jac p = g1_jac_load(a), q = g1_jac_load(b);
+    fp Z1Z1 = f_sqr(p.z), Z2Z2 = f_sqr(q.z);
+    fp H = f_sub(f_mul(q.x, Z1Z1), f_mul(p.x, Z2Z2));
+    fp rr = f_sub(f_mul(f_mul(q.y, p.z), Z1Z1), f_mul(f_mul(p.y, q.z), Z2Z2));
+    return (int)fp_is_zero(H) | (int)fp_limbs_are_zero(H) << 1 | (int)fp_is_zero(rr) << 2 | (int)fp_limbs_are_zero(rr) << 3;
+}
+int emu_g2_add_probe(const uint8_t* a, const uint8_t* b) {
+    g2_jac p = g2_jac_load(a), q = g2_jac_load(b);
+    fp2 Z1Z1 = f_sqr(p.z), Z2Z2 = f_sqr(q.z);
+    fp2 H = f_sub(f_mul(q.x, Z1Z1), f_mul(p.x, Z2Z2));
+    fp2 rr = f_sub(f_mul(f_mul(q.y, p.z), Z1Z1), f_mul(f_mul(p.y, q.z), Z2Z2));
+    return (int)fp2_is_zero(H) | (int)(fp_limbs_are_zero(H.c0) && fp_limbs_are_zero(H.c1)) << 1 | (int)fp2_is_zero(rr) << 2
+           | (int)(fp_limbs_are_zero(rr.c0) && fp_limbs_are_zero(rr.c1)) << 3;
+}
+// an accumulator that is not a fresh load (Jacobian, Z of the caller's choice) plus an affine point: the mixed addition of the point sums' lane
+// loops, and the same through the buckets' extended coordinates (X, Y, Z^2, Z^3)
+void emu_g1_add_aff(const uint8_t* a, const uint8_t* q, uint8_t* out) { g1_jac_store(out, jac_add_aff(g1_jac_load(a), g1_aff_load(q))); }
+void emu_g2_add_aff(const uint8_t* a, const uint8_t* q, uint8_t* out) { g2_jac_store(out, jac_add_aff(g2_jac_load(a), g2_aff_load(q))); }
+void emu_g1_xyzz_add_aff(const uint8_t* a, const uint8_t* q, uint8_t* out) {
+    g1_jac p = g1_jac_load(a);
+    fp zz = fp_sqr(p.z);
+    g1_jac_store(out, jac_from_xyzz(xyzz_add_aff(xyzz<fp>{p.x, p.y, zz, fp_mul(zz, p.z)}, g1_aff_load(q))));
+}
+void emu_g2_xyzz_add_aff(const uint8_t* a, const uint8_t* q, uint8_t* out) {
+    g2_jac p = g2_jac_load(a);
+    fp2 zz = fp2_sqr(p.z);
+    g2_jac_store(out, jac_from_xyzz(xyzz_add_aff(xyzz<fp2>{p.x, p.y, zz, fp2_mul(zz, p.z)}, g2_aff_load(q))));
+}
 // n pairs of (P Jacobian 144 B, Q Jacobian 288 B) -> final_exp(miller) 576 B
 void emu_pairing_product(const uint8_t* ps, const uint8_t* qs, uint32_t n, uint8_t* out, int do_final_exp) {
     fp12 L[N_LINES];

@@ -434,3 +434,63 @@ def test_team_formulas_equal_the_plain_ones(emu):
         for A, B in ((P, P2), (P2, P), (P, P), (P, g1_aff_to_jac_bytes(o.g1_neg(g1_jac_to_affine(P)))), (bytes(144), P), (P, bytes(144)), (bytes(144), bytes(144))):
             a, b = call(emu, "emu_g1_add_team", A, B, outlen=144), call(emu, "emu_g1_add", A, B, outlen=144)
             assert g1_jac_to_affine(a) == g1_jac_to_affine(b)
+
+
+def test_one_addition_in_every_class_for_every_pair_of_z(emu):
+    """The pair table of tests/test_gpu_point_sums.py on the CPU build, bounds tracked: for every ordered pair of Z values (util.LAMBDAS_FP /
+    LAMBDAS_FP2) an addition of equal points, of opposite points, with infinity on either side or both (all-zero, and Z = 0 under non-zero X, Y)
+    and a generic one, through jac_add and the lane-team form - also for a base of E(Fp) outside G1.  Equal or opposite operands with different Z
+    make H = U2 - U1 a non-zero multiple of p in signed limbs: the case fp_is_zero's quotient estimate has to get right."""
+    import small_multiples as sm
+    for name in ("g1", "g2", "outside"):
+        fam = sm.family(name)
+        dec, n = (g2_jac_to_affine, 288) if fam.g2 else (g1_jac_to_affine, 144)
+        fns = ("emu_g2_add", "emu_g2_add_team") if fam.g2 else ("emu_g1_add", "emu_g1_add_team")
+        classes = None if name != "outside" else ("equal", "opposite")
+        for cl, pair, a, b, want in sm.pair_table(fam, classes):
+            for fn in fns:
+                got = call(emu, fn, a, b, outlen=n)
+                assert dec(got) == want, (name, fn, cl, pair)
+                if want is None:
+                    assert got[n - n // 3:] == bytes(n // 3), (name, fn, cl, pair)          # an infinite sum decodes as infinity: Z = 0
+
+
+def test_mixed_addition_onto_an_accumulator_with_its_own_z(emu):
+    """jac_add_aff and xyzz_add_aff (the lane loops of the point sums, the Pippenger and signature buckets) with an accumulator whose Z is every
+    lambda of the set, against the affine operand that equals it, that is opposite to it, a generic one and the all-zero image; and an
+    accumulator at infinity (all-zero, and Z = 0 under non-zero X, Y)."""
+    import small_multiples as sm
+    from util import g1_inf_image, g2_inf_image
+    for name in ("g1", "g2", "outside"):
+        fam = sm.family(name)
+        dec, n = (g2_jac_to_affine, 288) if fam.g2 else (g1_jac_to_affine, 144)
+        fns = ("emu_g2_add_aff", "emu_g2_xyzz_add_aff") if fam.g2 else ("emu_g1_add_aff", "emu_g1_xyzz_add_aff")
+        for i, lam in enumerate(fam.lambdas):
+            k = 1 + i % 4
+            trash = g2_inf_image(lam, fam.T[k][1]) if fam.g2 else g1_inf_image(lam, fam.T[k][1])
+            for acc, q, want in ((fam.jac(k, lam), fam.aff(k), fam.T[2 * k]), (fam.jac(k, lam), fam.aff(-k), None),
+                                 (fam.jac(-k, lam), fam.aff(k + 3), fam.T[3]), (fam.jac(k, lam), fam.aff(0), fam.T[k]),
+                                 (bytes(n), fam.aff(k), fam.T[k]), (trash, fam.aff(-k), fam.T[-k]), (trash, fam.aff(0), None)):
+                for fn in fns:
+                    assert dec(call(emu, fn, acc, q, outlen=n)) == want, (name, fn, i)
+
+
+def test_hard_pairs_are_hard_and_add_correctly(emu):
+    """A guard on inputs and a check of results.  In the pair table above the operands' H is literally zero in every equal and opposite row (the
+    multiplier's outputs are that close to canonical); small_multiples.HARD_PAIRS are the searched exceptions.  The probe must report, for every
+    one of them, a value that is zero mod p with limbs that are not - H in the first two pairs of a family, r in the last two - and the
+    additions must still come out right.  If the probe disagrees the field arithmetic has changed: run small_multiples.search_hard_pairs again."""
+    import small_multiples as sm
+    for name in ("g1", "g2"):
+        fam = sm.family(name)
+        probe = emu.emu_g2_add_probe if fam.g2 else emu.emu_g1_add_probe
+        dec, n = (g2_jac_to_affine, 288) if fam.g2 else (g1_jac_to_affine, 144)
+        fns = ("emu_g2_add", "emu_g2_add_team") if fam.g2 else ("emu_g1_add", "emu_g1_add_team")
+        rows = sm.hard_pair_table(fam)
+        seen = [probe(a, b) for _, _, a, b, _ in rows]
+        assert sum(1 for v in seen if (v & 3) == 1) >= 4 and sum(1 for v in seen if (v & 12) == 4) >= 2, (name, seen, "search the hard pairs again")
+        plain = [probe(a, b) for cl, _, a, b, _ in sm.pair_table(fam, ("equal", "opposite"))]
+        assert set(plain) <= {15, 3}                          # what the fixed lambda set reaches: literal zeros only
+        for cl, pair, a, b, want in rows:
+            for fn in fns:
+                assert dec(call(emu, fn, a, b, outlen=n)) == want, (name, fn, cl, pair)

@@ -4,6 +4,7 @@ import hashlib
 import itertools
 import json
 import os
+import random
 import subprocess
 
 import bls12381_py as o
@@ -56,6 +57,49 @@ def g2_aff_to_jac_bytes(p):
     if p is None:
         return bytes(288)
     return o.g2_to_blst_affine(p) + o.fp_to_mont_bytes(1) + bytes(48)
+
+
+# ---- Jacobian images with a chosen Z.  (lam^2 x, lam^3 y, lam) is the point (x, y) for every lam != 0; two images of one point (or of a point and
+# its negative) with different lam are what two partial sums of a reduction look like when they meet, and the only inputs for which the
+# complete addition's H = U2 - U1 is a non-zero multiple of p in the device's redundant limbs instead of literally zero.
+_FP_ALL_HIGH = ((o.P >> 364) - 1 << 364) | ((1 << 364) - 1)          # below p; every 28-bit limb under the top one is 0xfffffff
+_lam_rng = random.Random(20261017)
+LAMBDAS_FP = (1, o.P - 1, 2, (o.P + 1) // 2, _FP_ALL_HIGH, _lam_rng.randrange(1, o.P), _lam_rng.randrange(1, o.P))
+LAMBDAS_FP2 = tuple((a, 0) for a in LAMBDAS_FP[:4]) + ((_FP_ALL_HIGH, _FP_ALL_HIGH),) + tuple(
+    (_lam_rng.randrange(1, o.P), _lam_rng.randrange(1, o.P)) for _ in range(2)) + ((0, 1), (o.P - 1, o.P - 1))
+assert _FP_ALL_HIGH < o.P and len(set(LAMBDAS_FP)) == 7 and len(set(LAMBDAS_FP2)) == 9
+
+
+def fp2_to_mont_bytes(a):
+    return o.fp_to_mont_bytes(a[0]) + o.fp_to_mont_bytes(a[1])
+
+
+def g1_jac_image(p, lam):
+    """blst_p1 image (Montgomery, R = 2^384, like g1_aff_to_jac_bytes) of (lam^2 x, lam^3 y, lam), lam in Fp*; None -> the all-zero image"""
+    if p is None:
+        return bytes(144)
+    lam %= o.P
+    assert lam
+    l2 = lam * lam % o.P
+    return o.fp_to_mont_bytes(p[0] * l2 % o.P) + o.fp_to_mont_bytes(p[1] * l2 * lam % o.P) + o.fp_to_mont_bytes(lam)
+
+
+def g2_jac_image(q, lam):
+    """blst_p2 image of (lam^2 x, lam^3 y, lam), lam in Fp2*; None -> the all-zero image"""
+    if q is None:
+        return bytes(288)
+    assert lam != (0, 0)
+    l2 = o.f2sqr(lam)
+    return fp2_to_mont_bytes(o.f2mul(q[0], l2)) + fp2_to_mont_bytes(o.f2mul(q[1], o.f2mul(l2, lam))) + fp2_to_mont_bytes(lam)
+
+
+def g1_inf_image(x, y):
+    """the point at infinity the way a formula may leave it: Z = 0 under arbitrary X, Y (blst_p1_is_inf looks at Z alone)"""
+    return o.fp_to_mont_bytes(x % o.P) + o.fp_to_mont_bytes(y % o.P) + bytes(48)
+
+
+def g2_inf_image(x, y):
+    return fp2_to_mont_bytes(x) + fp2_to_mont_bytes(y) + bytes(96)
 
 
 def fp12_from_bytes(b):
