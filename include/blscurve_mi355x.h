@@ -379,6 +379,45 @@ float mi355_bls_last_deser_ms(mi355_bls_ctx* ctx);   /* duration of the deserial
  * pks: n x 96 B, sigs: n x 192 B, host memory.  Returns 0 on success. */
 int mi355_bls_combine(mi355_bls_ctx* ctx, const uint8_t rnd[32], const void* pks, const void* sigs, size_t n, uint8_t out_pk[96],
                       uint8_t out_sig[192]);
+/* combine for MANY groups in ONE device pass: k groups of SignatureSet records that carry the same message (gossip: hundreds of
+ * unaggregated attestations per message) become k ordinary 320-byte records, so that hashing, cofactor clearing and the Miller lines of a
+ * following batchVerify run once per message instead of once per signature.  mi355_bls_combine stays the call for one huge group.
+ *   sets      n_sets x 320-byte SignatureSet records: the member table
+ *   idx       NULL: group g is records [offsets[g], offsets[g+1]) of the table itself (offsets[k] <= n_sets);
+ *             else: group g is records idx[offsets[g]] .. idx[offsets[g+1] - 1] (offsets[k] = the length of idx; repeats allowed)
+ *   offsets   k + 1 entries in HOST memory (also in the _device forms), non-decreasing
+ *   rnds      k x 32 bytes in HOST memory (also in the _device forms): secureRandomBytes of every group
+ *   status    k bytes, host memory: 0 ok, 1 empty group (the reference asserts), 2 the combined key is the point at infinity, 3 an index was
+ *             >= n_sets (it is never dereferenced), 4 the members' messages are not all equal (the combination would be unsound), 5 a
+ *             member's public key is the infinity image (the reference assumes there is none); precedence 3 > 4 > 5 > 1 > 2.  The record
+ *             of a group whose status is not 0 carries the infinity key (96 zero bytes), for which every verifier answers 0, and the
+ *             infinity signature.
+ * Record g is byte for byte the reference's combine(rnds[g], pks_g, sigs_g) with the first member's message: for L >= 2 members the scalars
+ * s_0 .. s_(L-1) of the chain seeded with rnds[g] (as mi355_bls_combine draws them) in list order, key = affine(sum [s_j]PK_j), signature =
+ * affine(sum [s_j]S_j) (192 zero bytes if that is infinity; an infinity signature among the members adds nothing); L == 1: the member's
+ * record, no scalar drawn.  The chain is per group: a record depends neither on the group's position nor on how its members are addressed.
+ * At most 2^26 members per call; nothing is bounded by max_sets.  Device pointers are 4-byte aligned.  The scalars and the random bytes are
+ * cleared from device memory before a call returns.
+ * Measured on one MI355X, 65 536 members (profiles/combine_sets_bench.json): combine_sets_device alone takes 4.2 - 5.6 ms for groups of 2 to
+ * 512; batch_verify_combined_device end to end against mi355_bls_batch_verify_device over the uncombined sets: groups of 4: 11.4 against
+ * 12.3 ms, 16: 7.4 against 12.3, 64: 7.7 against 11.8, 512: 7.7 against 11.8.  At groups of 2 the combined route LOSES (14.2 against
+ * 12.3 ms): send such batches through batch_verify as they are.
+ * combine_sets:  returns 1 when every status is 0, else 0; k == 0: 0, nothing written.  MI355_BLS_ERR_ARG for decreasing offsets, offsets[k] >
+ *                n_sets without idx, NULL pointers.  The _device form enqueues on `stream` (and the context's fork stream) and synchronises
+ *                once, for the status bytes; d_out_records: k x 320 bytes of device memory.
+ * batch_verify_combined:  combine_sets, then - if every status is 0 - mi355_bls_batch_verify with rnd over the k records; any other status: 0
+ *                and no verification pass.
+ * group_by_message:  host only, no GPU.  Groups the n records of a flat batch by their 32-byte message, stably: groups in the order their
+ *                message first appears, members in input order.  idx: n entries, offsets: room for n + 1 of which *k + 1 are written. */
+int mi355_bls_combine_sets(mi355_bls_ctx* ctx, const void* sets, size_t n_sets, const uint32_t* idx, const size_t* offsets, size_t k,
+                           const uint8_t* rnds, void* out_records, uint8_t* status);
+int mi355_bls_combine_sets_device(mi355_bls_ctx* ctx, const void* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                  const uint8_t* rnds, void* d_out_records, uint8_t* status, void* stream);
+int mi355_bls_batch_verify_combined(mi355_bls_ctx* ctx, const void* sets, size_t n_sets, const uint32_t* idx, const size_t* offsets, size_t k,
+                                    const uint8_t* rnds, const uint8_t rnd[32]);
+int mi355_bls_batch_verify_combined_device(mi355_bls_ctx* ctx, const void* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets,
+                                           size_t k, const uint8_t* rnds, const uint8_t rnd[32], void* stream);
+int mi355_bls_group_by_message(const void* sets, size_t n, uint32_t* idx, size_t* offsets, size_t* k);
 
 /* aggregateVerify(publicKeys, messages, signature) (bls_sig_min_pubkey.nim:153-199; ContextCoreAggregateVerify,
  * blst_min_pubkey_sig_core.nim:305-414): e(G1, sig) == prod_i e(pk_i, H(m_i)) for n (public key, message) pairs

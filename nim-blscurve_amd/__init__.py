@@ -107,6 +107,11 @@ def lib():
         L.mi355_bls_fast_aggregate_verify_each_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_batch_fast_aggregate_verify.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, ctypes.c_char_p]
         L.mi355_bls_batch_fast_aggregate_verify_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, ctypes.c_char_p, vp]
+        L.mi355_bls_combine_sets.argtypes = [vp, vp, sz, pu32, psz, sz, ctypes.c_char_p, vp, vp]
+        L.mi355_bls_combine_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, ctypes.c_char_p, vp, vp, vp]
+        L.mi355_bls_batch_verify_combined.argtypes = [vp, vp, sz, pu32, psz, sz, ctypes.c_char_p, ctypes.c_char_p]
+        L.mi355_bls_batch_verify_combined_device.argtypes = [vp, vp, sz, vp, psz, sz, ctypes.c_char_p, ctypes.c_char_p, vp]
+        L.mi355_bls_group_by_message.argtypes = [vp, sz, pu32, psz, psz]
         L.mi355_bls_p1s_mult_pippenger_scratch_sizeof.argtypes = [sz]
         L.mi355_bls_p1s_mult_pippenger_scratch_sizeof.restype = sz
         L.mi355_bls_p1s_mult_pippenger.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), sz, ctypes.POINTER(vp), sz]
@@ -608,6 +613,89 @@ def batchFastAggregateVerify_device(cache, d_keys, n_table, d_idx, offsets, d_ms
         return False
     return bool(_check(lib().mi355_bls_batch_fast_aggregate_verify_device(cache._h, d_keys, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k,
                                                                           d_msgs, d_sigs, rnd, stream)))
+
+
+COMB_MIXED, COMB_INF_KEY = 4, 5      # status bytes of combineSets beyond aggregateSets' own
+
+
+def _groups(sets, idx, offsets, rnds):
+    """The member table, addressing and random bytes of the combineSets family -> (records, n_sets, idx array or None, offsets array, k,
+    rnds).  sets: n x 320-byte SignatureSet records; idx: None or a sequence of table indices; offsets: k + 1 non-decreasing positions (into
+    idx, or into the table when idx is None); rnds: k x 32 bytes (or a list of k 32-byte strings), secureRandomBytes of every group."""
+    b = _as_records(sets)
+    offsets = [int(x) for x in offsets]
+    if not offsets or any(x < 0 for x in offsets):
+        raise ValueError("offsets: k + 1 non-negative positions")
+    k = len(offsets) - 1
+    if idx is not None:
+        idx = [int(x) for x in idx]
+        if any(x < 0 or x >= 1 << 32 for x in idx):
+            raise ValueError("indices are 32-bit unsigned")
+        if offsets[-1] != len(idx):
+            raise ValueError("offsets[k] is the length of the index array")
+    r = _join(rnds, 32, "rnds")
+    if len(r) != 32 * k:
+        raise ValueError("32 random bytes per group")
+    iarr = (ctypes.c_uint32 * max(len(idx), 1))(*idx) if idx is not None else None
+    return b, len(b) // SIGSET_BYTES, iarr, (ctypes.c_size_t * (k + 1))(*offsets), k, r
+
+
+def combineSets(cache, sets, idx, offsets, rnds):
+    """MultiSignatureSet.combine (bls_batch_verifier.nim:47-106) for every group in one device pass (mi355_bls_combine_sets); arguments as
+    _groups takes them.  -> (all_ok, k x 320-byte combined records, k status bytes: 0 ok, 1 empty group, 2 combined key at infinity, 3 index
+    out of range, 4 mixed messages, 5 a member with the infinity key; a record whose status is not 0 carries the infinity key)."""
+    b, n, iarr, offs, k, r = _groups(sets, idx, offsets, rnds)
+    if k == 0:
+        return False, b"", b""
+    out, st = ctypes.create_string_buffer(320 * k), ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_combine_sets(cache._h, b or b"\0", n, iarr, offs, k, r, out, st))
+    return bool(ok), out.raw, st.raw
+
+
+def combineSets_device(cache, d_sets, n_sets, d_idx, offsets, rnds, d_out, stream=0):
+    """Same with the member table, the indices (0 / None: none) and the output records in device memory (raw pointers); offsets and rnds
+    stay on the host.  -> (all_ok, status bytes)."""
+    k = len(offsets) - 1
+    if k <= 0:
+        return False, b""
+    r = _join(rnds, 32, "rnds")
+    if len(r) != 32 * k:
+        raise ValueError("32 random bytes per group")
+    st = ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_combine_sets_device(cache._h, d_sets, n_sets, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k, r, d_out, st, stream))
+    return bool(ok), st.raw
+
+
+def batchVerifyCombined(cache, sets, idx, offsets, rnds, secureRandomBytes):
+    """combineSets, then batchVerify with secureRandomBytes over the k combined records (mi355_bls_batch_verify_combined): False when a
+    group gives no record (any status but 0) or the batch does not verify; no groups -> False."""
+    rnd = _rnd32(secureRandomBytes)
+    b, n, iarr, offs, k, r = _groups(sets, idx, offsets, rnds)
+    if k == 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_verify_combined(cache._h, b or b"\0", n, iarr, offs, k, r, rnd)))
+
+
+def batchVerifyCombined_device(cache, d_sets, n_sets, d_idx, offsets, rnds, secureRandomBytes, stream=0):
+    rnd = _rnd32(secureRandomBytes)
+    k = len(offsets) - 1
+    if k <= 0:
+        return False
+    r = _join(rnds, 32, "rnds")
+    if len(r) != 32 * k:
+        raise ValueError("32 random bytes per group")
+    return bool(_check(lib().mi355_bls_batch_verify_combined_device(cache._h, d_sets, n_sets, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k, r, rnd,
+                                                                    stream)))
+
+
+def groupByMessage(sets):
+    """The records of a flat batch grouped by their 32-byte message, stably (mi355_bls_group_by_message; host only, no GPU): -> (idx,
+    offsets), groups in the order their message first appears, members in input order - what combineSets takes with the batch as table."""
+    b = _as_records(sets)
+    n = len(b) // SIGSET_BYTES
+    idx, offs, k = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_size_t * (n + 1))(), ctypes.c_size_t(0)
+    _check(lib().mi355_bls_group_by_message(b or b"\0", n, idx, offs, ctypes.byref(k)))
+    return list(idx)[:n], list(offs)[:k.value + 1]
 
 
 def verifyAggregate(cache, aggregate_p1, message, signature):

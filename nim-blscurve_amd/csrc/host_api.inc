@@ -121,6 +121,18 @@ struct mi355_bls_ctx {
     dev_buf<uint8_t> d_agg_in;       // host inputs staged: keys | signatures | messages | indices
     std::vector<uint32_t> agg_tab;   // the table of the call in flight: the async copy reads it
     std::vector<uint8_t> agg_status_h;
+    // same-message pre-aggregation (mi355_bls_combine_sets): sized by the call like the buffers above, which it shares (item table, G1
+    // partials, flag words, status bytes, records, staged inputs)
+    dev_buf<uint64_t> d_comb_s;      // s_j by position: blinding material, cleared before every return
+    dev_buf<uint8_t> d_comb_rnd;     // the groups' random bytes (cleared likewise)
+    dev_buf<uint32_t> d_comb_gather; // the member records by position, when the call addresses them through indices
+    dev_buf<uint4> d_comb_P;         // [s_j]PK_j, SoA Jacobian as k_pkmul writes it
+    dev_buf<uint32_t> d_comb_g2;     // [s_j]S_j, G2W words each
+    dev_buf<uint32_t> d_comb_part2;  // the plan's G2 partials
+    dev_buf<uint8_t> d_comb_pktab;   // the window tables of one chunk of members: k_pkmul's ...
+    dev_buf<uint4> d_comb_g2tab;     // ... and k_combsets_g2mul's
+    dev_buf<uint32_t> d_comb_pkflag; // k_pkmul's infinity-key word (the check items report such a key per group)
+    std::vector<uint64_t> comb_s_h;  // the chains the host walks, until the call's synchronisation
 
     // the batch workspace's pair store (ctx_build makes it; it never changes) and the per-set path's (each_reserve)
     pair_store batch_pairs() const { return {d_H, d_P, d_lines, stride}; }
@@ -1082,6 +1094,219 @@ extern "C" int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* c, const voi
     int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
     if (rc) return rc;
     return agg_batch(c, in, n_table, offsets, k, rnd, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Same-message pre-aggregation: MultiSignatureSet.combine (bls_batch_verifier.nim:47-106, core :570-647) for k groups of SignatureSet records
+// in one device pass.  Group g = positions [offsets[g], offsets[g + 1]) of the member sequence (the record table itself, or table entries
+// picked by index: the addressing of aggregate_sets) becomes ONE record - key sum [s_j]PK_j, the members' message, signature sum [s_j]S_j,
+// s_j from the chain seeded with rnds[g] - and a status byte.  Per member two 64-bit multiplications, per group two segmented sums over
+// the plan's item tables and a finish lane (kernels.hip, csrc/combsets.hpp); the key side on the caller's stream, the signature side on
+// the context's fork stream beside it.  The scalars and the random bytes are cleared on the device before the call returns.
+// ------------------------------------------------------------------------------------------
+// combination of k > 0 groups enqueued on st: records at d_out, status bytes in c->d_agg_status
+static int combsets_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k, const uint8_t* rnds,
+                            uint8_t* d_out, hipStream_t st) {
+    if (!d_sets || !offsets || !rnds || !d_out) return MI355_BLS_ERR_ARG;
+    if (((uintptr_t)d_sets | (uintptr_t)d_idx | (uintptr_t)d_out) & 3) {
+        g_err = "combine_sets: records and indices must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const plan::combsets_plan cp = plan::combsets_measure(offsets, k);
+    if (!cp.ok) {
+        g_err = "combine_sets: offsets decrease, or more than 2^26 members or 2^32 - 2 groups";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (!d_idx && offsets[k] > n_sets) {
+        g_err = "combine_sets: offsets[k] exceeds the number of records";
+        return MI355_BLS_ERR_ARG;
+    }
+    const size_t N = cp.members;
+    std::vector<size_t> rel(k + 1);
+    for (size_t g = 0; g <= k; g++) rel[g] = offsets[g] - cp.lo;
+    const plan::aggsets_plan p = plan::aggsets_measure(rel.data(), k);
+    if (!p.ok) {
+        g_err = "combine_sets: too many members";
+        return MI355_BLS_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    // item table | final_of | first position | length of every group
+    c->agg_tab.resize(p.items * 4 + 3 * k);
+    uint32_t *h_final = c->agg_tab.data() + p.items * 4, *h_first = h_final + k, *h_len = h_first + k;
+    plan::aggsets_fill(p, rel.data(), k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), h_final);
+    for (size_t g = 0; g < k; g++) h_first[g] = (uint32_t)rel[g], h_len[g] = (uint32_t)(rel[g + 1] - rel[g]);
+    const size_t n1 = N ? N : 1, it1 = p.items ? p.items : 1, tb = c->agg_tab.size() * 4, stride = (n1 + 63) / 64 * 64, tcap = cp.chunk_cap ? cp.chunk_cap : WAVE;
+    int rc = c->d_agg_part.reserve(it1 * (size_t)G1W * 4, it1 * (size_t)G1W);
+    if (!rc) rc = c->d_comb_part2.reserve(it1 * (size_t)G2W * 4, it1 * (size_t)G2W);
+    if (!rc) rc = c->d_agg_tab.reserve(tb, tb / 4);
+    if (!rc) rc = c->d_agg_bad.reserve(k * 4, k);
+    if (!rc) rc = c->d_agg_status.reserve(k, k / 4);
+    if (!rc) rc = c->d_comb_s.reserve(n1 * 8, n1 * 2);
+    if (!rc) rc = c->d_comb_rnd.reserve(k * 32, k * 8);
+    if (!rc) rc = c->d_comb_P.reserve(stride * 3 * 64, stride * 48);
+    if (!rc) rc = c->d_comb_g2.reserve(n1 * (size_t)G2W * 4, n1 * (size_t)G2W);
+    if (!rc) rc = c->d_comb_pktab.reserve(tcap * PKTAB_BYTES, 0);
+    if (!rc) rc = c->d_comb_g2tab.reserve(tcap * 8 * 6 * 64, 0);
+    if (!rc) rc = c->d_comb_pkflag.reserve(4, 0);
+    if (!rc && d_idx) rc = c->d_comb_gather.reserve(n1 * 320, n1 * 80);
+    if (rc) return rc;
+    const size_t P_stride = c->d_comb_P.bytes / (3 * 64), g2tcap = c->d_comb_g2tab.bytes / (8 * 6 * 64);      // what the buffers hold (they may be larger than this call needs)
+    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, k * 4, st));
+    HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), tb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->d_comb_rnd, rnds, k * 32, hipMemcpyHostToDevice, st));
+    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
+    const uint32_t *d_final = c->d_agg_tab + p.items * 4, *d_first = d_final + k, *d_len = d_first + k;
+    const uint32_t* idx = d_idx ? d_idx + cp.lo : nullptr;
+    const uint32_t* recs = reinterpret_cast<const uint32_t*>(d_sets) + (d_idx ? 0 : cp.lo * 80);
+    const uint32_t k32 = (uint32_t)k, N32 = (uint32_t)N;
+    if (N) {
+        if (idx) {
+            k_combsets_gather<<<(uint32_t)((N * 80 + 255) / 256), 256, 0, st>>>(reinterpret_cast<const uint32_t*>(d_sets), n_sets, idx, N32, c->d_comb_gather);
+            recs = c->d_comb_gather;
+        }
+        k_combsets_scalars<<<plan::waves_for(k32), WAVE, 0, st>>>(d_first, d_len, k32, c->d_comb_rnd, plan::COMB_CHAIN_LANE_MAX, c->d_comb_s);
+        if (cp.host_chains) {                    // the long groups' chains, walked here while the device walks the others'
+            c->comb_s_h.clear();
+            size_t total = 0;
+            for (size_t g = 0; g < k; g++)
+                if (plan::combsets_chain_on_host(h_len[g])) total += h_len[g];
+            c->comb_s_h.resize(total);
+            size_t at = 0;
+            for (size_t g = 0; g < k; g++) {
+                if (!plan::combsets_chain_on_host(h_len[g])) continue;
+                uint64_t* o = c->comb_s_h.data() + at;
+                combsets_chain(rnds + g * 32, h_len[g], [&](size_t j, uint64_t v) { o[j] = v; });
+                HIPCHK(hipMemcpyAsync(c->d_comb_s + h_first[g], o, (size_t)h_len[g] * 8, hipMemcpyHostToDevice, st));
+                at += h_len[g];
+            }
+        }
+        // fork: the signature side on the context's first fork stream, the key side here
+        hipStream_t s2 = ensure_side(c) ? (hipStream_t)c->side : st;
+        if (s2 != st) {
+            HIPCHK(hipEventRecord(c->ev[0], st));
+            HIPCHK(hipStreamWaitEvent(s2, c->ev[0], 0));
+        }
+        for (size_t a = 0; a < N; a += plan::COMB_MUL_CHUNK) {
+            const uint32_t m = (uint32_t)(N - a < plan::COMB_MUL_CHUNK ? N - a : plan::COMB_MUL_CHUNK);
+            k_combsets_g2mul<<<plan::waves_for(m), WAVE, 0, s2>>>(recs + a * 80, m, c->d_comb_s + a, c->d_comb_g2tab, g2tcap, c->d_comb_g2 + a * (size_t)G2W);
+        }
+        for (uint32_t l = 0; l < p.levels; l++) {
+            const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
+            k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, s2>>>(items + p.level_first[l], cnt, l == 0 ? c->d_comb_g2.p : c->d_comb_part2.p, c->d_comb_part2);
+        }
+        if (s2 != st) HIPCHK(hipEventRecord(c->ev[2], s2));
+        HIPCHK(hipMemsetAsync(c->d_comb_pkflag, 0, 4, st));
+        for (size_t a = 0; a < N; a += plan::COMB_MUL_CHUNK) {
+            const uint32_t m = (uint32_t)(N - a < plan::COMB_MUL_CHUNK ? N - a : plan::COMB_MUL_CHUNK);
+            k_pkmul<<<plan::waves_for(m), WAVE, 0, st>>>(reinterpret_cast<const uint8_t*>(recs + a * 80), m, c->d_comb_s + a, c->d_comb_P + a, P_stride, c->d_comb_pkflag,
+                                                         c->d_comb_pktab);
+        }
+        for (uint32_t l = 0; l < p.levels; l++) {
+            const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
+            if (l == 0) k_combsets_g1_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, c->d_comb_P, P_stride, recs, idx, n_sets, d_first, c->d_agg_part, c->d_agg_bad);
+            else k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + p.level_first[l], cnt, c->d_agg_part);
+        }
+        if (s2 != st) HIPCHK(hipStreamWaitEvent(st, c->ev[2], 0));
+    }
+    k_combsets_finish<<<plan::waves_for(k32), WAVE, 0, st>>>(d_final, d_first, d_len, k32, c->d_agg_part, c->d_comb_part2, c->d_agg_bad, recs, idx, n_sets,
+                                                             reinterpret_cast<uint32_t*>(d_out), c->d_agg_status);
+    HIPCHK(hipGetLastError());
+    // the scalars are blinding material: nothing of them stays on the device
+    if (N) HIPCHK(hipMemsetAsync(c->d_comb_s, 0, N * 8, st));
+    HIPCHK(hipMemsetAsync(c->d_comb_rnd, 0, k * 32, st));
+    return 0;
+}
+// the status bytes back (the call's synchronisation): 1 when every group gave a record; the host's chains go with it
+static int combsets_status(mi355_bls_ctx* c, size_t k, uint8_t* status, hipStream_t st) {
+    const int rc = aggsets_status(c, k, status, st);
+    std::fill(c->comb_s_h.begin(), c->comb_s_h.end(), 0);
+    return rc;
+}
+// host records (and indices) -> d_agg_in
+static int combsets_stage(mi355_bls_ctx* c, const void* sets, size_t n_sets, const uint32_t* idx, const size_t* offsets, size_t k, hipStream_t st,
+                          const uint8_t** d_sets, const uint32_t** d_idx) {
+    if (!sets || !offsets || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
+    const size_t n_idx = idx ? offsets[k] : 0, sb = n_sets * 320, all = sb + n_idx * 4 + 4;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->d_agg_in.reserve(all, all / 4);
+    if (rc) return rc;
+    uint8_t* d = c->d_agg_in;
+    if (sb) HIPCHK(hipMemcpyAsync(d, sets, sb, hipMemcpyHostToDevice, st));
+    if (n_idx) HIPCHK(hipMemcpyAsync(d + sb, idx, n_idx * 4, hipMemcpyHostToDevice, st));
+    *d_sets = d, *d_idx = idx ? reinterpret_cast<const uint32_t*>(d + sb) : nullptr;
+    return 0;
+}
+extern "C" int mi355_bls_combine_sets_device(mi355_bls_ctx* c, const void* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                             const uint8_t* rnds, void* d_out_records, uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing combined, nothing written
+    if (!status) return MI355_BLS_ERR_ARG;
+    int rc = combsets_enqueue(c, (const uint8_t*)d_sets, n_sets, d_idx, offsets, k, rnds, (uint8_t*)d_out_records, (hipStream_t)stream);
+    if (rc) return rc;
+    return combsets_status(c, k, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_combine_sets(mi355_bls_ctx* c, const void* sets, size_t n_sets, const uint32_t* idx, const size_t* offsets, size_t k, const uint8_t* rnds,
+                                      void* out_records, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!out_records || !status) return MI355_BLS_ERR_ARG;
+    const uint8_t* d_sets;
+    const uint32_t* d_idx;
+    int rc = combsets_stage(c, sets, n_sets, idx, offsets, k, nullptr, &d_sets, &d_idx);
+    if (!rc) rc = c->d_agg_rec.reserve(k * 320, k * 80);
+    if (!rc) rc = combsets_enqueue(c, d_sets, n_sets, d_idx, offsets, k, rnds, c->d_agg_rec, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out_records, c->d_agg_rec, k * 320, hipMemcpyDeviceToHost, nullptr));
+    return combsets_status(c, k, status, nullptr);
+}
+// batchVerify over the k combined records: a group that gives no record (any status but 0) ends the call with 0 before any verification pass
+static int combsets_batch(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k, const uint8_t* rnds,
+                          const uint8_t rnd[32], hipStream_t st) {
+    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
+    if (!rc) rc = combsets_enqueue(c, d_sets, n_sets, d_idx, offsets, k, rnds, c->d_agg_rec, st);
+    if (rc) return rc;
+    c->agg_status_h.resize(k);
+    rc = combsets_status(c, k, c->agg_status_h.data(), st);
+    if (rc != 1) return rc;
+    return verify_common(c, c->d_agg_rec, nullptr, k, rnd, 0, st);
+}
+extern "C" int mi355_bls_batch_verify_combined_device(mi355_bls_ctx* c, const void* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                                      const uint8_t* rnds, const uint8_t rnd[32], void* stream) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    return combsets_batch(c, (const uint8_t*)d_sets, n_sets, d_idx, offsets, k, rnds, rnd, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_batch_verify_combined(mi355_bls_ctx* c, const void* sets, size_t n_sets, const uint32_t* idx, const size_t* offsets, size_t k,
+                                               const uint8_t* rnds, const uint8_t rnd[32]) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    const uint8_t* d_sets;
+    const uint32_t* d_idx;
+    int rc = combsets_stage(c, sets, n_sets, idx, offsets, k, nullptr, &d_sets, &d_idx);
+    if (rc) return rc;
+    return combsets_batch(c, d_sets, n_sets, d_idx, offsets, k, rnds, rnd, nullptr);
+}
+// Host only, no GPU: the records of a flat batch grouped by their 32-byte message, stably - groups in the order their message first appears,
+// members in input order.  idx: n positions, offsets: n + 1 entries of which k + 1 are written.
+extern "C" int mi355_bls_group_by_message(const void* sets, size_t n, uint32_t* idx, size_t* offsets, size_t* k) {
+    if (!offsets || !k || (n && (!sets || !idx)) || n >= 0xffffffffu) return MI355_BLS_ERR_ARG;
+    const uint8_t* b = (const uint8_t*)sets;
+    std::unordered_map<std::string, uint32_t> group_of;
+    std::vector<uint32_t> of(n), count;
+    for (size_t i = 0; i < n; i++) {
+        const auto it = group_of.emplace(std::string((const char*)b + i * 320 + 96, 32), (uint32_t)count.size());
+        if (it.second) count.push_back(0);
+        of[i] = it.first->second;
+        count[of[i]]++;
+    }
+    offsets[0] = 0;
+    for (size_t g = 0; g < count.size(); g++) offsets[g + 1] = offsets[g] + count[g];
+    std::vector<size_t> cur(offsets, offsets + count.size());
+    for (size_t i = 0; i < n; i++) idx[cur[of[i]]++] = (uint32_t)i;
+    *k = count.size();
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/blscurve_mi355x.h"
@@ -34,6 +35,7 @@
 #include "pairing.hpp"
 #include "vereach.hpp"
 #include "aggsets.hpp"
+#include "combsets.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -2251,6 +2253,85 @@ __global__ void __launch_bounds__(WAVE) k_aggsets_finish(const uint32_t* __restr
     for (int i = 0; i < 8; i++) r[24 + i] = msgs[(size_t)s * 8 + i];
     for (int i = 0; i < 48; i++) r[32 + i] = sigs[(size_t)s * 48 + i];
     status[s] = e.status;
+}
+
+// ------------------------------------------------------------------------------------------
+// Same-message pre-aggregation of many groups (mi355_bls_combine_sets: MultiSignatureSet.combine, bls_batch_verifier.nim:47-106, core
+// :570-647, for k groups of SignatureSet records in one pass).  The arithmetic is csrc/combsets.hpp; members are numbered by position in
+// the call's member sequence, and `recs` holds the record of every position (the caller's table itself, or k_combsets_gather's copy).
+// Per member: s_j (k_combsets_scalars, or the host for a long group), [s_j]PK_j (k_pkmul on the member records, SoA Jacobian) and
+// [s_j]S_j (k_combsets_g2mul, internal G2 images).  Per group: the segmented sums over plan.hpp aggsets_fill's item tables - level 0 reads
+// the per-member products by position, higher levels partials (G1: k_aggsets_ln itself) - and k_combsets_finish.
+// ------------------------------------------------------------------------------------------
+// positions through an index array -> records by position, one lane per word; an index that is not below n_sets is not dereferenced and
+// leaves a zero record (the infinity key: k_pkmul and k_combsets_g2mul add nothing for it)
+__global__ void __launch_bounds__(256) k_combsets_gather(const uint32_t* __restrict__ sets, size_t n_sets, const uint32_t* __restrict__ idx, uint32_t n,
+                                                         uint32_t* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, pos = t / 80, w = t % 80;
+    if (pos >= n) return;
+    const size_t at = idx[pos];
+    out[t] = at < n_sets ? sets[at * 80 + w] : 0u;
+}
+// one lane per group of 2 .. lane_max members: its chain, s_j at the member's position.  A group of one draws no scalar (0: its products are
+// not computed, the finish lane copies the member); a longer group's scalars come from the host (plan.hpp combsets_chain_on_host).
+__global__ void __launch_bounds__(WAVE) k_combsets_scalars(const uint32_t* __restrict__ seg_first, const uint32_t* __restrict__ seg_len, uint32_t k,
+                                                           const uint8_t* __restrict__ rnds, uint32_t lane_max, uint64_t* __restrict__ s) {
+    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= k) return;
+    const uint32_t len = seg_len[g];
+    uint64_t* o = s + seg_first[g];
+    if (len == 1) o[0] = 0;
+    if (len < 2 || len > lane_max) return;
+    uint8_t rnd[32];
+    for (int i = 0; i < 32; i++) rnd[i] = rnds[(size_t)g * 32 + i];
+    combsets_chain(rnd, len, [&](size_t j, uint64_t v) { o[j] = v; });
+}
+// one lane per member of a chunk: [s]S (S: the blst_p2_affine image at word 32 of the member's record) -> internal G2 image `out`.  The
+// lane's window table is slots e * tcap + i, e < 8, of the SoA buffer `tab` (stride 8 tcap): a wave's loads of one entry are contiguous.
+__global__ void __launch_bounds__(WAVE) k_combsets_g2mul(const uint32_t* __restrict__ recs, uint32_t n, const uint64_t* __restrict__ s, uint4* __restrict__ tab,
+                                                         size_t tcap, uint32_t* __restrict__ out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const g2_aff q = ld_g2a_blst(recs + (size_t)i * 80 + 32);
+    const g2_jac r = combsets_mul_item(q, s[i], [&](int e, const g2_jac& t) { soa_st_g2(tab, 8 * tcap, (size_t)e * tcap + i, t); },
+                                       [&](int e) { return soa_ld_g2(tab, 8 * tcap, (size_t)e * tcap + i); });
+    st_g2_int(out + (size_t)i * G2W, r);
+}
+// level 0 of the key side, one lane per item: up to AGG_C of k_pkmul's products by position -> one partial, and the item's members checked
+// (combsets_check_item: its flags into the group's word)
+__global__ void __launch_bounds__(WAVE, 2) k_combsets_g1_l0(const uint4* __restrict__ items, uint32_t n_items, const uint4* __restrict__ P, size_t stride,
+                                                            const uint32_t* __restrict__ recs, const uint32_t* __restrict__ idx, size_t n_sets,
+                                                            const uint32_t* __restrict__ seg_first, uint32_t* __restrict__ part, uint32_t* __restrict__ seg_flags) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    const uint32_t fl = combsets_check_item(it.x, it.y, seg_first[it.w], [&](uint32_t pos) { return idx && idx[pos] >= n_sets; },
+                                            [&](uint32_t pos) { return recs + (size_t)pos * 80; });
+    if (fl) atomicOr(seg_flags + it.w, fl);
+    st_g1_int(part + (size_t)it.z * G1W, aggsets_ln_item(it.x, it.y, [&](uint32_t j) { return soa_ld_g1(P, stride, j); }));
+}
+// the signature side, one lane per item: up to AGG_C internal G2 images of `src` (level 0: the per-member products; above: the partials) ->
+// partial it.z of `dst`
+__global__ void __launch_bounds__(WAVE) k_combsets_g2_sum(const uint4* __restrict__ items, uint32_t n_items, const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    st_g2_int(dst + (size_t)it.z * G2W, combsets_sum_item<fp2>(it.x, it.y, [&](uint32_t j) { return ld_g2_int(src + (size_t)j * G2W); }));
+}
+// one lane per group: its last partials (final_of[g]; 0xffffffff: no member) to affine, the record and the status byte (combsets_finish_item)
+__global__ void __launch_bounds__(WAVE) k_combsets_finish(const uint32_t* __restrict__ final_of, const uint32_t* __restrict__ seg_first,
+                                                          const uint32_t* __restrict__ seg_len, uint32_t k, const uint32_t* __restrict__ part1,
+                                                          const uint32_t* __restrict__ part2, const uint32_t* __restrict__ seg_flags, const uint32_t* __restrict__ recs,
+                                                          const uint32_t* __restrict__ idx, size_t n_sets, uint32_t* __restrict__ records, uint8_t* __restrict__ status) {
+    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= k) return;
+    const uint32_t f = final_of[g], len = seg_len[g], first = seg_first[g];
+    const bool sums = len >= 2 && f != 0xffffffffu, have_first = len >= 1 && !(idx && idx[first] >= n_sets);
+    const combsets_end e = combsets_finish_item(len, seg_flags[g], sums ? ld_g1_int(part1 + (size_t)f * G1W) : jac_inf<fp>(),
+                                                sums ? ld_g2_int(part2 + (size_t)f * G2W) : jac_inf<fp2>(), have_first ? recs + (size_t)first * 80 : nullptr);
+    uint32_t* r = records + (size_t)g * 80;
+    for (int i = 0; i < 80; i++) r[i] = e.rec[i];
+    status[g] = e.status;
 }
 
 // ------------------------------------------------------------------------------------------

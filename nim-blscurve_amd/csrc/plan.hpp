@@ -301,6 +301,40 @@ inline void aggsets_fill(const aggsets_plan& p, const size_t* offsets, size_t k,
     }
 }
 
+// Same-message pre-aggregation of k groups (mi355_bls_combine_sets): the members are positions [offsets[0], offsets[k]) of the call's member
+// sequence, renumbered from 0; the two segmented sums run over aggsets_measure / aggsets_fill's tables for the renumbered offsets (level 0
+// reads the per-member products by position).
+//   Scalars: a group's SHA-256 chain is serial - one digest per four members, a few microseconds each on a lane - so one lane walks the chain
+//   of a group of up to COMB_CHAIN_LANE_MAX members (all groups side by side), and the HOST walks a longer group's chain while the device
+//   works on the lanes' (combsets_chain_on_host; mi355_bls_combine stays the call for one huge group).
+//   Products: the per-member multiplications keep window tables in context buffers (2 560 bytes per key, 3 072 per signature), so they run in
+//   chunks of COMB_MUL_CHUNK members and the tables never hold more than one chunk.
+//   COMB_MEMBERS_MAX: k_pkmul takes the byte stride of a row of its SoA output as a 32-bit value.
+constexpr uint32_t COMB_CHAIN_LANE_MAX = 1024;
+constexpr size_t COMB_MUL_CHUNK = 65536, COMB_MEMBERS_MAX = (size_t)1 << 26;
+inline bool combsets_chain_on_host(size_t len) { return len > COMB_CHAIN_LANE_MAX; }
+struct combsets_plan {
+    bool ok;                                 // false: offsets decrease, or more than COMB_MEMBERS_MAX members, or 2^32 - 1 groups or more
+    size_t lo, members;                      // positions [lo, lo + members) of the member sequence
+    size_t chunks, chunk_cap;                // multiplication launches per side; members the window tables hold
+    size_t host_chains;                      // groups whose chain the host walks
+};
+inline combsets_plan combsets_measure(const size_t* offsets, size_t k) {
+    combsets_plan p{};
+    if (k >= AGG_NONE) return p;
+    p.lo = k ? offsets[0] : 0;
+    for (size_t g = 0; g < k; g++) {
+        if (offsets[g + 1] < offsets[g]) return p;
+        p.host_chains += combsets_chain_on_host(offsets[g + 1] - offsets[g]);
+    }
+    p.members = k ? offsets[k] - p.lo : 0;
+    if (p.members > COMB_MEMBERS_MAX) return p;
+    p.chunks = (p.members + COMB_MUL_CHUNK - 1) / COMB_MUL_CHUNK;
+    p.chunk_cap = p.members < COMB_MUL_CHUNK ? (p.members + WAVE - 1) / WAVE * WAVE : COMB_MUL_CHUNK;
+    p.ok = true;
+    return p;
+}
+
 // chunk of the parallel_chunks partition (parallel_chunks.nim:42-66) that tuple t of n_total falls into, B chunks
 inline uint32_t chunk_of_tuple(size_t n_total, uint32_t B, size_t t) {
     size_t base = n_total / B, rem = n_total % B, cut = (base + 1) * rem;
