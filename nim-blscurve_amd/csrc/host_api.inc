@@ -6,6 +6,8 @@
 #include "devres.hpp"    // the owners of device buffers, events, streams and pinned memory
 using plan::SIG_SLOTS_MAX;
 static_assert(plan::WAVE == (uint32_t)WAVE && plan::N_LINES == (uint32_t)N_LINES, "plan.hpp restates the wave size and the Miller loop's step count");
+static_assert(plan::FP_WORDS == (uint32_t)FPW && plan::G1_WORDS == (uint32_t)G1W && plan::G2_WORDS == (uint32_t)G2W && plan::F12_WORDS == (uint32_t)F12W,
+              "plan.hpp restates the words of an element in device buffers");
 
 // ------------------------------------------------------------------------------------------
 // Context
@@ -221,7 +223,6 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     c->device = device;
     c->cap = max_sets;
     c->cap_io = max_sets;
-    c->stride = ((max_sets + 1 + SIG_SLOTS_MAX + 63) / 64) * 64;          // tuple pairs + the extra pair(s) of the signature side
     std::memset(&c->dst, 0, sizeof(c->dst));
     c->dst.len = sizeof(DST_SIG) - 1;
     std::memcpy(c->dst.b, DST_SIG, c->dst.len);
@@ -229,14 +230,10 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     c->slots = 4u * (uint32_t)prop.multiProcessorCount;
-    size_t nwaves = c->stride / 64;
-    // k_lineprod hands over (68 steps x nblk ranges x 64 lanes) partial products; nblk <= slots / 68, and never more ranges than waves of pairs
-    uint32_t nblk = c->slots / N_LINES;
-    if (nblk < 1) nblk = 1;
-    if (nblk > 64) nblk = 64;
-    if (nblk > nwaves) nblk = (uint32_t)nwaves;
-    c->nblk_cap = nblk;
-    c->mstride = ((2 * max_sets + 63) / 64) * 64;
+    const plan::ctx_sizes sz = plan::ctx_for(c->slots, max_sets);
+    c->stride = sz.stride;                         // tuple pairs + the extra pair(s) of the signature side
+    c->nblk_cap = sz.nblk_cap;
+    c->mstride = sz.mstride;
     int rc = 0;                                    // the first failure: nothing is created behind it
     const auto alloc = [&rc](auto& buf, size_t bytes) { rc = rc ? rc : buf.alloc(bytes); };
     alloc(c->d_sets, max_sets * 320);
@@ -256,7 +253,7 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     alloc(c->d_msg, 4096 + 192 + 64 + 288);      // message | affine signature | pad | Jacobian signature (AggregateSignature overloads)
     alloc(c->d_comp, max_sets * 320);          // wire-format staging: keys (<= 96 B) | messages (32 B) | signatures (<= 192 B)
     alloc(c->d_status, max_sets);
-    alloc(c->d_lpart, (size_t)N_LINES * (c->nblk_cap * (WAVE + 1) + 64) * F12W * 4);     // per-lane partial products of k_lineprod (+ k_fold's first-level results)
+    alloc(c->d_lpart, sz.lpart_words * 4);         // per-lane partial products of k_lineprod (+ k_fold's first-level results)
     alloc(c->d_L, (size_t)N_LINES * F12W * 4);
     alloc(c->d_states, 64 * 576);
     alloc(c->d_gt, 576);
@@ -264,7 +261,7 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     alloc(c->d_carry, 64);
     alloc(c->d_blob, MI355_BLS_BLOB_BYTES);
     alloc(c->d_flags, 16);
-    alloc(c->d_export, c->stride * 288 + 2048 * 2 * G1W * 4);
+    alloc(c->d_export, sz.export_bytes);
     if (rc) return rc;
     c->d_blob_out = c->d_blob;
     (void)ensure_side(c);                          // the fork streams (a context without them still works: nothing forks)
@@ -272,8 +269,8 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     for (auto& e : c->ev) rc = rc ? rc : e.create();
     for (dev_event* e : {&c->ev_hm, &c->ev_lp, &c->ev_s0, &c->ev_l0, &c->ev_deser0, &c->ev_deser1}) rc = rc ? rc : e->create();
     if (rc) return rc;
-    k_sig_consts<<<(256 + WAVE - 1) / WAVE, WAVE>>>(4, 256, c->d_sig_consts);
-    k_sig_consts<<<(2048 + WAVE - 1) / WAVE, WAVE>>>(8, 2048, c->d_sig_consts + (size_t)SIG_SLOTS_MAX * G1W);
+    k_sig_consts<<<plan::waves_for(256), WAVE>>>(4, 256, c->d_sig_consts);
+    k_sig_consts<<<plan::waves_for(2048), WAVE>>>(8, 2048, c->d_sig_consts + (size_t)SIG_SLOTS_MAX * G1W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     return 0;
@@ -363,9 +360,9 @@ extern "C" int mi355_bls_debug_g2_clear_cofactor(mi355_bls_ctx* c, const uint8_t
     HIPCHK(hipMemcpy(d_in, in_pairs, n * 576, hipMemcpyHostToDevice));
     const pair_store ps = c->batch_pairs();
     const uint32_t n32 = (uint32_t)n;
-    k_debug_to_soa<<<(2 * n32 + WAVE - 1) / WAVE, WAVE>>>(d_in, 2 * n32, c->d_M, c->mstride);
+    k_debug_to_soa<<<plan::waves_for(2 * n32), WAVE>>>(d_in, 2 * n32, c->d_M, c->mstride);
     launch_hash_clear(c, ps, n32, nullptr);                       // the kernels the batch path would launch for this context and size
-    k_export_g2<<<(n32 + 63) / 64, 64>>>(ps.H, ps.stride, n32, c->d_export);
+    k_export_g2<<<plan::waves_for(n32), WAVE>>>(ps.H, ps.stride, n32, c->d_export);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out_p2, c->d_export, n * 288, hipMemcpyDeviceToHost));      // blocking: d_in is idle when it goes
     return 0;
@@ -497,7 +494,7 @@ static int enqueue_line_products(mi355_bls_ctx* c, const pair_store& ps, uint32_
     k_lineprod<<<dim3(N_LINES, p.nblk), WAVE, 0, st>>>(ps.lines, npairs, ps.stride, p.m, c->d_lpart, p.nblk, p.per_lane);
     if (mid_ev) HIPCHK(hipEventRecord(mid_ev, st));
     if (c->fold_form) {
-        uint32_t* mid = c->d_lpart + (size_t)N_LINES * c->nblk_cap * WAVE * F12W;
+        uint32_t* mid = c->d_lpart + plan::lpart_mid_words(c->nblk_cap);
         k_fold<<<dim3(N_LINES, p.nb1), TAIL_THREADS, 0, st>>>(c->d_lpart, p.nblk * WAVE, p.per, p.live - (p.nb1 - 1) * p.per, p.nb1 > 1 ? mid : c->d_L);
         if (p.nb1 > 1) k_fold<<<dim3(N_LINES, 1), TAIL_THREADS, 0, st>>>(mid, p.nb1, p.nb1, p.nb1, c->d_L);
     } else {
@@ -522,7 +519,7 @@ static int run_slice(mi355_bls_ctx* c, mi355_bls_ctx* p, const uint8_t* d_sets, 
     if (serial) {
         HIPCHK(hipMemcpyAsync(c->d_r, p->h_r.data() + serial_off, n * 8, hipMemcpyHostToDevice, st));
     } else {
-        k_blind<<<(chunk_cnt + WAVE - 1) / WAVE, WAVE, 0, st>>>(p->d_rnd, n_total, nchunks, chunk_lo, chunk_cnt, tuple_base, n, p->d_carry + 8 * (slice & 1),
+        k_blind<<<plan::waves_for(chunk_cnt), WAVE, 0, st>>>(p->d_rnd, n_total, nchunks, chunk_lo, chunk_cnt, tuple_base, n, p->d_carry + 8 * (slice & 1),
                                                                 p->d_carry + 8 * ((slice + 1) & 1), c->d_r);
     }
     if (blind_done) HIPCHK(hipEventRecord(blind_done, st));
@@ -1162,7 +1159,7 @@ static int combsets_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_se
     const uint32_t k32 = (uint32_t)k, N32 = (uint32_t)N;
     if (N) {
         if (idx) {
-            k_combsets_gather<<<(uint32_t)((N * 80 + 255) / 256), 256, 0, st>>>(reinterpret_cast<const uint32_t*>(d_sets), n_sets, idx, N32, c->d_comb_gather);
+            k_combsets_gather<<<plan::gather_blocks_for(N * 80), plan::GATHER_THREADS, 0, st>>>(reinterpret_cast<const uint32_t*>(d_sets), n_sets, idx, N32, c->d_comb_gather);
             recs = c->d_comb_gather;
         }
         k_combsets_scalars<<<plan::waves_for(k32), WAVE, 0, st>>>(d_first, d_len, k32, c->d_comb_rnd, plan::COMB_CHAIN_LANE_MAX, c->d_comb_s);
@@ -1386,7 +1383,7 @@ static int verify_many(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_
             uint8_t* d_rr = c->d_comp + ((meta.size() * sizeof(many_meta) + 63) / 64) * 64;
             HIPCHK(hipMemcpyAsync(d_meta, meta.data(), meta.size() * sizeof(many_meta), hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(d_rr, rr.data(), rr.size(), hipMemcpyHostToDevice, st));
-            k_blind_many<<<(lanes + WAVE - 1) / WAVE, WAVE, 0, st>>>(d_rr, d_meta, (uint32_t)meta.size(), lanes, c->d_r);
+            k_blind_many<<<plan::waves_for(lanes), WAVE, 0, st>>>(d_rr, d_meta, (uint32_t)meta.size(), lanes, c->d_r);
         }
         int rc = run_pairs(c, d_sets, total, st);
         if (rc) return rc;
@@ -1689,7 +1686,7 @@ extern "C" int mi355_bls_fetch_stage(mi355_bls_ctx* c, int what, void* out, size
     if (!c || !out) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     size_t n = c->last_n;
-    uint32_t nb = (uint32_t)((n + 63) / 64);
+    uint32_t nb = plan::waves_for((uint32_t)n);
     switch (what) {
         case 0:
             if (out_bytes < n * 8) return MI355_BLS_ERR_ARG;
@@ -1697,13 +1694,13 @@ extern "C" int mi355_bls_fetch_stage(mi355_bls_ctx* c, int what, void* out, size
             return 0;
         case 1:
             if (out_bytes < n * 288 || n == 0) return MI355_BLS_ERR_ARG;
-            k_export_g2<<<nb, 64>>>(c->d_H, c->stride, (uint32_t)n, c->d_export);
+            k_export_g2<<<nb, WAVE>>>(c->d_H, c->stride, (uint32_t)n, c->d_export);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpy(out, c->d_export, n * 288, hipMemcpyDeviceToHost));
             return 0;
         case 2:
             if (out_bytes < n * 144 || n == 0) return MI355_BLS_ERR_ARG;
-            k_export_g1<<<nb, 64>>>(c->d_P, c->stride, (uint32_t)n, c->d_export);
+            k_export_g1<<<nb, WAVE>>>(c->d_P, c->stride, (uint32_t)n, c->d_export);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpy(out, c->d_export, n * 144, hipMemcpyDeviceToHost));
             return 0;
@@ -1742,13 +1739,10 @@ extern "C" int mi355_bls_last_timings(mi355_bls_ctx* c, float out[8]) {
 
 static int g1_sum_enqueue(mi355_bls_ctx* c, const uint8_t* d_pts, size_t n, hipStream_t st) {
     // result (blst_p1 image, 144 B) lands in d_agg1
-    uint32_t n32 = (uint32_t)n;
-    uint32_t nblk = (n32 + WAVE * 8 - 1) / (WAVE * 8);          // ~8 points per lane
-    if (nblk > c->slots * 2) nblk = c->slots * 2;
-    if (nblk < 1) nblk = 1;
-    uint32_t m = (n32 + nblk * WAVE - 1) / (nblk * WAVE);
-    k_g1_sum<<<nblk, WAVE, 0, st>>>(d_pts, n32, m, c->d_export);
-    k_g1_sum2<<<1, WAVE, 0, st>>>(c->d_export, nblk, c->d_agg1);
+    const uint32_t n32 = (uint32_t)n;
+    const plan::sum_plan p = plan::g1_sum_for(c->slots, n32);
+    k_g1_sum<<<p.nblk, WAVE, 0, st>>>(d_pts, n32, p.m, c->d_export);
+    k_g1_sum2<<<1, WAVE, 0, st>>>(c->d_export, p.nblk, c->d_agg1);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1774,14 +1768,10 @@ extern "C" int mi355_bls_g2_aggregate_device(mi355_bls_ctx* c, const void* d_sig
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipEventRecord(c->ev[0], st));
-    uint32_t n32 = (uint32_t)n;
-    uint32_t nblk = (n32 + WAVE * 8 - 1) / (WAVE * 8);          // ~8 points per lane
-    if (nblk > c->slots) nblk = c->slots;
-    if (nblk > 2048) nblk = 2048;                               // d_export holds 2048 x 2 G1-sized partials beside its export area
-    if (nblk < 1) nblk = 1;
-    uint32_t m = (n32 + nblk * WAVE - 1) / (nblk * WAVE);
-    k_g2_sum<<<nblk, WAVE, 0, st>>>((const uint8_t*)d_sigs, n32, m, c->d_export);
-    k_g2_sum2<<<1, WAVE, 0, st>>>(c->d_export, nblk, c->d_agg);
+    const uint32_t n32 = (uint32_t)n;
+    const plan::sum_plan p = plan::g2_sum_for(c->slots, n32);
+    k_g2_sum<<<p.nblk, WAVE, 0, st>>>((const uint8_t*)d_sigs, n32, p.m, c->d_export);
+    k_g2_sum2<<<1, WAVE, 0, st>>>(c->d_export, p.nblk, c->d_agg);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[1], st));
     HIPCHK(hipMemcpyAsync(out_p2, c->d_agg, 288, hipMemcpyDeviceToHost, st));
@@ -1932,70 +1922,36 @@ extern "C" int mi355_bls_fast_aggregate_verify(mi355_bls_ctx* c, const void* pks
 // ------------------------------------------------------------------------------------------
 // blst_p1s_mult_pippenger / blst_p2s_mult_pippenger replacement (host side)
 // ------------------------------------------------------------------------------------------
-// buckets per running-sum segment of k_pip_segred.  Rounds 3-4 used 8 from 2^12 buckets per window on (shorter running sums while the
-// segments still fill the chip); since the bucket kernel became the assembly loop (round 5) the reductions are what the MSM waits for and
-// 16-bucket segments - half as many segment lanes competing with the other window group's bucket kernel - are ahead again at 2^20 points:
-// 4.63 - 4.68 ms against 4.75 - 4.81, two in flight 3.77 - 3.80 against 3.88 - 4.03 (profiles/r05_ab/msm_knobs.txt).
-constexpr uint32_t MSM_SEG = 16;
-
-// Window plan for npoints x nbits: about log2(n) - 3 bits per window (signed digits: 2^(c-1) buckets), widths balanced.
-static pip_win pip_plan(size_t npoints, size_t nbits) {
-    uint32_t lg = 0;
-    while ((1ull << (lg + 1)) <= npoints) lg++;
-    int c = (int)lg - 3;
-    if (c < 5) c = 5;                                   // at least one 16-bucket segment per window
-    if (c > 16) c = 16;                                 // at most 2^15 buckets per window: the counters of the LDS counting sort
-    pip_win W{};
-    W.nbits = (uint32_t)nbits;
-    uint32_t ext = (uint32_t)nbits + 1;                  // one extra (zero) top bit: the top window absorbs the carry of the bias
-    W.nwin = (ext + c - 1) / c;
-    W.wbase = ext / W.nwin;
-    W.wrem = ext % W.nwin;
-    uint32_t widest = W.wbase + (W.wrem ? 1 : 0);
-    W.cbk = widest - 1;
-    if (W.cbk < 4) W.cbk = 4;
-    for (int j = 0; j < 9; j++) W.H[j] = 0;
-    for (uint32_t w = 0; w + 1 < W.nwin; w++) {
-        uint32_t off = w < W.wrem ? w * (W.wbase + 1) : W.wrem * (W.wbase + 1) + (w - W.wrem) * W.wbase;
-        uint32_t len = w < W.wrem ? W.wbase + 1 : W.wbase;
-        uint32_t bit = off + len - 1;                    // + 2^(len - 1) at window w
-        W.H[bit >> 5] |= 1u << (bit & 31);
-    }
-    return W;
-}
-
 extern "C" size_t mi355_bls_p1s_mult_pippenger_scratch_sizeof(size_t npoints) {
     (void)npoints;
     return 0;          // blst_p1s_mult_pippenger_scratch_sizeof (blst_abi.nim:336): the workspace lives on the device
 }
 
-// workspace for npoints points of `affb`-byte affine images (96: G1, 192: G2) under window plan W
-static int msm_reserve(msm_ws* m, size_t n, const pip_win& W, size_t affb) {
+// workspace for npoints points of `affb`-byte affine images (96: G1, 192: G2) under window plan W: every buffer as plan::msm_sizes_for gives it
+static int msm_reserve(msm_ws* m, size_t n, const plan::pip_win& W, size_t affb) {
     uint32_t total = W.nwin << W.cbk, cap_total = (uint32_t)(m->hist.bytes / 4);
     size_t pts_bytes = n * affb;
     if (pts_bytes <= m->d_pts.bytes && total <= cap_total) return 0;
-    size_t cb = pts_bytes > m->d_pts.bytes ? pts_bytes : m->d_pts.bytes;
-    uint32_t ct = total > cap_total ? total : cap_total;
+    const plan::msm_sizes sz = plan::msm_sizes_for(pts_bytes > m->d_pts.bytes ? pts_bytes : m->d_pts.bytes, total > cap_total ? total : cap_total);
     *m = msm_ws();                                       // everything goes first: a failed grow leaves an empty workspace
     msm_ws w;
     int rc = 0;                                          // the first failure: nothing is created behind it
     const auto alloc = [&rc](auto& buf, size_t bytes) { rc = rc ? rc : buf.alloc(bytes); };
-    size_t cn = cb / 96;                                 // point capacity counted in G1 points (a G2 point takes two)
-    alloc(w.d_pts, cb);
-    alloc(w.d_sc, cn * 32);
-    alloc(w.pts_int, cn * 2 * FPW * 4);
-    alloc(w.hist, (size_t)ct * 4);
-    alloc(w.offs, (size_t)ct * 4);
-    alloc(w.cursor, (size_t)ct * 4);
-    alloc(w.order, (size_t)ct * 4);
-    alloc(w.chist, 4 * 256 * 4);
-    alloc(w.shist, (size_t)ct * PIP_SLICES * 4);      // per-slice counters of the LDS counting sort
-    alloc(w.part, 64 * 16 * G2W * 4);                 // per window up to 16 partial sums
-    alloc(w.sorted, (size_t)cn * 64 * 4);          // up to 52 + 1 windows (nbits 256 at 5-bit windows)
-    alloc(w.buckets, (size_t)ct * 6 * 64);
-    alloc(w.segout, (size_t)(ct / 4 + 64) * 6 * 64);
-    alloc(w.winout, 64 * G2W * 4);
-    alloc(w.out, 288);
+    alloc(w.d_pts, sz.d_pts);
+    alloc(w.d_sc, sz.d_sc);
+    alloc(w.pts_int, sz.pts_int);
+    alloc(w.hist, sz.hist);
+    alloc(w.offs, sz.hist);
+    alloc(w.cursor, sz.hist);
+    alloc(w.order, sz.hist);
+    alloc(w.chist, sz.chist);
+    alloc(w.shist, sz.shist);
+    alloc(w.part, sz.part);
+    alloc(w.sorted, sz.sorted);
+    alloc(w.buckets, sz.buckets);
+    alloc(w.segout, sz.segout);
+    alloc(w.winout, sz.winout);
+    alloc(w.out, sz.out);
     for (dev_event* e : {&w.ev_fork, &w.ev_bucketed, &w.ev_g[0], &w.ev_tail[0], &w.ev_g[1], &w.ev_tail[1]}) rc = rc ? rc : e->create(hipEventDisableTiming);
     if (rc) return rc;
     *m = std::move(w);
@@ -2003,107 +1959,81 @@ static int msm_reserve(msm_ws* m, size_t n, const pip_win& W, size_t affb) {
 }
 
 // Everything up to the result in m->out (blst_p1 / blst_p2 image, device memory) is ENQUEUED on `st` with workspace m; nothing is
-// waited for.  timed: record the context's stage events.  allow_split: the window groups may use the context's side stream.
+// waited for: a walk over plan::msm_for's plan.  timed: record the context's stage events.  allow_split: the window groups may use the
+// context's side stream (asked for only when the plan would split).
 template <class F>
 static int msm_enqueue(mi355_bls_ctx* c, msm_ws* m, const void* d_points, size_t npoints, const void* d_scalars, uint32_t sbytes, size_t nbits,
                        hipStream_t st, bool timed, bool allow_split) {
-    constexpr size_t AFFB = sizeof(F) == sizeof(fp) ? 96 : 192;
-    pip_win W = pip_plan(npoints, nbits);
-    int rc = msm_reserve(m, npoints, W, AFFB);
+    constexpr bool G2 = sizeof(F) != sizeof(fp);
+    plan::msm_plan p = plan::msm_for(npoints, nbits, G2, allow_split, true);
+    if (p.ngroups > 1 && !ensure_side(c)) p = plan::msm_for(npoints, nbits, G2, allow_split, false);
+    int rc = msm_reserve(m, npoints, p.W, G2 ? 192 : 96);
     if (rc) return rc;
-    uint32_t n = (uint32_t)npoints, nw = W.nwin, total = nw << W.cbk, seg = MSM_SEG, segs_per_win = (1u << W.cbk) / seg,
-             nseg = nw * segs_per_win;
+    const pip_win W{p.W};
+    const uint32_t n = p.n, nw = W.nwin, total = p.total;
     const uint8_t* pts = (const uint8_t*)d_points;
     const uint8_t* sc = (const uint8_t*)d_scalars;
-    uint32_t nbp = (n + WAVE - 1) / WAVE;
-    uint32_t nsplit = segs_per_win >= 1024 ? 16 : (segs_per_win >= 128 ? 4 : 1);
-    // One group of windows = the whole pipeline on a range of windows [w0, w1): sort -> buckets -> segment sums -> window sums.
-    const bool lds_sort = W.cbk <= PIP_SORT_MAX_CBK && W.cbk >= 10 && n >= (1u << 15);        // counters of a window in LDS (large inputs)
-    auto count_sort = [&](uint32_t w0, uint32_t w1, hipStream_t s) {
-        uint32_t g0 = w0 << W.cbk, gc = (w1 - w0) << W.cbk;
-        if (lds_sort) {
-            uint32_t per = (n + PIP_SLICES - 1) / PIP_SLICES;
-            k_pip_hist_lds<<<dim3(PIP_SLICES, w1 - w0), PIP_SORT_THREADS, 0, s>>>(sc, sbytes, n, W, w0, per, m->shist);
-            k_pip_slice_scan<<<(gc + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->shist, PIP_SLICES, W.cbk, g0, gc, m->hist);
-            k_pip_scan_block<<<w1 - w0, PIP_SORT_THREADS, 0, s>>>(m->hist + g0, W.cbk, m->offs + g0);
-            k_pip_scatter_lds<<<dim3(PIP_SLICES, w1 - w0), PIP_SORT_THREADS, 0, s>>>(sc, sbytes, n, W, w0, per, m->shist, m->offs, m->sorted);
-        } else {
-            k_pip_hist<<<dim3(nbp, w1 - w0), WAVE, 0, s>>>(sc, sbytes, n, W, w0, m->hist);
-            k_msm_scan<<<w1 - w0, WAVE, 0, s>>>(m->hist + g0, W.cbk, m->offs + g0, m->cursor + g0);
-            k_pip_scatter<<<dim3(nbp, w1 - w0), WAVE, 0, s>>>(sc, sbytes, n, W, w0, m->cursor, m->sorted);
-        }
-    };
-    auto order_group = [&](uint32_t w0, uint32_t w1, uint32_t gi, hipStream_t s) {      // the group's buckets by load (indices relative to g0)
-        uint32_t g0 = w0 << W.cbk, gc = (w1 - w0) << W.cbk, nbo = (gc + WAVE * MSM_ORD_PER - 1) / (WAVE * MSM_ORD_PER);
+    auto order_group = [&](const plan::msm_group& G, uint32_t gi, hipStream_t s) {      // the group's buckets by load (indices relative to g0)
         uint32_t* chist = m->chist + 256 * gi;
-        k_msm_order_hist<<<nbo, WAVE, 0, s>>>(m->hist + g0, gc, chist);
+        k_msm_order_hist<<<G.order_grid, WAVE, 0, s>>>(m->hist + G.g0, G.gc, chist);
         k_msm_order_scan<<<1, 1, 0, s>>>(chist);
-        k_msm_order_scatter<<<nbo, WAVE, 0, s>>>(m->hist + g0, gc, chist, m->order + g0);
+        k_msm_order_scatter<<<G.order_grid, WAVE, 0, s>>>(m->hist + G.g0, G.gc, chist, m->order + G.g0);
     };
-    auto bucket_group = [&](uint32_t w0, uint32_t w1, hipStream_t s) {
-        uint32_t g0 = w0 << W.cbk, gc = (w1 - w0) << W.cbk;
-        k_pip_bucket<F><<<(gc + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->pts_int, m->sorted, m->offs, m->hist, m->order, n, W.cbk, total, g0, gc, m->buckets);
+    auto bucket_group = [&](const plan::msm_group& G, hipStream_t s) {
+        k_pip_bucket<F><<<G.bucket_grid, WAVE, 0, s>>>(m->pts_int, m->sorted, m->offs, m->hist, m->order, n, W.cbk, total, G.g0, G.gc, m->buckets);
     };
-    auto reduce_group = [&](uint32_t w0, uint32_t w1, hipStream_t s, uint32_t g) {
-        uint32_t t0 = w0 * segs_per_win, tc = (w1 - w0) * segs_per_win;
-        // G1: 4 or 2 lanes per segment (lane teams) while the team waves stay well inside the chip's 1024 one-per-SIMD wave slots (<= 960 waves: a
-        // kernel of exactly 1024 such waves finds a few SIMDs taken by the other group's reduction and runs a second round for the stragglers).
-        // profiles/r04_ab/msm_team.txt: 2^14 points 2.70 -> 2.29 ms, 2^16 2.56 -> 2.28, 2^18 3.28 -> 3.10 (two lanes); 2^20 would need 1024 waves per
-        // group and measured 5.2 - 5.4 ms against 5.1 - 5.2: one lane per segment there.
-        const int team = sizeof(F) != sizeof(fp) ? 1 : ((size_t)tc * 4 <= 61440 ? 4 : ((size_t)tc * 2 <= 61440 ? 2 : 1));
-        if (team == 4) k_pip_segred_team<4><<<(tc * 4 + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->buckets, total, W.cbk, seg, nseg, t0, tc, m->segout);
-        else if (team == 2) k_pip_segred_team<2><<<(tc * 2 + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->buckets, total, W.cbk, seg, nseg, t0, tc, m->segout);
-        else k_pip_segred<F><<<(tc + WAVE - 1) / WAVE, WAVE, 0, s>>>(m->buckets, total, W.cbk, seg, nseg, t0, tc, m->segout);
-        k_pip_winpart<F><<<dim3(w1 - w0, nsplit), WAVE, 0, s>>>(m->segout, nseg, segs_per_win, w0, m->part);
-        if constexpr (sizeof(F) == sizeof(fp)) {
+    auto reduce_group = [&](const plan::msm_group& G, hipStream_t s, uint32_t g) {
+        if (G.team == 4) k_pip_segred_team<4><<<G.segred_grid, WAVE, 0, s>>>(m->buckets, total, W.cbk, plan::MSM_SEG, p.nseg, G.t0, G.tc, m->segout);
+        else if (G.team == 2) k_pip_segred_team<2><<<G.segred_grid, WAVE, 0, s>>>(m->buckets, total, W.cbk, plan::MSM_SEG, p.nseg, G.t0, G.tc, m->segout);
+        else k_pip_segred<F><<<G.segred_grid, WAVE, 0, s>>>(m->buckets, total, W.cbk, plan::MSM_SEG, p.nseg, G.t0, G.tc, m->segout);
+        k_pip_winpart<F><<<dim3(G.w1 - G.w0, p.nsplit), WAVE, 0, s>>>(m->segout, p.nseg, p.segs_per_win, G.w0, m->part);
+        if constexpr (!G2) {
             // G1: the parts' sums and ONE Horner walk over the group's windows on the row arithmetic, continuing the walk of the group above (it runs
             // on another stream: ev_tail[g - 1]); the last group writes the result.  No per-window doubling chains, no k_pip_final.
             if (g) HIPCHK(hipStreamWaitEvent(s, m->ev_tail[g - 1], 0));
-            uint32_t waves = w1 - w0 < 16 ? w1 - w0 : 16;
-            k_pip_rowtail<<<1, waves * WAVE, 0, s>>>(m->part, nsplit, W, w0, w1, g ? m->winout + 48 * (g - 1) : nullptr, m->winout + 48 * g, m->out);
+            k_pip_rowtail<<<1, G.tail_lanes, 0, s>>>(m->part, p.nsplit, W, G.w0, G.w1, g ? m->winout + 48 * (g - 1) : nullptr, m->winout + 48 * g, m->out);
             HIPCHK(hipEventRecord(m->ev_tail[g], s));
         } else {
-            k_pip_winsum<F><<<w1 - w0, WAVE, 0, s>>>(m->part, nsplit, W, w0, m->winout);      // G2: window sums, then k_pip_final's Horner walk
+            k_pip_winsum<F><<<G.w1 - G.w0, WAVE, 0, s>>>(m->part, p.nsplit, W, G.w0, m->winout);      // G2: window sums, then k_pip_final's Horner walk
         }
         return 0;
     };
     HIPCHK(hipMemsetAsync(m->hist, 0, (size_t)total * 4, st));
-    HIPCHK(hipMemsetAsync(m->chist, 0, 4 * 256 * 4, st));
+    HIPCHK(hipMemsetAsync(m->chist, 0, plan::MSM_CHIST_BYTES, st));
     if (timed) HIPCHK(hipEventRecord(c->ev[0], st));
-    k_pip_convert<F><<<nbp, WAVE, 0, st>>>(pts, n, m->pts_int);
-    // The counting sort covers all windows; then two groups of windows, each on its own stream: the HIGH windows first (their
-    // results need the long doubling chains: up to nbits - c dependent doublings on one wave per window, ~1 ms of pure
-    // latency), the LOW windows' bucket kernel behind the high one, so that the high group's serial tail runs beside the bucket
-    // accumulation of the low group and only the short chains of the low windows are left at the end.  More groups lose more
-    // in the bucket kernels' tails than they hide.  Large inputs only: a small MSM is latency-bound in every stage.
-    const bool split = allow_split && nw >= 4 && (size_t)n * nw >= ((size_t)1 << 22) && ensure_side(c);
-    // Groups [cut[g + 1], cut[g]) from the high windows down: two halves.  Measured at 2^20 x 255 bits, 16 windows
-    // (profiles/r04_ab/msm_cuts.txt): cuts 5 .. 10 are within the noise of 8; three groups (10,4 / 11,5 / 12,6 / 9,3), whose last
-    // group's exposed reduction is shorter, are 1 - 3 % SLOWER alone and 10 % slower with two MSMs in flight - every extra group's
-    // bucket kernel has its own tail and shares the chip with one more reduction.
-    const uint32_t ngroups = split ? 2 : 1, cut[3] = {nw, split ? nw / 2 : 0, 0};
+    k_pip_convert<F><<<p.point_grid, WAVE, 0, st>>>(pts, n, m->pts_int);
+    // the counting sort covers all windows
+    if (p.lds_sort) {
+        k_pip_hist_lds<<<dim3(PIP_SLICES, nw), PIP_SORT_THREADS, 0, st>>>(sc, sbytes, n, W, 0, p.per, m->shist);
+        k_pip_slice_scan<<<p.slice_scan_grid, WAVE, 0, st>>>(m->shist, PIP_SLICES, W.cbk, 0, total, m->hist);
+        k_pip_scan_block<<<nw, PIP_SORT_THREADS, 0, st>>>(m->hist, W.cbk, m->offs);
+        k_pip_scatter_lds<<<dim3(PIP_SLICES, nw), PIP_SORT_THREADS, 0, st>>>(sc, sbytes, n, W, 0, p.per, m->shist, m->offs, m->sorted);
+    } else {
+        k_pip_hist<<<dim3(p.point_grid, nw), WAVE, 0, st>>>(sc, sbytes, n, W, 0, m->hist);
+        k_msm_scan<<<nw, WAVE, 0, st>>>(m->hist, W.cbk, m->offs, m->cursor);
+        k_pip_scatter<<<dim3(p.point_grid, nw), WAVE, 0, st>>>(sc, sbytes, n, W, 0, m->cursor, m->sorted);
+    }
     // group g runs on its own stream, its bucket kernel behind the bucket kernel of group g - 1: the (latency-bound, few-wave)
     // reduction of a group is dispatched before the next group's bucket kernel and runs beside it.  (Both bucket kernels enqueued at
     // once, the second on a lowest-priority stream so that its waves would only fill the tail of the first - 26 % of a bucket
     // kernel's wave slots idle on average, profiles/r03_pmc_summary_msm.json - was measured 3 % SLOWER: the 512-register reduction
     // waves of the first group then wait for whole SIMDs that the second group's 256-register waves keep half full.)
     hipStream_t gs[2] = {st, c->side};
-    count_sort(0, nw, st);
-    for (uint32_t g = 0; g < ngroups; g++) order_group(cut[g + 1], cut[g], g, st);
+    for (uint32_t g = 0; g < p.ngroups; g++) order_group(p.group[g], g, st);
     if (timed) HIPCHK(hipEventRecord(c->ev[1], st));
-    for (uint32_t g = 0; g < ngroups; g++) {
+    for (uint32_t g = 0; g < p.ngroups; g++) {
         if (g) HIPCHK(hipStreamWaitEvent(gs[g], m->ev_g[g - 1], 0));
-        bucket_group(cut[g + 1], cut[g], gs[g]);
+        bucket_group(p.group[g], gs[g]);
         HIPCHK(hipEventRecord(m->ev_g[g], gs[g]));
         if (g == 0 && timed) HIPCHK(hipEventRecord(c->ev[2], st));
-        if (int rc2 = reduce_group(cut[g + 1], cut[g], gs[g], g)) return rc2;
+        if (int rc2 = reduce_group(p.group[g], gs[g], g)) return rc2;
         if (g == 0 && timed) HIPCHK(hipEventRecord(c->ev[3], st));
     }
-    for (uint32_t g = 1; g < ngroups; g++) {
+    for (uint32_t g = 1; g < p.ngroups; g++) {
         HIPCHK(hipEventRecord(m->ev_g[g], gs[g]));
         HIPCHK(hipStreamWaitEvent(st, m->ev_g[g], 0));
     }
-    if constexpr (sizeof(F) != sizeof(fp)) k_pip_final<F><<<1, WAVE, 0, st>>>(m->winout, nw, m->out);
+    if constexpr (G2) k_pip_final<F><<<1, WAVE, 0, st>>>(m->winout, nw, m->out);
     if (timed) HIPCHK(hipEventRecord(c->ev[4], st));
     HIPCHK(hipGetLastError());
     return 0;
@@ -2142,7 +2072,7 @@ static int msm_host(mi355_bls_ctx* c, uint8_t* ret, const uint8_t* pts, size_t n
     constexpr size_t AFFB = sizeof(F) == sizeof(fp) ? 96 : 192;
     if (!c || nbits == 0 || nbits > 256 || npoints > (1u << 28)) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    int rc = msm_reserve(&c->msm, npoints, pip_plan(npoints, nbits), AFFB);
+    int rc = msm_reserve(&c->msm, npoints, plan::pip_for(npoints, nbits), AFFB);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->msm.d_pts, pts, npoints * AFFB, hipMemcpyHostToDevice, nullptr));
     HIPCHK(hipMemcpyAsync(c->msm.d_sc, scalars, npoints * sbytes, hipMemcpyHostToDevice, nullptr));
@@ -2247,7 +2177,7 @@ static int deser_enqueue(mi355_bls_ctx* c, const uint8_t* d_pks, const uint8_t* 
     }
     if (dflags > 7) return MI355_BLS_ERR_ARG;
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
-    k_deser<<<((uint32_t)n + WAVE - 1) / WAVE, WAVE, 0, st>>>(d_pks, d_msgs, d_sigs, (uint32_t)n, dflags, c->d_sets, c->d_status, c->d_flags);
+    k_deser<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>(d_pks, d_msgs, d_sigs, (uint32_t)n, dflags, c->d_sets, c->d_status, c->d_flags);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2358,7 +2288,7 @@ extern "C" int mi355_bls_sign_sets_device(mi355_bls_ctx* c, const void* d_sks32,
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
     HIPCHK(hipEventRecord(c->ev[0], st));
-    uint32_t nb = ((uint32_t)n + WAVE - 1) / WAVE;
+    uint32_t nb = plan::waves_for((uint32_t)n);
     k_sign_pk<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, (const uint8_t*)d_msgs32, (uint32_t)n, (uint8_t*)d_out_sets, c->d_status, c->d_flags);
     k_sign_sig<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, (const uint8_t*)d_msgs32, (uint32_t)n, c->dst, (uint8_t*)d_out_sets);
     HIPCHK(hipGetLastError());
@@ -2458,7 +2388,7 @@ static int aggv_slice(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* msgs,
     HIPCHK(hipMemcpyAsync(d_pk, pks, n * 96, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_off, offs, (n + 1) * 4, hipMemcpyHostToDevice, st));
     if (total) HIPCHK(hipMemcpyAsync(d_msgs, msgs, total, hipMemcpyHostToDevice, st));
-    uint32_t n32 = (uint32_t)n, nb = (n32 + WAVE - 1) / WAVE, npairs = n32 + (with_sig ? 1u : 0u), nb1 = (npairs + WAVE - 1) / WAVE;
+    uint32_t n32 = (uint32_t)n, nb = plan::waves_for(n32), npairs = n32 + (with_sig ? 1u : 0u), nb1 = plan::waves_for(npairs);
     HIPCHK(hipEventRecord(c->ev[0], st));
     const bool all32 = c->xmd.valid && plan::aggv_all32(offs, n);       // every message 32 bytes long (signing roots): the batch path's hashing kernels
     if (all32) {
@@ -2620,7 +2550,7 @@ static int jac_sum_device(mi355_bls_ctx* c, uint8_t* ret, const void* d_parts, s
 template <class F>
 static int jac_sum_host(mi355_bls_ctx* c, uint8_t* ret, const uint8_t* parts, size_t k) {
     constexpr size_t JACB = (sizeof(F) == sizeof(fp) ? 96 : 192) / 2 * 3;
-    if (!c || !ret || !parts || k == 0 || k * JACB > 2048 * 2 * G1W * 4) return MI355_BLS_ERR_ARG;
+    if (!c || !ret || !parts || k == 0 || k * JACB > plan::SUM_PARTS_BYTES) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(c->d_export, parts, k * JACB, hipMemcpyHostToDevice, nullptr));
     return jac_sum_device<F>(c, ret, c->d_export, k, JACB, nullptr);
@@ -2680,7 +2610,7 @@ static int msm_multi(mi355_bls_ctx* const ctxs[], size_t ngpu, uint8_t* ret, con
         const void *dp = d_pts ? d_pts[g] : nullptr, *ds = d_sc ? d_sc[g] : nullptr;
         if (!dp || !ds) {
             if (!pts || !sc) { rc = MI355_BLS_ERR_ARG; break; }
-            rc = msm_reserve(&c->msm, cnt, pip_plan(cnt, nbits), AFFB);
+            rc = msm_reserve(&c->msm, cnt, plan::pip_for(cnt, nbits), AFFB);
             if (rc) break;
             if (hipMemcpyAsync(c->msm.d_pts, pts + off * AFFB, cnt * AFFB, hipMemcpyHostToDevice, nullptr) != hipSuccess ||
                 hipMemcpyAsync(c->msm.d_sc, sc + off * 32, cnt * 32, hipMemcpyHostToDevice, nullptr) != hipSuccess) {

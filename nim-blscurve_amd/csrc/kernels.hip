@@ -40,6 +40,7 @@
 #include "teamvm.hpp"
 #include "rowfp.hpp"
 #include "rowvm.hpp"
+#include "plan.hpp"
 
 using namespace bls;
 
@@ -1443,11 +1444,10 @@ __global__ void __launch_bounds__(WAVE) k_msm_scatter(const uint8_t* __restrict_
 //   k_pip_winpart / k_pip_winsum    per window: sum of the segment values, times 2^(off_w) (lane-parallel doubling chain)
 //   k_pip_final     sum over the windows -> blst_p1 / blst_p2 image
 // ------------------------------------------------------------------------------------------
-struct pip_win {
-    uint32_t nwin, wbase, wrem, nbits;      // nwin windows over nbits + 1 bits (widths differ by at most one bit)
-    uint32_t cbk;                           // bucket index bits: 2^cbk buckets per window, cbk = widest window - 1
-    uint32_t H[9];                          // the bias: 2^(len - 1) at every window but the top one
-};
+// csrc/plan.hpp's window plan.  Not a `using`: a kernel's symbol spells the namespace of its argument types, so taking plan::pip_win itself
+// would rename every kernel below in the code object; the empty derived struct keeps their names and has the same layout.
+struct pip_win : plan::pip_win {};
+static_assert(sizeof(pip_win) == sizeof(plan::pip_win), "the same kernel argument");
 __device__ __forceinline__ uint32_t pip_off(const pip_win& W, uint32_t w) {
     return w < W.wrem ? w * (W.wbase + 1) : W.wrem * (W.wbase + 1) + (w - W.wrem) * W.wbase;
 }
@@ -1519,7 +1519,7 @@ __global__ void __launch_bounds__(WAVE) k_pip_scatter(const uint8_t* __restrict_
 //   k_pip_hist_lds     counts of one slice            -> shist[window][slice][bucket]
 //   k_pip_slice_scan   lane per bucket: exclusive prefix over the slices in place, total -> hist (then k_pip_scan_block -> offs)
 //   k_pip_scatter_lds  cursors = offs + slice prefix in LDS; position = ds_add_rtn
-constexpr uint32_t PIP_SORT_THREADS = 1024, PIP_SORT_MAX_CBK = 15, PIP_SLICES = 32;
+using plan::PIP_SORT_THREADS, plan::PIP_SORT_MAX_CBK, plan::PIP_SLICES;
 __global__ void __launch_bounds__(PIP_SORT_THREADS) k_pip_hist_lds(const uint8_t* __restrict__ sc, uint32_t sbytes, uint32_t n, pip_win W, uint32_t w0, uint32_t per,
                                                                    uint32_t* __restrict__ shist) {
     __shared__ uint32_t h[1u << PIP_SORT_MAX_CBK];
@@ -1591,7 +1591,7 @@ __global__ void __launch_bounds__(PIP_SORT_THREADS) k_pip_scatter_lds(const uint
 // buckets ordered by point count (descending) with a counting sort on min(count, 255)
 // Each wave bins MSM_ORD_PER buckets per lane into an LDS histogram first, so the 256 global bins see
 // one atomic per (wave, bin) instead of one per bucket.
-constexpr uint32_t MSM_ORD_PER = 16;
+using plan::MSM_ORD_PER;
 __global__ void __launch_bounds__(WAVE) k_msm_order_hist(const uint32_t* __restrict__ hist, uint32_t total, uint32_t* __restrict__ chist) {
     __shared__ uint32_t h[256];
     for (int i = threadIdx.x; i < 256; i += WAVE) h[i] = 0;

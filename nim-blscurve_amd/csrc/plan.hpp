@@ -10,6 +10,8 @@ namespace plan {
 
 constexpr uint32_t WAVE = 64;                // lanes of a wavefront: the workgroup of every one-lane-per-item kernel
 constexpr uint32_t N_LINES = 68;             // steps of the Miller loop (pairing.hpp)
+constexpr uint32_t FP_WORDS = 16;            // 32-bit words of an Fp element in device buffers; a G1 Jacobian point takes 3, a G2 one 6, an Fp12 value 12 of them
+constexpr uint32_t G1_WORDS = 3 * FP_WORDS, G2_WORDS = 6 * FP_WORDS, F12_WORDS = 12 * FP_WORDS;
 constexpr uint32_t SIG_SLOTS_MAX = 2048;     // 8 windows x 256 digits: the most extra pairs a slice has
 static_assert(((64u / 8) << 8) == SIG_SLOTS_MAX, "the buckets of the 8-bit digits");
 constexpr size_t SIG_WIDE_MIN = 40000;       // from here 8-bit digits (2048 extra pairs, 8 additions per tuple) beat 4-bit ones (256, 15)
@@ -25,6 +27,9 @@ inline uint32_t team_lines_max(uint32_t slots) { return slots * TEAM_LINES_ITEMS
 
 // waves of a kernel that gives every item one lane
 inline uint32_t waves_for(uint32_t count) { return (count + WAVE - 1) / WAVE; }
+// the same for the one kernel whose workgroups are four waves (k_combsets_gather: a lane per word of 80-word records, so the count is a size_t)
+constexpr uint32_t GATHER_THREADS = 256;
+inline uint32_t gather_blocks_for(size_t count) { return (uint32_t)((count + GATHER_THREADS - 1) / GATHER_THREADS); }
 
 // Which executor of the lane-team engine takes `count` items, the same ladder for clearing and Miller lines:
 //   ROWS   the row executor (four waves per item) while the grid stays well inside one wave per SIMD;
@@ -173,6 +178,54 @@ inline lineprod_plan lineprod_for(uint32_t slots, uint32_t nblk_cap, uint32_t st
     }
     return p;
 }
+
+// The context's own sizes (ctx_build allocates what this says): `stride` pairs per plane of the pair store (the tuple pairs, the (-G1, sig) pair
+// and the extra pairs of the signature side, in whole waves), `mstride` mapped points, the most pair ranges k_lineprod may be given (nblk <=
+// slots / 68, at most 64, and never more ranges than waves of pairs), and d_lpart: per Miller step nblk_cap x 64 per-lane partial products of
+// k_lineprod, then, from lpart_mid_words on, k_fold's first-level results (nb1 <= nblk_cap + 64 per step).  d_export holds `stride` exported G2
+// points (288 bytes each) and, beside them, SUM_PARTS_BYTES for the partials of the point sums below and the images mi355_bls_p1s_add /
+// p2s_add stage.
+constexpr uint32_t LINEPROD_RANGES_MAX = 64, FOLD_MID_ROOM = 64;
+constexpr uint32_t SUM_G2_PARTS_MAX = 2048;
+constexpr size_t SUM_PARTS_BYTES = 2048 * 2 * G1_WORDS * 4;
+static_assert((size_t)SUM_G2_PARTS_MAX * G2_WORDS * 4 == SUM_PARTS_BYTES, "2048 G2 partials, or twice as many G1 ones");
+struct ctx_sizes {
+    size_t stride, mstride;
+    uint32_t nblk_cap;
+    size_t lpart_words, lpart_mid_words;
+    size_t export_bytes;
+};
+inline size_t lpart_mid_words(uint32_t nblk_cap) { return (size_t)N_LINES * nblk_cap * WAVE * F12_WORDS; }
+inline ctx_sizes ctx_for(uint32_t slots, size_t max_sets) {
+    ctx_sizes s{};
+    s.stride = ((max_sets + 1 + SIG_SLOTS_MAX + WAVE - 1) / WAVE) * WAVE;
+    s.mstride = ((2 * max_sets + WAVE - 1) / WAVE) * WAVE;
+    const size_t nwaves = s.stride / WAVE;
+    uint32_t nblk = slots / N_LINES;
+    if (nblk < 1) nblk = 1;
+    if (nblk > LINEPROD_RANGES_MAX) nblk = LINEPROD_RANGES_MAX;
+    if (nblk > nwaves) nblk = (uint32_t)nwaves;
+    s.nblk_cap = nblk;
+    s.lpart_words = (size_t)N_LINES * (nblk * (WAVE + 1) + FOLD_MID_ROOM) * F12_WORDS;
+    s.lpart_mid_words = lpart_mid_words(nblk);
+    s.export_bytes = s.stride * 288 + SUM_PARTS_BYTES;
+    return s;
+}
+
+// Point sums (k_g1_sum / k_g2_sum, then one wave over the partials): nblk waves, lane l of wave b sums points (64 b + l) + j 64 nblk, j < m -
+// about 8 points per lane while the device has waves to give (G1: two per slot, G2: one), more per lane beyond.  Every wave leaves one partial
+// at the start of d_export: G1_WORDS (G2_WORDS) words each, within SUM_PARTS_BYTES.
+struct sum_plan {
+    uint32_t nblk, m;
+};
+inline sum_plan sum_for(uint32_t nblk_max, uint32_t n) {
+    uint32_t nblk = (n + WAVE * 8 - 1) / (WAVE * 8);
+    if (nblk > nblk_max) nblk = nblk_max;
+    if (nblk < 1) nblk = 1;
+    return {nblk, (n + nblk * WAVE - 1) / (nblk * WAVE)};
+}
+inline sum_plan g1_sum_for(uint32_t slots, uint32_t n) { return sum_for(slots < SUM_G2_PARTS_MAX ? slots * 2 : SUM_G2_PARTS_MAX * 2, n); }
+inline sum_plan g2_sum_for(uint32_t slots, uint32_t n) { return sum_for(slots < SUM_G2_PARTS_MAX ? slots : SUM_G2_PARTS_MAX, n); }
 
 // aggregateVerify's greedy slice [a, b): at most cap pairs, and the staged bytes (n + 1 offsets | per pair a 96-byte key and the message)
 // within the cap * 320 bytes of the staging buffer.  b == a: the message at `a` alone does not fit.
@@ -333,6 +386,176 @@ inline combsets_plan combsets_measure(const size_t* offsets, size_t k) {
     p.chunk_cap = p.members < COMB_MUL_CHUNK ? (p.members + WAVE - 1) / WAVE * WAVE : COMB_MUL_CHUNK;
     p.ok = true;
     return p;
+}
+
+// ------------------------------------------------------------------------------------------
+// Pippenger MSM (blst_p1s_mult_pippenger / blst_p2s_mult_pippenger): what msm_enqueue follows, and what msm_reserve allocates.
+// ------------------------------------------------------------------------------------------
+// The windows of a call, as the kernels take them (a kernel argument: the layout is fixed).
+struct pip_win {
+    uint32_t nwin, wbase, wrem, nbits;      // nwin windows over nbits + 1 bits (widths differ by at most one bit)
+    uint32_t cbk;                           // bucket index bits: 2^cbk buckets per window, cbk = widest window - 1
+    uint32_t H[9];                          // the bias: 2^(len - 1) at every window but the top one
+};
+static_assert(sizeof(pip_win) == 14 * 4, "five words and the nine of the bias, no padding");
+// buckets per running-sum segment of k_pip_segred.  Rounds 3-4 used 8 from 2^12 buckets per window on (shorter running sums while the
+// segments still fill the chip); since the bucket kernel became the assembly loop (round 5) the reductions are what the MSM waits for and
+// 16-bucket segments - half as many segment lanes competing with the other window group's bucket kernel - are ahead again at 2^20 points:
+// 4.63 - 4.68 ms against 4.75 - 4.81, two in flight 3.77 - 3.80 against 3.88 - 4.03 (profiles/r05_ab/msm_knobs.txt).
+constexpr uint32_t MSM_SEG = 16;
+constexpr uint32_t MSM_ORD_PER = 16;         // buckets a lane of k_msm_order_hist / k_msm_order_scatter bins
+// the counting sort with a window's counters in LDS: 1024-thread workgroups, one per (slice of the points, window); 2^15 counters are 128 KB
+constexpr uint32_t PIP_SORT_THREADS = 1024, PIP_SORT_MAX_CBK = 15, PIP_SLICES = 32;
+constexpr uint32_t PIP_SORT_MIN_CBK = 10, PIP_SORT_MIN_POINTS = 1u << 15;      // large inputs only; k_pip_scan_block gives a thread 2^cbk / 1024 buckets
+static_assert((1u << PIP_SORT_MIN_CBK) % PIP_SORT_THREADS == 0, "k_pip_scan_block: whole buckets per thread");
+constexpr uint32_t MSM_TEAM_LANES_MAX = 61440;     // lanes of a team reduction: 960 waves (see msm_for)
+constexpr uint32_t MSM_TAIL_WAVES_MAX = 16;        // k_pip_rowtail: one workgroup of at most 1024 lanes
+constexpr uint32_t MSM_SPLIT_MIN_WINDOWS = 4;
+constexpr size_t MSM_SPLIT_MIN_WORK = (size_t)1 << 22;      // points x windows
+// what the fixed-size buffers of the workspace are made for (msm_sizes_for); msm_extents says what a plan touches of them
+constexpr uint32_t MSM_WINDOWS_MAX = 64;     // 52 windows at most (nbits 256 at 5-bit windows); also the window sums k_pip_rowtail keeps in LDS
+constexpr uint32_t MSM_NSPLIT_MAX = 16, MSM_GROUPS_MAX = 2, MSM_CHIST_ROOM = 4;
+constexpr size_t MSM_CHIST_BYTES = MSM_CHIST_ROOM * 256 * 4;       // k_msm_order_*: 256 bins of bucket loads per window group
+static_assert(MSM_GROUPS_MAX <= MSM_CHIST_ROOM && MSM_TAIL_WAVES_MAX * WAVE <= 1024, "");
+
+// Window plan for npoints x nbits: about log2(n) - 3 bits per window (signed digits: 2^(c-1) buckets), widths balanced.
+inline pip_win pip_for(size_t npoints, size_t nbits) {
+    uint32_t lg = 0;
+    while ((1ull << (lg + 1)) <= npoints) lg++;
+    int c = (int)lg - 3;
+    if (c < 5) c = 5;                                   // at least one 16-bucket segment per window
+    if (c > 16) c = 16;                                 // at most 2^15 buckets per window: the counters of the LDS counting sort
+    pip_win W{};
+    W.nbits = (uint32_t)nbits;
+    uint32_t ext = (uint32_t)nbits + 1;                  // one extra (zero) top bit: the top window absorbs the carry of the bias
+    W.nwin = (ext + c - 1) / c;
+    W.wbase = ext / W.nwin;
+    W.wrem = ext % W.nwin;
+    uint32_t widest = W.wbase + (W.wrem ? 1 : 0);
+    W.cbk = widest - 1;
+    if (W.cbk < 4) W.cbk = 4;
+    for (uint32_t w = 0; w + 1 < W.nwin; w++) {
+        uint32_t off = w < W.wrem ? w * (W.wbase + 1) : W.wrem * (W.wbase + 1) + (w - W.wrem) * W.wbase;
+        uint32_t len = w < W.wrem ? W.wbase + 1 : W.wbase;
+        uint32_t bit = off + len - 1;                    // + 2^(len - 1) at window w
+        W.H[bit >> 5] |= 1u << (bit & 31);
+    }
+    return W;
+}
+
+// One group of windows [w0, w1) = the pipeline behind the counting sort on a range of windows: buckets by load -> bucket sums -> segment sums
+// -> window parts -> (G1) the row tail's Horner walk over the group, (G2) window sums.  Buckets [g0, g0 + gc), segments [t0, t0 + tc).
+struct msm_group {
+    uint32_t w0, w1, g0, gc, t0, tc;
+    uint32_t order_grid;               // k_msm_order_hist / k_msm_order_scatter: MSM_ORD_PER buckets per lane
+    uint32_t bucket_grid;              // k_pip_bucket: one lane per bucket
+    uint32_t team, segred_grid;        // k_pip_segred_team<team> (4, 2) | k_pip_segred (1): `team` lanes per segment
+    uint32_t tail_waves, tail_lanes;   // k_pip_rowtail's one workgroup (G1): a wave per window up to MSM_TAIL_WAVES_MAX
+};
+struct msm_plan {
+    pip_win W;
+    uint32_t n, total, segs_per_win, nseg;     // points; buckets and 16-bucket segments of all windows
+    uint32_t nsplit;                   // k_pip_winpart: partial sums per window
+    bool lds_sort;                     // k_pip_hist_lds / k_pip_slice_scan / k_pip_scan_block / k_pip_scatter_lds | k_pip_hist / k_msm_scan / k_pip_scatter
+    uint32_t per;                      //   points per slice (lds_sort)
+    uint32_t point_grid;               // k_pip_convert, and the x of k_pip_hist / k_pip_scatter: one lane per point
+    uint32_t slice_scan_grid;          // k_pip_slice_scan: one lane per bucket of all windows
+    uint32_t ngroups, cut[MSM_GROUPS_MAX + 1];      // group g = windows [cut[g + 1], cut[g]), from the high windows down
+    msm_group group[MSM_GROUPS_MAX];
+};
+// allow_split: the caller lets the window groups use the context's fork stream; have_side: that stream exists
+inline msm_plan msm_for(size_t npoints, size_t nbits, bool g2, bool allow_split, bool have_side) {
+    msm_plan p{};
+    p.W = pip_for(npoints, nbits);
+    const pip_win& W = p.W;
+    const uint32_t n = p.n = (uint32_t)npoints, nw = W.nwin;
+    p.total = nw << W.cbk;
+    p.segs_per_win = (1u << W.cbk) / MSM_SEG;
+    p.nseg = nw * p.segs_per_win;
+    p.nsplit = p.segs_per_win >= 1024 ? 16 : (p.segs_per_win >= 128 ? 4 : 1);
+    p.lds_sort = W.cbk <= PIP_SORT_MAX_CBK && W.cbk >= PIP_SORT_MIN_CBK && n >= PIP_SORT_MIN_POINTS;      // counters of a window in LDS (large inputs)
+    p.per = (n + PIP_SLICES - 1) / PIP_SLICES;
+    p.point_grid = waves_for(n);
+    p.slice_scan_grid = waves_for(p.total);
+    // The counting sort covers all windows; then two groups of windows, each on its own stream: the HIGH windows first (their
+    // results need the long doubling chains: up to nbits - c dependent doublings on one wave per window, ~1 ms of pure
+    // latency), the LOW windows' bucket kernel behind the high one, so that the high group's serial tail runs beside the bucket
+    // accumulation of the low group and only the short chains of the low windows are left at the end.  More groups lose more
+    // in the bucket kernels' tails than they hide.  Large inputs only: a small MSM is latency-bound in every stage.
+    const bool split = allow_split && nw >= MSM_SPLIT_MIN_WINDOWS && (size_t)n * nw >= MSM_SPLIT_MIN_WORK && have_side;
+    // Groups [cut[g + 1], cut[g]) from the high windows down: two halves.  Measured at 2^20 x 255 bits, 16 windows
+    // (profiles/r04_ab/msm_cuts.txt): cuts 5 .. 10 are within the noise of 8; three groups (10,4 / 11,5 / 12,6 / 9,3), whose last
+    // group's exposed reduction is shorter, are 1 - 3 % SLOWER alone and 10 % slower with two MSMs in flight - every extra group's
+    // bucket kernel has its own tail and shares the chip with one more reduction.
+    p.ngroups = split ? 2 : 1;
+    p.cut[0] = nw, p.cut[1] = split ? nw / 2 : 0, p.cut[2] = 0;
+    for (uint32_t g = 0; g < p.ngroups; g++) {
+        msm_group& G = p.group[g];
+        G.w0 = p.cut[g + 1], G.w1 = p.cut[g];
+        G.g0 = G.w0 << W.cbk, G.gc = (G.w1 - G.w0) << W.cbk;
+        G.t0 = G.w0 * p.segs_per_win, G.tc = (G.w1 - G.w0) * p.segs_per_win;
+        G.order_grid = (G.gc + WAVE * MSM_ORD_PER - 1) / (WAVE * MSM_ORD_PER);
+        G.bucket_grid = waves_for(G.gc);
+        // G1: 4 or 2 lanes per segment (lane teams) while the team waves stay well inside the chip's 1024 one-per-SIMD wave slots (<= 960 waves: a
+        // kernel of exactly 1024 such waves finds a few SIMDs taken by the other group's reduction and runs a second round for the stragglers).
+        // profiles/r04_ab/msm_team.txt: 2^14 points 2.70 -> 2.29 ms, 2^16 2.56 -> 2.28, 2^18 3.28 -> 3.10 (two lanes); 2^20 would need 1024 waves per
+        // group and measured 5.2 - 5.4 ms against 5.1 - 5.2: one lane per segment there.
+        G.team = g2 ? 1 : ((size_t)G.tc * 4 <= MSM_TEAM_LANES_MAX ? 4 : ((size_t)G.tc * 2 <= MSM_TEAM_LANES_MAX ? 2 : 1));
+        G.segred_grid = waves_for(G.tc * G.team);
+        G.tail_waves = G.w1 - G.w0 < MSM_TAIL_WAVES_MAX ? G.w1 - G.w0 : MSM_TAIL_WAVES_MAX;
+        G.tail_lanes = G.tail_waves * WAVE;
+    }
+    return p;
+}
+
+// The workspace's buffers in bytes.  msm_sizes_for: what msm_reserve allocates for its two capacities, the bytes of the staged points and the
+// buckets of all windows (hist.bytes / 4); it grows all of them or none.  msm_extents: what the kernels touch under a plan, read off their
+// indexing - a plan fits a workspace when no extent exceeds its size (tests/test_msm_plan.py holds every plan to that).
+struct msm_sizes {
+    size_t d_pts, d_sc;                // the host entries' staging: affine images, 32-byte scalars
+    size_t pts_int;                    // k_pip_convert: point i at word i x 2 coordinates x FP_WORDS (G2: x 2)
+    size_t hist;                       // one word per bucket: hist, offs, cursor, order alike
+    size_t chist;                      // group g's 256 bins at word 256 g
+    size_t shist;                      // k_pip_hist_lds: ((window x PIP_SLICES + slice) << cbk) + bucket
+    size_t part;                       // k_pip_winpart: a Jacobian point at (window x nsplit + part)
+    size_t sorted;                     // window w's point indices from word w x n
+    size_t buckets, segout;            // SoA Jacobian points: three (G2: six) coordinates of 64 bytes, rows of `total` / `nseg` points
+    size_t winout;                     // G2: a Jacobian point per window (k_pip_winsum); G1: group g's 48-word accumulator at word 48 g (k_pip_rowtail)
+    size_t out;                        // the blst_p1 / blst_p2 image
+};
+inline msm_sizes msm_sizes_for(size_t point_bytes, size_t buckets) {
+    const size_t cn = point_bytes / 96;                  // point capacity counted in G1 points (a G2 point takes two)
+    msm_sizes s{};
+    s.d_pts = point_bytes;
+    s.d_sc = cn * 32;
+    s.pts_int = cn * 2 * FP_WORDS * 4;
+    s.hist = buckets * 4;
+    s.chist = MSM_CHIST_BYTES;
+    s.shist = buckets * PIP_SLICES * 4;                  // per-slice counters of the LDS counting sort
+    s.part = (size_t)MSM_WINDOWS_MAX * MSM_NSPLIT_MAX * G2_WORDS * 4;
+    s.sorted = cn * MSM_WINDOWS_MAX * 4;
+    s.buckets = buckets * 6 * 64;
+    s.segout = (buckets / 4 + 64) * 6 * 64;
+    s.winout = (size_t)MSM_WINDOWS_MAX * G2_WORDS * 4;
+    s.out = 288;
+    return s;
+}
+inline msm_sizes msm_extents(const msm_plan& p, bool g2) {
+    const size_t n = p.n, coord = g2 ? 2 * FP_WORDS : FP_WORDS, jac = 3 * coord * 4;      // words of a coordinate; bytes of a Jacobian point
+    msm_sizes s{};
+    s.d_pts = n * (g2 ? 192 : 96);
+    s.d_sc = n * 32;
+    s.pts_int = n * 2 * coord * 4;
+    s.hist = (size_t)p.total * 4;
+    s.chist = (size_t)p.ngroups * 256 * 4;
+    s.shist = p.lds_sort ? ((size_t)p.W.nwin * PIP_SLICES << p.W.cbk) * 4 : 0;
+    s.part = (size_t)p.W.nwin * p.nsplit * jac;
+    s.sorted = (size_t)p.W.nwin * n * 4;
+    s.buckets = (size_t)p.total * jac;
+    s.segout = (size_t)p.nseg * jac;
+    s.winout = g2 ? (size_t)p.W.nwin * jac : (size_t)p.ngroups * 48 * 4;
+    s.out = g2 ? 288 : 144;
+    return s;
 }
 
 // chunk of the parallel_chunks partition (parallel_chunks.nim:42-66) that tuple t of n_total falls into, B chunks

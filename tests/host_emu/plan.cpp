@@ -1,5 +1,7 @@
 // The product's launch plans (csrc/plan.hpp: plain C++, no device type) as a host library for ctypes - tests/util.py plan_lib().
 // Structs go out as uint32 words in declaration order; tests/util.py names them.
+#include <initializer_list>
+
 #include "plan.hpp"
 using namespace plan;
 
@@ -12,6 +14,11 @@ static uint32_t* put(uint32_t* o, const lines_plan& p) {
     o = put(o, p.main);
     *o++ = p.extra_pairs;
     return put(o, p.extra);
+}
+
+static uint64_t* put(uint64_t* o, const msm_sizes& s) {
+    for (size_t v : {s.d_pts, s.d_sc, s.pts_int, s.hist, s.chist, s.shist, s.part, s.sorted, s.buckets, s.segout, s.winout, s.out}) *o++ = v;
+    return o;
 }
 
 extern "C" {
@@ -42,4 +49,40 @@ int plan_shard_workspaces(size_t nslices) { return shard_workspaces(nslices); }
 size_t plan_shard_slice_count(size_t n, size_t done, size_t nslices, uint32_t slice) { return shard_slice_count(n, done, nslices, slice); }
 int plan_shard_workspace_of(size_t nslices, uint32_t slice, int nl) { return shard_workspace_of(nslices, slice, nl); }
 uint32_t plan_chunk_of_tuple(size_t n_total, uint32_t B, size_t t) { return chunk_of_tuple(n_total, B, t); }
+// the MSM, the point sums and the context's sizes: 64-bit words, tests/util.py names them
+void plan_msm_constants(uint64_t o[14]) {
+    const uint64_t c[14] = {MSM_SEG, MSM_ORD_PER, PIP_SLICES, PIP_SORT_THREADS, PIP_SORT_MAX_CBK, MSM_TEAM_LANES_MAX, MSM_TAIL_WAVES_MAX, MSM_WINDOWS_MAX,
+                            MSM_NSPLIT_MAX, MSM_GROUPS_MAX, SUM_PARTS_BYTES, G1_WORDS, G2_WORDS, F12_WORDS};
+    for (int i = 0; i < 14; i++) o[i] = c[i];
+}
+// `count` plans, MSM_ROW words each: the plan, then msm_extents of it, then msm_sizes_for what msm_reserve grows an empty workspace to for the call
+enum { MSM_ROW = 14 + 13 + 2 * 12 + 2 * 12 };
+size_t plan_msm_row(void) { return MSM_ROW; }
+void plan_msm_many(const uint64_t* npoints, size_t count, size_t nbits, int g2, int allow_split, int have_side, uint64_t* o) {
+    for (size_t i = 0; i < count; i++) {
+        const msm_plan p = msm_for(npoints[i], nbits, g2 != 0, allow_split != 0, have_side != 0);
+        const uint32_t* w = &p.W.nwin;
+        for (int j = 0; j < 14; j++) *o++ = w[j];
+        for (uint32_t v : {p.n, p.total, p.segs_per_win, p.nseg, p.nsplit, (uint32_t)p.lds_sort, p.per, p.point_grid, p.slice_scan_grid, p.ngroups, p.cut[0], p.cut[1], p.cut[2]}) *o++ = v;
+        for (const msm_group& G : p.group)
+            for (uint32_t v : {G.w0, G.w1, G.g0, G.gc, G.t0, G.tc, G.order_grid, G.bucket_grid, G.team, G.segred_grid, G.tail_waves, G.tail_lanes}) *o++ = v;
+        o = put(o, msm_extents(p, g2 != 0));
+        o = put(o, msm_sizes_for(npoints[i] * (g2 ? 192 : 96), p.total));
+    }
+}
+// point sums of n[0 .. count): nblk, m each
+void plan_sum_many(int g2, uint32_t slots, const uint32_t* n, size_t count, uint32_t* o) {
+    for (size_t i = 0; i < count; i++) {
+        const sum_plan p = g2 ? g2_sum_for(slots, n[i]) : g1_sum_for(slots, n[i]);
+        *o++ = p.nblk, *o++ = p.m;
+    }
+}
+// plan_lineprod for npairs = first .. first + count - 1: six words each
+void plan_lineprod_many(uint32_t slots, uint32_t nblk_cap, uint32_t stride, uint32_t first, size_t count, int fold, uint32_t* o) {
+    for (size_t i = 0; i < count; i++, o += 6) plan_lineprod(slots, nblk_cap, stride, first + (uint32_t)i, fold, o);
+}
+void plan_ctx(uint32_t slots, size_t max_sets, uint64_t o[6]) {
+    const ctx_sizes s = ctx_for(slots, max_sets);
+    o[0] = s.stride, o[1] = s.mstride, o[2] = s.nblk_cap, o[3] = s.lpart_words, o[4] = s.lpart_mid_words, o[5] = s.export_bytes;
+}
 }

@@ -5,7 +5,7 @@ import random
 import pytest
 
 import bls12381_py as o
-from util import g1_jac_to_affine, golden
+from util import MSM_FORMS, g1_jac_to_affine, g2_jac_to_affine, golden, msm_hand_overs, msm_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -96,10 +96,11 @@ def test_msm_vs_c_oracle(m, cache, n):
 
 @pytest.mark.parametrize("n,nbits", [(40000, 255), (33000, 64), (70001, 130), (131072, 64), (100000, 256)])
 def test_msm_lds_sort_path(m, cache, n, nbits):
-    """n >= 2^15: the counting sort with a window's counters in LDS (k_pip_hist_lds / k_pip_scatter_lds) and the two window
-    groups; 32-byte scalar images (two 16-byte loads), blst's own (nbits + 7) / 8 spacing (8: word loads, 17: byte loads), a
-    ragged last slice, the exact blst argument list."""
+    """Sizes at which the plan (csrc/plan.hpp msm_for) sorts with a window's counters in LDS (k_pip_hist_lds / k_pip_scatter_lds),
+    some with the two window groups; 32-byte scalar images (two 16-byte loads), blst's own (nbits + 7) / 8 spacing (8: word loads,
+    17: byte loads), a ragged last slice, the exact blst argument list."""
     import c_oracle as co
+    assert msm_plan(n, nbits)["lds_sort"] == 1
     rng = random.Random(n)
     base = [co.sk_to_pk(rng.getrandbits(96) | 1) for _ in range(1500)]
     pts = b"".join(base[i % len(base)] for i in range(n))
@@ -111,6 +112,37 @@ def test_msm_lds_sort_path(m, cache, n, nbits):
     if nbits == 255:
         got = m.p1s_mult_pippenger(cache, pts, b"".join(k.to_bytes(32, "little") for k in ks), nbits)
         assert o.g1_to_blst_affine(g1_jac_to_affine(got)) == want
+
+
+@pytest.mark.parametrize("nbits,g2", [(64, False), (255, False), (255, True)])
+def test_msm_at_plan_hand_overs(m, cache, nbits, g2):
+    """The G1 MSM at both sides of every size below 2^18 points at which the plan (csrc/plan.hpp msm_for, asked through tests/util.py) changes what
+    msm_enqueue launches - the counting sort (global counters | LDS), the partial sums per window (1 | 4 | 16), one window group | two on two streams,
+    the lane-team width of the segment reduction - against the C restatement of the bucket method.  The sizes come from the plan; for 64 and 255
+    bits it has no change of the team width below 2^18 (four lanes throughout; two lanes: the 2^20 tests; one: G2).  g2: one G2 MSM at the smallest
+    size the plan splits."""
+    import c_oracle as co
+    overs = msm_hand_overs(nbits, 1 << 18, g2)
+    assert {f for f, _ in overs} >= ({"lds_sort", "nsplit", "ngroups"} if nbits == 255 else {"lds_sort", "nsplit"})
+    for f, t in overs:
+        assert f in MSM_FORMS and msm_plan(t, nbits, g2)[f] != msm_plan(t + 1, nbits, g2)[f], (f, t)
+    sizes = [min(t + 1 for f, t in overs if f == "ngroups")] if g2 else sorted({n for _, t in overs for n in (t, t + 1)})
+    rng = random.Random(nbits)
+    sc = b"".join(rng.getrandbits(nbits).to_bytes(32, "little") for _ in range(sizes[-1]))
+    if g2:
+        n = sizes[0]
+        assert (msm_plan(n - 1, nbits, True)["ngroups"], msm_plan(n, nbits, True)["ngroups"]) == (1, 2)
+        h = co.hash_to_g2(b"g2 split", o.DST_SIG)
+        base = [co.g2_mul(h, rng.randrange(1, o.R)) for _ in range(64)]
+        q = b"".join(base[i % 64] for i in range(n))
+        got = m.blst_p2s_mult_pippenger(q, sc, nbits)
+        assert o.g2_to_blst_affine(g2_jac_to_affine(got)) == co.msm_g2_pippenger(q, sc, nbits, 32)
+        return
+    base = [co.sk_to_pk(rng.getrandbits(96) | 1) for _ in range(1500)]
+    pts = b"".join(base[i % len(base)] for i in range(sizes[-1]))
+    for n in sizes:
+        got = m.p1s_mult_pippenger(cache, pts[:96 * n], sc[:32 * n], nbits)
+        assert o.g1_to_blst_affine(g1_jac_to_affine(got)) == co.msm_g1_pippenger(pts[:96 * n], sc[:32 * n], nbits), (n, msm_plan(n, nbits))
 
 
 def test_msm_linearity_at_2_20(m, cache):
@@ -200,7 +232,6 @@ def test_msm_multi_at_2_20_and_partial_merge(m, cache):
     import c_oracle as co
     import numpy as np
     import torch
-    from util import g2_jac_to_affine
     n = 1 << 20
     pts = _bench_points(n, 2020)
     sc = np.random.default_rng(2020).integers(0, 256, size=(n, 32), dtype=np.uint8).tobytes()

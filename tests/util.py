@@ -129,6 +129,14 @@ _LINES = ("main_pairs",) + tuple("main_" + f for f in _STAGE) + ("extra_pairs",)
 _SLICE = (("nb", "hash_map", "hash_map_grid") + tuple("clear_" + f for f in _STAGE) + ("pkmul_spread", "side", "pk_stream", "sig_stream", "cw", "nwin",
           "total", "lshift", "bucket_grid", "extra_apart") + tuple("extra_lines_" + f for f in _STAGE) + tuple("lines_" + f for f in _LINES))
 _LINEPROD = ("nblk", "m", "per_lane", "live", "per", "nb1")
+_MSM_CONSTANTS = ("MSM_SEG", "MSM_ORD_PER", "PIP_SLICES", "PIP_SORT_THREADS", "PIP_SORT_MAX_CBK", "MSM_TEAM_LANES_MAX", "MSM_TAIL_WAVES_MAX", "MSM_WINDOWS_MAX",
+                  "MSM_NSPLIT_MAX", "MSM_GROUPS_MAX", "SUM_PARTS_BYTES", "G1_WORDS", "G2_WORDS", "F12_WORDS")
+_MSM_GROUP = ("w0", "w1", "g0", "gc", "t0", "tc", "order_grid", "bucket_grid", "team", "segred_grid", "tail_waves", "tail_lanes")
+MSM_BUFFERS = ("d_pts", "d_sc", "pts_int", "hist", "chist", "shist", "part", "sorted", "buckets", "segout", "winout", "out")
+_MSM = (("nwin", "wbase", "wrem", "nbits", "cbk") + tuple("H%d" % j for j in range(9)) + ("n", "total", "segs_per_win", "nseg", "nsplit", "lds_sort", "per",
+        "point_grid", "slice_scan_grid", "ngroups", "cut0", "cut1", "cut2") + tuple("g%d_%s" % (g, f) for g in range(2) for f in _MSM_GROUP) +
+        tuple("touch_" + b for b in MSM_BUFFERS) + tuple("size_" + b for b in MSM_BUFFERS))
+_CTX = ("stride", "mstride", "nblk_cap", "lpart_words", "lpart_mid_words", "export_bytes")
 
 
 def plan_lib():
@@ -138,13 +146,16 @@ def plan_lib():
         here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emu")
         subprocess.check_call([os.path.join(here, "build_plan.sh")])
         L = ctypes.CDLL(os.path.join(here, "_build", "libplan.so"))
-        u32, sz, i, out = ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)
+        u32, sz, i, out, u64p = ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
         for name, res, args in (("plan_constants", None, (out,)), ("plan_team_rows_max", u32, (u32,)), ("plan_team_lines_max", u32, (u32,)),
                                 ("plan_team_form", u32, (u32, u32)), ("plan_lines", None, (u32, i, u32, u32, out)),
                                 ("plan_slice", None, (u32, i, i, sz, out)), ("plan_lineprod", None, (u32, u32, u32, u32, i, out)),
                                 ("plan_aggv_cut", sz, (out, sz, sz, sz)), ("plan_aggv_all32", i, (out, sz)), ("plan_shard_nslices", sz, (sz, sz)),
                                 ("plan_shard_workspaces", i, (sz,)), ("plan_shard_slice_count", sz, (sz, sz, sz, u32)),
-                                ("plan_shard_workspace_of", i, (sz, u32, i)), ("plan_chunk_of_tuple", u32, (sz, u32, sz))):
+                                ("plan_shard_workspace_of", i, (sz, u32, i)), ("plan_chunk_of_tuple", u32, (sz, u32, sz)),
+                                ("plan_msm_constants", None, (u64p,)), ("plan_msm_row", sz, ()), ("plan_msm_many", None, (u64p, sz, sz, i, i, i, u64p)),
+                                ("plan_sum_many", None, (i, u32, out, sz, out)), ("plan_ctx", None, (u32, sz, u64p)),
+                                ("plan_lineprod_many", None, (u32, u32, u32, u32, sz, i, out))):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         _PLAN = L
     return _PLAN
@@ -161,6 +172,10 @@ def __getattr__(name):
     """the plan's constants (TEAM_CLEAR_ITEMS_PER_SLOT, SIG_WIDE_MIN, ...), read from the compiled plan"""
     if name in _PLAN_CONSTANTS:
         return _plan_call("plan_constants", _PLAN_CONSTANTS)[name]
+    if name in _MSM_CONSTANTS:
+        out = (ctypes.c_uint64 * len(_MSM_CONSTANTS))()
+        plan_lib().plan_msm_constants(out)
+        return dict(zip(_MSM_CONSTANTS, out))[name]
     raise AttributeError(name)
 
 
@@ -177,6 +192,63 @@ def lines_plan(npairs, extra, S, coop=True):
 def lineprod_plan(S, nblk_cap, stride, npairs, fold):
     """plan.hpp lineprod_for"""
     return _plan_call("plan_lineprod", _LINEPROD, S, nblk_cap, stride, npairs, int(fold))
+
+
+def msm_plans(npoints, nbits, g2=False, allow_split=True, have_side=True):
+    """plan.hpp msm_for for every entry of `npoints` at once -> {field: numpy uint64 array}: the plan (g0_* / g1_*: its window groups), touch_<buffer>
+    = msm_extents of it, size_<buffer> = msm_sizes_for what msm_reserve grows an empty workspace to for that call (MSM_BUFFERS names the buffers)"""
+    import numpy as np
+    L = plan_lib()
+    assert L.plan_msm_row() == len(_MSM)
+    pts = np.ascontiguousarray(npoints, dtype=np.uint64)
+    rows = np.empty((len(pts), len(_MSM)), dtype=np.uint64)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.plan_msm_many(pts.ctypes.data_as(u64p), len(pts), nbits, int(g2), int(allow_split), int(have_side), rows.ctypes.data_as(u64p))
+    return {f: rows[:, j] for j, f in enumerate(_MSM)}
+
+
+def msm_plan(n, nbits, g2=False, allow_split=True, have_side=True):
+    """one plan -> {field: int}"""
+    return {f: int(v[0]) for f, v in msm_plans([n], nbits, g2, allow_split, have_side).items()}
+
+
+MSM_FORMS = ("lds_sort", "g0_team", "ngroups", "nsplit")      # what msm_enqueue launches differently from one size to the next
+
+
+def msm_hand_overs(nbits, below, g2=False):
+    """[(form, t)]: the plan of a call with fork streams changes `form` (of MSM_FORMS) between t and t + 1 points, for every t + 1 < below"""
+    import numpy as np
+    out = []
+    step = 1 << 14
+    for lo in range(1, below, step):                 # chunks that overlap by one size
+        p = msm_plans(np.arange(lo, min(lo + step + 1, below)), nbits, g2)
+        out += [(f, lo + int(j)) for f in MSM_FORMS for j in np.nonzero(p[f][1:] != p[f][:-1])[0]]
+    return sorted(out, key=lambda x: (x[1], x[0]))
+
+
+def sum_plans(g2, S, n):
+    """plan.hpp g1_sum_for / g2_sum_for for every entry of n -> (nblk, m) as numpy arrays"""
+    import numpy as np
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    n = np.ascontiguousarray(n, dtype=np.uint32)
+    rows = np.empty((len(n), 2), dtype=np.uint32)
+    plan_lib().plan_sum_many(int(g2), S, n.ctypes.data_as(u32p), len(n), rows.ctypes.data_as(u32p))
+    return rows[:, 0].astype(np.uint64), rows[:, 1].astype(np.uint64)
+
+
+def lineprod_plans(S, nblk_cap, stride, first, count, fold):
+    """plan.hpp lineprod_for for npairs = first .. first + count - 1 -> {field: numpy array}"""
+    import numpy as np
+    rows = np.empty((count, len(_LINEPROD)), dtype=np.uint32)
+    plan_lib().plan_lineprod_many(S, nblk_cap, stride, first, count, int(fold), rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    return {f: rows[:, j].astype(np.uint64) for j, f in enumerate(_LINEPROD)}
+
+
+def ctx_sizes(S, max_sets):
+    """plan.hpp ctx_for"""
+    out = (ctypes.c_uint64 * len(_CTX))()
+    plan_lib().plan_ctx(S, max_sets, out)
+    return dict(zip(_CTX, out))
 
 
 def rows_max(S):
