@@ -147,6 +147,38 @@ int mi355_bls_verify_each_device(mi355_bls_ctx* ctx, const void* d_sets, size_t 
 int mi355_bls_batch_verify_locate(mi355_bls_ctx* ctx, const void* sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[]);
 int mi355_bls_batch_verify_locate_device(mi355_bls_ctx* ctx, const void* d_sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[], void* stream);
 
+/* Proofs of possession for a table of keys in one device pass: popVerify (bls_sig_min_pubkey.nim:60-74) is
+ * coreVerifyNoGroupCheck(publicKey, rawFromPublic(publicKey), proof, DST_POP) - the check every aggregate entry point of this header
+ * leaves to the caller, and the one the reference's proof-taking overloads of verify / aggregateVerify / fastAggregateVerify
+ * (:104, :148, :220-225) loop over key by key.  pks96: n x 96-byte blst_p1_affine images; proofs192: n x 192-byte blst_p2_affine images
+ * (a ProofOfPossession is a Signature: 96 bytes on the wire, decoded by mi355_bls_deserialize_sets like any signature; the message column
+ * of that call is not used here).  The message of pair i is the 48-byte compressed form of key i, computed on the device.
+ *   pop_verify_each:  verdicts[i] = popVerify(pk_i, proof_i) exactly.  No blinding, no random bytes: verdict i depends on pair i alone.
+ *                     Infinity rules as mi355_bls_verify_each: an infinity key gives 0, an infinity proof gives 0 for a valid key.
+ *                     Preconditions as the reference's: points decoded and group-checked.  Any n (larger inputs run in slices).
+ *                     Returns 1 iff every verdict is 1 (n == 0: 0, nothing written), negative on a runtime failure.  Synchronous.
+ *   batch_pop_verify: NO reference counterpart (like mi355_bls_batch_verify_many): the blinded check of mi355_bls_batch_verify over the sets
+ *                     (pk_i, compress(pk_i), proof_i) under DST_POP, with the scalars drawn exactly as mi355_bls_batch_verify draws them for
+ *                     n sets and rnd (num_threads chains); mi355_bls_fetch_stage shows its stages as for any batch call.  1 / 0 / negative.
+ *   batch_pop_verify_locate:  the batch check first; if it passes: 1 and every verdict 1, no per-pair pass; if it fails: one
+ *                     pop_verify_each pass, returns 0 with the verdicts.
+ * The _device forms take the two arrays in device memory and a stream; verdicts stay host memory.
+ * COST at 65 536 keys on one MI355X (profiles/pop_verify_bench.json; ordinary signature sets over the same keys in the same run beside them):
+ * not measured yet: run nim-blscurve_amd/tools/bench_pop.py on an MI355X, which writes the four timings and the two ratios. */
+int mi355_bls_pop_verify_each(mi355_bls_ctx* ctx, const void* pks96, const void* proofs192, size_t n, uint8_t verdicts[]);
+int mi355_bls_pop_verify_each_device(mi355_bls_ctx* ctx, const void* d_pks96, const void* d_proofs192, size_t n, uint8_t verdicts[], void* stream);
+int mi355_bls_batch_pop_verify(mi355_bls_ctx* ctx, const void* pks96, const void* proofs192, size_t n, const uint8_t rnd[32]);
+int mi355_bls_batch_pop_verify_device(mi355_bls_ctx* ctx, const void* d_pks96, const void* d_proofs192, size_t n, const uint8_t rnd[32], void* stream);
+int mi355_bls_batch_pop_verify_locate(mi355_bls_ctx* ctx, const void* pks96, const void* proofs192, size_t n, const uint8_t rnd[32], uint8_t verdicts[]);
+int mi355_bls_batch_pop_verify_locate_device(mi355_bls_ctx* ctx, const void* d_pks96, const void* d_proofs192, size_t n, const uint8_t rnd[32],
+                                             uint8_t verdicts[], void* stream);
+/* rawFromPublic (blst_min_pubkey_sig_core.nim:135-137) / serialize(PublicKey) (bls_sig_io.nim:203-211), i.e. blst_p1_affine_compress, for n
+ * keys: 96-byte blst_p1_affine images in, 48 bytes each out (ZCash form: big-endian x, bit 7 of byte 0 set, bit 5 set when y is the
+ * lexicographically larger root; the all-zero infinity image gives 0xc0 and 47 zero bytes).  The device form writes device memory
+ * (d_out48: n x 48 B) and returns when the bytes are there.  Returns 0, negative on failure. */
+int mi355_bls_compress_public_keys(mi355_bls_ctx* ctx, const void* pks96, size_t n, uint8_t out48[]);
+int mi355_bls_compress_public_keys_device(mi355_bls_ctx* ctx, const void* d_pks96, size_t n, void* d_out48, void* stream);
+
 /* Multi-GPU sharding (replaces processSingleChunk + merge, bls_batch_verifier.nim:326-369).
  * The global batch of n_total sets is cut into B = min(n_total, num_threads) chunks by
  * parallel_chunks (parallel_chunks.nim:42-66); this call processes chunks [chunk_lo, chunk_hi),
@@ -457,6 +489,14 @@ int mi355_bls_sign_sets(mi355_bls_ctx* ctx, const uint8_t* sks32, const uint8_t*
 int mi355_bls_sign_sets_device(mi355_bls_ctx* ctx, const void* d_sks32, const void* d_msgs32, size_t n, void* d_out_sets, void* stream,
                                uint8_t* status);
 
+/* popProve (bls_sig_min_pubkey.nim:34-58) for n secret keys, the input generator of the PoP calls: pk_i = affine([sk_i]G1) as a 96-byte
+ * image, proof_i = affine([sk_i] hash_to_g2(rawFromPublic(pk_i), DST_POP)) as a 192-byte image.  sk == 0 or sk >= r: status[i] = 1 and zeroed
+ * outputs, as mi355_bls_sign_sets.  Returns 1 when every key was valid, 0 otherwise.  VARIABLE TIME like the signer above: for tests and
+ * benchmarks only, never for real keys. */
+int mi355_bls_pop_prove(mi355_bls_ctx* ctx, const uint8_t* sks32, size_t n, void* out_pks96, void* out_proofs192, uint8_t* status);
+int mi355_bls_pop_prove_device(mi355_bls_ctx* ctx, const void* d_sks32, size_t n, void* d_out_pks96, void* d_out_proofs192, void* stream,
+                               uint8_t* status);
+
 /* Stage outputs of the LAST batch call on this context, for parity tests (no reference
  * counterpart: BLST keeps these inside blst_pairing).  `what`:
  *   0: blinding scalars r_i           n x 8 B  (LE u64)
@@ -493,6 +533,8 @@ int mi355_bls_debug_fail_next_enqueue(mi355_bls_ctx* ctx);
  * mi355_bls_fetch_stage(4) is to the batch paths).  debug_verify_each_passes: per-set passes this context has made so far. */
 int mi355_bls_debug_verify_each_gt(mi355_bls_ctx* ctx, const void* sets, size_t n, uint8_t verdicts[], uint8_t* gt_out);
 int mi355_bls_debug_verify_each_passes(mi355_bls_ctx* ctx);
+/* mi355_bls_pop_verify_each with the value of every pair (n x 576 B), as mi355_bls_debug_verify_each_gt */
+int mi355_bls_debug_pop_verify_each_gt(mi355_bls_ctx* ctx, const void* pks96, const void* proofs192, size_t n, uint8_t verdicts[], uint8_t* gt_out);
 size_t mi355_bls_debug_multi_enqueue_us(float* out, size_t cap);
 /* Batches submitted and not yet waited for, over all contexts of the process: what the library looks at when it chooses between the
  * low-latency and the least-work fold of the line products (a batch enqueued while this is zero has the chip to itself).  The tests

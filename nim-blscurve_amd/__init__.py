@@ -65,6 +65,17 @@ def lib():
         L.mi355_bls_batch_verify_locate_device.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp]
         L.mi355_bls_debug_verify_each_gt.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p]
         L.mi355_bls_debug_verify_each_passes.argtypes = [vp]
+        L.mi355_bls_pop_verify_each.argtypes = [vp, vp, vp, sz, ctypes.c_char_p]
+        L.mi355_bls_pop_verify_each_device.argtypes = [vp, vp, vp, sz, ctypes.c_char_p, vp]
+        L.mi355_bls_debug_pop_verify_each_gt.argtypes = [vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p]
+        L.mi355_bls_batch_pop_verify.argtypes = [vp, vp, vp, sz, ctypes.c_char_p]
+        L.mi355_bls_batch_pop_verify_device.argtypes = [vp, vp, vp, sz, ctypes.c_char_p, vp]
+        L.mi355_bls_batch_pop_verify_locate.argtypes = [vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p]
+        L.mi355_bls_batch_pop_verify_locate_device.argtypes = [vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp]
+        L.mi355_bls_compress_public_keys.argtypes = [vp, vp, sz, ctypes.c_char_p]
+        L.mi355_bls_compress_public_keys_device.argtypes = [vp, vp, sz, vp, vp]
+        L.mi355_bls_pop_prove.argtypes = [vp, ctypes.c_char_p, sz, vp, vp, vp]
+        L.mi355_bls_pop_prove_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
         L.mi355_bls_batch_shard_device.argtypes = [vp, vp, sz, u32, u32, ctypes.c_char_p, vp, ctypes.c_char_p, ctypes.POINTER(i32)]
         L.mi355_bls_batch_shard_submit_device.argtypes = [vp, vp, sz, u32, u32, ctypes.c_char_p, vp, vp]
         L.mi355_bls_batch_shard_wait.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i32)]
@@ -431,6 +442,129 @@ def batchVerifyLocate_device(cache, d_ptr, n, secureRandomBytes, stream=0):
     out = ctypes.create_string_buffer(n)
     ok = _check(lib().mi355_bls_batch_verify_locate_device(cache._h, d_ptr, n, rnd, out, stream))
     return bool(ok), [v == 1 for v in out.raw]
+
+
+def _keys_and_proofs(publicKeys, proofs):
+    """n x 96-byte blst_p1_affine images, n x 192-byte blst_p2_affine images (lists or concatenated) -> (keys, proofs, n).  A proof of possession is a
+    Signature on the wire (96 bytes): deserializeSets decodes it like any signature, with a message column that is not used."""
+    pk = bytes(publicKeys) if isinstance(publicKeys, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in publicKeys)
+    pr = bytes(proofs) if isinstance(proofs, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in proofs)
+    if len(pk) % 96 or len(pr) % 192 or len(pk) // 96 != len(pr) // 192:
+        raise ValueError("n x 96-byte public keys (blst_p1_affine), n x 192-byte proofs (blst_p2_affine)")
+    return pk, pr, len(pk) // 96
+
+
+def popVerifyEach(cache, publicKeys, proofs):
+    """popVerify(publicKey, proof) (bls_sig_min_pubkey.nim:60-74) for every (key, proof) pair in one device pass (mi355_bls_pop_verify_each):
+    -> [bool], one per pair; no random bytes, pair i's verdict depends on pair i alone.  Empty input -> []."""
+    pk, pr, n = _keys_and_proofs(publicKeys, proofs)
+    if n == 0:
+        return []
+    out = ctypes.create_string_buffer(n)
+    _check(lib().mi355_bls_pop_verify_each(cache._h, pk, pr, n, out))
+    return [v == 1 for v in out.raw]
+
+
+def popVerifyEach_device(cache, d_pks, d_proofs, n, stream=0):
+    """Same with the n keys and n proofs in device memory."""
+    if n == 0:
+        return []
+    out = ctypes.create_string_buffer(n)
+    _check(lib().mi355_bls_pop_verify_each_device(cache._h, d_pks, d_proofs, n, out, stream))
+    return [v == 1 for v in out.raw]
+
+
+def popVerifyEachValues(cache, publicKeys, proofs):
+    """Test hook (mi355_bls_debug_pop_verify_each_gt): -> ([bool], [576-byte blst_fp12 image of final_exp(f_i)])."""
+    pk, pr, n = _keys_and_proofs(publicKeys, proofs)
+    if n == 0:
+        return [], []
+    out, gt = ctypes.create_string_buffer(n), ctypes.create_string_buffer(n * 576)
+    _check(lib().mi355_bls_debug_pop_verify_each_gt(cache._h, pk, pr, n, out, gt))
+    raw = gt.raw
+    return [v == 1 for v in out.raw], [raw[576 * i:576 * i + 576] for i in range(n)]
+
+
+def batchPopVerify(cache, publicKeys, proofs, secureRandomBytes):
+    """The blinded batch check over the sets (pk_i, compress(pk_i), proof_i) under DST_POP (mi355_bls_batch_pop_verify; no reference
+    counterpart): one verdict for the whole table; empty input -> False."""
+    pk, pr, n = _keys_and_proofs(publicKeys, proofs)
+    rnd = _rnd32(secureRandomBytes)
+    if n == 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_pop_verify(cache._h, pk, pr, n, rnd)))
+
+
+def batchPopVerify_device(cache, d_pks, d_proofs, n, secureRandomBytes, stream=0):
+    """Same with the n keys and n proofs in device memory."""
+    rnd = _rnd32(secureRandomBytes)
+    if n == 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_pop_verify_device(cache._h, d_pks, d_proofs, n, rnd, stream)))
+
+
+def batchPopVerifyLocate(cache, publicKeys, proofs, secureRandomBytes):
+    """batchPopVerify first; a failing table gets one popVerifyEach pass (mi355_bls_batch_pop_verify_locate).
+    -> (ok, [bool] per pair), as batchVerifyLocate; empty input -> (False, [])."""
+    pk, pr, n = _keys_and_proofs(publicKeys, proofs)
+    rnd = _rnd32(secureRandomBytes)
+    if n == 0:
+        return False, []
+    out = ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_batch_pop_verify_locate(cache._h, pk, pr, n, rnd, out))
+    return bool(ok), [v == 1 for v in out.raw]
+
+
+def batchPopVerifyLocate_device(cache, d_pks, d_proofs, n, secureRandomBytes, stream=0):
+    """Same with the n keys and n proofs in device memory."""
+    rnd = _rnd32(secureRandomBytes)
+    if n == 0:
+        return False, []
+    out = ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_batch_pop_verify_locate_device(cache._h, d_pks, d_proofs, n, rnd, out, stream))
+    return bool(ok), [v == 1 for v in out.raw]
+
+
+def compressPublicKeys(cache, publicKeys):
+    """rawFromPublic / serialize (bls_sig_io.nim:203-211) for n keys (mi355_bls_compress_public_keys): n x 96-byte images -> [48-byte strings]."""
+    pk = bytes(publicKeys) if isinstance(publicKeys, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in publicKeys)
+    if len(pk) % 96:
+        raise ValueError("n x 96-byte public keys (blst_p1_affine)")
+    n = len(pk) // 96
+    if n == 0:
+        return []
+    out = ctypes.create_string_buffer(48 * n)
+    _check(lib().mi355_bls_compress_public_keys(cache._h, pk, n, out))
+    raw = out.raw
+    return [raw[48 * i:48 * i + 48] for i in range(n)]
+
+
+def compressPublicKeys_device(cache, d_pks, n, d_out, stream=0):
+    """Same with the keys and the n x 48 output bytes in device memory (raw pointers)."""
+    if n:
+        _check(lib().mi355_bls_compress_public_keys_device(cache._h, d_pks, n, d_out, stream))
+
+
+def popProve(cache, secret_keys):
+    """popProve (bls_sig_min_pubkey.nim:34-58) for n secret keys on the device, VARIABLE TIME (test and bench inputs only, like signSets).
+    secret_keys: n x 32-byte little-endian scalars (list or concatenated).
+    -> (all_valid, n x 96-byte keys, n x 192-byte proofs, per-key status bytes: 1 = sk == 0 or sk >= r, outputs zeroed)."""
+    sk = bytes(secret_keys) if isinstance(secret_keys, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in secret_keys)
+    if len(sk) % 32:
+        raise ValueError("n x 32-byte secret keys")
+    n = len(sk) // 32
+    if n == 0:
+        return True, b"", b"", b""
+    pks, prs, st = ctypes.create_string_buffer(96 * n), ctypes.create_string_buffer(192 * n), ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_pop_prove(cache._h, sk, n, pks, prs, st))
+    return bool(ok), pks.raw, prs.raw, st.raw
+
+
+def popProve_device(cache, d_sks, n, d_out_pks, d_out_proofs, stream=0):
+    """Same with the scalars and both outputs resident in device memory (raw pointers)."""
+    st = ctypes.create_string_buffer(max(n, 1))
+    ok = _check(lib().mi355_bls_pop_prove_device(cache._h, d_sks, n, d_out_pks, d_out_proofs, stream, st))
+    return bool(ok), st.raw[:n]
 
 
 def batchVerifySerial(cache, input_, secureRandomBytes):

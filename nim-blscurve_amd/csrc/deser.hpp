@@ -81,6 +81,30 @@ BLS_HDN bool g1_uncompress(g1_aff& out, bool& inf, const uint8_t* b) {
     return true;
 }
 
+// The inverse: blst_p1_affine_compress (rawFromPublic / serialize of a PublicKey, bls_sig_io.nim:203-211).  Affine in, so no inversion: the
+// canonical x big-endian, bit 383 set, bit 381 set when y is the lexicographically larger root; the affine infinity image (x = y = 0) gives
+// 0xc0 and 47 zero bytes.  The word form is what a lane hashes (popVerify's message): word 0 holds bytes 0..3, most significant first.
+BLS_HD void g1_compress_words(uint32_t (&be)[12], const g1_aff& p) {
+    const bool inf = aff_is_inf(p);
+    uint32_t w[12];
+    fp_relimb_to32(w, fp_from_mont(p.x));
+    const bool large = fp_is_lex_largest(p.y);
+#pragma unroll
+    for (int i = 0; i < 12; i++) be[i] = inf ? 0u : w[11 - i];
+    be[0] |= inf ? 0xc0000000u : (large ? 0xa0000000u : 0x80000000u);
+}
+BLS_HD void g1_compress(uint8_t out[48], const g1_aff& p) {
+    uint32_t be[12];
+    g1_compress_words(be, p);
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        out[4 * i] = (uint8_t)(be[i] >> 24);
+        out[4 * i + 1] = (uint8_t)(be[i] >> 16);
+        out[4 * i + 2] = (uint8_t)(be[i] >> 8);
+        out[4 * i + 3] = (uint8_t)be[i];
+    }
+}
+
 BLS_HDN bool g2_uncompress(g2_aff& out, bool& inf, const uint8_t* b) {
     inf = false;
     out = g2_aff{fp2_zero(), fp2_zero()};

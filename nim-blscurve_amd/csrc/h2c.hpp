@@ -3,6 +3,8 @@
 // (reference blst_abi.nim:383, 504-507; call site blst_min_pubkey_sig_core.nim:558-568).
 // Output stays Jacobian: the Miller loop consumes projective Q, so no field inversion per tuple.
 #pragma once
+#include <cassert>
+
 #include "curve.hpp"
 #include "sha256.hpp"
 
@@ -57,38 +59,50 @@ BLS_HDN void hash_to_field_fp2x2(fp2& u0, fp2& u1, const uint8_t* msg, uint32_t 
     u1.c1 = fp_from_be_words16(uni + 48);
 }
 
-// expand_message_xmd for 32-byte messages (every SignatureSet message, bls_batch_verifier.nim:42) with everything
-// that does not depend on the message folded into constants per DST, built once on the host:
-//   b_0 = H(Z_pad(64) | msg(32) | 0x0100 | 0x00 | DST | len):  state after Z_pad, block 2 = msg | tail[0..32), block 3
+// expand_message_xmd for 32-byte messages (every SignatureSet message, bls_batch_verifier.nim:42) and for 48-byte ones (popVerify's message:
+// the compressed public key, bls_sig_min_pubkey.nim:60-74) with everything that does not depend on the message folded into constants per
+// DST, built once on the host.  With a message of ML bytes (a multiple of 4, 32 or 48 here):
+//   b_0 = H(Z_pad(64) | msg(ML) | 0x0100 | 0x00 | DST | len):  state after Z_pad, block 2 = msg | tail[0..64-ML), block 3 = tail[64-ML..) | padding
 //   b_i = H((b_0 ^ b_(i-1))(32) | i | DST | len):              block 1 = x | tail_i[0..32), block 2 (the same for all i)
-// 18 compressions per message and no byte-wise buffering.  Valid for 28 <= dst_len <= 83 (the tails then span exactly
-// the block boundaries used here); other lengths take hash_to_field_fp2x2.
+// 18 compressions per message and no byte-wise buffering.  The tails must span exactly the block boundaries used here.  b_0's tail is
+// dst_len + 4 bytes: it fills block 2 (dst_len + 4 >= 64 - ML) and what is left fits block 3 with the 0x80 byte and the 8-byte bit count
+// (dst_len + 4 - (64 - ML) + 9 <= 64), i.e. 60 - ML <= dst_len <= 115 - ML: 28..83 for ML = 32, 12..67 for ML = 48.  b_i's tail is dst_len + 2
+// bytes behind 32: 28 <= dst_len <= 83 whatever the message.  So the form is valid for 28 <= dst_len <= 83 (32-byte messages) and for
+// 28 <= dst_len <= 67 (48-byte messages); other lengths take hash_to_field_fp2x2.  (The scheme's two tags are 43 bytes long.)
 struct xmd32_consts {
-    uint32_t h_zpad[8], b0_w8[8], b0_blk3[16], bi_w8[8][8], bi_blk2[16];
+    uint32_t h_zpad[8], b0_w[8], b0_blk3[16], bi_w8[8][8], bi_blk2[16];
+    uint32_t valid;
+};
+struct xmd48_consts {
+    uint32_t h_zpad[8], b0_w[4], b0_blk3[16], bi_w8[8][8], bi_blk2[16];
     uint32_t valid;
 };
 inline void xmd32_pack(uint32_t* w, const uint8_t* bytes, int nwords) {
     for (int i = 0; i < nwords; i++)
         w[i] = ((uint32_t)bytes[4 * i] << 24) | ((uint32_t)bytes[4 * i + 1] << 16) | ((uint32_t)bytes[4 * i + 2] << 8) | bytes[4 * i + 3];
 }
-inline xmd32_consts xmd32_precompute(const uint8_t* dst, uint32_t dst_len) {
-    xmd32_consts c{};
-    c.valid = dst_len >= 28 && dst_len <= 83;
+// C: the constants of a message of ML bytes (xmd32_consts: 32, xmd48_consts: 48)
+template <class C, uint32_t ML>
+inline C xmd_precompute(const uint8_t* dst, uint32_t dst_len) {
+    static_assert(ML % 4 == 0 && ML >= 32 && ML < 64 && sizeof(C{}.b0_w) == 64 - ML, "block 2 of b_0 = the message and 64 - ML bytes of the tail");
+    C c{};
+    const bool b0_ok = dst_len + 4 >= 64 - ML && dst_len + 4 - (64 - ML) + 9 <= 64, bi_ok = dst_len >= 28 && dst_len <= 83;
+    c.valid = b0_ok && bi_ok;
     if (!c.valid) return c;
     uint8_t blk[192];
     uint32_t w[16];
     sha256_init(c.h_zpad);
     for (int i = 0; i < 16; i++) w[i] = 0;
     sha256_compress_core(c.h_zpad, w);                                   // Z_pad: 64 zero bytes
-    // b_0: tail = 0x01 0x00 | 0x00 | DST | len, message length 64 + 32 + dst_len + 4 bytes
+    // b_0: tail = 0x01 0x00 | 0x00 | DST | len, message length 64 + ML + dst_len + 4 bytes
     for (int i = 0; i < 192; i++) blk[i] = 0;
-    uint32_t t0 = dst_len + 4, tot0 = 96 + t0;
+    uint32_t t0 = dst_len + 4, tot0 = 64 + ML + t0;
     blk[0] = 1;
     for (uint32_t i = 0; i < dst_len; i++) blk[3 + i] = dst[i];
     blk[3 + dst_len] = (uint8_t)dst_len;
     blk[t0] = 0x80;
-    xmd32_pack(c.b0_w8, blk, 8);
-    xmd32_pack(c.b0_blk3, blk + 32, 16);
+    xmd32_pack(c.b0_w, blk, (64 - ML) / 4);
+    xmd32_pack(c.b0_blk3, blk + (64 - ML), 16);
     c.b0_blk3[15] = tot0 * 8;
     // b_i: tail_i = i | DST | len, message length 32 + dst_len + 2 bytes
     uint32_t t1 = dst_len + 2, tot1 = 32 + t1;
@@ -106,14 +120,26 @@ inline xmd32_consts xmd32_precompute(const uint8_t* dst, uint32_t dst_len) {
     }
     return c;
 }
-BLS_HD void hash_to_field_fp2x2_msg32(fp2& u0, fp2& u1, const uint32_t (&msg_be)[8], const xmd32_consts& c) {
+inline xmd32_consts xmd32_precompute(const uint8_t* dst, uint32_t dst_len) {
+    const xmd32_consts c = xmd_precompute<xmd32_consts, 32>(dst, dst_len);
+    assert(c.valid == (dst_len >= 28 && dst_len <= 83));
+    return c;
+}
+inline xmd48_consts xmd48_precompute(const uint8_t* dst, uint32_t dst_len) {
+    const xmd48_consts c = xmd_precompute<xmd48_consts, 48>(dst, dst_len);
+    assert(c.valid == (dst_len >= 28 && dst_len <= 67));                 // the range derived above
+    return c;
+}
+// msg_be: the message as MW big-endian words
+template <int MW, class C>
+BLS_HD void hash_to_field_fp2x2_prepared(fp2& u0, fp2& u1, const uint32_t (&msg_be)[MW], const C& c) {
     uint32_t b0[8], bi[8], w[16], uni[64];
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-        b0[i] = c.h_zpad[i];
-        w[i] = msg_be[i];
-        w[8 + i] = c.b0_w8[i];
-    }
+    for (int i = 0; i < 8; i++) b0[i] = c.h_zpad[i];
+#pragma unroll
+    for (int i = 0; i < MW; i++) w[i] = msg_be[i];
+#pragma unroll
+    for (int i = 0; i < 16 - MW; i++) w[MW + i] = c.b0_w[i];
     sha256_compress(b0, w);
 #pragma unroll
     for (int i = 0; i < 16; i++) w[i] = c.b0_blk3[i];
@@ -143,6 +169,8 @@ BLS_HD void hash_to_field_fp2x2_msg32(fp2& u0, fp2& u1, const uint32_t (&msg_be)
     u1.c0 = fp_from_be_words16(uni + 32);
     u1.c1 = fp_from_be_words16(uni + 48);
 }
+BLS_HD void hash_to_field_fp2x2_msg32(fp2& u0, fp2& u1, const uint32_t (&msg_be)[8], const xmd32_consts& c) { hash_to_field_fp2x2_prepared<8>(u0, u1, msg_be, c); }
+BLS_HD void hash_to_field_fp2x2_msg48(fp2& u0, fp2& u1, const uint32_t (&msg_be)[12], const xmd48_consts& c) { hash_to_field_fp2x2_prepared<12>(u0, u1, msg_be, c); }
 
 // (is_square(N/D), y) with y = sqrt(N/D) if square, else sqrt(Z * N/D); Z = -(2+u), norm(Z) = 5.
 // Two Fp exponentiations; the first also yields 1/norm(D).

@@ -101,6 +101,8 @@ struct mi355_bls_ctx {
     float timings[8] = {};
     dst_t dst;
     xmd32_consts xmd;                // message-independent SHA-256 words of expand_message_xmd for this DST
+    dst_t dst_pop;                   // popVerify's tag and its constants for 48-byte messages (compressed keys): the PoP calls pass them, `dst` / `xmd` never change
+    xmd48_consts xmd_pop;
     std::vector<uint64_t> h_r;       // host-computed scalar chains (serial blinding chain, combine)
     msm_ws msm;                      // lazily sized MSM workspace
     std::vector<uint8_t> av_pks, av_msgs;      // streaming aggregateVerify (mi355_bls_aggv_*): the pairs collected so far
@@ -187,6 +189,7 @@ extern "C" int mi355_bls_recommend_hw_queues(void) {
 }
 
 static const char DST_SIG[] = "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_";   // bls_sig_min_pubkey.nim:31
+static const char DST_POP[] = "BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_";   // bls_sig_min_pubkey.nim:32
 
 extern "C" const char* mi355_bls_last_error(void) { return g_err.c_str(); }
 // Batches submitted and not yet waited for, over all contexts of the process.  A batch enqueued while this is zero has the chip to itself
@@ -227,6 +230,10 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     c->dst.len = sizeof(DST_SIG) - 1;
     std::memcpy(c->dst.b, DST_SIG, c->dst.len);
     c->xmd = xmd32_precompute(c->dst.b, c->dst.len);
+    std::memset(&c->dst_pop, 0, sizeof(c->dst_pop));
+    c->dst_pop.len = sizeof(DST_POP) - 1;
+    std::memcpy(c->dst_pop.b, DST_POP, c->dst_pop.len);
+    c->xmd_pop = xmd48_precompute(c->dst_pop.b, c->dst_pop.len);
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     c->slots = 4u * (uint32_t)prop.multiProcessorCount;
@@ -323,8 +330,18 @@ static int io_reserve(mi355_bls_ctx* c, size_t n) {
 }
 
 // 320-byte records -> d_M: the two mapped points of every message (two lanes per message)
-static void launch_hash_map(mi355_bls_ctx* c, const uint8_t* d_sets, uint32_t n32, hipStream_t st) {
+// pop (here and in every routine below that takes it): the records are popVerify's, key | unused | proof - the message of record i is its own
+// key in compressed form, hashed under DST_POP.  Same plan, same grids: the PoP kernels are the same bodies with another message source.
+static void launch_hash_map(mi355_bls_ctx* c, const uint8_t* d_sets, uint32_t n32, hipStream_t st, bool pop = false) {
     const plan::hash_map_plan p = plan::hash_map_for(c->slots, c->coop, n32);
+    if (pop) {
+        switch (p.form) {
+            case plan::HASH_MAP_ROWS: k_hash_map_rows_pop<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst_pop, c->xmd_pop, c->d_M, c->mstride); break;
+            case plan::HASH_MAP_SPREAD: k_hash_map_spread_pop<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst_pop, c->xmd_pop, c->d_M, c->mstride); break;
+            case plan::HASH_MAP_PLAIN: k_hash_map_pop<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst_pop, c->xmd_pop, c->d_M, c->mstride); break;
+        }
+        return;
+    }
     switch (p.form) {
         case plan::HASH_MAP_ROWS: k_hash_map_rows<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride); break;
         case plan::HASH_MAP_SPREAD: k_hash_map_spread<<<p.grid, WAVE, 0, st>>>(d_sets, n32, c->dst, c->xmd, c->d_M, c->mstride); break;
@@ -509,12 +526,12 @@ static int enqueue_line_products(mi355_bls_ctx* c, const pair_store& ps, uint32_
 // the signature side (bucket fold).  A batch that fills the chip runs them one after the other on the caller's stream (each is a
 // whole-chip kernel).  A small batch in latency mode runs the last two on the context's side stream beside the hashing: they
 // are all latency-bound there (a few waves each), so this takes about a millisecond off the call.
-static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStream_t st);
+static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStream_t st, bool pop = false);
 // c: the workspace this slice runs in (the caller's context or one of its lanes); p: the caller's context, which holds what the slices
 // of one call share - the random bytes, the carried chain state, the host-computed serial chain.  blind_done (may be null) is
 // recorded behind the blinding kernel: the next slice's chains continue from the state this one leaves.
 static int run_slice(mi355_bls_ctx* c, mi355_bls_ctx* p, const uint8_t* d_sets, size_t n_total, uint32_t nchunks, uint32_t chunk_lo, uint32_t chunk_cnt,
-                     size_t tuple_base, size_t n, int serial, size_t serial_off, uint32_t slice, hipStream_t st, hipEvent_t blind_done) {
+                     size_t tuple_base, size_t n, int serial, size_t serial_off, uint32_t slice, hipStream_t st, hipEvent_t blind_done, bool pop = false) {
     HIPCHK(hipEventRecord(c->ev[0], st));
     if (serial) {
         HIPCHK(hipMemcpyAsync(c->d_r, p->h_r.data() + serial_off, n * 8, hipMemcpyHostToDevice, st));
@@ -523,11 +540,11 @@ static int run_slice(mi355_bls_ctx* c, mi355_bls_ctx* p, const uint8_t* d_sets, 
                                                                 p->d_carry + 8 * ((slice + 1) & 1), c->d_r);
     }
     if (blind_done) HIPCHK(hipEventRecord(blind_done, st));
-    return run_pairs(c, d_sets, n, st);
+    return run_pairs(c, d_sets, n, st, pop);
 }
 // Everything behind the blinding scalars (d_r[0 .. n) are ready on `st`): hashing, [r]PK, the signature side, Miller lines, line
 // products, the committed state of these n tuples in d_states slot 0.
-static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStream_t st) {
+static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStream_t st, bool pop) {
     const uint32_t n32 = (uint32_t)n;
     const pair_store ps = c->batch_pairs();
     HIPCHK(hipEventRecord(c->ev[1], st));
@@ -551,7 +568,7 @@ static int run_pairs(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStrea
     if (fork || fork_sig) HIPCHK(hipStreamWaitEvent(c->side, c->ev[1], 0));
     if (fork && sd != c->side) HIPCHK(hipStreamWaitEvent(sd, c->ev[1], 0));
     // ---- hashing (caller's stream)
-    launch_hash_map(c, d_sets, n32, st);
+    launch_hash_map(c, d_sets, n32, st, pop);
     HIPCHK(hipEventRecord(c->ev_hm, st));
     launch_hash_clear(c, ps, n32, st);
     HIPCHK(hipEventRecord(c->ev[2], st));
@@ -648,7 +665,7 @@ static int ensure_lanes(mi355_bls_ctx* c, int want) {
 // boundary cuts is carried over (k_blind).  src_dev: the shard's records in device memory, or src_host: in host memory
 // (staged slice by slice through d_sets).  After a sliced call fetch_stage(0..3) shows the LAST slice.
 static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* src_host, size_t n_total, uint32_t nchunks, uint32_t chunk_lo, uint32_t chunk_cnt,
-                     size_t tuple_base, size_t n, int serial, const uint8_t rnd[32], hipStream_t st) {
+                     size_t tuple_base, size_t n, int serial, const uint8_t rnd[32], hipStream_t st, bool pop = false) {
     (void)chunk_lo; (void)chunk_cnt;
     HIPCHK(hipSetDevice(c->device));
     if (c->fail_next_enqueue) {                                 // test hook: an enqueue failure after earlier shards of a multi-device call went out
@@ -669,7 +686,7 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
         const uint8_t* d = src_dev ? src_dev : c->d_sets;
         if (!src_dev) HIPCHK(hipMemcpyAsync(c->d_sets, src_host, n * 320, hipMemcpyHostToDevice, st));
         uint32_t c_lo = serial ? 0 : plan::chunk_of_tuple(n_total, nchunks, tuple_base), c_hi = serial ? 1 : plan::chunk_of_tuple(n_total, nchunks, tuple_base + n - 1) + 1;
-        return run_slice(c, c, d, n_total, nchunks, c_lo, c_hi - c_lo, tuple_base, n, serial, 0, 0, st, nullptr);
+        return run_slice(c, c, d, n_total, nchunks, c_lo, c_hi - c_lo, tuple_base, n, serial, 0, 0, st, nullptr, pop);
     }
     // ---- several slices: pipelined over the workspaces of this context and of up to two lanes, each on its own stream.  Slice i starts
     // when slice i - 1 (on another workspace) has finished hashing and its public-key multiplications, exactly as bench.py staggers the
@@ -709,7 +726,7 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
         }
         const uint8_t* d = src_dev ? src_dev + 320 * done : x->d_sets;
         if (!src_dev) HIPCHK(hipMemcpyAsync(x->d_sets, src_host + 320 * done, cnt * 320, hipMemcpyHostToDevice, sx));
-        int rc = run_slice(x, c, d, n_total, nchunks, c_lo, c_hi - c_lo, t0, cnt, serial, done, slice, sx, c->ev_blind[slice % 3]);
+        int rc = run_slice(x, c, d, n_total, nchunks, c_lo, c_hi - c_lo, t0, cnt, serial, done, slice, sx, c->ev_blind[slice % 3], pop);
         if (rc) {
             // earlier slices are still running on the lane streams and read the caller's records and this context's chain state: drain
             // them before the error goes back (the caller may free its buffers then); the error of the failed enqueue is what is reported
@@ -760,12 +777,12 @@ static int collect_timings(mi355_bls_ctx* c, int last_ev) {
 }
 
 // Enqueue a whole batch verification (nothing is waited for); the verdict lands in the context's pinned host words.
-static int verify_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, const uint8_t* h_sets, size_t n, const uint8_t rnd[32], int serial, hipStream_t st) {
+static int verify_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, const uint8_t* h_sets, size_t n, const uint8_t rnd[32], int serial, hipStream_t st, bool pop = false) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if ((!d_sets && !h_sets) || n == 0) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     uint32_t B = (uint32_t)(n < c->num_threads ? n : c->num_threads);
-    int rc = run_shard(c, d_sets, h_sets, n, B, 0, serial ? 1 : B, 0, n, serial, rnd, st);
+    int rc = run_shard(c, d_sets, h_sets, n, B, 0, serial ? 1 : B, 0, n, serial, rnd, st, pop);
     if (rc) return rc;
     launch_k_tail(c, st, c->d_L, c->d_states, 1, 2, c->d_gt, c->d_flags + 1, 144, 0);
     HIPCHK(hipEventRecord(c->ev[8], st));
@@ -794,10 +811,10 @@ static int verify_wait(mi355_bls_ctx* c) {
     c->timings[7] += fin;
     return (c->h_flags[0] == 0 && c->h_flags[1] == 1) ? 1 : 0;
 }
-static int verify_common(mi355_bls_ctx* c, const uint8_t* d_sets, const uint8_t* h_sets, size_t n, const uint8_t rnd[32], int serial, hipStream_t st) {
+static int verify_common(mi355_bls_ctx* c, const uint8_t* d_sets, const uint8_t* h_sets, size_t n, const uint8_t rnd[32], int serial, hipStream_t st, bool pop = false) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if (n == 0) return 0;                      // bls_batch_verifier.nim:137-139, :312-314
-    int rc = verify_enqueue(c, d_sets, h_sets, n, rnd, serial, st);
+    int rc = verify_enqueue(c, d_sets, h_sets, n, rnd, serial, st, pop);
     if (rc) return rc;
     return verify_wait(c);
 }
@@ -851,7 +868,7 @@ static int each_reserve(mi355_bls_ctx* c, size_t n, bool want_gt) {
     }
     return want_gt ? c->d_each_gt.reserve(n * 576, 0) : 0;
 }
-static int each_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, size_t n, uint8_t verdicts[], uint8_t* gt_out, hipStream_t st) {
+static int each_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, size_t n, uint8_t verdicts[], uint8_t* gt_out, hipStream_t st, bool pop = false) {
     if (!c) return MI355_BLS_ERR_ARG;
     if (n == 0) return 0;                      // nothing verified, nothing written
     if (!verdicts || (!d_src && !h_src)) return MI355_BLS_ERR_ARG;
@@ -869,7 +886,7 @@ static int each_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src
         const uint8_t* src = d_src ? d_src + done * 320 : c->d_sets;
         if (!d_src) HIPCHK(hipMemcpyAsync(c->d_sets, h_src + done * 320, m * 320, hipMemcpyHostToDevice, st));      // behind the last slice's kernels on the same stream
         const plan::each_plan p = plan::each_for(c->slots, c->coop, m32);
-        launch_hash_map(c, src, m32, st);                                  // H(msg_i) -> pair slot i, in the forms the batch path takes for m messages
+        launch_hash_map(c, src, m32, st, pop);                             // H(msg_i) -> pair slot i, in the forms the batch path takes for m messages
         launch_hash_clear(c, ps, m32, st);
         k_each_setup<<<p.setup_grid, WAVE, 0, st>>>(src, m32, ps.H, ps.P, ps.stride);
         launch_lines(ps, p.lines, st);
@@ -911,17 +928,17 @@ extern "C" int mi355_bls_debug_verify_each_gt(mi355_bls_ctx* c, const void* sets
 extern "C" int mi355_bls_debug_verify_each_passes(mi355_bls_ctx* c) { return c ? c->each_passes : MI355_BLS_ERR_ARG; }
 
 // batchVerify first; only a failing batch pays for the per-set pass
-static int locate_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, size_t n, const uint8_t rnd[32], uint8_t verdicts[], hipStream_t st) {
+static int locate_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, size_t n, const uint8_t rnd[32], uint8_t verdicts[], hipStream_t st, bool pop = false) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if (n == 0) return 0;
     if (!verdicts || (!d_src && !h_src)) return MI355_BLS_ERR_ARG;
-    int rc = verify_common(c, d_src, h_src, n, rnd, 0, st);
+    int rc = verify_common(c, d_src, h_src, n, rnd, 0, st, pop);
     if (rc < 0) return rc;
     if (rc == 1) {
         std::memset(verdicts, 1, n);
         return 1;
     }
-    rc = each_run(c, d_src, h_src, n, verdicts, nullptr, st);
+    rc = each_run(c, d_src, h_src, n, verdicts, nullptr, st, pop);
     return rc < 0 ? rc : 0;
 }
 extern "C" int mi355_bls_batch_verify_locate(mi355_bls_ctx* c, const void* sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[]) {
@@ -929,6 +946,91 @@ extern "C" int mi355_bls_batch_verify_locate(mi355_bls_ctx* c, const void* sets,
 }
 extern "C" int mi355_bls_batch_verify_locate_device(mi355_bls_ctx* c, const void* d_sets, size_t n, const uint8_t rnd[32], uint8_t verdicts[], void* stream) {
     return locate_run(c, (const uint8_t*)d_sets, nullptr, n, rnd, verdicts, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// popVerify for a table of keys (bls_sig_min_pubkey.nim:60-74: coreVerifyNoGroupCheck(publicKey, compress(publicKey), proof, DST_POP)), the check
+// the reference's proof-taking overloads (:104, :148, :220-225) loop over key by key.  n keys and n proofs become n records in the staging
+// buffer (k_pop_records); the per-set pass, the blinded batch pass and the locate form then run on them with `pop` set, i.e. with the PoP
+// forms of the hash-map kernels and nothing else changed: slicing, stages, verdict bytes as for SignatureSets.
+// ------------------------------------------------------------------------------------------
+// keys | proofs (host memory when `host`, staged through d_comp; else device memory) -> n records at c->d_sets, enqueued on `st`
+static int pop_stage(mi355_bls_ctx* c, const void* pks, const void* proofs, size_t n, bool host, hipStream_t st) {
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const uint8_t *dk = (const uint8_t*)pks, *dp = (const uint8_t*)proofs;
+    if (host) {
+        HIPCHK(hipMemcpyAsync(c->d_comp, pks, n * 96, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(c->d_comp + c->cap_io * 96, proofs, n * 192, hipMemcpyHostToDevice, st));
+        dk = c->d_comp, dp = c->d_comp + c->cap_io * 96;
+    }
+    k_pop_records<<<plan::pop_records_grid(n), 256, 0, st>>>(reinterpret_cast<const uint32_t*>(dk), reinterpret_cast<const uint32_t*>(dp), n,
+                                                             reinterpret_cast<uint32_t*>(c->d_sets.p));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+static int pop_each(mi355_bls_ctx* c, const void* pks, const void* proofs, size_t n, uint8_t verdicts[], uint8_t* gt_out, bool host, hipStream_t st) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;                      // nothing verified, nothing written
+    if (!pks || !proofs || !verdicts || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (int rc = pop_stage(c, pks, proofs, n, host, st)) return rc;
+    return each_run(c, c->d_sets, nullptr, n, verdicts, gt_out, st, true);
+}
+static int pop_batch(mi355_bls_ctx* c, const void* pks, const void* proofs, size_t n, const uint8_t rnd[32], uint8_t* verdicts, bool locate, bool host, hipStream_t st) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!pks || !proofs || (locate && !verdicts) || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (int rc = pop_stage(c, pks, proofs, n, host, st)) return rc;
+    return locate ? locate_run(c, c->d_sets, nullptr, n, rnd, verdicts, st, true) : verify_common(c, c->d_sets, nullptr, n, rnd, 0, st, true);
+}
+extern "C" int mi355_bls_pop_verify_each(mi355_bls_ctx* c, const void* pks96, const void* proofs192, size_t n, uint8_t verdicts[]) {
+    return pop_each(c, pks96, proofs192, n, verdicts, nullptr, true, nullptr);
+}
+extern "C" int mi355_bls_pop_verify_each_device(mi355_bls_ctx* c, const void* d_pks96, const void* d_proofs192, size_t n, uint8_t verdicts[], void* stream) {
+    return pop_each(c, d_pks96, d_proofs192, n, verdicts, nullptr, false, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_debug_pop_verify_each_gt(mi355_bls_ctx* c, const void* pks96, const void* proofs192, size_t n, uint8_t verdicts[], uint8_t* gt_out) {
+    if (!gt_out) return MI355_BLS_ERR_ARG;
+    return pop_each(c, pks96, proofs192, n, verdicts, gt_out, true, nullptr);
+}
+extern "C" int mi355_bls_batch_pop_verify(mi355_bls_ctx* c, const void* pks96, const void* proofs192, size_t n, const uint8_t rnd[32]) {
+    return pop_batch(c, pks96, proofs192, n, rnd, nullptr, false, true, nullptr);
+}
+extern "C" int mi355_bls_batch_pop_verify_device(mi355_bls_ctx* c, const void* d_pks96, const void* d_proofs192, size_t n, const uint8_t rnd[32], void* stream) {
+    return pop_batch(c, d_pks96, d_proofs192, n, rnd, nullptr, false, false, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_batch_pop_verify_locate(mi355_bls_ctx* c, const void* pks96, const void* proofs192, size_t n, const uint8_t rnd[32], uint8_t verdicts[]) {
+    return pop_batch(c, pks96, proofs192, n, rnd, verdicts, true, true, nullptr);
+}
+extern "C" int mi355_bls_batch_pop_verify_locate_device(mi355_bls_ctx* c, const void* d_pks96, const void* d_proofs192, size_t n, const uint8_t rnd[32],
+                                                        uint8_t verdicts[], void* stream) {
+    return pop_batch(c, d_pks96, d_proofs192, n, rnd, verdicts, true, false, (hipStream_t)stream);
+}
+// rawFromPublic / serialize for n keys (bls_sig_io.nim:203-211).  The device form leaves the bytes in device memory and returns when they are there.
+extern "C" int mi355_bls_compress_public_keys_device(mi355_bls_ctx* c, const void* d_pks96, size_t n, void* d_out48, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!d_pks96 || !d_out48 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    k_compress_pks<<<plan::waves_for((uint32_t)n), WAVE, 0, (hipStream_t)stream>>>((const uint8_t*)d_pks96, (uint32_t)n, (uint32_t*)d_out48);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+extern "C" int mi355_bls_compress_public_keys(mi355_bls_ctx* c, const void* pks96, size_t n, uint8_t out48[]) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!pks96 || !out48 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(c->d_comp, pks96, n * 96, hipMemcpyHostToDevice, nullptr));
+    int rc = mi355_bls_compress_public_keys_device(c, c->d_comp, n, c->d_comp + c->cap_io * 96, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(out48, c->d_comp + c->cap_io * 96, n * 48, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2318,6 +2420,52 @@ extern "C" int mi355_bls_sign_sets(mi355_bls_ctx* c, const uint8_t* sks32, const
     if (rc < 0) return rc;
     HIPCHK(hipMemcpy(out_sets, c->d_sets, n * 320, hipMemcpyDeviceToHost));
     HIPCHK(hipMemsetAsync(c->d_comp, 0, n * 32, nullptr));          // do not leave the scalars in the staging buffer
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return rc;
+}
+
+// popProve (bls_sig_min_pubkey.nim:34-58) for n secret keys: the keys by k_sign_pk (into the staging records, with zero messages), the proofs by
+// k_pop_prove_sig, which also packs the keys.  Variable time: test / bench input generation only, like the signer above.
+extern "C" int mi355_bls_pop_prove_device(mi355_bls_ctx* c, const void* d_sks32, size_t n, void* d_out_pks96, void* d_out_proofs192, void* stream, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 1;
+    if (!d_sks32 || !d_out_pks96 || !d_out_proofs192 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rcr = io_reserve(c, n)) return rcr;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t* d_zero = c->d_comp + c->cap_io * 96;                  // n x 32 zero bytes: k_sign_pk copies a message into every record.  (The host form's
+                                                                   // proofs land here afterwards, behind k_sign_pk on the same stream.)
+    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
+    HIPCHK(hipMemsetAsync(d_zero, 0, n * 32, st));
+    HIPCHK(hipEventRecord(c->ev[0], st));
+    uint32_t nb = plan::waves_for((uint32_t)n);
+    k_sign_pk<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, d_zero, (uint32_t)n, c->d_sets, c->d_status, c->d_flags);
+    k_pop_prove_sig<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, c->d_sets, (uint32_t)n, c->dst_pop, (uint8_t*)d_out_pks96, (uint8_t*)d_out_proofs192);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev[1], st));
+    uint32_t fl[4];
+    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
+    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < 8; i++) c->timings[i] = 0;
+    HIPCHK(hipEventElapsedTime(&c->timings[0], c->ev[0], c->ev[1]));
+    c->timings[7] = c->timings[0];
+    return fl[2] ? 0 : 1;
+}
+extern "C" int mi355_bls_pop_prove(mi355_bls_ctx* c, const uint8_t* sks32, size_t n, void* out_pks96, void* out_proofs192, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 1;
+    if (!sks32 || !out_pks96 || !out_proofs192 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (int rcr = io_reserve(c, n)) return rcr;
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t* d_sk = c->d_comp + c->cap_io * 288;                   // d_comp (cap_io x 320 B): keys out at 0, proofs out at cap_io x 96, the scalars behind them
+    HIPCHK(hipMemcpyAsync(d_sk, sks32, n * 32, hipMemcpyHostToDevice, nullptr));
+    int rc = mi355_bls_pop_prove_device(c, d_sk, n, c->d_comp, c->d_comp + c->cap_io * 96, nullptr, status);
+    if (rc < 0) return rc;
+    HIPCHK(hipMemcpy(out_pks96, c->d_comp, n * 96, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_proofs192, c->d_comp + c->cap_io * 96, n * 192, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemsetAsync(d_sk, 0, n * 32, nullptr));               // do not leave the scalars in the staging buffer
     HIPCHK(hipStreamSynchronize(nullptr));
     return rc;
 }

@@ -315,48 +315,89 @@ __global__ void __launch_bounds__(WAVE) k_blind_many(const uint8_t* __restrict__
 // each other's issue gaps; k_hash_clear: one lane per message adds the two points and clears the cofactor
 // (G2 arithmetic: needs the full register file).
 // t: the (message, u) pair this lane maps; store: whether it writes the result (the row form below computes every pair in sixteen lanes)
-template <class Pow>
-__device__ __forceinline__ void hash_map_body_with(const uint8_t* __restrict__ sets, uint32_t t, bool store, const dst_t& dst, const xmd32_consts& xc, uint4* __restrict__ M,
-                                                   size_t mstride, const Pow& pw) {
-    const uint32_t i = t >> 1;
-    const uint32_t* mw = reinterpret_cast<const uint32_t*>(sets + (size_t)i * 320 + 96);
-    fp2 u0, u1;
-    if (xc.valid) {                                   // wave-uniform: constants of this DST prepared on the host
-        uint32_t mbe[8];
+// msg: where the message of a record comes from and how it is hashed to the two field elements - a functor, like `pw`:
+//   msg_from_record   the 32 bytes at offset 96 of the record, under the context's DST (every SignatureSet path)
+//   msg_from_key      popVerify (bls_sig_min_pubkey.nim:60-74): the message is the record's own public key in its 48-byte compressed form
+//                     (g1_compress, computed in the lane: two multiplications and a comparison), under DST_POP; the record's message slot is not read
+struct msg_from_record {
+    const dst_t& dst;
+    const xmd32_consts& xc;
+    __device__ __forceinline__ void operator()(fp2& u0, fp2& u1, const uint8_t* __restrict__ rec) const {
+        const uint32_t* mw = reinterpret_cast<const uint32_t*>(rec + 96);
+        if (xc.valid) {                                   // wave-uniform: constants of this DST prepared on the host
+            uint32_t mbe[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) mbe[j] = bswap32(mw[j]);
-        hash_to_field_fp2x2_msg32(u0, u1, mbe, xc);
-    } else {
-        uint8_t msg[32];
+            for (int j = 0; j < 8; j++) mbe[j] = bswap32(mw[j]);
+            hash_to_field_fp2x2_msg32(u0, u1, mbe, xc);
+        } else {
+            uint8_t msg[32];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            uint32_t w = mw[j];
-            msg[4 * j] = (uint8_t)w;
-            msg[4 * j + 1] = (uint8_t)(w >> 8);
-            msg[4 * j + 2] = (uint8_t)(w >> 16);
-            msg[4 * j + 3] = (uint8_t)(w >> 24);
+            for (int j = 0; j < 8; j++) {
+                uint32_t w = mw[j];
+                msg[4 * j] = (uint8_t)w;
+                msg[4 * j + 1] = (uint8_t)(w >> 8);
+                msg[4 * j + 2] = (uint8_t)(w >> 16);
+                msg[4 * j + 3] = (uint8_t)(w >> 24);
+            }
+            hash_to_field_fp2x2(u0, u1, msg, 32, dst.b, dst.len);
         }
-        hash_to_field_fp2x2(u0, u1, msg, 32, dst.b, dst.len);
     }
+};
+struct msg_from_key {
+    const dst_t& dst;
+    const xmd48_consts& xc;
+    __device__ __forceinline__ void operator()(fp2& u0, fp2& u1, const uint8_t* __restrict__ rec) const {
+        uint32_t mbe[12];
+        g1_compress_words(mbe, ld_g1a_blst(reinterpret_cast<const uint32_t*>(rec)));
+        if (xc.valid) {                                   // wave-uniform, as above
+            hash_to_field_fp2x2_msg48(u0, u1, mbe, xc);
+        } else {
+            uint8_t msg[48];
+#pragma unroll
+            for (int j = 0; j < 12; j++) {
+                msg[4 * j] = (uint8_t)(mbe[j] >> 24);
+                msg[4 * j + 1] = (uint8_t)(mbe[j] >> 16);
+                msg[4 * j + 2] = (uint8_t)(mbe[j] >> 8);
+                msg[4 * j + 3] = (uint8_t)mbe[j];
+            }
+            hash_to_field_fp2x2(u0, u1, msg, 48, dst.b, dst.len);
+        }
+    }
+};
+template <class Msg, class Pow>
+__device__ __forceinline__ void hash_map_body_with(const uint8_t* __restrict__ sets, uint32_t t, bool store, const Msg& msg, uint4* __restrict__ M, size_t mstride,
+                                                   const Pow& pw) {
+    const uint32_t i = t >> 1;
+    fp2 u0, u1;
+    msg(u0, u1, sets + (size_t)i * 320);
     fp2 u = fp2_select((t & 1) != 0, u1, u0);
     const g2_jac q = iso3_g2(sswu_g2_with(u, pw));
     if (store) soa_st_g2(M, mstride, t, q);
 }
-__device__ __forceinline__ void hash_map_body(const uint8_t* __restrict__ sets, uint32_t n, const dst_t& dst, const xmd32_consts& xc, uint4* __restrict__ M, size_t mstride) {
+template <class Msg>
+__device__ __forceinline__ void hash_map_body(const uint8_t* __restrict__ sets, uint32_t n, const Msg& msg, uint4* __restrict__ M, size_t mstride) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if ((t >> 1) >= n) return;
-    hash_map_body_with(sets, t, true, dst, xc, M, mstride, pow_in_lane{});
+    hash_map_body_with(sets, t, true, msg, M, mstride, pow_in_lane{});
 }
 __global__ void __launch_bounds__(WAVE, 2) k_hash_map(const uint8_t* __restrict__ sets, uint32_t n, dst_t dst, xmd32_consts xc, uint4* __restrict__ M,
                                                          size_t mstride) {
-    hash_map_body(sets, n, dst, xc, M, mstride);
+    hash_map_body(sets, n, msg_from_record{dst, xc}, M, mstride);
+}
+__global__ void __launch_bounds__(WAVE, 2) k_hash_map_pop(const uint8_t* __restrict__ sets, uint32_t n, dst_t dst, xmd48_consts xc, uint4* __restrict__ M,
+                                                             size_t mstride) {
+    hash_map_body(sets, n, msg_from_key{dst, xc}, M, mstride);
 }
 // The same kernel for grids of at most one wave per SIMD (latency mode, up to 32 768 messages): the whole register file (nothing spills around the
 // square-root chains) and one wave per SIMD guaranteed - the dispatcher packs the 256-register form two per SIMD before every SIMD has a wave, and a
 // wave that shares its SIMD takes 1.4 x as long.
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_hash_map_spread(const uint8_t* __restrict__ sets, uint32_t n, dst_t dst, xmd32_consts xc, uint4* __restrict__ M, size_t mstride) {
-    hash_map_body(sets, n, dst, xc, M, mstride);
+    hash_map_body(sets, n, msg_from_record{dst, xc}, M, mstride);
+}
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_hash_map_spread_pop(const uint8_t* __restrict__ sets, uint32_t n, dst_t dst, xmd48_consts xc, uint4* __restrict__ M, size_t mstride) {
+    hash_map_body(sets, n, msg_from_key{dst, xc}, M, mstride);
 }
 // Small batches (at most one wave per SIMD at FOUR pairs per wave): a (message, u) pair per DPP row - the sixteen lanes of a row run the same hashing and
 // map arithmetic, and the two square-root exponentiations, 924 dependent products that are most of this kernel's time, run ALONG the row (rowfp.hpp:
@@ -378,15 +419,27 @@ struct pow_per_row {
         return fp_reduce(out);
     }
 };
+template <class Msg>
+__device__ __forceinline__ void hash_map_rows_body(const uint8_t* __restrict__ sets, uint32_t n, const Msg& msg, uint4* __restrict__ M, size_t mstride,
+                                                   uint32_t* powtab) {
+    const uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 4);
+    const bool live = t < 2 * n;
+    const row_ctx RC = row_ctx_make();
+    hash_map_body_with(sets, live ? t : 0u, live && (threadIdx.x & 15u) == 0, msg, M, mstride, pow_per_row{RC, powtab + threadIdx.x});
+}
 #endif
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_hash_map_rows(const uint8_t* __restrict__ sets, uint32_t n, dst_t dst, xmd32_consts xc, uint4* __restrict__ M, size_t mstride) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t powtab[16 * WAVE];
-    const uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 4);
-    const bool live = t < 2 * n;
-    const row_ctx RC = row_ctx_make();
-    hash_map_body_with(sets, live ? t : 0u, live && (threadIdx.x & 15u) == 0, dst, xc, M, mstride, pow_per_row{RC, powtab + threadIdx.x});
+    hash_map_rows_body(sets, n, msg_from_record{dst, xc}, M, mstride, powtab);
+#endif
+}
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_hash_map_rows_pop(const uint8_t* __restrict__ sets, uint32_t n, dst_t dst, xmd48_consts xc, uint4* __restrict__ M, size_t mstride) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t powtab[16 * WAVE];
+    hash_map_rows_body(sets, n, msg_from_key{dst, xc}, M, mstride, powtab);
 #endif
 }
 // base point of the doubling chains parked in three LDS slots (21 KB of the 40 KB a wave may use)
@@ -2381,6 +2434,49 @@ __global__ void __launch_bounds__(WAVE) k_sign_sig(const uint8_t* __restrict__ s
     fp2 x = fp2_select(ok, fp2_mul(a.x, zi2), fp2_zero()), y = fp2_select(ok, fp2_mul(a.y, fp2_mul(zi2, zi)), fp2_zero());
     uint32_t* o = reinterpret_cast<uint32_t*>(sets + (size_t)i * 320) + 32;
     st_fp_blst(o, x.c0); st_fp_blst(o + 12, x.c1); st_fp_blst(o + 24, y.c0); st_fp_blst(o + 36, y.c1);
+}
+
+// popProve (bls_sig_min_pubkey.nim:34-58): proof = affine([sk] hash_to_g2(compress(pk), 48, DST_POP)), pk where k_sign_pk left it (offset 0 of
+// record i); the key and the proof go out as two packed arrays.  Variable time like k_sign_sig: test / bench input generation only.
+__global__ void __launch_bounds__(WAVE) k_pop_prove_sig(const uint8_t* __restrict__ sks, const uint8_t* __restrict__ sets, uint32_t n, dst_t dst,
+                                                        uint8_t* __restrict__ out_pks, uint8_t* __restrict__ out_proofs) {
+    uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n) return;
+    uint32_t kk[8];
+    bool ok = sk_load_check(kk, sks + (size_t)i * 32);
+    const uint32_t* pkw = reinterpret_cast<const uint32_t*>(sets + (size_t)i * 320);
+    uint32_t* opk = reinterpret_cast<uint32_t*>(out_pks + (size_t)i * 96);
+    for (int j = 0; j < 24; j++) opk[j] = pkw[j];                     // zeros for a refused scalar (k_sign_pk)
+    uint8_t msg[48];
+    g1_compress(msg, ld_g1a_blst(pkw));
+    g2_jac h = hash_to_g2(msg, 48, dst.b, dst.len);
+    g2_jac a = jac_mul_256_jac(h, kk);
+    fp2 zi = fp2_inv(a.z), zi2 = fp2_sqr(zi);
+    fp2 x = fp2_select(ok, fp2_mul(a.x, zi2), fp2_zero()), y = fp2_select(ok, fp2_mul(a.y, fp2_mul(zi2, zi)), fp2_zero());
+    uint32_t* o = reinterpret_cast<uint32_t*>(out_proofs + (size_t)i * 192);
+    st_fp_blst(o, x.c0); st_fp_blst(o + 12, x.c1); st_fp_blst(o + 24, y.c0); st_fp_blst(o + 36, y.c1);
+}
+
+// ------------------------------------------------------------------------------------------
+// popVerify for a table of keys (mi355_bls_pop_verify_each / mi355_bls_batch_pop_verify): n keys (96-byte blst_p1_affine images) and n proofs
+// (192-byte blst_p2_affine images) become n 320-byte records  key | 32 zero bytes | proof; the PoP forms of the hash-map kernels hash the
+// key itself, and everything behind them takes the records as any SignatureSet (nothing there reads the message slot).  One thread per word.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_pop_records(const uint32_t* __restrict__ pks, const uint32_t* __restrict__ proofs, uint64_t n, uint32_t* __restrict__ recs) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n * 80) return;
+    const uint64_t i = j / 80;
+    const uint32_t w = (uint32_t)(j % 80);
+    recs[j] = w < 24 ? pks[i * 24 + w] : w < 32 ? 0u : proofs[i * 48 + (w - 32)];
+}
+// rawFromPublic / serialize (bls_sig_io.nim:203-211: blst_p1_affine_compress) for n keys: 96-byte images in, 48 bytes each out
+__global__ void __launch_bounds__(WAVE) k_compress_pks(const uint8_t* __restrict__ pks, uint32_t n, uint32_t* __restrict__ out) {
+    uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n) return;
+    uint32_t be[12];
+    g1_compress_words(be, ld_g1a_blst(reinterpret_cast<const uint32_t*>(pks + (size_t)i * 96)));
+#pragma unroll
+    for (int j = 0; j < 12; j++) out[(size_t)i * 12 + j] = bswap32(be[j]);
 }
 
 // shard state for the device-resident exchange: 576-byte committed state, then the ok word (1 = no update failed), zero padding

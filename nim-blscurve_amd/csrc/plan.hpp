@@ -72,6 +72,12 @@ inline hash_map_plan hash_map_for(uint32_t slots, bool coop, uint32_t n32) {
     return {HASH_MAP_PLAIN, waves};
 }
 
+// popVerify's records (k_pop_records: a lane per word of n 80-word records, workgroups of four waves).  The PoP hash-map kernels take
+// hash_map_for's plan as it is: same forms, same hand-over sizes.  POP_MAX_KEYS: what a context's capacity is bounded by, too.
+constexpr size_t POP_MAX_KEYS = (size_t)1 << 30;
+constexpr uint32_t POP_RECORD_THREADS = 256;
+inline uint32_t pop_records_grid(size_t n) { return (uint32_t)((n * 80 + POP_RECORD_THREADS - 1) / POP_RECORD_THREADS); }
+
 // cofactor clearing of n32 mapped point pairs: the engine (then k_clear_fix) or k_hash_clear
 inline stage clear_for(uint32_t slots, bool coop, uint32_t n32) {
     return coop && n32 <= team_clear_max(slots) ? team_stage(slots, n32) : one_lane_stage(n32);
