@@ -524,6 +524,30 @@ int mi355_bls_debug_g2_clear_cofactor(mi355_bls_ctx* ctx, const uint8_t* in_pair
  * domain separation tag (1 .. 64 bytes): holds the device against published hash-to-curve vectors (RFC 9380 J.10.1), whose DST is not the scheme's. */
 int mi355_bls_debug_hash_to_g2(mi355_bls_ctx* ctx, const uint8_t* msg, size_t msg_len, const uint8_t* dst, size_t dst_len, uint8_t out_p2[288]);
 
+/* TEST HOOK: the device's field arithmetic bodies on CHOSEN operands.  An operand is a RAW fp image: 14 signed 28-bit limbs in 14 uint32 words,
+ * the in-register form (csrc/fp.hpp), not blst bytes; results come back raw as well (14 words each), so that a test can check the documented
+ * output bounds.  a, b, out: host memory, n <= max_sets operands each.  The caller keeps every operand inside the contract of the operation
+ * (tests/fp_operands.py; tests/test_fp_operands_emu.py proves it on the bounds-tracked CPU build).
+ *   lane operations (one operand pair per lane, the out-of-line bodies the product calls, in a kernel compiled for 256 registers like k_hash_map):
+ *     FP_MUL a b, FP_SQR a, FP_SQR_N1 / FP_SQR_N4 fp_sqr_n(a, 1 / 4), FP_REDUCE a, FP_INV a, FP_POW fp_recip_sqrt_pow(a) (the assembly body);
+ *     FP_DOT2: a and b hold TWO images per result, out[i] = a[2i] b[2i] + a[2i+1] b[2i+1];
+ *     PRED: word 0 of out[i] = fp_is_zero(a[i]) | fp_eq(a[i], b[i]) << 1 | fp2_sgn0((a[i], b[i])) << 2, words 1..13 zero
+ *   row operations (a wave with row constants and an LDS power table, as k_hash_map_rows and k_hash_one set it up):
+ *     ROW_MUL a b / ROW_SQR a (four operands per wave, one per DPP row), POW_PER_ROW (k_hash_map_rows' form: four operands per wave),
+ *     POW_TWO_ROWS (k_hash_one's form: the operands of lanes 0 and 1 of a wave); the two POW forms return a^((p-3)/4) as the functor does. */
+enum {
+    MI355_BLS_FPOP_FP_MUL = 0, MI355_BLS_FPOP_FP_SQR = 1, MI355_BLS_FPOP_FP_SQR_N1 = 2, MI355_BLS_FPOP_FP_SQR_N4 = 3, MI355_BLS_FPOP_FP_DOT2 = 4,
+    MI355_BLS_FPOP_FP_REDUCE = 5, MI355_BLS_FPOP_FP_INV = 6, MI355_BLS_FPOP_FP_POW = 7, MI355_BLS_FPOP_PRED = 8,
+    MI355_BLS_FPOP_ROW_MUL = 16, MI355_BLS_FPOP_ROW_SQR = 17, MI355_BLS_FPOP_POW_PER_ROW = 18, MI355_BLS_FPOP_POW_TWO_ROWS = 19
+};
+int mi355_bls_debug_fp_op(mi355_bls_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
+
+/* TEST HOOK: the SSWU map + 3-isogeny of the batch path on CHOSEN field elements: us = n pairs (u0, u1) of Fp2 elements as raw images
+ * (4 x 14 words per pair), out_p2 = 2n blst_p2 images (Jacobian, 288 B): the mapped points before cofactor clearing.  The kernel is the
+ * form hash_map_for names for this context and n (rows / spread / plain), with the body of k_hash_map* and the field elements loaded where
+ * those hash a message. */
+int mi355_bls_debug_map_to_g2(mi355_bls_ctx* ctx, const uint32_t* us, size_t n, uint8_t* out_p2);
+
 /* Test hooks (no reference counterpart).  debug_fail_next_enqueue: the next batch / shard enqueue on this context fails with
  * MI355_BLS_ERR_HIP before touching the device (exercises the multi-device driver's clean-up path).  debug_multi_enqueue_us:
  * host time in microseconds, counted from the start of the last mi355_bls_batch_verify_multi* call of this thread, at which each

@@ -161,6 +161,8 @@ def lib():
         L.mi355_bls_last_fold_form.argtypes = [vp]
         L.mi355_bls_debug_g2_clear_cofactor.argtypes = [vp, cp, sz, cp]
         L.mi355_bls_debug_hash_to_g2.argtypes = [vp, cp, sz, cp, sz, cp]
+        L.mi355_bls_debug_fp_op.argtypes = [vp, i32, cp, cp, sz, cp]
+        L.mi355_bls_debug_map_to_g2.argtypes = [vp, cp, sz, cp]
         L.mi355_bls_debug_multi_enqueue_us.argtypes = [ctypes.POINTER(ctypes.c_float), sz]
         L.mi355_bls_debug_multi_enqueue_us.restype = sz
         L.mi355_bls_fetch_stage.argtypes = [vp, i32, vp, sz]
@@ -419,6 +421,35 @@ def verifyEachValues(cache, input_):
 def verifyEachPasses(cache):
     """per-set passes the cache's context has made (test hook)"""
     return _check(lib().mi355_bls_debug_verify_each_passes(cache._h))
+
+
+FPOP = {"fp_mul": 0, "fp_sqr": 1, "fp_sqr_n1": 2, "fp_sqr_n4": 3, "fp_dot2": 4, "fp_reduce": 5, "fp_inv": 6, "fp_pow": 7, "pred": 8,
+        "row_mul": 16, "row_sqr": 17, "pow_per_row": 18, "pow_two_rows": 19}      # MI355_BLS_FPOP_*
+FP_IMAGE_BYTES = 56                   # a raw fp image: 14 uint32 words, signed 28-bit limbs
+
+
+def debugFpOp(cache, op, a, b=None):
+    """Test hook (mi355_bls_debug_fp_op): the device's field arithmetic bodies on chosen raw images.  a, b: bytes of n images each (FPOP "fp_dot2":
+    2n each); b defaults to a.  -> the bytes of n raw results (the predicate word of "pred" in word 0 of each)."""
+    b = a if b is None else b
+    per = FP_IMAGE_BYTES * (2 if op == "fp_dot2" else 1)
+    if len(a) % per or len(a) != len(b):
+        raise ValueError("operands must be the same number of 56-byte images")
+    n = len(a) // per
+    out = ctypes.create_string_buffer(max(n, 1) * FP_IMAGE_BYTES)
+    _check(lib().mi355_bls_debug_fp_op(cache._h, FPOP[op], bytes(a), bytes(b), n, out))
+    return out.raw
+
+
+def debugMapToG2(cache, us):
+    """Test hook (mi355_bls_debug_map_to_g2): us = bytes of n pairs (u0, u1) of Fp2 elements as raw images (224 bytes per pair) -> the bytes of the 2n
+    mapped points (288-byte Jacobian images), by the form of the map kernel the batch path would take for this cache and n."""
+    if len(us) % (4 * FP_IMAGE_BYTES):
+        raise ValueError("us must be pairs of Fp2 elements: 224 bytes each")
+    n = len(us) // (4 * FP_IMAGE_BYTES)
+    out = ctypes.create_string_buffer(max(n, 1) * 576)
+    _check(lib().mi355_bls_debug_map_to_g2(cache._h, bytes(us), n, out))
+    return out.raw
 
 
 def batchVerifyLocate(cache, input_, secureRandomBytes):

@@ -406,6 +406,57 @@ extern "C" int mi355_bls_debug_hash_to_g2(mi355_bls_ctx* c, const uint8_t* msg, 
     return 0;
 }
 
+// TEST HOOK: out[i] = op(a[i], b[i]) on raw fp images (14 words each, host memory) through the device's own arithmetic bodies: k_debug_fp_lane for the
+// lane operations, k_debug_fp_rows for the DPP row forms (see the header for the codes and FP_DOT2's two images per operand)
+extern "C" int mi355_bls_debug_fp_op(mi355_bls_ctx* c, int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+    if (!c || !a || !b || !out || n == 0 || n > c->cap) return MI355_BLS_ERR_ARG;
+    const bool lane = op >= MI355_BLS_FPOP_FP_MUL && op <= MI355_BLS_FPOP_PRED, rows = op >= MI355_BLS_FPOP_ROW_MUL && op <= MI355_BLS_FPOP_POW_TWO_ROWS;
+    if (!lane && !rows) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t in_bytes = n * FP_N * 4 * (op == MI355_BLS_FPOP_FP_DOT2 ? 2 : 1), out_bytes = n * FP_N * 4;
+    dev_buf<uint32_t> d_a, d_b, d_out;
+    if (int rc = d_a.alloc(in_bytes)) return rc;
+    if (int rc = d_b.alloc(in_bytes)) return rc;
+    if (int rc = d_out.alloc(out_bytes)) return rc;
+    HIPCHK(hipMemcpy(d_a, a, in_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_b, b, in_bytes, hipMemcpyHostToDevice));
+    const uint32_t n32 = (uint32_t)n;
+    if (lane)
+        k_debug_fp_lane<<<plan::waves_for(n32), WAVE>>>(op, d_a, d_b, n32, d_out);
+    else
+        k_debug_fp_rows<<<op == MI355_BLS_FPOP_POW_TWO_ROWS ? (n32 + 1) / 2 : (n32 + 3) / 4, WAVE>>>(op, d_a, d_b, n32, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));             // blocking: the buffers are idle when they go
+    return 0;
+}
+
+// TEST HOOK: n pairs (u0, u1) of Fp2 elements as raw images -> the 2n mapped points iso3(sswu(u)) (Jacobian blst_p2 images), through the map's body in
+// the form the batch path would launch for this context and n: hash_map_for's plan and grid, the kernels' launch bounds, d_M as the destination
+extern "C" int mi355_bls_debug_map_to_g2(mi355_bls_ctx* c, const uint32_t* us, size_t n, uint8_t* out_p2) {
+    if (!c || !us || !out_p2 || n == 0 || n > c->cap) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<uint8_t> rec(n * 320, 0);                                        // a "record" per message, as hash_map_body addresses them: the four images, then padding
+    for (size_t i = 0; i < n; i++) std::memcpy(rec.data() + i * 320, us + i * 4 * FP_N, 4 * FP_N * 4);
+    dev_buf<uint8_t> d_us;
+    dev_buf<uint32_t> d_out;
+    if (int rc = d_us.alloc(n * 320)) return rc;
+    if (int rc = d_out.alloc(2 * n * 288)) return rc;
+    HIPCHK(hipMemcpy(d_us, rec.data(), n * 320, hipMemcpyHostToDevice));
+    const uint32_t n32 = (uint32_t)n;
+    const plan::hash_map_plan p = plan::hash_map_for(c->slots, c->coop, n32);
+    switch (p.form) {
+        case plan::HASH_MAP_ROWS: k_debug_map_rows<<<p.grid, WAVE>>>(d_us, n32, c->d_M, c->mstride); break;
+        case plan::HASH_MAP_SPREAD: k_debug_map_spread<<<p.grid, WAVE>>>(d_us, n32, c->d_M, c->mstride); break;
+        case plan::HASH_MAP_PLAIN: k_debug_map<<<p.grid, WAVE>>>(d_us, n32, c->d_M, c->mstride); break;
+    }
+    k_export_g2<<<plan::waves_for(2 * n32), WAVE>>>(c->d_M, c->mstride, 2 * n32, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out_p2, d_out, 2 * n * 288, hipMemcpyDeviceToHost));        // blocking, as above
+    return 0;
+}
+
 extern "C" int mi355_bls_ctx_set_num_threads(mi355_bls_ctx* c, uint32_t nt) {
     if (!c || nt == 0) return MI355_BLS_ERR_ARG;
     c->num_threads = nt;

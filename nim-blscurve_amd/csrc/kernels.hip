@@ -623,6 +623,95 @@ struct pow_two_rows {
         return fp_reduce(out);
     }
 };
+// ------------------------------------------------------------------------------------------
+// Test entries: the arithmetic bodies above on CHOSEN operands (mi355_bls_debug_fp_op, mi355_bls_debug_map_to_g2).  On the batch path they only ever
+// see what SHA-256 or a point formula produces - uniformly random, canonical field elements; these kernels hand them raw images (14 words per Fp
+// value, the in-register form) and give back what they return, unreduced.  The caller keeps the operands inside each body's contract.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ fp ld_raw_fp(const uint32_t* __restrict__ w) {
+    fp r;
+#pragma unroll
+    for (int i = 0; i < FP_N; i++) r.l[i] = w[i];
+    return r;
+}
+__device__ __forceinline__ void st_raw_fp(uint32_t* __restrict__ w, const fp& r) {
+#pragma unroll
+    for (int i = 0; i < FP_N; i++) w[i] = r.l[i];
+}
+// one operand pair per lane through the out-of-line bodies the product calls; 256 registers like k_hash_map, so that the exponentiation's assembly
+// statement runs under the register budget it is used in
+__global__ void __launch_bounds__(WAVE, 2) k_debug_fp_lane(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t at = (size_t)FP_N * (op == MI355_BLS_FPOP_FP_DOT2 ? 2 * i : i);      // FP_DOT2: two images per operand
+    const fp x = ld_raw_fp(a + at), y = ld_raw_fp(b + at);
+    fp r = fp_zero();
+    switch (op) {                       // wave-uniform
+        case MI355_BLS_FPOP_FP_MUL: r = fp_mul(x, y); break;
+        case MI355_BLS_FPOP_FP_SQR: r = fp_sqr(x); break;
+        case MI355_BLS_FPOP_FP_SQR_N1: r = fp_sqr_n(x, 1); break;
+        case MI355_BLS_FPOP_FP_SQR_N4: r = fp_sqr_n(x, 4); break;
+        case MI355_BLS_FPOP_FP_DOT2: r = fp_dot2(x, y, ld_raw_fp(a + at + FP_N), ld_raw_fp(b + at + FP_N)); break;
+        case MI355_BLS_FPOP_FP_REDUCE: r = fp_reduce(x); break;
+        case MI355_BLS_FPOP_FP_INV: r = fp_inv(x); break;
+        case MI355_BLS_FPOP_FP_POW: r = fp_recip_sqrt_pow(x); break;
+        default: r.l[0] = (fp_is_zero(x) ? 1u : 0u) | (fp_eq(x, y) ? 2u : 0u) | fp2_sgn0(fp2{x, y}) << 2; break;      // MI355_BLS_FPOP_PRED
+    }
+    st_raw_fp(out + (size_t)FP_N * i, r);
+}
+// the row forms: a wave with its row constants and an LDS power table, as k_hash_map_rows and k_hash_one set them up.  ROW_MUL / ROW_SQR / POW_PER_ROW:
+// operand 4 b + r in row r of block b; POW_TWO_ROWS: operands 2 b and 2 b + 1 in the lanes k_hash_one keeps u0 and u1 in.  Every lane runs the
+// arithmetic (the rows exchange values); a row past the end works on operand 0 and stores nothing.
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_debug_fp_rows(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t n, uint32_t* __restrict__ out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t powtab[16 * WAVE];
+    const row_ctx RC = row_ctx_make();
+    const uint32_t l16 = threadIdx.x & 15u;
+    if (op == MI355_BLS_FPOP_POW_TWO_ROWS) {
+        const uint32_t i = 2 * blockIdx.x + (l16 == 1 ? 1u : 0u);
+        const fp r = pow_two_rows{RC, powtab + threadIdx.x}(ld_raw_fp(a + (size_t)FP_N * (i < n ? i : 0u)));
+        if (threadIdx.x < 2 && i < n) st_raw_fp(out + (size_t)FP_N * i, r);
+        return;
+    }
+    const uint32_t i = 4 * blockIdx.x + (threadIdx.x >> 4);
+    const bool live = i < n;
+    const size_t at = (size_t)FP_N * (live ? i : 0u);
+    if (op == MI355_BLS_FPOP_POW_PER_ROW) {
+        const fp r = pow_per_row{RC, powtab + threadIdx.x}(ld_raw_fp(a + at));
+        if (live && l16 == 0) st_raw_fp(out + at, r);
+        return;
+    }
+    const rw x = row_load(a + at);
+    const rw r = row_mul(RC, x, op == MI355_BLS_FPOP_ROW_MUL ? row_load(b + at) : x);
+    if (live && l16 < (uint32_t)FP_N) out[at + l16] = (uint32_t)r;
+#endif
+}
+// A third message source of hash_map_body beside msg_from_record and msg_from_key: the two field elements are LOADED - four raw Fp images at the start
+// of the record's 320 bytes - where the others hash.  Three kernels with the launch bounds and attributes of k_hash_map, k_hash_map_spread and
+// k_hash_map_rows: the SSWU map and the isogeny in every form the batch path launches them in.
+struct msg_from_u {
+    __device__ __forceinline__ void operator()(fp2& u0, fp2& u1, const uint8_t* __restrict__ rec) const {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(rec);
+        u0.c0 = ld_raw_fp(w); u0.c1 = ld_raw_fp(w + FP_N);
+        u1.c0 = ld_raw_fp(w + 2 * FP_N); u1.c1 = ld_raw_fp(w + 3 * FP_N);
+    }
+};
+__global__ void __launch_bounds__(WAVE, 2) k_debug_map(const uint8_t* __restrict__ us, uint32_t n, uint4* __restrict__ M, size_t mstride) {
+    hash_map_body(us, n, msg_from_u{}, M, mstride);
+}
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_debug_map_spread(const uint8_t* __restrict__ us, uint32_t n, uint4* __restrict__ M, size_t mstride) {
+    hash_map_body(us, n, msg_from_u{}, M, mstride);
+}
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_debug_map_rows(const uint8_t* __restrict__ us, uint32_t n, uint4* __restrict__ M, size_t mstride) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t powtab[16 * WAVE];
+    hash_map_rows_body(us, n, msg_from_u{}, M, mstride, powtab);
+#endif
+}
+
 // ONE message of any length (fastAggregateVerify / coreVerify shape): latency is all that matters, so a wave works on
 // it cooperatively: the two SSWU maps run in roles 0 and 1, the doubling chains of the cofactor clearing spread
 // their independent products over roles 0..2.  Every group of 8 lanes does the same work.

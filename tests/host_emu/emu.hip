@@ -11,6 +11,7 @@
 #define BLS_ROW_EMU 1                    // rowfp.hpp on 64 emulated lanes
 #include "rowfp.hpp"
 #include "rowvm.hpp"
+#include "../../include/blscurve_mi355x.h"      // the operation codes of mi355_bls_debug_fp_op
 using namespace bls;
 static rw emu_row_of4(const uint8_t* p192) { return row_pick(row_from_fp(fp_load_le(p192)), row_from_fp(fp_load_le(p192 + 48)), row_from_fp(fp_load_le(p192 + 96)), row_from_fp(fp_load_le(p192 + 144))); }
 static void emu_row_to4(uint8_t* r192, const rw& x) {
@@ -321,6 +322,67 @@ void emu_cyc_sqr(const uint8_t* a576, int n, uint8_t* out576) {
     fp2* tr[6] = {&r.c0.a0, &r.c0.a1, &r.c0.a2, &r.c1.a0, &r.c1.a1, &r.c1.a2};
     for (int t = 0; t < 6; t++) *tr[t] = A[c12_flat_of_tower(t)];
     fp12_store_le(out576, r);
+}
+// RAW operands (tests/fp_operands.py): 14 words per image, each tagged with the bounds its family declares, through the operations of
+// mi355_bls_debug_fp_op (same codes, same operand layout) - the tracker aborts if a chosen operand is outside the contract of its operation
+static fp emu_raw(const uint32_t* w, uint32_t vb, uint32_t lb) {
+    fp r;
+    for (int i = 0; i < FP_N; i++) r.l[i] = w[i];
+    BLS_SET_VB(r, vb); BLS_SET_LB(r, lb);
+    (void)vb; (void)lb;
+    return r;
+}
+static void emu_raw_out(uint32_t* w, const fp& r) { for (int i = 0; i < FP_N; i++) w[i] = r.l[i]; }
+static rw emu_raw_rows(const uint32_t* a, uint32_t i0, uint32_t n, uint32_t per, uint32_t vb, uint32_t lb) {      // row j <- operand i0 + j % per (operand 0 past the end)
+    rw r[4];
+    for (uint32_t j = 0; j < 4; j++) { const uint32_t i = i0 + j % per; r[j] = row_from_fp(emu_raw(a + (size_t)FP_N * (i < n ? i : 0), vb, lb)); }
+    return row_pick(r[0], r[1], r[2], r[3]);
+}
+int emu_fp_op(int op, const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t vba, uint32_t lba, uint32_t vbb, uint32_t lbb, uint32_t* out) {
+    if (op >= MI355_BLS_FPOP_ROW_MUL) {
+        if (op > MI355_BLS_FPOP_POW_TWO_ROWS) return -1;
+        const row_ctx C = row_ctx_make();
+        const uint32_t per = op == MI355_BLS_FPOP_POW_TWO_ROWS ? 2 : 4;             // operands per wave; two rows each in k_hash_one's form (rows 0 / 2 and 1 / 3)
+        for (uint32_t i0 = 0; i0 < n; i0 += per) {
+            const rw x = emu_raw_rows(a, i0, n, per, vba, lba);
+            rw r;
+            if (op == MI355_BLS_FPOP_ROW_MUL) r = row_mul(C, x, emu_raw_rows(b, i0, n, per, vbb, lbb));
+            else if (op == MI355_BLS_FPOP_ROW_SQR) r = row_mul(C, x, x);
+            else { row_tab_array T; r = row_pow_sched(C, x, k::SW_PM3D4, k::SW_PM3D4_LEN, T); }
+            const rw rows[4] = {row_from<0>(r), row_from<1>(r), row_from<2>(r), row_from<3>(r)};
+            for (uint32_t j = 0; j < per && i0 + j < n; j++) {
+                fp v = row_to_fp(rows[j]);
+                emu_raw_out(out + (size_t)FP_N * (i0 + j), op >= MI355_BLS_FPOP_POW_PER_ROW ? fp_reduce(v) : v);      // the functors reduce what they hand back
+            }
+        }
+        return 0;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const bool two = op == MI355_BLS_FPOP_FP_DOT2;
+        const fp x = emu_raw(a + (size_t)FP_N * (two ? 2 * i : i), vba, lba), y = emu_raw(b + (size_t)FP_N * (two ? 2 * i : i), vbb, lbb);
+        fp r = fp_zero();
+        switch (op) {
+            case MI355_BLS_FPOP_FP_MUL: r = fp_mul(x, y); break;
+            case MI355_BLS_FPOP_FP_SQR: r = fp_sqr(x); break;
+            case MI355_BLS_FPOP_FP_SQR_N1: r = fp_sqr_n(x, 1); break;
+            case MI355_BLS_FPOP_FP_SQR_N4: r = fp_sqr_n(x, 4); break;
+            case MI355_BLS_FPOP_FP_DOT2: r = fp_dot2(x, y, emu_raw(a + (size_t)FP_N * (2 * i + 1), vba, lba), emu_raw(b + (size_t)FP_N * (2 * i + 1), vbb, lbb)); break;
+            case MI355_BLS_FPOP_FP_REDUCE: r = fp_reduce(x); break;
+            case MI355_BLS_FPOP_FP_INV: r = fp_inv(x); break;
+            case MI355_BLS_FPOP_FP_POW: r = fp_recip_sqrt_pow(x); break;
+            case MI355_BLS_FPOP_PRED: r.l[0] = (uint32_t)fp_is_zero(x) | (uint32_t)fp_eq(x, y) << 1 | fp2_sgn0(fp2{x, y}) << 2; break;
+            default: return -1;
+        }
+        emu_raw_out(out + (size_t)FP_N * i, r);
+    }
+    return 0;
+}
+// mi355_bls_debug_map_to_g2's arithmetic: n pairs (u0, u1) of raw Fp2 images -> 2n Jacobian points iso3(sswu(u)), 288 B each
+void emu_map_to_g2(const uint32_t* us, uint32_t n, uint32_t vb, uint32_t lb, uint8_t* out) {
+    for (uint32_t t = 0; t < 2 * n; t++) {
+        const fp2 u{emu_raw(us + (size_t)FP_N * 2 * t, vb, lb), emu_raw(us + (size_t)FP_N * (2 * t + 1), vb, lb)};
+        g2_jac_store(out + (size_t)288 * t, iso3_g2(sswu_g2(u)));
+    }
 }
 void emu_c12_mul(const uint8_t* a, const uint8_t* b, uint8_t* out) { emu_c12_rowphase(a, b, 0, out); }
 void emu_c12_sqr(const uint8_t* a, uint8_t* out) { emu_c12_rowphase(a, a, 1, out); }
