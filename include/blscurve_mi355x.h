@@ -303,6 +303,54 @@ int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* ctx, const void* keys, 
 int mi355_bls_batch_fast_aggregate_verify_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
                                                  size_t k, const void* d_msgs32, const void* d_sigs192, const uint8_t rnd[32], void* stream);
 
+/* aggregateAll on signatures for MANY groups in ONE device pass: the signature half of the same template
+ * (genAggregatorProcedures(AggregateSignature, Signature, p2), blst_min_pubkey_sig_core.nim:142-211), each sum finished to its affine image
+ * (blst_p2_to_affine) and serialised (serialize(Signature), bls_sig_io.nim:225-234) - what a node that aggregates the unaggregated
+ * attestations of a slot sends.  mi355_bls_g2_aggregate takes one group per call and leaves a Jacobian point; a device call costs about
+ * 2.2 ms whatever its size, so k groups that way cost k times that.
+ *   sigs192   n_table x 192-byte blst_p2_affine images: the signature table
+ *   idx, offsets   the addressing of mi355_bls_aggregate_sets (idx == NULL: group g is signatures [offsets[g], offsets[g+1]) of the table)
+ *   out_sigs192    k x 192 bytes: the blst_p2_affine image of aggregateAll(signatures of group g), packed by group
+ *   out_sigs96     k x 96 bytes: that aggregate's compressed wire form.  Either output may be NULL, not both.
+ *   status    k bytes, host memory:
+ *             0 ok;
+ *             1 empty group (the reference returns false): both outputs are the infinity encodings;
+ *             2 the sum is the point at infinity - a legal signature (bls_sig_io.nim:56), so the outputs are its valid encodings (192 zero
+ *               bytes; 0xc0 and 95 zero bytes); flagged so that a caller can tell;
+ *             3 an index was >= n_table: it is never dereferenced, 3 wins over 1 and 2, the outputs are the infinity encodings.
+ * An all-zero member (the affine infinity image) adds nothing, as in mi355_bls_g2_aggregate.  Device pointers are 4-byte aligned.
+ * Preconditions as the reference's: signatures decoded and group-checked (mi355_bls_deserialize_signatures).  Any k and any group lengths
+ * up to 2^32 - 2 signatures in all; nothing here is bounded by max_sets.
+ * Returns 1 when every status is 0, else 0; k == 0: 0, nothing written.  MI355_BLS_ERR_ARG for decreasing offsets, offsets[k] > n_table
+ * without idx, NULL inputs, both outputs NULL.  The _device form enqueues on `stream` and synchronises it once, for the status bytes; its
+ * d_out_sigs192 (k x 192 bytes, packed) is exactly the d_sigs192 argument of mi355_bls_aggregate_sets_device and
+ * mi355_bls_batch_fast_aggregate_verify_device, so wire signatures in, grouped aggregates out and their verification against committee keys
+ * all stay on the device.
+ * Level 0 of the sum keeps the key side's 8 signatures per lane (csrc/plan.hpp AGG_C); a smaller count was not tried.
+ * COST for k groups against one mi355_bls_g2_aggregate_device call per group (profiles/aggregate_signatures_bench.json):
+ * not measured yet: run nim-blscurve_amd/tools/bench_aggsigs.py on an MI355X, which writes both timings, the host oracle's and the spread. */
+int mi355_bls_aggregate_signature_sets(mi355_bls_ctx* ctx, const void* sigs192, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                       void* out_sigs192, void* out_sigs96, uint8_t* status);
+int mi355_bls_aggregate_signature_sets_device(mi355_bls_ctx* ctx, const void* d_sigs192, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                              size_t k, void* d_out_sigs192, void* d_out_sigs96, uint8_t* status, void* stream);
+/* serialize(Signature) (bls_sig_io.nim:225-234), i.e. blst_p2_affine_compress, for n signatures: 192-byte blst_p2_affine images in, 96 bytes
+ * each out (ZCash form: big-endian x.c1 then x.c0, bit 7 of byte 0 set, bit 5 set when y is the lexicographically larger root - decided by
+ * y.c1 unless it is zero, then by y.c0; the all-zero infinity image gives 0xc0 and 95 zero bytes).  The device form writes device memory
+ * (d_out96: n x 96 B, 4-byte aligned like d_sigs192) and returns when the bytes are there.  Returns 0, negative on failure. */
+int mi355_bls_compress_signatures(mi355_bls_ctx* ctx, const void* sigs192, size_t n, uint8_t out96[]);
+int mi355_bls_compress_signatures_device(mi355_bls_ctx* ctx, const void* d_sigs192, size_t n, void* d_out96, void* stream);
+/* Signature.fromBytes (bls_sig_io.nim:42-58) for n signatures that arrive without a key or a message (an attestation's signature): the
+ * signature half of mi355_bls_deserialize_sets_ex, by the same decoder.  sigs: n x 96 bytes, or n x 192 with
+ * MI355_BLS_DESER_SIG_UNCOMPRESSED; MI355_BLS_DESER_KNOWN_ON_CURVE skips the subgroup check; MI355_BLS_DESER_PK_UNCOMPRESSED is
+ * MI355_BLS_ERR_ARG (flags are defined with that call, below).  out_sigs192: n x 192-byte blst_p2_affine images, zeroed where status[i] is not 0;
+ * status[i]: 0 ok, 4 bad encoding, 5 not in G2, as mi355_bls_deserialize_sets gives them.  The infinity signature is allowed (status 0, the
+ * all-zero image).  Returns 1 when every status is 0, else 0 (n == 0: 1); negative on failure.  Any n.  The host form's out_sigs192 and
+ * both forms' status may be NULL; the _device form reads d_sigs and writes d_out_sigs192 (4-byte aligned) in device memory, status stays
+ * host memory. */
+int mi355_bls_deserialize_signatures(mi355_bls_ctx* ctx, const uint8_t* sigs, size_t n, uint32_t flags, void* out_sigs192, uint8_t* status);
+int mi355_bls_deserialize_signatures_device(mi355_bls_ctx* ctx, const void* d_sigs, size_t n, uint32_t flags, void* d_out_sigs192, uint8_t* status,
+                                            void* stream);
+
 /* coreVerifyNoGroupCheck on an AggregatePublicKey the caller already holds (core :269-297): agg_p1 = blst_p1 (Jacobian, 144 B), e.g.
  * mi355_bls_p1s_add of the per-rank mi355_bls_g1_aggregate_device partial sums of a key-sharded fastAggregateVerify (one process per
  * GPU).  Aggregate at infinity -> 0. */

@@ -118,6 +118,12 @@ def lib():
         L.mi355_bls_fast_aggregate_verify_each_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_batch_fast_aggregate_verify.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, ctypes.c_char_p]
         L.mi355_bls_batch_fast_aggregate_verify_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, ctypes.c_char_p, vp]
+        L.mi355_bls_aggregate_signature_sets.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp]
+        L.mi355_bls_aggregate_signature_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
+        L.mi355_bls_compress_signatures.argtypes = [vp, vp, sz, ctypes.c_char_p]
+        L.mi355_bls_compress_signatures_device.argtypes = [vp, vp, sz, vp, vp]
+        L.mi355_bls_deserialize_signatures.argtypes = [vp, ctypes.c_char_p, sz, u32, vp, vp]
+        L.mi355_bls_deserialize_signatures_device.argtypes = [vp, vp, sz, u32, vp, vp, vp]
         L.mi355_bls_combine_sets.argtypes = [vp, vp, sz, pu32, psz, sz, ctypes.c_char_p, vp, vp]
         L.mi355_bls_combine_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, ctypes.c_char_p, vp, vp, vp]
         L.mi355_bls_batch_verify_combined.argtypes = [vp, vp, sz, pu32, psz, sz, ctypes.c_char_p, ctypes.c_char_p]
@@ -778,6 +784,105 @@ def batchFastAggregateVerify_device(cache, d_keys, n_table, d_idx, offsets, d_ms
         return False
     return bool(_check(lib().mi355_bls_batch_fast_aggregate_verify_device(cache._h, d_keys, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k,
                                                                           d_msgs, d_sigs, rnd, stream)))
+
+
+def _signature_lists(signatures):
+    """The signature lists of aggregateSignatureSets -> (table bytes, n_table, idx array or None, offsets array, k).  signatures: a list of
+    signature lists (each a list of 192-byte blst_p2_affine images, or their concatenation) - they are laid end to end and no index array is
+    sent - or a tuple (table, idx, offsets) as aggregateSets takes it for keys."""
+    if isinstance(signatures, tuple):
+        table, idx, offsets = signatures
+        table = _join(table, 192, "signature table")
+        offsets = [int(x) for x in offsets]
+        if idx is not None:
+            idx = [int(x) for x in idx]
+            if any(x < 0 or x >= 1 << 32 for x in idx):
+                raise ValueError("indices are 32-bit unsigned")
+            if offsets and offsets[-1] != len(idx):
+                raise ValueError("offsets[k] is the length of the index array")
+    else:
+        lists = [_join(x, 192, "signatures") for x in signatures]
+        table, idx, offsets = b"".join(lists), None, [0]
+        for x in lists:
+            offsets.append(offsets[-1] + len(x) // 192)
+    if not offsets or any(x < 0 for x in offsets):
+        raise ValueError("offsets: k + 1 non-negative positions")
+    k = len(offsets) - 1
+    iarr = (ctypes.c_uint32 * max(len(idx), 1))(*idx) if idx is not None else None
+    return table, len(table) // 192, iarr, (ctypes.c_size_t * (k + 1))(*offsets), k
+
+
+def aggregateSignatureSets(cache, signatures, want192=True, want96=True):
+    """aggregateAll on signatures (blst_min_pubkey_sig_core.nim:142-211) for every group in one device pass, finished and serialised
+    (mi355_bls_aggregate_signature_sets); signatures as _signature_lists takes them.  -> (all_ok, k x 192-byte blst_p2_affine images or None,
+    k x 96-byte wire forms or None, k status bytes: 0 ok, 1 empty group, 2 the aggregate is the point at infinity (its valid encodings are
+    returned), 3 index out of range)."""
+    if not (want192 or want96):
+        raise ValueError("at least one of the two outputs")
+    table, n_table, idx, offs, k = _signature_lists(signatures)
+    if k == 0:
+        return False, (b"" if want192 else None), (b"" if want96 else None), b""
+    o192 = ctypes.create_string_buffer(192 * k) if want192 else None
+    o96 = ctypes.create_string_buffer(96 * k) if want96 else None
+    st = ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_aggregate_signature_sets(cache._h, table or b"\0", n_table, idx, offs, k, o192, o96, st))
+    return bool(ok), (o192.raw if want192 else None), (o96.raw if want96 else None), st.raw
+
+
+def aggregateSignatureSets_device(cache, d_sigs, n_table, d_idx, offsets, d_out192, d_out96, stream=0):
+    """Same with the signature table, the indices (0 / None: none) and the outputs (0 / None: not wanted; not both) in device memory (raw
+    pointers); offsets stay on the host.  d_out192 is what aggregateSets_device / batchFastAggregateVerify_device take as d_sigs.
+    -> (all_ok, status bytes)."""
+    k = len(offsets) - 1
+    if k <= 0:
+        return False, b""
+    st = ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_aggregate_signature_sets_device(cache._h, d_sigs, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k,
+                                                                d_out192 or None, d_out96 or None, st, stream))
+    return bool(ok), st.raw
+
+
+def compressSignatures(cache, signatures):
+    """serialize(Signature) (bls_sig_io.nim:225-234) for n signatures (mi355_bls_compress_signatures): n x 192-byte images -> [96-byte strings]."""
+    sg = _join(signatures, 192, "signatures (blst_p2_affine)")
+    n = len(sg) // 192
+    if n == 0:
+        return []
+    out = ctypes.create_string_buffer(96 * n)
+    _check(lib().mi355_bls_compress_signatures(cache._h, sg, n, out))
+    raw = out.raw
+    return [raw[96 * i:96 * i + 96] for i in range(n)]
+
+
+def compressSignatures_device(cache, d_sigs, n, d_out, stream=0):
+    """Same with the signatures and the n x 96 output bytes in device memory (raw pointers)."""
+    if n:
+        _check(lib().mi355_bls_compress_signatures_device(cache._h, d_sigs, n, d_out, stream))
+
+
+def deserializeSignatures(cache, signatures, sig_uncompressed=False, known_on_curve=False):
+    """Signature.fromBytes (bls_sig_io.nim:42-58) for n signatures without key or message (mi355_bls_deserialize_signatures): n x 96 bytes
+    (n x 192 with sig_uncompressed); known_on_curve: fromBytesKnownOnCurve.  -> (all_ok, n x 192-byte images, zeroed on failure, status bytes:
+    0 ok, 4 bad encoding, 5 not in G2)."""
+    unit = 192 if sig_uncompressed else 96
+    sg = _join(signatures, unit, "wire signatures")
+    n = len(sg) // unit
+    if n == 0:
+        return True, b"", b""
+    flags = (2 if sig_uncompressed else 0) | (4 if known_on_curve else 0)      # DESER_SIG_UNCOMPRESSED, DESER_KNOWN_ON_CURVE
+    out, st = ctypes.create_string_buffer(192 * n), ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_deserialize_signatures(cache._h, sg, n, flags, out, st))
+    return bool(ok), out.raw, st.raw
+
+
+def deserializeSignatures_device(cache, d_sigs, n, d_out192, sig_uncompressed=False, known_on_curve=False, stream=0):
+    """Same with the wire bytes and the n x 192 output bytes in device memory (raw pointers).  -> (all_ok, status bytes)."""
+    if n == 0:
+        return True, b""
+    flags = (2 if sig_uncompressed else 0) | (4 if known_on_curve else 0)
+    st = ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_deserialize_signatures_device(cache._h, d_sigs, n, flags, d_out192, st, stream))
+    return bool(ok), st.raw
 
 
 COMB_MIXED, COMB_INF_KEY = 4, 5      # status bytes of combineSets beyond aggregateSets' own

@@ -105,6 +105,31 @@ BLS_HD void g1_compress(uint8_t out[48], const g1_aff& p) {
     }
 }
 
+// The G2 twin: blst_p2_affine_compress (serialize of a Signature, bls_sig_io.nim:225-234).  x.c1 then x.c0, canonical and big-endian, in
+// words 0..11 and 12..23; the flags in word 0.  The sign bit is the rule g2_uncompress applies: y.c1 decides unless it is zero, then y.c0.
+// The affine infinity image gives 0xc0 and 95 zero bytes.
+BLS_HD void g2_compress_words(uint32_t (&be)[24], const g2_aff& p) {
+    const bool inf = aff_is_inf(p);
+    uint32_t w1[12], w0[12];
+    fp_relimb_to32(w1, fp_from_mont(p.x.c1));
+    fp_relimb_to32(w0, fp_from_mont(p.x.c0));
+    const bool large = fp_is_zero(p.y.c1) ? fp_is_lex_largest(p.y.c0) : fp_is_lex_largest(p.y.c1);
+#pragma unroll
+    for (int i = 0; i < 12; i++) be[i] = inf ? 0u : w1[11 - i], be[12 + i] = inf ? 0u : w0[11 - i];
+    be[0] |= inf ? 0xc0000000u : (large ? 0xa0000000u : 0x80000000u);
+}
+BLS_HD void g2_compress(uint8_t out[96], const g2_aff& p) {
+    uint32_t be[24];
+    g2_compress_words(be, p);
+#pragma unroll
+    for (int i = 0; i < 24; i++) {
+        out[4 * i] = (uint8_t)(be[i] >> 24);
+        out[4 * i + 1] = (uint8_t)(be[i] >> 16);
+        out[4 * i + 2] = (uint8_t)(be[i] >> 8);
+        out[4 * i + 3] = (uint8_t)be[i];
+    }
+}
+
 BLS_HDN bool g2_uncompress(g2_aff& out, bool& inf, const uint8_t* b) {
     inf = false;
     out = g2_aff{fp2_zero(), fp2_zero()};
@@ -204,16 +229,21 @@ constexpr uint32_t DESER_F_PK_UNCOMPRESSED = 1, DESER_F_SIG_UNCOMPRESSED = 2, DE
 // One tuple: wire-format (pk, sig) -> validated affine points.  Returns the deser_status.
 //   fromBytes (bls_sig_io.nim:42-58, 81-99): decode, "public key is not infinity", subgroup checks (infinity signature allowed)
 //   fromBytesKnownOnCurve (:60-79, 101-121): the same without the subgroup checks
+// the signature half on its own (mi355_bls_deserialize_signatures: a signature that arrives without key and message)
+BLS_HD uint8_t deserialize_signature(g2_aff& sig, const uint8_t* sigb, uint32_t flags) {
+    bool inf;
+    const bool ok = (flags & DESER_F_SIG_UNCOMPRESSED) ? g2_deserialize(sig, inf, sigb) : g2_uncompress(sig, inf, sigb);
+    if (!ok) return DESER_SIG_BAD_ENCODING;
+    if (!(flags & DESER_F_KNOWN_ON_CURVE) && !inf && !g2_in_subgroup(sig)) return DESER_SIG_NOT_IN_G2;
+    return DESER_OK;
+}
 BLS_HD uint8_t deserialize_tuple(g1_aff& pk, g2_aff& sig, const uint8_t* pkb, const uint8_t* sigb, uint32_t flags) {
     bool inf;
     bool ok = (flags & DESER_F_PK_UNCOMPRESSED) ? g1_deserialize(pk, inf, pkb) : g1_uncompress(pk, inf, pkb);
     if (!ok) return DESER_PK_BAD_ENCODING;
     if (inf) return DESER_PK_INFINITY;
     if (!(flags & DESER_F_KNOWN_ON_CURVE) && !g1_in_subgroup(pk)) return DESER_PK_NOT_IN_G1;
-    ok = (flags & DESER_F_SIG_UNCOMPRESSED) ? g2_deserialize(sig, inf, sigb) : g2_uncompress(sig, inf, sigb);
-    if (!ok) return DESER_SIG_BAD_ENCODING;
-    if (!(flags & DESER_F_KNOWN_ON_CURVE) && !inf && !g2_in_subgroup(sig)) return DESER_SIG_NOT_IN_G2;
-    return DESER_OK;
+    return deserialize_signature(sig, sigb, flags);
 }
 
 }  // namespace bls

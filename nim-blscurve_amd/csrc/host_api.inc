@@ -137,6 +137,9 @@ struct mi355_bls_ctx {
     dev_buf<uint4> d_comb_g2tab;     // ... and k_combsets_g2mul's
     dev_buf<uint32_t> d_comb_pkflag; // k_pkmul's infinity-key word (the check items report such a key per group)
     std::vector<uint64_t> comb_s_h;  // the chains the host walks, until the call's synchronisation
+    // per-group signature aggregation (mi355_bls_aggregate_signature_sets): sized by the call (plan.hpp aggsigs_sizes_for), made at the first
+    // such call; it shares the item table, flag words, status bytes and staged inputs above and combine_sets' G2 partials (d_comb_part2)
+    dev_buf<uint8_t> d_aggsig_out;   // the host form's outputs: k x 192 bytes | k x 96 bytes
 
     // the batch workspace's pair store (ctx_build makes it; it never changes) and the per-set path's (each_reserve)
     pair_store batch_pairs() const { return {d_H, d_P, d_lines, stride}; }
@@ -1244,6 +1247,148 @@ extern "C" int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* c, const voi
     int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
     if (rc) return rc;
     return agg_batch(c, in, n_table, offsets, k, rnd, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-group signature aggregation: aggregateAll on signatures (genAggregatorProcedures(AggregateSignature, Signature, p2),
+// blst_min_pubkey_sig_core.nim:142-211) for k groups in one device pass, each finished to its blst_p2_affine image and serialised
+// (bls_sig_io.nim:225-234).  The addressing, the plan and the item table are aggregate_sets' (group g = positions [offsets[g], offsets[g + 1])
+// of the signature sequence: the table itself, or table entries picked by index); level 0 is k_aggsigs_l0, higher levels k_combsets_g2_sum,
+// then k_aggsigs_finish, all on the caller's stream.
+// ------------------------------------------------------------------------------------------
+// aggregation of k > 0 groups enqueued on st: images at d_out192, wire forms at d_out96 (either may be null), status bytes in c->d_agg_status
+static int aggsigs_enqueue(mi355_bls_ctx* c, const uint8_t* d_sigs, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k, uint8_t* d_out192,
+                           uint8_t* d_out96, hipStream_t st) {
+    if (!d_sigs || !offsets || (!d_out192 && !d_out96)) return MI355_BLS_ERR_ARG;
+    if (((uintptr_t)d_sigs | (uintptr_t)d_idx | (uintptr_t)d_out192 | (uintptr_t)d_out96) & 3) {
+        g_err = "aggregate_signature_sets: signatures, indices and outputs must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const plan::aggsets_plan p = k < plan::AGG_NONE ? plan::aggsets_measure(offsets, k) : plan::aggsets_plan{};
+    if (!p.ok) {
+        g_err = "aggregate_signature_sets: offsets decrease, or more than 2^32 - 2 signatures or groups";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (!d_idx && offsets[k] > n_table) {
+        g_err = "aggregate_signature_sets: offsets[k] exceeds the number of signatures";
+        return MI355_BLS_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    c->agg_tab.resize(p.items * 4 + k);
+    plan::aggsets_fill(p, offsets, k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), c->agg_tab.data() + p.items * 4);
+    // grown with a quarter of slack; every entry point that used the old buffers has drained its stream before returning
+    const plan::aggsigs_sizes sz = plan::aggsigs_sizes_for(p, k);
+    int rc = c->d_comb_part2.reserve(sz.part, sz.part / 4);
+    if (!rc) rc = c->d_agg_tab.reserve(sz.tab, sz.tab / 4);
+    if (!rc) rc = c->d_agg_bad.reserve(sz.bad, sz.bad / 4);
+    if (!rc) rc = c->d_agg_status.reserve(sz.status, sz.status / 4);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, sz.bad, st));
+    HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), sz.tab, hipMemcpyHostToDevice, st));
+    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
+    for (uint32_t l = 0; l < p.levels; l++) {
+        const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
+        if (l == 0)
+            k_aggsigs_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, reinterpret_cast<const uint32_t*>(d_sigs), n_table, d_idx, c->d_comb_part2, c->d_agg_bad);
+        else
+            k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + p.level_first[l], cnt, c->d_comb_part2, c->d_comb_part2);
+    }
+    k_aggsigs_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(c->d_agg_tab + p.items * 4, (uint32_t)k, c->d_comb_part2, c->d_agg_bad,
+                                                                   reinterpret_cast<uint32_t*>(d_out192), reinterpret_cast<uint32_t*>(d_out96), c->d_agg_status);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int mi355_bls_aggregate_signature_sets_device(mi355_bls_ctx* c, const void* d_sigs192, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                                         size_t k, void* d_out_sigs192, void* d_out_sigs96, uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing aggregated, nothing written
+    if (!status) return MI355_BLS_ERR_ARG;
+    int rc = aggsigs_enqueue(c, (const uint8_t*)d_sigs192, n_table, d_idx, offsets, k, (uint8_t*)d_out_sigs192, (uint8_t*)d_out_sigs96, (hipStream_t)stream);
+    if (rc) return rc;
+    return aggsets_status(c, k, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_aggregate_signature_sets(mi355_bls_ctx* c, const void* sigs192, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                                  void* out_sigs192, void* out_sigs96, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!sigs192 || !offsets || !status || (!out_sigs192 && !out_sigs96) || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    // signatures | indices -> d_agg_in (both parts 4-byte aligned)
+    const size_t n_idx = idx ? offsets[k] : 0, sb = n_table * 192, all = sb + n_idx * 4 + 4;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->d_agg_in.reserve(all, all / 4);
+    if (!rc) rc = c->d_aggsig_out.reserve(k * 288, k * 72);
+    if (rc) return rc;
+    uint8_t *d = c->d_agg_in, *o192 = c->d_aggsig_out, *o96 = o192 + k * 192;
+    if (sb) HIPCHK(hipMemcpyAsync(d, sigs192, sb, hipMemcpyHostToDevice, nullptr));
+    if (n_idx) HIPCHK(hipMemcpyAsync(d + sb, idx, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+    rc = aggsigs_enqueue(c, d, n_table, idx ? reinterpret_cast<const uint32_t*>(d + sb) : nullptr, offsets, k, out_sigs192 ? o192 : nullptr,
+                         out_sigs96 ? o96 : nullptr, nullptr);
+    if (rc) return rc;
+    if (out_sigs192) HIPCHK(hipMemcpyAsync(out_sigs192, o192, k * 192, hipMemcpyDeviceToHost, nullptr));
+    if (out_sigs96) HIPCHK(hipMemcpyAsync(out_sigs96, o96, k * 96, hipMemcpyDeviceToHost, nullptr));
+    return aggsets_status(c, k, status, nullptr);
+}
+
+// serialize for n signatures (bls_sig_io.nim:225-234).  The device form leaves the bytes in device memory and returns when they are there.
+extern "C" int mi355_bls_compress_signatures_device(mi355_bls_ctx* c, const void* d_sigs192, size_t n, void* d_out96, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!d_sigs192 || !d_out96 || n > plan::POP_MAX_KEYS || (((uintptr_t)d_sigs192 | (uintptr_t)d_out96) & 3)) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    k_compress_sigs<<<plan::waves_for((uint32_t)n), WAVE, 0, (hipStream_t)stream>>>((const uint32_t*)d_sigs192, (uint32_t)n, (uint32_t*)d_out96);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+extern "C" int mi355_bls_compress_signatures(mi355_bls_ctx* c, const void* sigs192, size_t n, uint8_t out96[]) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!sigs192 || !out96 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(c->d_comp, sigs192, n * 192, hipMemcpyHostToDevice, nullptr));
+    int rc = mi355_bls_compress_signatures_device(c, c->d_comp, n, c->d_comp + c->cap_io * 192, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(out96, c->d_comp + c->cap_io * 192, n * 96, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Signature.fromBytes (bls_sig_io.nim:42-58) for n signatures without key or message: k_deser's signature half.  The device form leaves the
+// images in device memory (d_out_sigs192) and brings the status bytes to the host; 1 when every status is 0.
+extern "C" int mi355_bls_deserialize_signatures_device(mi355_bls_ctx* c, const void* d_sigs, size_t n, uint32_t dflags, void* d_out_sigs192, uint8_t* status,
+                                                       void* stream) {
+    if (!c || dflags > 7 || (dflags & DESER_F_PK_UNCOMPRESSED)) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 1;
+    if (!d_sigs || !d_out_sigs192 || n > plan::POP_MAX_KEYS || ((uintptr_t)d_out_sigs192 & 3)) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;                     // the status bytes' device buffer
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
+    k_deser_sigs<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>((const uint8_t*)d_sigs, (uint32_t)n, dflags, (uint32_t*)d_out_sigs192, c->d_status, c->d_flags);
+    HIPCHK(hipGetLastError());
+    uint32_t fl[4];
+    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
+    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return fl[2] ? 0 : 1;
+}
+extern "C" int mi355_bls_deserialize_signatures(mi355_bls_ctx* c, const uint8_t* sigs, size_t n, uint32_t dflags, void* out_sigs192, uint8_t* status) {
+    if (!c || dflags > 7 || (dflags & DESER_F_PK_UNCOMPRESSED)) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 1;
+    if (!sigs || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(c->d_comp, sigs, n * ((dflags & DESER_F_SIG_UNCOMPRESSED) ? 192 : 96), hipMemcpyHostToDevice, nullptr));
+    int rc = mi355_bls_deserialize_signatures_device(c, c->d_comp, n, dflags, c->d_sets, status, nullptr);
+    if (rc < 0) return rc;
+    if (out_sigs192) HIPCHK(hipMemcpy(out_sigs192, c->d_sets, n * 192, hipMemcpyDeviceToHost));
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -36,6 +36,7 @@
 #include "vereach.hpp"
 #include "aggsets.hpp"
 #include "combsets.hpp"
+#include "aggsigs.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -2474,6 +2475,64 @@ __global__ void __launch_bounds__(WAVE) k_combsets_finish(const uint32_t* __rest
     uint32_t* r = records + (size_t)g * 80;
     for (int i = 0; i < 80; i++) r[i] = e.rec[i];
     status[g] = e.status;
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-group signature aggregation (mi355_bls_aggregate_signature_sets: aggregateAll on signatures, blst_min_pubkey_sig_core.nim:142-211, for
+// the signature list of every group of a call, then finish and serialize, bls_sig_io.nim:225-234).  The arithmetic is csrc/aggsigs.hpp, the
+// item tables are plan.hpp aggsets_fill's; partials are internal G2 images (G2W words), partial i written by item i of the table.  Levels
+// above 0 are k_combsets_g2_sum as it stands.
+// ------------------------------------------------------------------------------------------
+// level 0, one lane per item: up to AGG_C signatures (192-byte blst_p2_affine images; through idx into a table of n_table signatures when
+// idx != nullptr) -> one partial.  An index that is not below n_table is not dereferenced: the lane sets the group's word and goes on.
+__global__ void __launch_bounds__(WAVE) k_aggsigs_l0(const uint4* __restrict__ items, uint32_t n_items, const uint32_t* __restrict__ sigs, size_t n_table,
+                                                     const uint32_t* __restrict__ idx, uint32_t* __restrict__ part, uint32_t* __restrict__ seg_bad) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    const g2_jac acc = aggsigs_l0_item(it.x, it.y, idx, n_table, [&](size_t t) { return ld_g2a_blst(sigs + t * 48); },
+                                       [&]() { atomicOr(seg_bad + it.w, 1u); });
+    st_g2_int(part + (size_t)it.z * G2W, acc);
+}
+// one lane per group: its last partial (final_of[g]; 0xffffffff: no member at all) to affine; the 192-byte image to out192, the 96-byte wire
+// form to out96 (either may be null), packed by group, and the status byte
+__global__ void __launch_bounds__(WAVE) k_aggsigs_finish(const uint32_t* __restrict__ final_of, uint32_t k, const uint32_t* __restrict__ part,
+                                                         const uint32_t* __restrict__ seg_bad, uint32_t* __restrict__ out192, uint32_t* __restrict__ out96,
+                                                         uint8_t* __restrict__ status) {
+    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= k) return;
+    const uint32_t f = final_of[g];
+    const bool empty = f == 0xffffffffu;
+    const aggsigs_end e = aggsigs_finish_item(empty, seg_bad[g] != 0, empty ? jac_inf<fp2>() : ld_g2_int(part + (size_t)f * G2W));
+    if (out192)
+        for (int i = 0; i < 48; i++) out192[(size_t)g * 48 + i] = e.sig[i];
+    if (out96)
+        for (int i = 0; i < 24; i++) out96[(size_t)g * 24 + i] = e.wire[i];
+    status[g] = e.status;
+}
+// serialize (bls_sig_io.nim:225-234: blst_p2_affine_compress) for n signatures: 192-byte images in, 96 bytes each out
+__global__ void __launch_bounds__(WAVE) k_compress_sigs(const uint32_t* __restrict__ sigs, uint32_t n, uint32_t* __restrict__ out) {
+    uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n) return;
+    uint32_t wire[24];
+    aggsigs_compress_item(wire, ld_g2a_blst(sigs + (size_t)i * 48));
+#pragma unroll
+    for (int j = 0; j < 24; j++) out[(size_t)i * 24 + j] = wire[j];
+}
+// Signature.fromBytes (bls_sig_io.nim:42-58) for n signatures that arrive without key and message: k_deser's signature half
+// (deser.hpp deserialize_signature) -> 192-byte images, zeroed where the status is not 0
+__global__ void __launch_bounds__(WAVE) k_deser_sigs(const uint8_t* __restrict__ sigs, uint32_t n, uint32_t dflags, uint32_t* __restrict__ out,
+                                                     uint8_t* __restrict__ status, uint32_t* __restrict__ flags) {
+    uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n) return;
+    g2_aff sg;
+    const uint8_t st = deserialize_signature(sg, sigs + (size_t)i * ((dflags & DESER_F_SIG_UNCOMPRESSED) ? 192 : 96), dflags);
+    status[i] = st;
+    if (st != DESER_OK) atomicOr(flags + 2, 1u);
+    const bool ok = st == DESER_OK;
+    sg = g2_aff{fp2_select(ok, sg.x, fp2_zero()), fp2_select(ok, sg.y, fp2_zero())};
+    uint32_t* o = out + (size_t)i * 48;
+    st_fp_blst(o, sg.x.c0); st_fp_blst(o + 12, sg.x.c1); st_fp_blst(o + 24, sg.y.c0); st_fp_blst(o + 36, sg.y.c1);
 }
 
 // ------------------------------------------------------------------------------------------

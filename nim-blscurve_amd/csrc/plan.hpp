@@ -394,6 +394,18 @@ inline combsets_plan combsets_measure(const size_t* offsets, size_t k) {
     return p;
 }
 
+// Per-group signature aggregation (mi355_bls_aggregate_signature_sets): the segmented sum of aggsets_measure / aggsets_fill over G2.  Level 0
+// keeps AGG_C signatures per item (at 65 536 members in groups of 16 that is 8 192 lanes, 128 waves: a smaller count would fill more of the
+// chip at level 0 but add a level to every group longer than it; not measured, so the key side's value stands).  The workspace of a call,
+// in bytes: a G2 partial per item (one at least), the item table with final_of behind it, a flag word and a status byte per group, and the
+// host form's two output arrays.  Nothing here depends on the context's max_sets.
+struct aggsigs_sizes {
+    size_t part, tab, bad, status, out192, out96;
+};
+inline aggsigs_sizes aggsigs_sizes_for(const aggsets_plan& p, size_t k) {
+    return {(p.items ? p.items : 1) * (size_t)G2_WORDS * 4, (p.items * 4 + k) * 4, k * 4, k, k * 192, k * 96};
+}
+
 // ------------------------------------------------------------------------------------------
 // Pippenger MSM (blst_p1s_mult_pippenger / blst_p2s_mult_pippenger): what msm_enqueue follows, and what msm_reserve allocates.
 // ------------------------------------------------------------------------------------------
