@@ -350,6 +350,45 @@ int mi355_bls_compress_signatures_device(mi355_bls_ctx* ctx, const void* d_sigs1
 int mi355_bls_deserialize_signatures(mi355_bls_ctx* ctx, const uint8_t* sigs, size_t n, uint32_t flags, void* out_sigs192, uint8_t* status);
 int mi355_bls_deserialize_signatures_device(mi355_bls_ctx* ctx, const void* d_sigs, size_t n, uint32_t flags, void* d_out_sigs192, uint8_t* status,
                                             void* stream);
+/* recover(signs, ids) (blst_recovery.nim:150-156: lagrangeInterpolation, :90-121, at 0 in the exponent) for k groups of threshold-signature
+ * shares in one device pass: group g's t_g shares, made with Shamir shares of one secret key, give the signature of that key.
+ *   sigs192, n_table, idx, offsets   the addressing of mi355_bls_aggregate_signature_sets: a table of 192-byte blst_p2_affine images, an
+ *                  optional index array, k + 1 host offsets (group g = positions [offsets[g], offsets[g+1]) of the share sequence)
+ *   ids32          32 bytes per SEQUENCE POSITION: ids32[32 p ..] belongs to position p of the index array, or of the table when idx is NULL;
+ *                  offsets[k] x 32 bytes in all
+ *   out_sigs192    k x 192 bytes: the blst_p2_affine image of the recovered signature, packed by group
+ *   out_sigs96     k x 96 bytes: its compressed wire form.  Either output may be NULL, not both.
+ *   status    k bytes, host memory, in this precedence:
+ *             3 an index was >= n_table (never dereferenced);
+ *             1 empty group (the reference: "invalid inputs");
+ *             6 MI355_BLS_REC_ZERO_ID: two or more shares and an id that is 0 mod r (the reference tests this before duplicates);
+ *             7 MI355_BLS_REC_DUP_ID: two or more shares and two ids equal mod r;
+ *             2 the interpolated point is the point at infinity: its valid encodings are returned (192 zero bytes; 0xc0 and 95 zero bytes);
+ *             0 recovered.  Any status but 0 and 2 also yields the infinity encodings.
+ * CONTRACT FOR AN ID: the 32 little-endian bytes of a blst_scalar (ID.fromUint32(a) lays word a[0] lowest, so the reference test's
+ * [0, .., 0, x] is x 2^224), and the id's VALUE is that 256-bit integer mod r - blst_fr_from_scalar is a Montgomery multiplication by R^2,
+ * which reduces.  This is this library's contract; the reference's own tests only use ids below r.
+ * A group of one share returns that share whatever its id, 0 included (the reference returns before it looks at the id).  An all-zero share
+ * (the infinity image) contributes nothing.  Device pointers are 4-byte aligned.  Shares are decoded and group-checked by the caller
+ * (mi355_bls_deserialize_signatures).  VARIABLE TIME: signature shares and public ids only - the secret-key half of blst_recovery.nim
+ * (genSecretShare, recover(secrets, ids), add) is not offered and stays on the CPU.
+ * Any k and any group lengths below 2^32 - 1 positions in all: the call runs in chunks of whole groups (csrc/plan.hpp REC_MEMBERS_CHUNK),
+ * so its device workspace does not grow with the call; nothing is bounded by max_sets.  Work is O(t^2) field products per group, as in the
+ * reference, beside t G2 multiplications by 255-bit scalars, one lane per share.
+ * Returns 1 when every status is 0, else 0; k == 0: 0, nothing written.  MI355_BLS_ERR_ARG for decreasing offsets, offsets[k] > n_table
+ * without idx, NULL inputs, both outputs NULL.  The _device form enqueues on `stream` and synchronises it once per chunk, for the status
+ * bytes; its d_out_sigs192 (k x 192 bytes, packed) is exactly the d_sigs192 argument of mi355_bls_aggregate_sets_device and
+ * mi355_bls_batch_fast_aggregate_verify_device - that is why the call exists: decoded shares in, recovered signatures out and their
+ * verification all stay on the device.
+ * COST (profiles/recover_signatures_bench.json, nim-blscurve_amd/tools/bench_recover.py): 256 groups of 3 .. 7 shares 7.7 - 7.9 ms, 65 536 groups
+ * 38 - 73 ms, device-resident; the floor is one wave's 255-bit multiplication, about 7.5 ms, so for ONE group a single
+ * mi355_bls_p2s_mult_pippenger call with host coefficients (about 5 ms) is the faster route. */
+#define MI355_BLS_REC_ZERO_ID 6
+#define MI355_BLS_REC_DUP_ID 7
+int mi355_bls_recover_signature_sets(mi355_bls_ctx* ctx, const void* sigs192, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                     const void* ids32, void* out_sigs192, void* out_sigs96, uint8_t* status);
+int mi355_bls_recover_signature_sets_device(mi355_bls_ctx* ctx, const void* d_sigs192, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                            size_t k, const void* d_ids32, void* d_out_sigs192, void* d_out_sigs96, uint8_t* status, void* stream);
 
 /* coreVerifyNoGroupCheck on an AggregatePublicKey the caller already holds (core :269-297): agg_p1 = blst_p1 (Jacobian, 144 B), e.g.
  * mi355_bls_p1s_add of the per-rank mi355_bls_g1_aggregate_device partial sums of a key-sharded fastAggregateVerify (one process per

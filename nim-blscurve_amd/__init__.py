@@ -120,6 +120,8 @@ def lib():
         L.mi355_bls_batch_fast_aggregate_verify_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, ctypes.c_char_p, vp]
         L.mi355_bls_aggregate_signature_sets.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp]
         L.mi355_bls_aggregate_signature_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
+        L.mi355_bls_recover_signature_sets.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp, vp]
+        L.mi355_bls_recover_signature_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp, vp]
         L.mi355_bls_compress_signatures.argtypes = [vp, vp, sz, ctypes.c_char_p]
         L.mi355_bls_compress_signatures_device.argtypes = [vp, vp, sz, vp, vp]
         L.mi355_bls_deserialize_signatures.argtypes = [vp, ctypes.c_char_p, sz, u32, vp, vp]
@@ -839,6 +841,67 @@ def aggregateSignatureSets_device(cache, d_sigs, n_table, d_idx, offsets, d_out1
     st = ctypes.create_string_buffer(k)
     ok = _check(lib().mi355_bls_aggregate_signature_sets_device(cache._h, d_sigs, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k,
                                                                 d_out192 or None, d_out96 or None, st, stream))
+    return bool(ok), st.raw
+
+
+REC_ZERO_ID, REC_DUP_ID = 6, 7         # status bytes of recoverSignatureSets beyond 0 .. 3
+
+
+def idFromUint32(words):
+    """ID.fromUint32 (blst_recovery.nim): 8 uint32 words, words[0] lowest -> the 32 little-endian bytes of the id."""
+    words = [int(w) for w in words]
+    if len(words) != 8 or any(w < 0 or w >= 1 << 32 for w in words):
+        raise ValueError("an id is 8 uint32 words")
+    return b"".join(w.to_bytes(4, "little") for w in words)
+
+
+def _ids_by_position(ids, n_members):
+    """ids: a list of lists of 32-byte ids (one list per group), or their concatenation by position -> n_members x 32 bytes"""
+    if isinstance(ids, (bytes, bytearray, memoryview)):
+        b = bytes(ids)
+        if len(b) % 32:
+            raise ValueError("ids: 32 bytes each")
+    else:
+        flat = []
+        for x in ids:
+            flat += [bytes(x)] if isinstance(x, (bytes, bytearray, memoryview)) else [bytes(e) for e in x]
+        if any(len(e) != 32 for e in flat):
+            raise ValueError("ids: 32 bytes each")
+        b = b"".join(flat)
+    if len(b) != 32 * n_members:
+        raise ValueError("one id per member: %d ids for %d members" % (len(b) // 32, n_members))
+    return b
+
+
+def recoverSignatureSets(cache, signatures, ids, want192=True, want96=True):
+    """recover(signs, ids) (blst_recovery.nim:150-156) for every group of threshold-signature shares in one device pass
+    (mi355_bls_recover_signature_sets); signatures as _signature_lists takes them, ids as a list of lists of 32-byte ids (idFromUint32) or
+    their concatenation by sequence position; an id's value is its 256-bit little-endian integer mod r.  -> (all_ok, k x 192-byte
+    blst_p2_affine images or None, k x 96-byte wire forms or None, k status bytes: 0 recovered, 1 empty group, 2 the recovered point is
+    infinity, 3 index out of range, REC_ZERO_ID, REC_DUP_ID).  VARIABLE TIME: signature shares only, never secret keys."""
+    if not (want192 or want96):
+        raise ValueError("at least one of the two outputs")
+    table, n_table, idx, offs, k = _signature_lists(signatures)
+    idb = _ids_by_position(ids, offs[k] if k else 0)
+    if k == 0:
+        return False, (b"" if want192 else None), (b"" if want96 else None), b""
+    o192 = ctypes.create_string_buffer(192 * k) if want192 else None
+    o96 = ctypes.create_string_buffer(96 * k) if want96 else None
+    st = ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_recover_signature_sets(cache._h, table or b"\0", n_table, idx, offs, k, idb or b"\0", o192, o96, st))
+    return bool(ok), (o192.raw if want192 else None), (o96.raw if want96 else None), st.raw
+
+
+def recoverSignatureSets_device(cache, d_sigs, n_table, d_idx, offsets, d_ids, d_out192, d_out96, stream=0):
+    """Same with the share table, the indices (0 / None: none), the ids (32 bytes per sequence position) and the outputs (0 / None: not
+    wanted; not both) in device memory (raw pointers); offsets stay on the host.  d_out192 is what aggregateSets_device /
+    batchFastAggregateVerify_device take as d_sigs.  -> (all_ok, status bytes)."""
+    k = len(offsets) - 1
+    if k <= 0:
+        return False, b""
+    st = ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_recover_signature_sets_device(cache._h, d_sigs, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k, d_ids,
+                                                              d_out192 or None, d_out96 or None, st, stream))
     return bool(ok), st.raw
 
 

@@ -459,6 +459,57 @@ BLS_HDN jac<F> jac_mul_256_jac(const jac<F>& p, const uint32_t (&kk)[8]) {
     return acc;
 }
 
+// [k]P for a 256-bit scalar (8 little-endian words) with signed 4-bit windows: jac_mul_u64_w4_body's scheme carried to 64 digits plus the
+// final carry - k = sum d_j 16^j, d_j in [-8, 8], a table of 1..8 times P, 256 doublings and at most 65 additions where the bit-serial
+// jac_mul_256 pays an addition at almost every one of its 256 bits in a wave of different scalars.  The digits are not stored: bit j of
+// `cin` is the carry INTO window j, so d_j = nibble_j + cin_j - 16 cin_(j+1) comes out of registers at the window it is used.
+// The accumulator can meet +-T[d] (scalars such as 16^j 8 + 8, or a run of doublings that lands on a table entry): the addition is the
+// complete one.  NOT constant time.  One copy of the doubling, the mixed addition and the addition, as in jac_mul_u64_w4_body.
+template <class F>
+BLS_MID jac<F> jac_mul_256_w4_body(const aff<F>& p, const uint32_t (&kk)[8]) {
+    jac<F> T[8];
+    T[0] = jac_from_aff(p);
+#pragma clang loop unroll(disable)
+    for (int i = 1; i < 8; i++) {
+        if (i & 1)
+            T[i] = jac_dbl(T[i >> 1]);              // 2, 4, 6, 8 times P
+        else
+            T[i] = jac_add_aff(T[i - 1], p);        // 3, 5, 7 times P
+    }
+    uint64_t cin = 0;
+    uint32_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < 64; j++) {
+        cin |= (uint64_t)carry << j;
+        carry = ((kk[j >> 3] >> (4 * (j & 7))) & 15u) + carry > 8u;
+    }
+    jac<F> acc = jac_select(carry != 0, T[0], jac_inf<F>());      // the final carry: digit 64
+#pragma clang loop unroll(disable)
+    for (int w = 7; w >= 0; w--) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++)
+            if (q == w) word = kk[q];
+#pragma clang loop unroll(disable)
+        for (int n = 7; n >= 0; n--) {
+#pragma clang loop unroll(disable)
+            for (int k4 = 0; k4 < 4; k4++) acc = jac_dbl(acc);
+            const int j = 8 * w + n;
+            const int d = (int)((word >> (4 * n)) & 15u) + (int)((cin >> j) & 1u) - 16 * (int)carry;
+            carry = (uint32_t)((cin >> j) & 1u);   // the carry into window j = the carry out of window j - 1: what the next round takes off
+            if (d != 0) {
+                jac<F> t = T[(d < 0 ? -d : d) - 1];
+                if (d < 0) t = jac_neg(t);
+                acc = jac_add_body(acc, t);
+            }
+        }
+    }
+    return acc;
+}
+// out-of-line form (its own register budget); k_recover_mul inlines the body so that the kernel's launch bounds govern it
+template <class F>
+BLS_HDN jac<F> jac_mul_256_w4(const aff<F>& p, const uint32_t (&kk)[8]) { return jac_mul_256_w4_body(p, kk); }
+
 BLS_HD g1_aff g1_aff_load(const uint8_t* p) { return g1_aff{fp_load_le(p), fp_load_le(p + 48)}; }
 BLS_HD g2_aff g2_aff_load(const uint8_t* p) { return g2_aff{fp2_load_le(p), fp2_load_le(p + 96)}; }
 BLS_HD void g1_jac_store(uint8_t* p, const g1_jac& a) {

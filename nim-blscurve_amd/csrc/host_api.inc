@@ -1331,6 +1331,109 @@ extern "C" int mi355_bls_aggregate_signature_sets(mi355_bls_ctx* c, const void* 
     return aggsets_status(c, k, status, nullptr);
 }
 
+// ------------------------------------------------------------------------------------------
+// Threshold-signature recovery: recover(signs, ids) (blst_recovery.nim:150-156; lagrangeInterpolation :90-121 in the exponent) for k groups
+// in one device pass.  The addressing is aggregate_signature_sets' (a table of blst_p2_affine images, optional indices, k + 1 host offsets);
+// ids holds 32 bytes per sequence position.  The call runs in the chunks of plan.hpp recover_chunk_end: per chunk k_recover_mul (a lane per
+// member), the segmented sum (k_combsets_g2_sum at every level, level 0 over the products) and k_recover_finish, all on the caller's stream,
+// then the chunk's status bytes come back (its synchronisation: the host table of the next chunk reuses the vector).  It shares combine_sets'
+// product and partial buffers (d_comb_g2, d_comb_part2) and aggregate_sets' table, flag and status buffers.
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(plan::rec_item) == 16, "k_recover_mul loads an item as one uint4");
+// h_out192 / h_out96: the host form - the device outputs are then the chunk's own (d_aggsig_out) and copied out chunk by chunk
+static int recover_run(mi355_bls_ctx* c, const uint8_t* d_sigs, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k, const uint8_t* d_ids,
+                       uint8_t* d_out192, uint8_t* d_out96, uint8_t* h_out192, uint8_t* h_out96, uint8_t* status, hipStream_t st) {
+    const bool host_out = h_out192 || h_out96;
+    if (!d_sigs || !offsets || !d_ids || !status || (!host_out && !d_out192 && !d_out96)) return MI355_BLS_ERR_ARG;
+    if (((uintptr_t)d_sigs | (uintptr_t)d_idx | (uintptr_t)d_ids | (uintptr_t)d_out192 | (uintptr_t)d_out96) & 3) {
+        g_err = "recover_signature_sets: signatures, indices, ids and outputs must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const plan::recover_plan rp = plan::recover_measure(offsets, k);
+    if (!rp.ok) {
+        g_err = "recover_signature_sets: offsets decrease, or 2^32 - 1 positions or groups, or more";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (!d_idx && offsets[k] > n_table) {
+        g_err = "recover_signature_sets: offsets[k] exceeds the number of signatures";
+        return MI355_BLS_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (host_out) {
+        if (int rc = c->d_aggsig_out.reserve(rp.max_groups * 288, rp.max_groups * 72)) return rc;
+    }
+    std::vector<size_t> ro;
+    int all = 1;
+    for (size_t g0 = 0; g0 < k;) {
+        const size_t g1 = plan::recover_chunk_end(offsets, k, g0), kc = g1 - g0, base = offsets[g0], m = offsets[g1] - base;
+        ro.resize(kc + 1);
+        for (size_t i = 0; i <= kc; i++) ro[i] = offsets[g0 + i] - base;
+        const plan::aggsets_plan p = plan::aggsets_measure(ro.data(), kc);
+        if (!p.ok) return MI355_BLS_ERR_ARG;           // cannot happen below 2^32 - 1 positions
+        const plan::recover_sizes sz = plan::recover_sizes_for(p, m, kc);
+        c->agg_tab.resize(sz.tab / 4);
+        uint32_t* tab = c->agg_tab.data();
+        const size_t t_items = m * 4, t_final = t_items + p.items * 4, t_len = t_final + kc;
+        plan::recover_fill(offsets, g0, g1, reinterpret_cast<plan::rec_item*>(tab));
+        plan::aggsets_fill(p, ro.data(), kc, reinterpret_cast<plan::agg_item*>(tab + t_items), tab + t_final);
+        for (size_t i = 0; i < kc; i++) tab[t_len + i] = (uint32_t)(ro[i + 1] - ro[i]);
+        // grown with a quarter of slack, never beyond what the largest chunk needs; the previous chunk has drained the stream
+        int rc = c->d_comb_g2.reserve(sz.prod, sz.prod / 4);
+        if (!rc) rc = c->d_comb_part2.reserve(sz.part, sz.part / 4);
+        if (!rc) rc = c->d_agg_tab.reserve(sz.tab, sz.tab / 4);
+        if (!rc) rc = c->d_agg_bad.reserve(sz.flags, sz.flags / 4);
+        if (!rc) rc = c->d_agg_status.reserve(sz.status, sz.status / 4);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, sz.flags, st));
+        HIPCHK(hipMemcpyAsync(c->d_agg_tab, tab, sz.tab, hipMemcpyHostToDevice, st));
+        const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
+        if (m)
+            k_recover_mul<<<plan::waves_for((uint32_t)m), WAVE, 0, st>>>(items, (uint32_t)m, reinterpret_cast<const uint32_t*>(d_sigs), n_table, d_idx,
+                                                                        reinterpret_cast<const uint32_t*>(d_ids), (uint32_t)base, c->d_comb_g2, c->d_agg_bad);
+        for (uint32_t l = 0; l < p.levels; l++) {
+            const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
+            k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + m + p.level_first[l], cnt, l == 0 ? c->d_comb_g2.p : c->d_comb_part2.p, c->d_comb_part2);
+        }
+        uint8_t* o192 = host_out ? (h_out192 ? c->d_aggsig_out.p : nullptr) : (d_out192 ? d_out192 + g0 * 192 : nullptr);
+        uint8_t* o96 = host_out ? (h_out96 ? c->d_aggsig_out.p + kc * 192 : nullptr) : (d_out96 ? d_out96 + g0 * 96 : nullptr);
+        k_recover_finish<<<plan::waves_for((uint32_t)kc), WAVE, 0, st>>>(c->d_agg_tab + t_final, c->d_agg_tab + t_len, (uint32_t)kc, c->d_comb_part2, c->d_agg_bad,
+                                                                        reinterpret_cast<uint32_t*>(o192), reinterpret_cast<uint32_t*>(o96), c->d_agg_status);
+        HIPCHK(hipGetLastError());
+        if (h_out192) HIPCHK(hipMemcpyAsync(h_out192 + g0 * 192, o192, kc * 192, hipMemcpyDeviceToHost, st));
+        if (h_out96) HIPCHK(hipMemcpyAsync(h_out96 + g0 * 96, o96, kc * 96, hipMemcpyDeviceToHost, st));
+        const int ok = aggsets_status(c, kc, status + g0, st);
+        if (ok < 0) return ok;
+        all &= ok;
+        g0 = g1;
+    }
+    return all;
+}
+extern "C" int mi355_bls_recover_signature_sets_device(mi355_bls_ctx* c, const void* d_sigs192, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                                       size_t k, const void* d_ids32, void* d_out_sigs192, void* d_out_sigs96, uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing recovered, nothing written
+    return recover_run(c, (const uint8_t*)d_sigs192, n_table, d_idx, offsets, k, (const uint8_t*)d_ids32, (uint8_t*)d_out_sigs192, (uint8_t*)d_out_sigs96, nullptr,
+                       nullptr, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_recover_signature_sets(mi355_bls_ctx* c, const void* sigs192, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                                const void* ids32, void* out_sigs192, void* out_sigs96, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!sigs192 || !offsets || !ids32 || !status || (!out_sigs192 && !out_sigs96) || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    // signatures | ids | indices -> d_agg_in (every part 4-byte aligned)
+    const size_t n_idx = idx ? offsets[k] : 0, sb = n_table * 192, ib = offsets[k] * 32, all = sb + ib + n_idx * 4 + 4;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = c->d_agg_in.reserve(all, all / 4)) return rc;
+    uint8_t* d = c->d_agg_in;
+    if (sb) HIPCHK(hipMemcpyAsync(d, sigs192, sb, hipMemcpyHostToDevice, nullptr));
+    if (ib) HIPCHK(hipMemcpyAsync(d + sb, ids32, ib, hipMemcpyHostToDevice, nullptr));
+    if (n_idx) HIPCHK(hipMemcpyAsync(d + sb + ib, idx, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+    return recover_run(c, d, n_table, idx ? reinterpret_cast<const uint32_t*>(d + sb + ib) : nullptr, offsets, k, d + sb, nullptr, nullptr, (uint8_t*)out_sigs192,
+                       (uint8_t*)out_sigs96, status, nullptr);
+}
+
 // serialize for n signatures (bls_sig_io.nim:225-234).  The device form leaves the bytes in device memory and returns when they are there.
 extern "C" int mi355_bls_compress_signatures_device(mi355_bls_ctx* c, const void* d_sigs192, size_t n, void* d_out96, void* stream) {
     if (!c) return MI355_BLS_ERR_ARG;

@@ -37,6 +37,7 @@
 #include "aggsets.hpp"
 #include "combsets.hpp"
 #include "aggsigs.hpp"
+#include "recover.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -2533,6 +2534,50 @@ __global__ void __launch_bounds__(WAVE) k_deser_sigs(const uint8_t* __restrict__
     sg = g2_aff{fp2_select(ok, sg.x, fp2_zero()), fp2_select(ok, sg.y, fp2_zero())};
     uint32_t* o = out + (size_t)i * 48;
     st_fp_blst(o, sg.x.c0); st_fp_blst(o + 12, sg.x.c1); st_fp_blst(o + 24, sg.y.c0); st_fp_blst(o + 36, sg.y.c1);
+}
+
+// ------------------------------------------------------------------------------------------
+// Threshold-signature recovery of many groups (mi355_bls_recover_signature_sets: recover(signs, ids), blst_recovery.nim:150-156, i.e.
+// lagrangeInterpolation :90-121 in the exponent, for k groups in one pass).  The arithmetic is csrc/recover.hpp and csrc/fr.hpp; the member
+// items are plan.hpp recover_fill's (the four words pos, seg_first, seg_len, seg of plan::rec_item, one 16-byte load).  Per member:
+// k_recover_mul.  Per group: the segmented sum over plan.hpp aggsets_fill's tables by k_combsets_g2_sum as it stands - level 0 reads the
+// products by position - and k_recover_finish.
+// ------------------------------------------------------------------------------------------
+// one lane per member of a chunk: its Lagrange coefficient from the ids of its group (ids: 32 little-endian bytes per position of the call,
+// 4-byte aligned), then [coefficient] S for its share S (a 192-byte blst_p2_affine image; through idx into a table of n_table shares when
+// idx != nullptr) -> product number pos - base of `prod` (internal G2 image).  The window table of curve.hpp jac_mul_256_w4_body is the
+// lane's own.  An index that is not below n_table is not dereferenced.  The lane's flags go into its group's word.
+__global__ void __launch_bounds__(WAVE) k_recover_mul(const uint4* __restrict__ items, uint32_t n_items, const uint32_t* __restrict__ sigs, size_t n_table,
+                                                      const uint32_t* __restrict__ idx, const uint32_t* __restrict__ ids, uint32_t base,
+                                                      uint32_t* __restrict__ prod, uint32_t* __restrict__ seg_flags) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    uint32_t fl = 0;
+    const fr_words cf = recover_coeff_item(it.x, it.y, it.z, [&](uint32_t pos) {
+        uint32_t w[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) w[j] = ids[(size_t)pos * 8 + j];
+        return fr_from_words(w);
+    }, fl);
+    const g2_jac r = recover_mul_item(cf, it.x, idx, n_table, [&](size_t t) { return ld_g2a_blst(sigs + t * 48); }, fl);
+    if (fl) atomicOr(seg_flags + it.w, fl);
+    st_g2_int(prod + (size_t)(it.x - base) * G2W, r);
+}
+// one lane per group of a chunk: its last partial (final_of[g]; 0xffffffff: no member at all) to affine; the 192-byte image to out192, the
+// 96-byte wire form to out96 (either may be null), packed by group, and the status byte (recover_finish_item)
+__global__ void __launch_bounds__(WAVE) k_recover_finish(const uint32_t* __restrict__ final_of, const uint32_t* __restrict__ seg_len, uint32_t k,
+                                                         const uint32_t* __restrict__ part, const uint32_t* __restrict__ seg_flags, uint32_t* __restrict__ out192,
+                                                         uint32_t* __restrict__ out96, uint8_t* __restrict__ status) {
+    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= k) return;
+    const uint32_t f = final_of[g];
+    const aggsigs_end e = recover_finish_item(seg_len[g], seg_flags[g], f == 0xffffffffu ? jac_inf<fp2>() : ld_g2_int(part + (size_t)f * G2W));
+    if (out192)
+        for (int i = 0; i < 48; i++) out192[(size_t)g * 48 + i] = e.sig[i];
+    if (out96)
+        for (int i = 0; i < 24; i++) out96[(size_t)g * 24 + i] = e.wire[i];
+    status[g] = e.status;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -406,6 +406,67 @@ inline aggsigs_sizes aggsigs_sizes_for(const aggsets_plan& p, size_t k) {
     return {(p.items ? p.items : 1) * (size_t)G2_WORDS * 4, (p.items * 4 + k) * 4, k * 4, k, k * 192, k * 96};
 }
 
+// Threshold-signature recovery of k groups (mi355_bls_recover_signature_sets): one lane per member computes its Lagrange coefficient and
+// its product [l]S (k_recover_mul: waves_for(members) workgroups of WAVE lanes), the products are summed per group by the segmented sum of
+// aggsets_measure / aggsets_fill over the renumbered offsets (level 0 reads the products by position, as combine_sets does), and a lane per
+// group finishes (k_recover_finish).
+//   A product is an internal G2 image of 384 bytes, so a call runs in CHUNKS of whole groups and the workspace holds one chunk: a chunk takes
+//   groups while it stays within REC_MEMBERS_CHUNK members and REC_MEMBERS_CHUNK groups (empty groups have no members to count), and a
+//   group longer than that is a chunk of its own.  REC_MEMBERS_CHUNK is a MEMORY bound (24 MiB of products), not a tuned value: 65 536
+//   lanes are already 1 024 waves, one per SIMD of the chip, so a larger chunk has nothing to win.
+//   Refused: offsets that decrease, and what the 32-bit tables cannot address (2^32 - 1 positions or groups, or more).  Nothing for its size.
+constexpr size_t REC_MEMBERS_CHUNK = 65536;
+struct rec_item {
+    uint32_t pos, seg_first, seg_len, seg;   // the member at position pos of the call; its group's first position, length and number within the chunk
+};
+// groups [g0, end) are the chunk that starts at group g0 < k (chunk: the product takes the constant; the CPU tests walk small ones)
+inline size_t recover_chunk_end(const size_t* offsets, size_t k, size_t g0, size_t chunk = REC_MEMBERS_CHUNK) {
+    size_t g = g0 + 1;                       // one group at least, however long
+    while (g < k && g - g0 < chunk && offsets[g + 1] - offsets[g0] <= chunk) g++;
+    return g;
+}
+struct recover_plan {
+    bool ok;
+    size_t lo, members;                      // positions [lo, lo + members) of the member sequence
+    size_t chunks;
+    size_t max_members, max_groups;          // of the largest chunk: what the workspace is sized by
+};
+inline recover_plan recover_measure(const size_t* offsets, size_t k, size_t chunk = REC_MEMBERS_CHUNK) {
+    recover_plan p{};
+    if (k >= AGG_NONE) return p;
+    for (size_t g = 0; g < k; g++)
+        if (offsets[g + 1] < offsets[g]) return p;
+    if (k && offsets[k] >= AGG_NONE) return p;
+    p.lo = k ? offsets[0] : 0;
+    p.members = k ? offsets[k] - p.lo : 0;
+    for (size_t g0 = 0; g0 < k;) {
+        const size_t g1 = recover_chunk_end(offsets, k, g0, chunk), m = offsets[g1] - offsets[g0];
+        if (m > p.max_members) p.max_members = m;
+        if (g1 - g0 > p.max_groups) p.max_groups = g1 - g0;
+        p.chunks++;
+        g0 = g1;
+    }
+    p.ok = true;
+    return p;
+}
+// the member items of a chunk (groups [g0, g1), m = offsets[g1] - offsets[g0] entries)
+inline void recover_fill(const size_t* offsets, size_t g0, size_t g1, rec_item* items) {
+    size_t at = 0;
+    for (size_t g = g0; g < g1; g++)
+        for (size_t pos = offsets[g]; pos < offsets[g + 1]; pos++)
+            items[at++] = rec_item{(uint32_t)pos, (uint32_t)offsets[g], (uint32_t)(offsets[g + 1] - offsets[g]), (uint32_t)(g - g0)};
+}
+// The workspace of one chunk of `members` members in `groups` groups whose segmented sum is `p`, in bytes: the products, the sum's
+// partials (one at least), the tables (member items | sum items | final_of | group lengths), a flag word and a status byte per group, and
+// the host form's two output arrays.
+struct recover_sizes {
+    size_t prod, part, tab, flags, status, out192, out96;
+};
+inline recover_sizes recover_sizes_for(const aggsets_plan& p, size_t members, size_t groups) {
+    return {(members ? members : 1) * (size_t)G2_WORDS * 4, (p.items ? p.items : 1) * (size_t)G2_WORDS * 4, ((members + p.items) * 4 + 2 * groups) * 4,
+            groups * 4, groups, groups * 192, groups * 96};
+}
+
 // ------------------------------------------------------------------------------------------
 // Pippenger MSM (blst_p1s_mult_pippenger / blst_p2s_mult_pippenger): what msm_enqueue follows, and what msm_reserve allocates.
 // ------------------------------------------------------------------------------------------
