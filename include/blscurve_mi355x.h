@@ -333,6 +333,36 @@ int mi355_bls_aggregate_signature_sets(mi355_bls_ctx* ctx, const void* sigs192, 
                                        void* out_sigs192, void* out_sigs96, uint8_t* status);
 int mi355_bls_aggregate_signature_sets_device(mi355_bls_ctx* ctx, const void* d_sigs192, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
                                               size_t k, void* d_out_sigs192, void* d_out_sigs96, uint8_t* status, void* stream);
+/* aggregateVerify for MANY groups in ONE device pass: aggregateVerify(publicKeys, messages, signature) (bls_sig_min_pubkey.nim:127-199 ->
+ * ContextCoreAggregateVerify, blst_min_pubkey_sig_core.nim:305-414) for k groups of (key, message) pairs with DISTINCT messages, each under one
+ * aggregate signature: out[g] = [ e(-G1, sig_g) * prod_j e(pk_gj, H(m_gj)) == 1 ].  mi355_bls_aggregate_verify checks one aggregate per call
+ * and pays a device call and a synchronisation for each.
+ *   keys, n_table, idx, offsets   the addressing of mi355_bls_aggregate_sets: a table of 96-byte blst_p1_affine images; idx == NULL: group g is
+ *             keys [offsets[g], offsets[g+1]) of the table (offsets[k] <= n_table); else group g is keys idx[offsets[g]] ..
+ *             idx[offsets[g+1] - 1] (offsets[k] = the length of idx; repeats allowed).  offsets: k + 1 entries in HOST memory, non-decreasing.
+ *   msgs32    offsets[k] x 32 bytes: the message of every POSITION p at byte 32 p - by position, never through idx.  Messages are 32 bytes
+ *             (signing roots) as in every batched entry point; other lengths stay with mi355_bls_aggregate_verify, one aggregate per call.
+ *   sigs192   k x 192-byte blst_p2_affine images, packed, one per group: the very buffer mi355_bls_aggregate_signature_sets_device writes.
+ *   out       k bytes, host memory: 0 or 1.  0 for an empty group (bls_sig_min_pubkey.nim:167-169), for a group with a key at infinity (update
+ *             returns false) and for a group with an index >= n_table, which is never dereferenced.  A signature at infinity contributes
+ *             e(-G1, inf) = 1, as in mi355_bls_verify_each.
+ * Device pointers are 4-byte aligned.  Preconditions as the reference's: keys and signatures decoded and group-checked, proofs of possession
+ * verified by the caller.  No input is refused for its size: the call runs in slices of at most max_sets pairs - whole groups while they fit,
+ * a longer group in parts whose Miller values are multiplied together on the device - and the workspace is sized by a slice, not by the call
+ * (up to 2^32 - 2 pairs and groups: the tables are 32-bit).
+ * Returns 1 iff every out[g] is 1; k == 0: 0, nothing written.  MI355_BLS_ERR_ARG for decreasing offsets, offsets[k] > n_table without idx,
+ * NULL pointers.  The _device form enqueues on `stream` and synchronises it once, for the verdict bytes.
+ * The width of the per-step line products (csrc/plan.hpp AGGV_C = 8) and the hand-over between the two tail forms (verify_each's) are not
+ * measured for this path.  COST against one mi355_bls_aggregate_verify call per group: nim-blscurve_amd/tools/bench_aggverify_each.py
+ * writes profiles/aggregate_verify_each_bench.json on an MI355X; README.md says whether it has been run.
+ * debug_aggregate_verify_each_gt: TEST HOOK, the host form with gt_out = k x 576 bytes, the blst_fp12 image of every group's final
+ * exponentiation (zero bytes for an empty group). */
+int mi355_bls_aggregate_verify_each(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                    const void* msgs32, const void* sigs192, uint8_t* out);
+int mi355_bls_aggregate_verify_each_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                           const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream);
+int mi355_bls_debug_aggregate_verify_each_gt(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                             const void* msgs32, const void* sigs192, uint8_t* out, uint8_t* gt_out);
 /* serialize(Signature) (bls_sig_io.nim:225-234), i.e. blst_p2_affine_compress, for n signatures: 192-byte blst_p2_affine images in, 96 bytes
  * each out (ZCash form: big-endian x.c1 then x.c0, bit 7 of byte 0 set, bit 5 set when y is the lexicographically larger root - decided by
  * y.c1 unless it is zero, then by y.c0; the all-zero infinity image gives 0xc0 and 95 zero bytes).  The device form writes device memory

@@ -118,6 +118,9 @@ def lib():
         L.mi355_bls_fast_aggregate_verify_each_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_batch_fast_aggregate_verify.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, ctypes.c_char_p]
         L.mi355_bls_batch_fast_aggregate_verify_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, ctypes.c_char_p, vp]
+        L.mi355_bls_aggregate_verify_each.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp]
+        L.mi355_bls_aggregate_verify_each_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
+        L.mi355_bls_debug_aggregate_verify_each_gt.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_aggregate_signature_sets.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp]
         L.mi355_bls_aggregate_signature_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_recover_signature_sets.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp, vp]
@@ -786,6 +789,62 @@ def batchFastAggregateVerify_device(cache, d_keys, n_table, d_idx, offsets, d_ms
         return False
     return bool(_check(lib().mi355_bls_batch_fast_aggregate_verify_device(cache._h, d_keys, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k,
                                                                           d_msgs, d_sigs, rnd, stream)))
+
+
+def _position_messages(messages, n_positions):
+    """The per-position messages of aggregateVerifyEach -> n_positions x 32 bytes.  messages: their concatenation, a flat list of 32-byte
+    messages, or a list of per-group lists (laid end to end, like the key lists of _key_lists)."""
+    if isinstance(messages, (bytes, bytearray, memoryview)):
+        ms = bytes(messages)
+    else:
+        ms = b"".join(bytes(e) if isinstance(e, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in e) for e in messages)
+    if len(ms) != 32 * n_positions:
+        raise ValueError("one 32-byte message per position: %d x 32 bytes" % n_positions)
+    return ms
+
+
+def _pair_lists(keys, messages, signatures):
+    """keys as _key_lists takes them, one 192-byte signature per group, one 32-byte message per position (_position_messages)."""
+    k = len(keys[2]) - 1 if isinstance(keys, tuple) else len(keys)
+    table, n_table, idx, offs, k, _, sg = _key_lists(keys, bytes(32 * max(k, 0)), signatures)
+    return table, n_table, idx, offs, k, _position_messages(messages, offs[k]), sg
+
+
+def aggregateVerifyEach(cache, keys, messages, signatures):
+    """aggregateVerify (bls_sig_min_pubkey.nim:127-199) for every group of (key, message) pairs under its aggregate signature, in one device
+    pass (mi355_bls_aggregate_verify_each): -> [bool], one per group.  keys as _key_lists takes them; messages: one 32-byte message per
+    position (_position_messages); signatures: one 192-byte blst_p2_affine image per group.  An empty group, a group with an infinity key
+    and a group with an index out of the table give False."""
+    table, n_table, idx, offs, k, ms, sg = _pair_lists(keys, messages, signatures)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_aggregate_verify_each(cache._h, table or b"\0", n_table, idx, offs, k, ms or b"\0", sg, out))
+    return [v == 1 for v in out.raw]
+
+
+def aggregateVerifyEach_device(cache, d_keys, n_table, d_idx, offsets, d_msgs, d_sigs, stream=0):
+    """Same with the key table, the indices (0 / None: none), the per-position messages and the k signatures in device memory (raw
+    pointers); offsets stay on the host.  d_sigs is what aggregateSignatureSets_device writes as d_out192."""
+    k = len(offsets) - 1
+    if k <= 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_aggregate_verify_each_device(cache._h, d_keys, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k, d_msgs, d_sigs,
+                                                         out, stream))
+    return [v == 1 for v in out.raw]
+
+
+def aggregateVerifyEachValues(cache, keys, messages, signatures):
+    """Test hook (mi355_bls_debug_aggregate_verify_each_gt): -> ([bool], [576-byte blst_fp12 image of final_exp(f_g)]); an empty group's
+    value is 576 zero bytes."""
+    table, n_table, idx, offs, k, ms, sg = _pair_lists(keys, messages, signatures)
+    if k == 0:
+        return [], []
+    out, gt = ctypes.create_string_buffer(k), ctypes.create_string_buffer(k * 576)
+    _check(lib().mi355_bls_debug_aggregate_verify_each_gt(cache._h, table or b"\0", n_table, idx, offs, k, ms or b"\0", sg, out, gt))
+    raw = gt.raw
+    return [v == 1 for v in out.raw], [raw[576 * i:576 * i + 576] for i in range(k)]
 
 
 def _signature_lists(signatures):

@@ -140,6 +140,14 @@ struct mi355_bls_ctx {
     // per-group signature aggregation (mi355_bls_aggregate_signature_sets): sized by the call (plan.hpp aggsigs_sizes_for), made at the first
     // such call; it shares the item table, flag words, status bytes and staged inputs above and combine_sets' G2 partials (d_comb_part2)
     dev_buf<uint8_t> d_aggsig_out;   // the host form's outputs: k x 192 bytes | k x 96 bytes
+    // per-group aggregateVerify (mi355_bls_aggregate_verify_each): sized by the largest SLICE of a call (plan.hpp aggveach_*), grown on demand;
+    // it shares the per-set path's pair store, verdict bytes and values, the flag words above and, for the host form, the staged inputs
+    dev_buf<uint32_t> d_aggv_part;   // the partials of a slice: per Miller step an Fp12 each
+    dev_buf<uint32_t> d_aggv_step;   // the step values of a slice's groups: N_LINES x F12W words per group
+    dev_buf<uint32_t> d_aggv_tab;    // a slice's groups | items
+    dev_buf<uint32_t> d_aggv_carry;  // the open group's Miller value (a blst_fp12 image), and a second slot for the engine form's part
+    dev_buf<uint32_t> d_aggv_work;   // the engine form's block per workgroup
+    std::vector<uint32_t> aggv_tab;  // the tables of every slice of the call in flight: the async copies read them
 
     // the batch workspace's pair store (ctx_build makes it; it never changes) and the per-set path's (each_reserve)
     pair_store batch_pairs() const { return {d_H, d_P, d_lines, stride}; }
@@ -1247,6 +1255,155 @@ extern "C" int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* c, const voi
     int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
     if (rc) return rc;
     return agg_batch(c, in, n_table, offsets, k, rnd, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-group aggregateVerify: aggregateVerify (bls_sig_min_pubkey.nim:127-199 -> ContextCoreAggregateVerify, core :305-414) for k groups of
+// (key, message) pairs with one aggregate signature each, in one device pass.  The keys are addressed as aggregate_sets addresses them; the
+// messages are 32 bytes each and follow the POSITIONS (never the indices).  The call runs in slices of at most max_sets pairs (plan.hpp
+// aggveach_cut): per slice one copy of its tables, the records and pair slots (k_aggveach_records), hashing and Miller lines in the forms the
+// per-set path takes, the segmented line product level by level, and the tail in the form plan::aggveach_for names.  A group longer than a
+// slice hands its Miller value from part to part in d_aggv_carry.  The verdict bytes of all slices collect in d_each_v and come back in one
+// copy: the call's only synchronisation.
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(plan::aggv_group) == 16, "k_aggveach_* load a group as one uint4");
+static int aggveach_run(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, uint8_t* out, uint8_t* gt_out, hipStream_t st) {
+    if (!in.keys || !in.msgs || !in.sigs || !offsets || !out) return MI355_BLS_ERR_ARG;
+    if (((uintptr_t)in.keys | (uintptr_t)in.msgs | (uintptr_t)in.sigs | (uintptr_t)in.idx) & 3) {
+        g_err = "aggregate_verify_each: keys, messages, signatures and indices must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (k >= plan::AGG_NONE || !agg_offsets_ok(offsets, k) || offsets[k] >= plan::AGG_NONE) {
+        g_err = "aggregate_verify_each: offsets decrease, or more than 2^32 - 2 pairs or groups";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (!in.idx && offsets[k] > n_table) {
+        g_err = "aggregate_verify_each: offsets[k] exceeds the number of keys";
+        return MI355_BLS_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    // pass 1: the slices and their tables (groups | items, slice after slice), and what the largest slice needs
+    struct slice_rec {
+        plan::aggv_slice s;
+        plan::aggveach_tab t;
+        size_t tab_at;
+    };
+    std::vector<slice_rec> slices;
+    c->aggv_tab.clear();
+    size_t max_part = 0, max_ng = 0, max_tab = 0;
+    for (size_t g = 0, pos = offsets[0];;) {
+        const plan::aggv_slice s = plan::aggveach_cut(offsets, k, g, pos, c->cap);
+        if (s.pairs() == 0) break;
+        const size_t at = c->aggv_tab.size();
+        c->aggv_tab.resize(at + (size_t)s.ng * 4);
+        plan::aggveach_groups(offsets, s, reinterpret_cast<plan::aggv_group*>(c->aggv_tab.data() + at));
+        const plan::aggveach_tab t = plan::aggveach_measure(reinterpret_cast<const plan::aggv_group*>(c->aggv_tab.data() + at), s.ng);
+        c->aggv_tab.resize(at + ((size_t)s.ng + t.items) * 4);
+        plan::aggveach_fill(t, reinterpret_cast<const plan::aggv_group*>(c->aggv_tab.data() + at), s.ng,
+                            reinterpret_cast<plan::agg_item*>(c->aggv_tab.data() + at + (size_t)s.ng * 4));
+        slices.push_back({s, t, at});
+        if (t.partials > max_part) max_part = t.partials;
+        if (s.ng > max_ng) max_ng = s.ng;
+        if (((size_t)s.ng + t.items) * 4 > max_tab) max_tab = ((size_t)s.ng + t.items) * 4;
+        g = s.next_g(), pos = s.pos1;
+    }
+    int rc = each_reserve(c, k, gt_out != nullptr);
+    const size_t pw = plan::aggveach_part_words(max_part) * 4, sw = plan::aggveach_step_words(max_ng) * 4;
+    if (!rc) rc = c->d_agg_bad.reserve(k * 4, k);
+    if (!rc) rc = c->d_aggv_part.reserve(pw, pw / 4);
+    if (!rc) rc = c->d_aggv_step.reserve(sw, sw / 4);
+    if (!rc) rc = c->d_aggv_tab.reserve(max_tab * 4 + 16, max_tab);
+    if (!rc) rc = c->d_aggv_carry.reserve(2 * 576, 0);
+    if (!rc) rc = c->d_aggv_work.reserve((size_t)plan::each_engine_grid_max(c->slots) * AGGV_WORK_WORDS * 4, 0);
+    if (rc) return rc;
+    const pair_store ps = c->each_pairs();
+    HIPCHK(hipEventRecord(c->ev[0], st));
+    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, k * 4, st));
+    HIPCHK(hipMemsetAsync(c->d_each_v, 0, k, st));                     // an empty group has no lane: its verdict is 0, its value zero bytes
+    if (gt_out) HIPCHK(hipMemsetAsync(c->d_each_gt, 0, k * 576, st));
+    uint32_t* dg = gt_out ? c->d_each_gt.p : nullptr;
+    for (const slice_rec& sr : slices) {
+        const plan::aggv_slice& s = sr.s;
+        const uint32_t P = (uint32_t)s.pairs(), nsig = s.sigs();
+        const plan::aggveach_plan p = plan::aggveach_for(c->slots, c->coop, P, nsig, s.ng);
+        HIPCHK(hipMemcpyAsync(c->d_aggv_tab, c->aggv_tab.data() + sr.tab_at, ((size_t)s.ng + sr.t.items) * 16, hipMemcpyHostToDevice, st));
+        const uint4* gtab = reinterpret_cast<const uint4*>(c->d_aggv_tab.p);
+        const uint4* items = gtab + s.ng;
+        k_aggveach_records<<<p.setup_grid, WAVE, 0, st>>>(in.keys, n_table, in.idx, s.pos0, P, reinterpret_cast<const uint32_t*>(in.msgs), gtab, s.ng, nsig,
+                                                          reinterpret_cast<const uint32_t*>(in.sigs), reinterpret_cast<uint32_t*>(c->d_sets.p), ps.H, ps.P,
+                                                          ps.stride, c->d_agg_bad);
+        launch_hash_map(c, c->d_sets, P, st);                              // H(msg_i) -> pair slot i, in the forms the batch path takes for P messages
+        launch_hash_clear(c, ps, P, st);
+        launch_lines(ps, p.lines, st);
+        const uint32_t n_part = (uint32_t)(sr.t.partials ? sr.t.partials : 1);
+        for (uint32_t l = 0; l < sr.t.levels; l++) {
+            const uint32_t cnt = (uint32_t)(sr.t.level_first[l + 1] - sr.t.level_first[l]);
+            const dim3 grid(plan::waves_for(cnt), N_LINES);
+            if (l == 0) k_aggveach_l0<<<grid, WAVE, 0, st>>>(items, cnt, ps.lines, ps.stride, P, c->d_aggv_part, n_part, c->d_aggv_step);
+            else k_aggveach_ln<<<grid, WAVE, 0, st>>>(items + sr.t.level_first[l], cnt, c->d_aggv_part, n_part, c->d_aggv_step);
+        }
+        if (!p.tail_engine) {
+            k_aggveach_tail<<<p.tail_grid, WAVE, 0, st>>>(c->d_aggv_step, gtab, s.ng, c->d_agg_bad, c->d_aggv_carry, c->d_each_v, dg);
+        } else {
+            k_aggveach_engine_rows<<<p.tail_grid, K_TAIL_THREADS, 0, st>>>(c->d_aggv_step, gtab, s.ng, c->d_agg_bad, c->d_aggv_carry, c->d_each_v, dg, c->d_aggv_work);
+            if (s.open_in && s.open_out) k_state_mul<<<1, TAIL_THREADS, 0, st>>>(c->d_aggv_carry, 0, 0, 1);      // the part's value into the carried one
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev[1], st));
+    HIPCHK(hipMemcpyAsync(out, c->d_each_v, k, hipMemcpyDeviceToHost, st));
+    if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, c->d_each_gt, k * 576, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->last_n = 0;                             // fetch_stage shows the last call, and this one left no batch stages
+    c->sig_slots = 0;
+    c->agg_valid = false;
+    c->have_gt = false;
+    rc = collect_timings(c, 1);
+    if (rc) return rc;
+    int all = 1;
+    for (size_t g = 0; g < k; g++) all &= out[g] == 1;
+    return all;
+}
+extern "C" int mi355_bls_aggregate_verify_each_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                                      const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing verified, nothing written
+    return aggveach_run(c, agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, n_table, offsets, k, out, nullptr,
+                        (hipStream_t)stream);
+}
+// host inputs -> d_agg_in (keys | signatures | messages by position | indices: every part 4-byte aligned), then the device form
+static int aggveach_host(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k, const void* msgs32,
+                         const void* sigs192, uint8_t* out, uint8_t* gt_out) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!keys || !offsets || !msgs32 || !sigs192 || !out || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
+    if (offsets[k] >= plan::AGG_NONE || (!idx && offsets[k] > n_table)) {      // before anything is staged (aggveach_run says the same)
+        g_err = "aggregate_verify_each: offsets[k] exceeds the number of keys, or 2^32 - 2 pairs";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const size_t n_pos = offsets[k], kb = n_table * 96, sb = k * 192, mb = n_pos * 32, all = kb + sb + mb + (idx ? n_pos * 4 : 0) + 4;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->d_agg_in.reserve(all, all / 4);
+    if (rc) return rc;
+    uint8_t* d = c->d_agg_in;
+    if (kb) HIPCHK(hipMemcpyAsync(d, keys, kb, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(d + kb, sigs192, sb, hipMemcpyHostToDevice, nullptr));
+    if (mb) HIPCHK(hipMemcpyAsync(d + kb + sb, msgs32, mb, hipMemcpyHostToDevice, nullptr));
+    if (idx && n_pos) HIPCHK(hipMemcpyAsync(d + kb + sb + mb, idx, n_pos * 4, hipMemcpyHostToDevice, nullptr));
+    const agg_in in{d, idx ? reinterpret_cast<const uint32_t*>(d + kb + sb + mb) : nullptr, d + kb + sb, d + kb};
+    return aggveach_run(c, in, n_table, offsets, k, out, gt_out, nullptr);
+}
+extern "C" int mi355_bls_aggregate_verify_each(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                               const void* msgs32, const void* sigs192, uint8_t* out) {
+    return aggveach_host(c, keys, n_table, idx, offsets, k, msgs32, sigs192, out, nullptr);
+}
+// TEST HOOK: the same pass with the 576-byte value of every group (zero bytes for an empty group)
+extern "C" int mi355_bls_debug_aggregate_verify_each_gt(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                                        const void* msgs32, const void* sigs192, uint8_t* out, uint8_t* gt_out) {
+    if (k && !gt_out) return MI355_BLS_ERR_ARG;
+    return aggveach_host(c, keys, n_table, idx, offsets, k, msgs32, sigs192, out, gt_out);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@
 #include "h2c.hpp"
 #include "pairing.hpp"
 #include "vereach.hpp"
+#include "aggveach.hpp"
 #include "aggsets.hpp"
 #include "combsets.hpp"
 #include "aggsigs.hpp"
@@ -2354,6 +2355,136 @@ __global__ void __launch_bounds__(TAIL_THREADS) k_each_engine(const uint4* __res
 __global__ void __launch_bounds__(K_TAIL_THREADS) k_each_engine_rows(const uint4* __restrict__ lines, size_t stride, uint32_t m, const uint8_t* __restrict__ sets,
                                                                      uint8_t* __restrict__ verdicts, uint32_t* __restrict__ gt, uint32_t* __restrict__ work) {
     each_engine_body<true>(lines, stride, m, sets, verdicts, gt, work);
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-group aggregateVerify of many groups (mi355_bls_aggregate_verify_each; aggregateVerify, bls_sig_min_pubkey.nim:127-199, for every group
+// of a call): the arithmetic is csrc/aggveach.hpp, the slices, groups and item tables are plan.hpp aggveach_*'s.  A slice of P pairs in ng
+// groups uses P + nsig pairs of the per-set path's pair store: pair i = (pk_i, H(msg_i)), H where the hashing kernels leave it; pair
+// P + l = (-G1, sig) of the slice's group l (every group but one that goes on into the next slice).  gtab: the slice's groups, the four
+// words g, first, count, flags of plan::aggv_group, one 16-byte load.
+// ------------------------------------------------------------------------------------------
+// One lane per pair slot.  i < P: the key of position pos0 + i (through idx into the table of n_table keys when idx != nullptr; an index
+// that is not below n_table is not dereferenced) and the position's message into record i of `recs` (the 320-byte layout the hash-map kernels
+// read: key at 0, message at 96), the key into pair slot i; an infinity key or a bad index raises the word of the pair's group in `bad`
+// (indexed by the group's number in the call).  P <= i < P + nsig: (-G1, sig of group i - P) into pair slot i.
+__global__ void __launch_bounds__(WAVE) k_aggveach_records(const uint8_t* __restrict__ keys, size_t n_table, const uint32_t* __restrict__ idx, size_t pos0, uint32_t P,
+                                                           const uint32_t* __restrict__ msgs, const uint4* __restrict__ gtab, uint32_t ng, uint32_t nsig,
+                                                           const uint32_t* __restrict__ sigs, uint32_t* __restrict__ recs, uint4* __restrict__ H,
+                                                           uint4* __restrict__ Pst, size_t stride, uint32_t* __restrict__ bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < P) {
+        uint32_t lo = 0, hi = ng - 1;                        // the last group whose first pair is not behind i
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1) >> 1;
+            if (gtab[mid].y <= i) lo = mid; else hi = mid - 1;
+        }
+        const size_t pos = pos0 + i, t = idx ? (size_t)idx[pos] : pos;
+        const bool in_table = t < n_table;
+        uint32_t* r = recs + (size_t)i * 80;
+        const uint32_t* kw = reinterpret_cast<const uint32_t*>(keys + (in_table ? t : 0) * 96);
+        for (int j = 0; j < 24; j++) r[j] = in_table ? kw[j] : 0u;
+        for (int j = 0; j < 8; j++) r[24 + j] = msgs[pos * 8 + j];
+        const g1_aff pk = ld_g1a_blst(r);
+        if (!in_table || aff_is_inf(pk)) atomicOr(bad + gtab[lo].x, 1u);
+        soa_st_g1(Pst, stride, i, jac_from_aff(pk));
+    } else if (i < P + nsig) {
+        soa_st_g1(Pst, stride, i, g1_jac{fp_from_const(k::G1_X), fp_from_const(k::G1_NEG_Y), fp_one()});
+        soa_st_g2(H, stride, i, jac_from_aff(ld_g2a_blst(sigs + (size_t)gtab[i - P].x * 48)));
+    }
+}
+// The segmented line product, one lane per (item, step): blockIdx.y = the Miller step, the items of a step side by side in the wave (the
+// line store is SoA by pair within a step: the lanes of consecutive items read pairs C apart of the same plane).  A FINAL item writes its
+// group's step value (reduced: the Fp12 engine takes it as it is), any other partial it.z of the step.
+__device__ __forceinline__ void aggveach_put(const uint4& it, uint32_t s, const fp12& v, uint32_t* __restrict__ part, uint32_t n_part, uint32_t* __restrict__ step) {
+    if (it.y & plan::AGGV_FINAL) st_fp12_int(step + ((size_t)it.z * N_LINES + s) * F12W, fp12_reduce(v));
+    else st_fp12_int(part + ((size_t)s * n_part + it.z) * F12W, v);
+}
+__global__ void __launch_bounds__(WAVE) k_aggveach_l0(const uint4* __restrict__ items, uint32_t n_items, const uint4* __restrict__ lines, size_t stride, uint32_t P,
+                                                      uint32_t* __restrict__ part, uint32_t n_part, uint32_t* __restrict__ step) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    const uint4* b = lines + (size_t)s * 24 * stride;
+    const fp12 v = aggveach_l0_item(it.x, it.y & plan::AGGV_COUNT, (it.y & plan::AGGV_SIG) != 0, P + it.w, [&](uint32_t j) {
+        return line_t{soa_ld2(b, stride, 0, j), soa_ld2(b, stride, 2, j), soa_ld2(b, stride, 4, j)};
+    });
+    aggveach_put(it, s, v, part, n_part, step);
+}
+__global__ void __launch_bounds__(WAVE) k_aggveach_ln(const uint4* __restrict__ items, uint32_t n_items, uint32_t* __restrict__ part, uint32_t n_part,
+                                                      uint32_t* __restrict__ step) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    const uint32_t* src = part + (size_t)s * n_part * F12W;
+    const fp12 v = aggveach_ln_item(it.x, it.y & plan::AGGV_COUNT, [&](uint32_t j) { return ld_fp12_int(src + (size_t)j * F12W); });
+    aggveach_put(it, s, v, part, n_part, step);
+}
+__device__ __forceinline__ fp12 ld_fp12_blst(const uint32_t* g) {
+    fp12 a;
+    fp2* c[6] = {&a.c0.a0, &a.c0.a1, &a.c0.a2, &a.c1.a0, &a.c1.a1, &a.c1.a2};
+    for (int t = 0; t < 6; t++) *c[t] = fp2{ld_fp_blst(g + 24 * t), ld_fp_blst(g + 24 * t + 12)};
+    return a;
+}
+__device__ __forceinline__ void st_fp12_blst(uint32_t* g, const fp12& a) {
+    const fp2* c[6] = {&a.c0.a0, &a.c0.a1, &a.c0.a2, &a.c1.a0, &a.c1.a1, &a.c1.a2};
+    for (int t = 0; t < 6; t++) {
+        st_fp_blst(g + 24 * t, c[t]->c0);
+        st_fp_blst(g + 24 * t + 12, c[t]->c1);
+    }
+}
+// One lane per group of the slice: the Horner over its 68 step values, the value carried from the slice before multiplied in (OPEN_IN),
+// then either the Miller value handed on to the next slice (OPEN_OUT: `carry`, a blst_fp12 image; only one group of a slice is open at
+// either end, so one lane at most reads it and one writes it) or the final exponentiation and the verdict.  verdicts / gt (may be null:
+// the debug hook, 576-byte blst_fp12 images) are indexed by the group's number in the call.  One wave per SIMD, like k_each_tail: the Fp12
+// working set of the tower functions wants the whole register file (registers / scratch of the build: the library's .kmeta.json).
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_aggveach_tail(const uint32_t* __restrict__ step, const uint4* __restrict__ gtab, uint32_t ng, const uint32_t* __restrict__ bad, uint32_t* __restrict__ carry,
+                uint8_t* __restrict__ verdicts, uint32_t* __restrict__ gt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ng) return;
+    const uint4 gr = gtab[i];
+    const uint32_t* v = step + (size_t)i * N_LINES * F12W;
+    fp12 f = aggveach_horner([&](int s) { return ld_fp12_int(v + (size_t)s * F12W); });
+    if (gr.w & plan::AGGV_OPEN_IN) f = aggveach_carry(f, ld_fp12_blst(carry));
+    if (gr.w & plan::AGGV_OPEN_OUT) {
+        st_fp12_blst(carry, f);
+        return;
+    }
+    const aggveach_out o = aggveach_verdict(f, bad[gr.x] != 0);
+    verdicts[gr.x] = o.ok ? 1 : 0;
+    if (gt) st_fp12_blst(gt + (size_t)gr.x * 144, o.value);
+}
+// The same per group on the lane-cooperative Fp12 engine: tail_body is handed the group's 68 step values where the step store holds them
+// (no forming loop: each_engine_body's wave 0 has nothing to do here).  A workgroup takes groups blockIdx.x, blockIdx.x + gridDim.x, ...;
+// its block of `work` (AGGV_WORK_WORDS words) holds the Miller value | the carried value | the final value | the verdict word, the first
+// two 144 words apart as tail_body's state list wants them.  A group that goes on into the next slice (OPEN_OUT) leaves its Miller value in
+// slot 1 of `carry` when it has a carried value itself (the host multiplies slot 1 into slot 0 behind this kernel: k_state_mul), in slot 0
+// when it starts here.
+// The engine runs in latency mode only (plan.hpp aggveach_for), so there is the rows variant alone.
+constexpr uint32_t AGGV_WORK_CARRY = 144, AGGV_WORK_GT = 288, AGGV_WORK_V = 432, AGGV_WORK_WORDS = 448;
+__device__ __forceinline__ void aggveach_engine_body(const uint32_t* __restrict__ step, const uint4* __restrict__ gtab, uint32_t ng, const uint32_t* __restrict__ bad,
+                                                     uint32_t* __restrict__ carry, uint8_t* __restrict__ verdicts, uint32_t* __restrict__ gt, uint32_t* __restrict__ work) {
+    uint32_t* W = work + (size_t)blockIdx.x * AGGV_WORK_WORDS;
+    for (uint32_t i = blockIdx.x; i < ng; i += gridDim.x) {                // workgroup-uniform
+        const uint4 gr = gtab[i];
+        const bool open_in = (gr.w & plan::AGGV_OPEN_IN) != 0, open_out = (gr.w & plan::AGGV_OPEN_OUT) != 0;
+        if (open_in && !open_out && threadIdx.x < 144) W[AGGV_WORK_CARRY + threadIdx.x] = carry[threadIdx.x];
+        __syncthreads();
+        tail_body<true>(step + (size_t)i * N_LINES * F12W, open_out ? carry + (open_in ? 144 : 0) : W, open_in ? 2 : 1, open_out ? 1 : 3, W + AGGV_WORK_GT,
+                        W + AGGV_WORK_V, 144, 0);
+        __syncthreads();
+        if (!open_out) {
+            if (threadIdx.x == 0) verdicts[gr.x] = (W[AGGV_WORK_V] == 1u && bad[gr.x] == 0) ? 1 : 0;
+            if (gt && threadIdx.x < 144) gt[(size_t)gr.x * 144 + threadIdx.x] = W[AGGV_WORK_GT + threadIdx.x];
+        }
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(K_TAIL_THREADS) k_aggveach_engine_rows(const uint32_t* __restrict__ step, const uint4* __restrict__ gtab, uint32_t ng,
+                                                                         const uint32_t* __restrict__ bad, uint32_t* __restrict__ carry, uint8_t* __restrict__ verdicts,
+                                                                         uint32_t* __restrict__ gt, uint32_t* __restrict__ work) {
+    aggveach_engine_body(step, gtab, ng, bad, carry, verdicts, gt, work);
 }
 
 // ------------------------------------------------------------------------------------------

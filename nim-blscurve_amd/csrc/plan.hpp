@@ -467,6 +467,133 @@ inline recover_sizes recover_sizes_for(const aggsets_plan& p, size_t members, si
             groups * 4, groups, groups * 192, groups * 96};
 }
 
+// Per-group aggregateVerify (mi355_bls_aggregate_verify_each): k groups of (key, message) pairs in CSR form, one aggregate signature each.
+// The call runs in SLICES of at most `cap` pairs of the per-set path's pair store (2 cap slots: the pairs, then one (-G1, sig) pair per
+// group that ends in the slice - never more than the pairs, a group in a slice has a pair there).
+//   Cutting (aggveach_cut): a slice takes whole groups while they fit; a group that does not fit the room left starts the next slice; a group
+//   longer than a slice is walked in parts of `cap` pairs, each part a slice of its own, and its last part is followed by whole groups
+//   again.  So at most one group is open at a slice boundary (open_out: the last group of the slice goes on; open_in: the first one came
+//   from the slice before), and its Miller value so far waits in one Fp12 of device memory.  Empty groups occupy nothing: no pair, no
+//   signature slot, no item; their verdict is 0.
+//   Per Miller step the lines of a group's pairs, and the line of its signature pair in the part that ends it, are multiplied in levels of
+//   one-lane items, like aggsets_fill's sums: a level-0 item takes up to C consecutive pairs of ONE group (and, the first item of a group
+//   that ends here, its signature line), an item above up to C partials.  The item that leaves a group with one value is FINAL: it
+//   writes the group's step value (dst = the group's number in the slice) instead of a partial, so a group of up to C pairs is one item
+//   and has no partial at all.  Partials are numbered per slice, (group, level) after (group, level).
+//   AGGV_C = 8: a partial is an Fp12 per Miller step, 68 x 768 bytes = 51 KiB, and only items that are not final write one - at most
+//   P / (C - 1) of them for P pairs, so at C = 8 the partial store stays below a seventh of the slice's line store (68 x 384 bytes per
+//   pair); C = 4 would take a third of it, C = 16 leaves a lane sixteen dependent products at level 0.  NOT MEASURED.
+//   The tail takes each_for's rule with the slice's groups as m: the Fp12 engine up to each_engine_max(slots) groups in latency mode,
+//   one lane per group beyond and in throughput mode (inherited from verify_each, not measured for this path).
+constexpr uint32_t AGGV_C = 8;
+constexpr uint32_t AGGV_MAX_LEVELS = 32;                 // C >= 2 and fewer than 2^30 pairs per slice
+constexpr uint32_t AGGV_FINAL = 0x80000000u, AGGV_SIG = 0x40000000u, AGGV_COUNT = 0x3fffffffu;      // an item's count word
+constexpr uint32_t AGGV_OPEN_IN = 1, AGGV_OPEN_OUT = 2;  // a group's flags word
+struct aggv_slice {
+    size_t g0, g1;                     // the slice's pairs belong to groups of [g0, g1) (empty ones among them have none)
+    size_t pos0, pos1;                 // positions [pos0, pos1) of the call's pair sequence
+    uint32_t ng;                       // groups with pairs in the slice
+    bool open_in, open_out;
+    size_t pairs() const { return pos1 - pos0; }
+    uint32_t sigs() const { return ng - (open_out ? 1 : 0); }
+    size_t next_g() const { return open_out ? g1 - 1 : g1; }
+};
+// the slice that starts at position pos, which belongs to group g or a later one (g == k or pairs() == 0: nothing is left)
+inline aggv_slice aggveach_cut(const size_t* offsets, size_t k, size_t g, size_t pos, size_t cap) {
+    aggv_slice s{};
+    while (g < k && offsets[g + 1] <= pos) g++;             // finished and empty groups
+    s.g0 = s.g1 = g, s.pos0 = s.pos1 = pos;
+    if (g == k) return s;
+    s.open_in = pos > offsets[g];
+    for (; g < k; g++) {
+        const size_t left = offsets[g + 1] - s.pos1, room = cap - (s.pos1 - s.pos0);
+        if (left == 0) continue;
+        if (left > room) {
+            if (s.pos1 == s.pos0) s.pos1 += room, s.ng++, s.g1 = g + 1, s.open_out = true;      // a part of a group longer than a slice, alone
+            break;
+        }
+        s.pos1 += left, s.ng++, s.g1 = g + 1;
+    }
+    return s;
+}
+struct aggv_group {
+    uint32_t g, first, count, flags;   // the group's number in the call; its pairs first .. + count of the slice; AGGV_OPEN_*
+};
+// the slice's groups (s.ng entries)
+inline void aggveach_groups(const size_t* offsets, const aggv_slice& s, aggv_group* out) {
+    uint32_t at = 0;
+    for (size_t g = s.g0; g < s.g1; g++) {
+        const size_t a = offsets[g] > s.pos0 ? offsets[g] : s.pos0, b = offsets[g + 1] < s.pos1 ? offsets[g + 1] : s.pos1;
+        if (b <= a) continue;
+        out[at++] = aggv_group{(uint32_t)g, (uint32_t)(a - s.pos0), (uint32_t)(b - a),
+                               (a > offsets[g] ? AGGV_OPEN_IN : 0u) | (b < offsets[g + 1] ? AGGV_OPEN_OUT : 0u)};
+    }
+}
+struct aggveach_tab {
+    uint32_t levels;
+    size_t level_first[AGGV_MAX_LEVELS + 1];      // items [level_first[l], level_first[l + 1]) are level l
+    size_t items, partials;
+};
+inline aggveach_tab aggveach_measure(const aggv_group* gr, uint32_t ng, uint32_t C = AGGV_C) {
+    aggveach_tab t{};
+    size_t per_level[AGGV_MAX_LEVELS] = {};
+    for (uint32_t i = 0; i < ng; i++) {
+        size_t n = gr[i].count;
+        for (uint32_t l = 0;; l++) {
+            n = (n + C - 1) / C;
+            per_level[l] += n;
+            if (l + 1 > t.levels) t.levels = l + 1;
+            if (n == 1) break;
+            t.partials += n;
+        }
+    }
+    for (uint32_t l = 0; l < t.levels; l++) t.level_first[l + 1] = t.level_first[l] + per_level[l];
+    t.items = t.level_first[t.levels];
+    return t;
+}
+// the item table (t.items entries): src_first = a pair of the slice (level 0) or a partial (above), count = the operands | AGGV_FINAL |
+// AGGV_SIG, dst = a partial, or the group's number in the slice for a FINAL item, seg = that number
+inline void aggveach_fill(const aggveach_tab& t, const aggv_group* gr, uint32_t ng, agg_item* items, uint32_t C = AGGV_C) {
+    size_t cur[AGGV_MAX_LEVELS], pcur = 0;
+    for (uint32_t l = 0; l < AGGV_MAX_LEVELS; l++) cur[l] = l < t.levels ? t.level_first[l] : 0;
+    for (uint32_t i = 0; i < ng; i++) {
+        size_t n = gr[i].count, src = gr[i].first;
+        for (uint32_t l = 0;; l++) {
+            const size_t m = (n + C - 1) / C, base = cur[l];
+            for (size_t j = 0; j < m; j++) {
+                const size_t left = n - j * C;
+                const uint32_t sig = l == 0 && j == 0 && !(gr[i].flags & AGGV_OPEN_OUT) ? AGGV_SIG : 0u;
+                items[base + j] = agg_item{(uint32_t)(src + j * C), (uint32_t)(left < C ? left : C) | sig | (m == 1 ? AGGV_FINAL : 0u),
+                                           (uint32_t)(m == 1 ? i : pcur + j), i};
+            }
+            cur[l] += m;
+            if (m == 1) break;
+            src = pcur, pcur += m, n = m;
+        }
+    }
+}
+// One slice of `pairs` pairs and `sigs` signature pairs in `ng` groups: the record / pair-slot kernel (a lane per pair slot), the Miller
+// lines of all pairs + sigs pairs in the form the per-set path takes for as many, and the tail by each_for's rule on ng.  A level of
+// `count` items runs as (waves_for(count), N_LINES) waves: a lane per (item, step), the items of a step side by side in a wave.
+struct aggveach_plan {
+    uint32_t setup_grid;
+    lines_plan lines;
+    bool tail_engine;                  // k_aggveach_engine_rows: tail_grid workgroups, each walks groups i, i + tail_grid, ... | k_aggveach_tail: tail_grid waves
+    uint32_t tail_grid;
+};
+inline aggveach_plan aggveach_for(uint32_t slots, bool coop, uint32_t pairs, uint32_t sigs, uint32_t ng) {
+    aggveach_plan p{};
+    p.setup_grid = waves_for(pairs + sigs);
+    p.lines = lines_for(slots, coop, pairs + sigs, 0);
+    p.tail_engine = coop && ng <= each_engine_max(slots);
+    p.tail_grid = p.tail_engine ? (ng < each_engine_grid_max(slots) ? ng : each_engine_grid_max(slots)) : waves_for(ng);
+    return p;
+}
+// the stores of one slice, in words: a partial and a group's step values are N_LINES internal Fp12 images (partial p of step s at
+// (s x partials + p) x F12_WORDS; group i's step s at (i x N_LINES + s) x F12_WORDS, the 68 values the tail walks side by side)
+inline size_t aggveach_part_words(size_t partials) { return (partials ? partials : 1) * (size_t)N_LINES * F12_WORDS; }
+inline size_t aggveach_step_words(size_t ng) { return (ng ? ng : 1) * (size_t)N_LINES * F12_WORDS; }
+
 // ------------------------------------------------------------------------------------------
 // Pippenger MSM (blst_p1s_mult_pippenger / blst_p2s_mult_pippenger): what msm_enqueue follows, and what msm_reserve allocates.
 // ------------------------------------------------------------------------------------------
