@@ -665,6 +665,15 @@ int mi355_bls_debug_fp_op(mi355_bls_ctx* ctx, int op, const uint32_t* a, const u
  * those hash a message. */
 int mi355_bls_debug_map_to_g2(mi355_bls_ctx* ctx, const uint32_t* us, size_t n, uint8_t* out_p2);
 
+/* TEST HOOK: mi355_bls_batch_verify_serial with blinding scalars of the CALLER'S choice: r[i] (non-zero u64) takes the place of the i-th link of the
+ * SHA-256 chain, everything behind the scalars is the serial call's for this n on this context - the same plan (csrc/plan.hpp slice_for), k_pkmul or
+ * k_pkmul_spread, the signature side's digit sort and buckets, the same forks, the same verdict (1 / 0) - and mi355_bls_fetch_stage 0 .. 5 work after
+ * it as after any batch call.  The production scalars come from a hash no test can steer; this puts the scalar-dependent code (signed digits and
+ * their carries, a not-started accumulator, zero digits, waves whose lanes all agree, empty and crowded buckets) under inputs picked for it
+ * (tests/blind_scalars.py).  sets, r: host memory; one slice only, 1 <= n <= max_sets.  MI355_BLS_ERR_ARG for a null pointer, n == 0, n > max_sets,
+ * a context with a batch pending, or ANY r[i] == 0 (the chain never yields zero: the hook does not take the kernels outside their contract). */
+int mi355_bls_debug_batch_verify_scalars(mi355_bls_ctx* ctx, const void* sets, size_t n, const uint64_t r[]);
+
 /* Test hooks (no reference counterpart).  debug_fail_next_enqueue: the next batch / shard enqueue on this context fails with
  * MI355_BLS_ERR_HIP before touching the device (exercises the multi-device driver's clean-up path).  debug_multi_enqueue_us:
  * host time in microseconds, counted from the start of the last mi355_bls_batch_verify_multi* call of this thread, at which each

@@ -174,6 +174,7 @@ def lib():
         L.mi355_bls_debug_hash_to_g2.argtypes = [vp, cp, sz, cp, sz, cp]
         L.mi355_bls_debug_fp_op.argtypes = [vp, i32, cp, cp, sz, cp]
         L.mi355_bls_debug_map_to_g2.argtypes = [vp, cp, sz, cp]
+        L.mi355_bls_debug_batch_verify_scalars.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_uint64)]
         L.mi355_bls_debug_multi_enqueue_us.argtypes = [ctypes.POINTER(ctypes.c_float), sz]
         L.mi355_bls_debug_multi_enqueue_us.restype = sz
         L.mi355_bls_fetch_stage.argtypes = [vp, i32, vp, sz]
@@ -461,6 +462,17 @@ def debugMapToG2(cache, us):
     out = ctypes.create_string_buffer(max(n, 1) * 576)
     _check(lib().mi355_bls_debug_map_to_g2(cache._h, bytes(us), n, out))
     return out.raw
+
+
+def debugBatchVerifyScalars(cache, sets, scalars):
+    """Test hook (mi355_bls_debug_batch_verify_scalars): batchVerifySerial of one slice with scalars[i] (a non-zero u64) as the blinding scalar of
+    set i instead of the SHA-256 chain; cache.fetch(0 .. 5) show its stages.  1 <= n <= cache.max_sets; a zero scalar is refused."""
+    rec = _as_records(sets)
+    n = len(rec) // SIGSET_BYTES
+    if len(scalars) != n:
+        raise ValueError("one scalar per set: %d sets, %d scalars" % (n, len(scalars)))
+    r = (ctypes.c_uint64 * max(n, 1))(*scalars)
+    return bool(_check(lib().mi355_bls_debug_batch_verify_scalars(cache._h, rec, n, r)))
 
 
 def batchVerifyLocate(cache, input_, secureRandomBytes):

@@ -727,7 +727,7 @@ static int ensure_lanes(mi355_bls_ctx* c, int want) {
 // boundary cuts is carried over (k_blind).  src_dev: the shard's records in device memory, or src_host: in host memory
 // (staged slice by slice through d_sets).  After a sliced call fetch_stage(0..3) shows the LAST slice.
 static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* src_host, size_t n_total, uint32_t nchunks, uint32_t chunk_lo, uint32_t chunk_cnt,
-                     size_t tuple_base, size_t n, int serial, const uint8_t rnd[32], hipStream_t st, bool pop = false) {
+                     size_t tuple_base, size_t n, int serial, const uint8_t rnd[32], hipStream_t st, bool pop = false, const uint64_t* chosen_r = nullptr) {
     (void)chunk_lo; (void)chunk_cnt;
     HIPCHK(hipSetDevice(c->device));
     if (c->fail_next_enqueue) {                                 // test hook: an enqueue failure after earlier shards of a multi-device call went out
@@ -740,7 +740,8 @@ static int run_shard(mi355_bls_ctx* c, const uint8_t* src_dev, const uint8_t* sr
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
     if (serial) {
         c->h_r.resize(n);
-        host_serial_chain(rnd, n, c->h_r.data());
+        if (chosen_r) std::memcpy(c->h_r.data(), chosen_r, n * 8);      // test hook (mi355_bls_debug_batch_verify_scalars): the caller's scalars in the chain's place
+        else host_serial_chain(rnd, n, c->h_r.data());
     }
     const size_t nslices = plan::shard_nslices(n, c->cap);
     c->alone = nslices == 1 && g_in_flight.load(std::memory_order_relaxed) == 0;       // slices of one call overlap each other: throughput form
@@ -839,12 +840,13 @@ static int collect_timings(mi355_bls_ctx* c, int last_ev) {
 }
 
 // Enqueue a whole batch verification (nothing is waited for); the verdict lands in the context's pinned host words.
-static int verify_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, const uint8_t* h_sets, size_t n, const uint8_t rnd[32], int serial, hipStream_t st, bool pop = false) {
+static int verify_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, const uint8_t* h_sets, size_t n, const uint8_t rnd[32], int serial, hipStream_t st, bool pop = false,
+                          const uint64_t* chosen_r = nullptr) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if ((!d_sets && !h_sets) || n == 0) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     uint32_t B = (uint32_t)(n < c->num_threads ? n : c->num_threads);
-    int rc = run_shard(c, d_sets, h_sets, n, B, 0, serial ? 1 : B, 0, n, serial, rnd, st, pop);
+    int rc = run_shard(c, d_sets, h_sets, n, B, 0, serial ? 1 : B, 0, n, serial, rnd, st, pop, chosen_r);
     if (rc) return rc;
     launch_k_tail(c, st, c->d_L, c->d_states, 1, 2, c->d_gt, c->d_flags + 1, 144, 0);
     HIPCHK(hipEventRecord(c->ev[8], st));
@@ -907,6 +909,20 @@ static int verify_host(mi355_bls_ctx* c, const void* sets, size_t n, const uint8
 
 extern "C" int mi355_bls_batch_verify(mi355_bls_ctx* c, const void* sets, size_t n, const uint8_t rnd[32]) { return verify_host(c, sets, n, rnd, 0); }
 extern "C" int mi355_bls_batch_verify_serial(mi355_bls_ctx* c, const void* sets, size_t n, const uint8_t rnd[32]) { return verify_host(c, sets, n, rnd, 1); }
+
+// TEST HOOK: mi355_bls_batch_verify_serial of one slice (1 <= n <= max_sets, host memory) with the blinding scalars r[0 .. n) of the CALLER'S choice where
+// that call computes its SHA-256 chain: the serial branch of run_shard / run_slice with h_r filled from r, so the plan, the kernels behind the
+// scalars ([r]PK, the signature side's sort and buckets), the forks and the verdict are that call's.  A zero scalar is refused: the chain never
+// yields one, and the kernels are not taken outside their contract.
+extern "C" int mi355_bls_debug_batch_verify_scalars(mi355_bls_ctx* c, const void* sets, size_t n, const uint64_t r[]) {
+    if (!c || !sets || !r || n == 0 || n > c->cap) return MI355_BLS_ERR_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (r[i] == 0) return MI355_BLS_ERR_ARG;
+    static const uint8_t no_rnd[32] = {0};                               // the serial branch reads no random bytes on the device
+    int rc = verify_enqueue(c, nullptr, (const uint8_t*)sets, n, no_rnd, 1, nullptr, false, r);      // refuses a busy context
+    if (rc) return rc;
+    return verify_wait(c);
+}
 
 // ------------------------------------------------------------------------------------------
 // Per-set verdicts: verify (bls_sig_min_pubkey.nim:108-125 -> coreVerifyNoGroupCheck, core :269-297) applied to every set of the input in

@@ -17,8 +17,11 @@ acc == +-entry cannot happen for a point of G1 (16 x prefix = +-d has no solutio
 lane's flag and the kernel recomputes the lane with the compiled complete formulas (keys outside G1 that a caller did not subgroup-check).
 
 `--selftest`: asmlib's interpreter runs the generated blocks (doubling, addition, table preparation) through the whole algorithm for random
-scalars against big-integer group arithmetic; the digit extraction and the loop control are raw text, covered by the GPU parity tests
-(tests/test_gpu_batch.py: every [r_i]PK_i sample against the oracle)."""
+scalars, and for the scalars `--scalars HEX...` names (even ones included: a zero digit at window 0, a not-started accumulator through all
+sixteen windows), against big-integer group arithmetic.  The digit extraction and the loop control are raw text that the interpreter does not
+run: the selftest restates them (`windows_of`), and on the device they are covered by tests/test_gpu_blind_scalars.py, which puts chosen scalars -
+every digit value at every position, both carries, every not-started depth, waves whose lanes all agree (the branches on an empty execution
+mask) - through k_pkmul and k_pkmul_spread and holds every [r_i]PK_i to the oracle, beside the random scalars of tests/test_gpu_batch.py."""
 import argparse
 import random
 import sys
@@ -186,7 +189,16 @@ def same_point(Pa, Pb):
     return mmul(Pa[0], zb) == mmul(Pb[0], za) and mmul(Pa[1], mmul(zb, Pb[2])) == mmul(Pb[1], mmul(za, Pa[2]))
 
 
-def selftest(seed=4):
+def windows_of(r):
+    """the raw-text loop of kernel_text() restated: [(j, doublings in front, |d|, d < 0)] for j = 16 .. 0 - k' = r + 0x8888888888888888, digit j = nibble j of
+    k' minus 8, digit 16 = the carry; no doublings in front of digit 16, four in front of every other one WHATEVER the accumulator holds"""
+    kp = r + 0x8888888888888888
+    digs = [((kp >> (4 * j)) & 15) - 8 for j in range(16)] + [kp >> 64]
+    assert sum(d * 16 ** j for j, d in enumerate(digs)) == r and digs[16] in (0, 1)
+    return [(j, 0 if j == 16 else 4, abs(digs[j]), digs[j] < 0) for j in range(16, -1, -1)]
+
+
+def selftest(seed=4, scalars=()):
     rnd = random.Random(seed)
     dbl, dout = gen_dbl()
     add, aout = gen_add()
@@ -207,9 +219,11 @@ def selftest(seed=4):
         ly = limbs_of(y)
         put(mach, EY, [(-l) & 0xffffffff for l in ly] if neg else ly)
 
-    for trial in range(3):
+    chosen = list(scalars) or [rnd.getrandbits(64) | 1 for _ in range(3)]
+    assert all(0 < r < 1 << 64 for r in chosen), "a blinding scalar is a non-zero u64"
+    n_first = n_add_all = 0
+    for r in chosen:
         pk = (rnd.randrange(P), rnd.randrange(P), R1)                   # any triple with Z = 1: the formulas are polynomial identities
-        r = rnd.getrandbits(64) | 1
         # ---- the table 1 .. 8 times PK, each entry with Z^2, Z^3, built by the generated blocks
         def run_prep():
             mach.run(prep)
@@ -234,28 +248,31 @@ def selftest(seed=4):
             table.append(run_prep())
             assert table[i][1] == mmul(ref[i][2], ref[i][2]) and table[i][2] == mmul(ref[i][2], table[i][1])
         # ---- the windows
-        kp = r + 0x8888888888888888
-        digs = [((kp >> (4 * j)) & 15) - 8 for j in range(16)] + [kp >> 64]
-        assert sum(d * 16 ** j for j, d in enumerate(digs)) == r
+        # (the doublings in front of the first non-zero digit run on whatever the table's construction left in the accumulator, as on the device: the
+        # block must stay inside its bounds there too, which the interpreter asserts, and `first` then overwrites the accumulator)
         started, acc_ref, n_add = False, None, 0
-        for j in range(16, -1, -1):
-            if j < 16:
-                for _ in range(4):
-                    mach.run(dbl)
-                    if started:
-                        acc_ref = rdbl(acc_ref)
-            d = digs[j]
-            if d == 0:
+        for j, ndbl, mag, neg in windows_of(r):
+            for _ in range(ndbl):
+                mach.run(dbl)
+                if started:
+                    acc_ref = rdbl(acc_ref)
+                for reg, bd in zip((AX, AY, AZ), PIN):
+                    check_limbs(mach, reg, bd[1])
+            if mag == 0:                                                 # lanes with d == 0 are masked out of the gather, `add` and `first`
+                if started:
+                    assert acc_regs() == acc_ref, ("window", j, "zero digit")
                 continue
-            ent = table[abs(d) - 1]
-            set_entry(ent, d < 0)
-            eref = (ent[0][0], (-ent[0][1]) % P if d < 0 else ent[0][1], ent[0][2])
+            ent = table[mag - 1]
+            set_entry(ent, neg)
+            eref = (ent[0][0], (-ent[0][1]) % P if neg else ent[0][1], ent[0][2])
             if not started:
-                mach.run(first); acc_ref = eref; started = True
+                mach.run(first); acc_ref = eref; started = True; n_first += 1
             else:
                 mach.run(add); acc_ref = radd(acc_ref, eref); n_add += 1
                 assert mach.v[V_T] != 0, "a point of prime order never meets acc == +-entry"
-            assert acc_regs() == acc_ref, ("window", j)
+            assert acc_regs() == acc_ref, ("scalar", hex(r), "window", j)
+        assert started and n_add == sum(1 for w in windows_of(r) if w[2]) - 1, hex(r)
+        n_add_all += n_add
         # as a group element: r * PK by plain double-and-add with the same formulas
         want = None
         for bit in range(63, -1, -1):
@@ -269,6 +286,8 @@ def selftest(seed=4):
     assert mach.v[V_T] == 0, "acc == entry must be detected (Z3 == 0)"
     c0 = dict(mach.count); mach.run(dbl); c1 = dict(mach.count); mach.run(add); c2 = dict(mach.count)
     nd, md, na, ma = c1["valu"] - c0["valu"], c1["mad"] - c0["mad"], c2["valu"] - c1["valu"], c2["mad"] - c1["mad"]
+    if scalars:
+        print("gen_pkmul_asm selftest: %d chosen scalars, %d first entries, %d additions" % (len(chosen), n_first, n_add_all))
     print("gen_pkmul_asm selftest ok: doubling %d instructions (%d multiply-adds), addition %d (%d); per scalar ~%d instructions, %.1f %% multiply-adds"
           % (nd, md, na, ma, 68 * nd + 20 * na + 8 * 900, 100.0 * (68 * md + 20 * ma + 8 * 700) / (68 * nd + 20 * na + 8 * 900)))
 
@@ -416,10 +435,11 @@ def clobbers():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--selftest", action="store_true")
+    ap.add_argument("--scalars", nargs="+", metavar="HEX", help="with --selftest: run these 64-bit scalars (hexadecimal, non-zero) instead of three random odd ones")
     ap.add_argument("-o", "--out")
     a = ap.parse_args()
     if a.selftest:
-        selftest()
+        selftest(scalars=[int(x, 16) for x in a.scalars or ()])
         return
     lines = [l if l.startswith(".L") else "\\t" + l for l in kernel_text()]
     txt = ("// GENERATED by nim-blscurve_amd/tools/gen_pkmul_asm.py -- do not edit.\n"

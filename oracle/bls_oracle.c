@@ -439,10 +439,8 @@ static uint64_t ctx_next_scalar(pctx* c) {
     do { oracle_sha256(c->seed, 32, c->seed); r = 0; for (int i = 0; i < 8; i++) r |= (uint64_t)c->seed[i] << (8 * i); } while (r == 0);
     return r;
 }
-/* update(): returns 0 on BLST_PK_IS_INFINITY */
-static int ctx_update(pctx* c, const uint8_t* set320, uint64_t* r_out, uint8_t* h_out, uint8_t* rpk_out) {
-    uint64_t r = ctx_next_scalar(c);
-    if (r_out) *r_out = r;
+/* update() with the blinding scalar r: returns 0 on BLST_PK_IS_INFINITY */
+static int ctx_update_r(pctx* c, const uint8_t* set320, uint64_t r, uint8_t* h_out, uint8_t* rpk_out) {
     g1a pk = ld_g1a(set320); g2a sig = ld_g2a(set320 + 128);
     if (pk.inf) return 0;
     if (!sig.inf) { g2j sj = g2_from_aff(&sig), rs = g2_mul_u64(&sj, r); c->aggr = g2_add(&c->aggr, &rs); }
@@ -453,6 +451,12 @@ static int ctx_update(pctx* c, const uint8_t* set320, uint64_t* r_out, uint8_t* 
     c->Q[c->nq] = h; c->P[c->nq] = rpa; c->nq++;
     if (c->nq == 8) ctx_flush(c);
     return 1;
+}
+/* update(): the scalar is the next link of the context's chain */
+static int ctx_update(pctx* c, const uint8_t* set320, uint64_t* r_out, uint8_t* h_out, uint8_t* rpk_out) {
+    uint64_t r = ctx_next_scalar(c);
+    if (r_out) *r_out = r;
+    return ctx_update_r(c, set320, r, h_out, rpk_out);
 }
 static void ctx_merge(pctx* a, const pctx* b) {
     if (b->gt_set) { a->gt = a->gt_set ? f12_mul(&a->gt, &b->gt) : b->gt; a->gt_set = 1; }
@@ -491,6 +495,39 @@ int oracle_batch_verify(const uint8_t* sets, size_t n, const uint8_t rnd[32], in
         for (size_t i = off; i < off + len; i++)
             if (!ctx_update(&ctx[c], sets + 320 * i, r_out ? r_out + i : NULL, h_out ? h_out + 192 * i : NULL, rpk_out ? rpk_out + 96 * i : NULL)) { ok[c] = 0; break; }
         ctx_flush(&ctx[c]);   /* commit */
+    }
+    int all = 1;
+    for (size_t c = 0; c < B; c++) all &= ok[c];
+    int res = 0;
+    if (all) { for (size_t c = 1; c < B; c++) ctx_merge(&ctx[0], &ctx[c]); res = ctx_finalverify(&ctx[0], gt_out, agg_out); }
+    free(ctx); free(ok);
+    return res;
+}
+
+/* batchVerifySerial (oracle_batch_verify, nthreads == 0) with the blinding scalars r[0 .. n) of the caller's choice (all non-zero) where update() draws
+ * them from the chain: the checker of mi355_bls_debug_batch_verify_scalars.  The sets are split over OpenMP threads, one pairing context each, merged
+ * in order: the GT product and the signature sum commute and every output is canonical, so the values are the one-context path's, bit for bit.
+ * Optional outputs (may be NULL): rPK (n x 96), aggsig (192), gt (576). */
+int oracle_batch_verify_scalars(const uint8_t* sets, size_t n, const uint64_t* r, uint8_t* rpk_out, uint8_t* agg_out, uint8_t* gt_out) {
+    if (n == 0) return 0;
+    for (size_t i = 0; i < n; i++) if (r[i] == 0) return 0;
+    int T = 1;
+#ifdef _OPENMP
+    T = omp_get_max_threads();
+#endif
+    size_t B = (size_t)T < n ? (size_t)T : n;
+    pctx* ctx = (pctx*)malloc(B * sizeof(pctx));
+    int* ok = (int*)malloc(B * sizeof(int));
+    size_t base = n / B, rem = n % B;
+    const uint8_t no_rnd[32] = {0};      /* seeds a chain nobody draws from */
+#pragma omp parallel for schedule(static, 1)
+    for (long c = 0; c < (long)B; c++) {
+        size_t off = (size_t)c < rem ? (base + 1) * c : base * c + rem, len = (size_t)c < rem ? base + 1 : base;
+        ctx_init(&ctx[c], no_rnd, NULL, 0, DST_SIG, sizeof(DST_SIG) - 1);
+        ok[c] = 1;
+        for (size_t i = off; i < off + len; i++)
+            if (!ctx_update_r(&ctx[c], sets + 320 * i, r[i], NULL, rpk_out ? rpk_out + 96 * i : NULL)) { ok[c] = 0; break; }
+        ctx_flush(&ctx[c]);
     }
     int all = 1;
     for (size_t c = 0; c < B; c++) all &= ok[c];

@@ -14,6 +14,7 @@ def lib():
         L = ctypes.CDLL(os.path.join(ROOT, "oracle", "_build", "libbls_oracle.so"))
         vp, sz, i32, cp = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p
         L.oracle_batch_verify.argtypes = [cp, sz, cp, i32, vp, vp, vp, vp, vp]
+        L.oracle_batch_verify_scalars.argtypes = [cp, sz, ctypes.POINTER(ctypes.c_uint64), vp, vp, vp]
         L.oracle_hash_to_g2.argtypes = [cp, sz, cp, sz, cp]
         L.oracle_sk_to_pk.argtypes = [cp, cp]
         L.oracle_sign.argtypes = [cp, cp, sz, cp]
@@ -52,6 +53,16 @@ def batch_verify(sets, rnd, nthreads, stages=False):
     g = ctypes.create_string_buffer(576)
     ok = bool(lib().oracle_batch_verify(sets, n, rnd, nthreads, r, h, p, a, g))
     return ok, {"r": list(r)[:n], "H": h.raw, "rPK": p.raw, "aggsig": a.raw, "gt": g.raw}
+
+
+def batch_verify_scalars(sets, scalars):
+    """batchVerifySerial with scalars[i] (non-zero u64) as the blinding scalar of set i -> (verdict, {"rPK", "aggsig", "gt"})"""
+    n = len(sets) // 320
+    assert len(scalars) == n and n > 0
+    r = (ctypes.c_uint64 * n)(*scalars)
+    p, a, g = ctypes.create_string_buffer(96 * n), ctypes.create_string_buffer(192), ctypes.create_string_buffer(576)
+    ok = bool(lib().oracle_batch_verify_scalars(sets, n, r, p, a, g))
+    return ok, {"rPK": p.raw, "aggsig": a.raw, "gt": g.raw}
 
 
 def make_batch(n, seed=0):

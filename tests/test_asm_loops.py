@@ -126,6 +126,24 @@ def test_pkmul_blocks_match_bigint_model():
     assert md == 2334 and ma == 5077 and nd <= 3050 and na <= 6700
 
 
+def test_pkmul_blocks_on_chosen_scalars():
+    """The same blocks for the named subset of tests/blind_scalars.py (SELFTEST): 1 (sixteen windows of doublings on a not-started accumulator),
+    16^8 and 2^32 - 1, 8 * 16^15 (the carry digit 16 out of one negative digit), 2^64 - 1 (carry, fifteen zero digits, -1), all digits -8,
+    0x8888888888888888 and a few random ones - even scalars included, whose digit 0 is zero.  The selftest walks the windows as the raw-text loop
+    does (tools/gen_pkmul_asm.py windows_of): `first` for the first non-zero digit, `add` for every later one, nothing for a zero digit."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import blind_scalars as bs
+    names = [nm for nm, _ in bs.SELFTEST]
+    for must in ("1", "16^8", "8*16^15", "2^64-1", "0x7777777777777778", "0x8888888888888888", "2^32-1"):
+        assert must in names
+    assert len(bs.SELFTEST) <= 16 and sum(nm.startswith("random") for nm in names) >= 3
+    out = run("gen_pkmul_asm.py", "--selftest", "--scalars", *["%x" % v for _, v in bs.SELFTEST])
+    assert "selftest ok" in out
+    m = re.search(r"(\d+) chosen scalars, (\d+) first entries, (\d+) additions", out)
+    nonzero = [sum(1 for d in bs.digits(v) if d) for _, v in bs.SELFTEST]
+    assert [int(x) for x in m.groups()] == [len(bs.SELFTEST), len(bs.SELFTEST), sum(nonzero) - len(nonzero)]
+
+
 def test_pkmul_text_is_one_statement():
     t = run("gen_pkmul_asm.py")
     assert "#define BLS_PKMUL_ASM_BODY" in t and "#define BLS_PKMUL_ASM_CLOBBERS" in t

@@ -42,6 +42,37 @@ def test_batch_fixtures():
     assert co.batch_verify(b"", bytes(32), 4) is False
 
 
+def test_batch_verify_with_chosen_scalars_equals_the_serial_chain_and_python():
+    """oracle_batch_verify_scalars (checker of mi355_bls_debug_batch_verify_scalars): fed the scalars oracle_batch_verify(nthreads = 0) drew, it
+    gives that call's verdict, [r_i]PK_i, aggregated signature and GT value bit for bit - on a valid batch (more sets than threads or fewer) and on
+    one with two signatures swapped; and on family scalars of tests/blind_scalars.py its [r]PK and sum [r_i]S_i are the Python oracle's."""
+    import blind_scalars as bs
+    rnd = o.sha256(b"chosen scalars")
+    for n in (1, 3, 41):
+        rec = co.make_batch(n, seed=100 + n)
+        bad = bytearray(rec)
+        if n > 1:
+            bad[128:320], bad[320 + 128:640] = rec[320 + 128:640], rec[128:320]
+        for sets in (rec, bytes(bad)):
+            ok, st = co.batch_verify(sets, rnd, 0, stages=True)
+            ok2, st2 = co.batch_verify_scalars(sets, st["r"])
+            assert ok2 is ok and ok is (sets == rec)
+            assert st2["rPK"] == st["rPK"] and st2["aggsig"] == st["aggsig"] and st2["gt"] == st["gt"], n
+    picked = ["1", "2^32", "2^64-8", "2^63-1", "0x7777777777777778"]
+    names = ["all_minus_8: 0x7777777777777778" if p.startswith("0x") else "edges: " + p for p in picked] + ["equal_nibbles: 0xF repeated", "single_digit: 8*16^15"]
+    rs = [bs.BY_NAME[nm] for nm in names]
+    rec = co.make_batch(len(rs), seed=7)
+    ok, st = co.batch_verify_scalars(rec, rs)
+    assert ok is True and fp12_from_bytes(st["gt"]) == o.F12_ONE
+    want = None
+    for i, r in enumerate(rs):
+        pk, sig = o.g1_from_blst_affine(rec[320 * i:320 * i + 96]), o.g2_from_blst_affine(rec[320 * i + 128:320 * i + 320])
+        assert st["rPK"][96 * i:96 * i + 96] == o.g1_to_blst_affine(o.g1_mul(pk, r)), names[i]
+        want = o.g2_add(want, o.g2_mul(sig, r))
+    assert st["aggsig"] == o.g2_to_blst_affine(want)
+    assert co.batch_verify_scalars(rec, [0] + rs[1:])[0] is False      # a zero scalar is outside the contract: refused
+
+
 def test_make_batch_is_valid_and_tamper_detected():
     rec = co.make_batch(12, seed=5)
     rnd = o.sha256(b"Mr F was here")
