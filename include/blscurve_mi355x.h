@@ -302,6 +302,51 @@ int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* ctx, const void* keys, 
                                           const void* msgs32, const void* sigs192, const uint8_t rnd[32]);
 int mi355_bls_batch_fast_aggregate_verify_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
                                                  size_t k, const void* d_msgs32, const void* d_sigs192, const uint8_t rnd[32], void* stream);
+/* The same records from the form the host holds: m fixed committees (index lists into the key table, the same for an epoch) and, per set, a
+ * committee number and one bit per committee position (aggregation_bits of an attestation, sync_committee_bits of a sync aggregate).  The
+ * key of set s is aggregateAll (blst_min_pubkey_sig_core.nim:179-195) over the keys of committee which[s] whose bit is 1, in committee
+ * order - the first step of fastAggregateVerify (bls_sig_min_pubkey.nim:234-258) - and record s is byte for byte what
+ * mi355_bls_aggregate_sets writes for the expanded index list.
+ *   keys, n_table, idx   the key table and the optional index array, as above
+ *   c_offsets   m + 1 entries in HOST memory, non-decreasing: committee c is positions [c_offsets[c], c_offsets[c+1]) (of idx, or of the table)
+ *   which       k committee numbers (< m) in HOST memory, also in the _device forms; repeats in any order (sixteen aggregators of one
+ *               committee are sixteen sets)
+ *   bits        the k fields packed end to end in set order; a set whose committee has L positions owns exactly ceil(L / 8) bytes, SSZ bit
+ *               order: position i is bit i % 8 of byte i / 8.  Bits at positions >= L of the last byte are ignored (a bitlist's delimiter
+ *               bit may stay).  Byte-aligned; every other device pointer is 4-byte aligned.
+ *   committee_aggs   NULL, or the aggregate key of every committee: m 96-byte blst_p1_affine images agg_stride bytes apart (96: packed; 320:
+ *               the records mi355_bls_aggregate_sets(_device) wrote for the committees themselves with the same idx and c_offsets - how
+ *               a host makes them, once per epoch).  agg_stride >= 96 and a multiple of 4.  With them, a set of which more than half
+ *               signed (2 * popcount > L) and whose committee's image is not all zero is computed as subtractAll
+ *               (blst_min_pubkey_sig_core.nim:197-209): the committee's aggregate minus the keys whose bit is 0.  Every other set - a
+ *               tie at exactly half included - is summed directly.  The route never shows in a record or a status byte.
+ *               PRECONDITION, like a decoded key: an image that is not all zero IS the aggregate of its committee.
+ *   status      as above: 0 ok, 1 no bit set (also a committee of length 0), 2 the sum is the point at infinity, 3 a participating position
+ *               holds an index >= n_table (never dereferenced; 3 wins over 1 and 2; on both routes every index is checked before it is used)
+ * Returns and k == 0 as the calls above.  MI355_BLS_ERR_ARG for decreasing c_offsets, c_offsets[m] > n_table without idx, a which[s] >= m,
+ * NULL pointers, a bad agg_stride, or more than 2^32 - 2 level-0 items (one per 8 positions of a set).  Nothing is bounded by max_sets.
+ * COST: one lane per 8 positions of a set, whose time is its number of selected keys; the levels above and the finish as aggregate_sets.
+ *       Measured figures: profiles/aggregate_bits_bench.json, DESIGN.md 3.2.2a.
+ * debug_aggregate_bits_routes: TEST HOOK - out[0] / out[1] = sets of the context's last bits call summed directly / by exclusion. */
+int mi355_bls_aggregate_sets_bits(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
+                                  const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k, const void* msgs32,
+                                  const void* sigs192, void* out_records, uint8_t* status);
+int mi355_bls_aggregate_sets_bits_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets, size_t m,
+                                         const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits, size_t k,
+                                         const void* d_msgs32, const void* d_sigs192, void* d_out_records, uint8_t* status, void* stream);
+int mi355_bls_fast_aggregate_verify_each_bits(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
+                                              const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k,
+                                              const void* msgs32, const void* sigs192, uint8_t* out);
+int mi355_bls_fast_aggregate_verify_each_bits_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets,
+                                                     size_t m, const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits,
+                                                     size_t k, const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream);
+int mi355_bls_batch_fast_aggregate_verify_bits(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
+                                               const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k,
+                                               const void* msgs32, const void* sigs192, const uint8_t rnd[32]);
+int mi355_bls_batch_fast_aggregate_verify_bits_device(mi355_bls_ctx* ctx, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets,
+                                                      size_t m, const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits,
+                                                      size_t k, const void* d_msgs32, const void* d_sigs192, const uint8_t rnd[32], void* stream);
+int mi355_bls_debug_aggregate_bits_routes(mi355_bls_ctx* ctx, uint32_t out[2]);
 
 /* aggregateAll on signatures for MANY groups in ONE device pass: the signature half of the same template
  * (genAggregatorProcedures(AggregateSignature, Signature, p2), blst_min_pubkey_sig_core.nim:142-211), each sum finished to its affine image

@@ -118,6 +118,13 @@ def lib():
         L.mi355_bls_fast_aggregate_verify_each_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_batch_fast_aggregate_verify.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, ctypes.c_char_p]
         L.mi355_bls_batch_fast_aggregate_verify_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, ctypes.c_char_p, vp]
+        L.mi355_bls_aggregate_sets_bits.argtypes = [vp, vp, sz, pu32, psz, sz, vp, sz, pu32, vp, sz, vp, vp, vp, vp]
+        L.mi355_bls_aggregate_sets_bits_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, sz, pu32, vp, sz, vp, vp, vp, vp, vp]
+        L.mi355_bls_fast_aggregate_verify_each_bits.argtypes = [vp, vp, sz, pu32, psz, sz, vp, sz, pu32, vp, sz, vp, vp, vp]
+        L.mi355_bls_fast_aggregate_verify_each_bits_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, sz, pu32, vp, sz, vp, vp, vp, vp]
+        L.mi355_bls_batch_fast_aggregate_verify_bits.argtypes = [vp, vp, sz, pu32, psz, sz, vp, sz, pu32, vp, sz, vp, vp, ctypes.c_char_p]
+        L.mi355_bls_batch_fast_aggregate_verify_bits_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, sz, pu32, vp, sz, vp, vp, ctypes.c_char_p, vp]
+        L.mi355_bls_debug_aggregate_bits_routes.argtypes = [vp, pu32]
         L.mi355_bls_aggregate_verify_each.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp]
         L.mi355_bls_aggregate_verify_each_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_debug_aggregate_verify_each_gt.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp, vp]
@@ -801,6 +808,127 @@ def batchFastAggregateVerify_device(cache, d_keys, n_table, d_idx, offsets, d_ms
         return False
     return bool(_check(lib().mi355_bls_batch_fast_aggregate_verify_device(cache._h, d_keys, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k,
                                                                           d_msgs, d_sigs, rnd, stream)))
+
+
+def _bit_sets(committees, which, bits, messages, signatures, committee_aggs, agg_stride):
+    """The arguments of the aggregateSetsBits family -> (key table bytes, n_table, idx array or None, c_offsets array, m, aggregates or None,
+    agg_stride, which array, bits, k, messages, signatures).  committees: as _key_lists takes key lists (a list of key lists laid end to
+    end, or a tuple (table, idx, c_offsets)); which: k committee numbers; bits: the packed fields, or a list of one bytes object per set -
+    set s owns exactly ceil(L / 8) bytes, L the length of its committee, position i at bit i % 8 of byte i // 8; committee_aggs: None, or
+    m 96-byte aggregate keys agg_stride bytes apart (320: the records aggregateSets wrote for the committees)."""
+    if isinstance(committees, tuple):
+        m = len(committees[2]) - 1
+    else:
+        committees = list(committees)
+        m = len(committees)
+    table, n_table, idx, offs, m, _, _ = _key_lists(committees, bytes(32 * max(m, 0)), bytes(192 * max(m, 0)))
+    if any(offs[c + 1] < offs[c] for c in range(m)):
+        raise ValueError("committee offsets do not decrease")
+    which = [int(x) for x in which]
+    if any(x < 0 or x >= m for x in which):
+        raise ValueError("which: committee numbers below %d" % m)
+    k = len(which)
+    need = [(offs[c + 1] - offs[c] + 7) // 8 for c in which]
+    if isinstance(bits, (bytes, bytearray, memoryview)):
+        bits = bytes(bits)
+    else:
+        bits = [bytes(b) for b in bits]
+        if len(bits) != k or any(len(b) != n for b, n in zip(bits, need)):
+            raise ValueError("bits: one field of ceil(L / 8) bytes per set")
+        bits = b"".join(bits)
+    if len(bits) != sum(need):
+        raise ValueError("bits: %d bytes for these sets, not %d" % (sum(need), len(bits)))
+    ms, sg = _join(messages, 32, "messages"), _join(signatures, 192, "signatures")
+    if len(ms) != 32 * k or len(sg) != 192 * k:
+        raise ValueError("one 32-byte message and one 192-byte signature per set")
+    if committee_aggs is not None:
+        committee_aggs, agg_stride = bytes(committee_aggs), int(agg_stride)
+        if agg_stride < 96 or agg_stride % 4:
+            raise ValueError("agg_stride: at least 96 and a multiple of 4")
+        if m and len(committee_aggs) < (m - 1) * agg_stride + 96:
+            raise ValueError("committee_aggs: one 96-byte aggregate per committee, agg_stride bytes apart")
+    return table, n_table, idx, offs, m, committee_aggs, agg_stride, (ctypes.c_uint32 * max(k, 1))(*which), bits, k, ms, sg
+
+
+def aggregateSetsBits(cache, committees, which, bits, messages, signatures, committee_aggs=None, agg_stride=96):
+    """aggregateSets from committees and participation bits (mi355_bls_aggregate_sets_bits): the key of set s is aggregateAll over the keys
+    of committee which[s] whose bit is set - computed, where committee_aggs is given and more than half of the committee signed, as
+    subtractAll (blst_min_pubkey_sig_core.nim:197-209) of the absentees from the committee's aggregate.  Arguments as _bit_sets takes
+    them.  -> (all_ok, k x 320-byte records, k status bytes), byte for byte aggregateSets' for the expanded index lists."""
+    table, n_table, idx, offs, m, aggs, stride, wh, bits, k, ms, sg = _bit_sets(committees, which, bits, messages, signatures, committee_aggs, agg_stride)
+    if k == 0:
+        return False, b"", b""
+    out, st = ctypes.create_string_buffer(320 * k), ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_aggregate_sets_bits(cache._h, table or b"\0", n_table, idx, offs, m, aggs, stride, wh, bits or b"\0", k, ms, sg, out, st))
+    return bool(ok), out.raw, st.raw
+
+
+def _bits_device_args(c_offsets, which):
+    m, k = len(c_offsets) - 1, len(which)
+    if m < 0 or any(int(x) < 0 or int(x) >= m for x in which):
+        raise ValueError("which: committee numbers below %d" % max(m, 0))
+    return (ctypes.c_size_t * (m + 1))(*c_offsets), m, (ctypes.c_uint32 * max(k, 1))(*which), k
+
+
+def aggregateSetsBits_device(cache, d_keys, n_table, d_idx, c_offsets, d_committee_aggs, agg_stride, which, d_bits, d_msgs, d_sigs, d_out, stream=0):
+    """Same with the key table, the indices (0 / None: none), the committee aggregates (0 / None: none), the bits, messages, signatures and
+    the output records in device memory (raw pointers); c_offsets and which stay on the host.  -> (all_ok, status bytes)."""
+    offs, m, wh, k = _bits_device_args(c_offsets, which)
+    if k == 0:
+        return False, b""
+    st = ctypes.create_string_buffer(k)
+    ok = _check(lib().mi355_bls_aggregate_sets_bits_device(cache._h, d_keys, n_table, d_idx or None, offs, m, d_committee_aggs or None, agg_stride, wh, d_bits, k,
+                                                           d_msgs, d_sigs, d_out, st, stream))
+    return bool(ok), st.raw
+
+
+def fastAggregateVerifyEachBits(cache, committees, which, bits, messages, signatures, committee_aggs=None, agg_stride=96):
+    """fastAggregateVerify (bls_sig_min_pubkey.nim:234-258) of every set's participants (mi355_bls_fast_aggregate_verify_each_bits):
+    -> [bool], one per set; a set without a set bit gives False."""
+    table, n_table, idx, offs, m, aggs, stride, wh, bits, k, ms, sg = _bit_sets(committees, which, bits, messages, signatures, committee_aggs, agg_stride)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_fast_aggregate_verify_each_bits(cache._h, table or b"\0", n_table, idx, offs, m, aggs, stride, wh, bits or b"\0", k, ms, sg, out))
+    return [v == 1 for v in out.raw]
+
+
+def fastAggregateVerifyEachBits_device(cache, d_keys, n_table, d_idx, c_offsets, d_committee_aggs, agg_stride, which, d_bits, d_msgs, d_sigs, stream=0):
+    offs, m, wh, k = _bits_device_args(c_offsets, which)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_fast_aggregate_verify_each_bits_device(cache._h, d_keys, n_table, d_idx or None, offs, m, d_committee_aggs or None, agg_stride, wh,
+                                                                   d_bits, k, d_msgs, d_sigs, out, stream))
+    return [v == 1 for v in out.raw]
+
+
+def batchFastAggregateVerifyBits(cache, committees, which, bits, messages, signatures, secureRandomBytes, committee_aggs=None, agg_stride=96):
+    """batchVerify over the sets (aggregateAll(participants_s), message_s, signature_s) (mi355_bls_batch_fast_aggregate_verify_bits): False
+    when a set gives no key or the batch does not verify; no sets -> False."""
+    rnd = _rnd32(secureRandomBytes)
+    table, n_table, idx, offs, m, aggs, stride, wh, bits, k, ms, sg = _bit_sets(committees, which, bits, messages, signatures, committee_aggs, agg_stride)
+    if k == 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_fast_aggregate_verify_bits(cache._h, table or b"\0", n_table, idx, offs, m, aggs, stride, wh, bits or b"\0", k, ms,
+                                                                        sg, rnd)))
+
+
+def batchFastAggregateVerifyBits_device(cache, d_keys, n_table, d_idx, c_offsets, d_committee_aggs, agg_stride, which, d_bits, d_msgs, d_sigs, secureRandomBytes,
+                                        stream=0):
+    rnd = _rnd32(secureRandomBytes)
+    offs, m, wh, k = _bits_device_args(c_offsets, which)
+    if k == 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_fast_aggregate_verify_bits_device(cache._h, d_keys, n_table, d_idx or None, offs, m, d_committee_aggs or None,
+                                                                               agg_stride, wh, d_bits, k, d_msgs, d_sigs, rnd, stream)))
+
+
+def debug_aggregate_bits_routes(cache):
+    """Test hook (mi355_bls_debug_aggregate_bits_routes): (sets summed directly, sets by exclusion) of the cache's last bits call."""
+    out = (ctypes.c_uint32 * 2)()
+    _check(lib().mi355_bls_debug_aggregate_bits_routes(cache._h, out))
+    return out[0], out[1]
 
 
 def _position_messages(messages, n_positions):

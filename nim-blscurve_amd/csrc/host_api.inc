@@ -125,6 +125,10 @@ struct mi355_bls_ctx {
     dev_buf<uint8_t> d_agg_in;       // host inputs staged: keys | signatures | messages | indices
     std::vector<uint32_t> agg_tab;   // the table of the call in flight: the async copy reads it
     std::vector<uint8_t> agg_status_h;
+    // key aggregation by participation bits (mi355_bls_aggregate_sets_bits): shares the buffers above (the flag words carry the two route
+    // counters behind the k per-set words, the table is items | sets)
+    dev_buf<uint8_t> d_aggb_mode;    // per set: the mode byte (aggbits.hpp AGGB_*)
+    uint32_t aggb_routes[2] = {0, 0};      // sets of the last bits call summed directly / by exclusion (mi355_bls_debug_aggregate_bits_routes)
     // same-message pre-aggregation (mi355_bls_combine_sets): sized by the call like the buffers above, which it shares (item table, G1
     // partials, flag words, status bytes, records, staged inputs)
     dev_buf<uint64_t> d_comb_s;      // s_j by position: blinding material, cleared before every return
@@ -1271,6 +1275,199 @@ extern "C" int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* c, const voi
     int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
     if (rc) return rc;
     return agg_batch(c, in, n_table, offsets, k, rnd, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Key aggregation by participation bits: the records of aggregate_sets for k sets given as (committee number, one bit per committee
+// position) over m fixed committees - aggregateAll over the keys whose bit is set, or, where the committee's own aggregate is given and more
+// than half of it signed, subtractAll (blst_min_pubkey_sig_core.nim:197-209) of the absentees from that aggregate.  The plan (plan.hpp
+// aggbits_fill) depends on the committee lengths alone: one table copy, k_aggbits_mode, k_aggbits_l0, the levels of k_aggsets_ln and
+// k_aggbits_finish follow on the caller's stream without a read-back in between.
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(plan::aggb_set) == 16, "k_aggbits_mode / k_aggbits_finish load a set as one uint4");
+// device addresses of a call's inputs beyond agg_in's (aggs == nullptr: no bases)
+struct aggb_in {
+    agg_in a;
+    const uint8_t* aggs;
+    size_t agg_stride;
+    const uint8_t* bits;
+};
+static bool aggb_args_ok(size_t n_table, bool have_idx, const size_t* c_offsets, size_t m, const void* aggs, size_t agg_stride, const uint32_t* which, size_t k) {
+    if (!c_offsets || !which) return false;
+    if (aggs && (agg_stride < 96 || agg_stride % 4)) {
+        g_err = "aggregate_sets_bits: agg_stride is at least 96 and a multiple of 4";
+        return false;
+    }
+    if (!agg_offsets_ok(c_offsets, m) || (!have_idx && m && c_offsets[m] > n_table)) {
+        g_err = "aggregate_sets_bits: committee offsets decrease, or c_offsets[m] exceeds the number of keys";
+        return false;
+    }
+    for (size_t s = 0; s < k; s++)
+        if (which[s] >= m) {
+            g_err = "aggregate_sets_bits: a set names a committee that is not there";
+            return false;
+        }
+    return true;
+}
+// aggregation of k > 0 sets enqueued on st: records at d_out, status bytes in c->d_agg_status, the route census on its way to c->aggb_routes
+static int aggbits_enqueue(mi355_bls_ctx* c, const aggb_in& in, size_t n_table, const size_t* c_offsets, size_t m, const uint32_t* which, size_t k, uint8_t* d_out,
+                           hipStream_t st) {
+    if (!in.a.keys || !in.a.msgs || !in.a.sigs || !in.bits || !d_out) return MI355_BLS_ERR_ARG;
+    if (((uintptr_t)in.a.keys | (uintptr_t)in.a.msgs | (uintptr_t)in.a.sigs | (uintptr_t)in.a.idx | (uintptr_t)in.aggs | (uintptr_t)d_out) & 3) {
+        g_err = "aggregate_sets_bits: keys, messages, signatures, indices, committee aggregates and records must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (!aggb_args_ok(n_table, in.a.idx != nullptr, c_offsets, m, in.aggs, in.agg_stride, which, k)) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const plan::aggbits_plan p = plan::aggbits_measure(c_offsets, m, which, k);
+    if (!p.ok) {
+        g_err = "aggregate_sets_bits: more than 2^32 - 2 positions, sets or level-0 items";
+        return MI355_BLS_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    c->agg_tab.resize((p.items + k) * 4);
+    plan::aggbits_fill(p, c_offsets, which, k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), reinterpret_cast<plan::aggb_set*>(c->agg_tab.data() + p.items * 4));
+    const size_t pb = (p.items ? p.items : 1) * (size_t)G1W * 4, tb = c->agg_tab.size() * 4;
+    int rc = c->d_agg_part.reserve(pb, pb / 4);
+    if (!rc) rc = c->d_agg_tab.reserve(tb, tb / 4);
+    if (!rc) rc = c->d_agg_bad.reserve((k + 2) * 4, k);
+    if (!rc) rc = c->d_agg_status.reserve(k, k / 4);
+    if (!rc) rc = c->d_aggb_mode.reserve(k, k / 4);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, (k + 2) * 4, st));
+    HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), tb, hipMemcpyHostToDevice, st));
+    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
+    const uint4* sets = items + p.items;
+    uint32_t* routes = c->d_agg_bad + k;
+    k_aggbits_mode<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(sets, (uint32_t)k, in.bits, in.aggs, in.agg_stride, c->d_aggb_mode, routes);
+    for (uint32_t l = 0; l < p.levels; l++) {
+        const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
+        if (l == 0) k_aggbits_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, in.a.keys, n_table, in.a.idx, in.bits, c->d_aggb_mode, c->d_agg_part, c->d_agg_bad);
+        else k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + p.level_first[l], cnt, c->d_agg_part);
+    }
+    k_aggbits_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(sets, (uint32_t)k, c->d_agg_part, c->d_agg_bad, c->d_aggb_mode, in.aggs, in.agg_stride,
+                                                                   reinterpret_cast<const uint32_t*>(in.a.msgs), reinterpret_cast<const uint32_t*>(in.a.sigs),
+                                                                   reinterpret_cast<uint32_t*>(d_out), c->d_agg_status);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->aggb_routes, routes, 8, hipMemcpyDeviceToHost, st));      // there when aggsets_status has synchronised
+    return 0;
+}
+// host inputs -> d_agg_in (keys | signatures | messages | indices | committee aggregates, packed | bits: the byte-aligned part last)
+static int aggb_stage(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m, const void* aggs, size_t agg_stride,
+                      const uint32_t* which, const void* bits, size_t k, const void* msgs, const void* sigs, hipStream_t st, aggb_in* out) {
+    if (!keys || !msgs || !sigs || !bits || !aggb_args_ok(n_table, idx != nullptr, c_offsets, m, aggs, agg_stride, which, k)) return MI355_BLS_ERR_ARG;
+    const plan::aggbits_plan p = plan::aggbits_measure(c_offsets, m, which, k);
+    if (!p.ok) {
+        g_err = "aggregate_sets_bits: more than 2^32 - 2 positions, sets or level-0 items";
+        return MI355_BLS_ERR_ARG;
+    }
+    const size_t n_idx = idx ? c_offsets[m] : 0, kb = n_table * 96, sb = k * 192, mb = k * 32, ib = n_idx * 4, ab = aggs ? m * 96 : 0;
+    const size_t all = kb + sb + mb + ib + ab + p.bits_bytes + 4;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->d_agg_in.reserve(all, all / 4);
+    if (rc) return rc;
+    uint8_t* d = c->d_agg_in;
+    if (kb) HIPCHK(hipMemcpyAsync(d, keys, kb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d + kb, sigs, sb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d + kb + sb, msgs, mb, hipMemcpyHostToDevice, st));
+    if (ib) HIPCHK(hipMemcpyAsync(d + kb + sb + mb, idx, ib, hipMemcpyHostToDevice, st));
+    uint8_t* da = d + kb + sb + mb + ib;
+    if (ab) HIPCHK(hipMemcpy2DAsync(da, 96, aggs, agg_stride, 96, m, hipMemcpyHostToDevice, st));
+    if (p.bits_bytes) HIPCHK(hipMemcpyAsync(da + ab, bits, p.bits_bytes, hipMemcpyHostToDevice, st));
+    *out = aggb_in{agg_in{d, idx ? reinterpret_cast<const uint32_t*>(d + kb + sb + mb) : nullptr, d + kb + sb, d + kb}, aggs ? da : nullptr, 96, da + ab};
+    return 0;
+}
+extern "C" int mi355_bls_aggregate_sets_bits_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets, size_t m,
+                                                    const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits, size_t k,
+                                                    const void* d_msgs32, const void* d_sigs192, void* d_out_records, uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing aggregated, nothing written
+    if (!status) return MI355_BLS_ERR_ARG;
+    const aggb_in in{agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, (const uint8_t*)d_committee_aggs, agg_stride,
+                     (const uint8_t*)d_bits};
+    int rc = aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, (uint8_t*)d_out_records, (hipStream_t)stream);
+    if (rc) return rc;
+    return aggsets_status(c, k, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_aggregate_sets_bits(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
+                                             const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k, const void* msgs32,
+                                             const void* sigs192, void* out_records, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!out_records || !status) return MI355_BLS_ERR_ARG;
+    aggb_in in;
+    int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in);
+    if (!rc) rc = c->d_agg_rec.reserve(k * 320, k * 80);
+    if (!rc) rc = aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, c->d_agg_rec, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out_records, c->d_agg_rec, k * 320, hipMemcpyDeviceToHost, nullptr));
+    return aggsets_status(c, k, status, nullptr);
+}
+// the records into the context's own buffer, then the per-set pass on them, as agg_each
+static int aggb_each(mi355_bls_ctx* c, const aggb_in& in, size_t n_table, const size_t* c_offsets, size_t m, const uint32_t* which, size_t k, uint8_t* out,
+                     hipStream_t st) {
+    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
+    if (!rc) rc = aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, c->d_agg_rec, st);
+    if (rc) return rc;
+    return each_run(c, c->d_agg_rec, nullptr, k, out, nullptr, st);
+}
+extern "C" int mi355_bls_fast_aggregate_verify_each_bits_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets,
+                                                                size_t m, const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits,
+                                                                size_t k, const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!out) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const aggb_in in{agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, (const uint8_t*)d_committee_aggs, agg_stride,
+                     (const uint8_t*)d_bits};
+    return aggb_each(c, in, n_table, c_offsets, m, which, k, out, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_fast_aggregate_verify_each_bits(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
+                                                         const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k,
+                                                         const void* msgs32, const void* sigs192, uint8_t* out) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!out) return MI355_BLS_ERR_ARG;
+    aggb_in in;
+    int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in);
+    if (rc) return rc;
+    return aggb_each(c, in, n_table, c_offsets, m, which, k, out, nullptr);
+}
+// batchVerify over the records, as agg_batch: any status but 0 ends the call with 0 before any verification pass
+static int aggb_batch(mi355_bls_ctx* c, const aggb_in& in, size_t n_table, const size_t* c_offsets, size_t m, const uint32_t* which, size_t k, const uint8_t rnd[32],
+                      hipStream_t st) {
+    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
+    if (!rc) rc = aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, c->d_agg_rec, st);
+    if (rc) return rc;
+    c->agg_status_h.resize(k);
+    rc = aggsets_status(c, k, c->agg_status_h.data(), st);
+    if (rc != 1) return rc;
+    return verify_common(c, c->d_agg_rec, nullptr, k, rnd, 0, st);
+}
+extern "C" int mi355_bls_batch_fast_aggregate_verify_bits_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets,
+                                                                 size_t m, const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits,
+                                                                 size_t k, const void* d_msgs32, const void* d_sigs192, const uint8_t rnd[32], void* stream) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const aggb_in in{agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, (const uint8_t*)d_committee_aggs, agg_stride,
+                     (const uint8_t*)d_bits};
+    return aggb_batch(c, in, n_table, c_offsets, m, which, k, rnd, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_batch_fast_aggregate_verify_bits(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
+                                                          const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k,
+                                                          const void* msgs32, const void* sigs192, const uint8_t rnd[32]) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    aggb_in in;
+    int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in);
+    if (rc) return rc;
+    return aggb_batch(c, in, n_table, c_offsets, m, which, k, rnd, nullptr);
+}
+extern "C" int mi355_bls_debug_aggregate_bits_routes(mi355_bls_ctx* c, uint32_t out[2]) {
+    if (!c || !out) return MI355_BLS_ERR_ARG;
+    out[0] = c->aggb_routes[0], out[1] = c->aggb_routes[1];
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -36,6 +36,7 @@
 #include "vereach.hpp"
 #include "aggveach.hpp"
 #include "aggsets.hpp"
+#include "aggbits.hpp"
 #include "combsets.hpp"
 #include "aggsigs.hpp"
 #include "recover.hpp"
@@ -2523,6 +2524,60 @@ __global__ void __launch_bounds__(WAVE) k_aggsets_finish(const uint32_t* __restr
     const uint32_t f = final_of[s];
     const bool empty = f == 0xffffffffu;
     const aggsets_end e = aggsets_finish_item(empty, seg_bad[s] != 0, empty ? jac_inf<fp>() : ld_g1_int(part + (size_t)f * G1W));
+    uint32_t* r = records + (size_t)s * 80;
+    for (int i = 0; i < 24; i++) r[i] = e.pk[i];
+    for (int i = 0; i < 8; i++) r[24 + i] = msgs[(size_t)s * 8 + i];
+    for (int i = 0; i < 48; i++) r[32 + i] = sigs[(size_t)s * 48 + i];
+    status[s] = e.status;
+}
+
+// ------------------------------------------------------------------------------------------
+// Key aggregation by participation bits (mi355_bls_aggregate_sets_bits: aggregateAll over the committee keys whose bit is set, or
+// subtractAll, blst_min_pubkey_sig_core.nim:197-209, of the absentees from the committee's aggregate).  The arithmetic is csrc/aggbits.hpp,
+// the tables are plan.hpp aggbits_fill's: items as above with the byte offset of a level-0 item's bits in its dst word, and per set the
+// four words bits_first, len, committee, final_of of plan::aggb_set.  Levels above level 0 are k_aggsets_ln's.
+// ------------------------------------------------------------------------------------------
+// one lane per set: its route and emptiness (aggbits.hpp AGGB_*) from its field and its committee's base (aggs == nullptr: no bases), and
+// the census of routes in routes[0] (summed directly) / routes[1] (by exclusion)
+__global__ void __launch_bounds__(WAVE) k_aggbits_mode(const uint4* __restrict__ sets, uint32_t k, const uint8_t* __restrict__ bits, const uint8_t* __restrict__ aggs,
+                                                       size_t agg_stride, uint8_t* __restrict__ mode, uint32_t* __restrict__ routes) {
+    uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= k) return;
+    const uint4 st = sets[s];
+    uint32_t any = 0;
+    if (aggs) {
+        const uint32_t* b = reinterpret_cast<const uint32_t*>(aggs + (size_t)st.z * agg_stride);
+        for (int i = 0; i < 24; i++) any |= b[i];
+    }
+    const uint8_t md = aggbits_mode_item(bits + st.x, st.y, any == 0);
+    mode[s] = md;
+    atomicAdd(routes + (md & AGGB_EXCLUDE), 1u);
+}
+// level 0, one lane per item: the keys that the item's bits select among up to AGGB_P committee positions (the complement on the exclusion
+// route) -> one partial.  Bounds check as in k_aggsets_l0.
+__global__ void __launch_bounds__(WAVE, 2) k_aggbits_l0(const uint4* __restrict__ items, uint32_t n_items, const uint8_t* __restrict__ keys, size_t n_table,
+                                                        const uint32_t* __restrict__ idx, const uint8_t* __restrict__ bits, const uint8_t* __restrict__ mode,
+                                                        uint32_t* __restrict__ part, uint32_t* __restrict__ seg_bad) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    const g1_jac acc = aggbits_l0_item(it.x, it.y, bits + it.z, (mode[it.w] & AGGB_EXCLUDE) != 0, idx, n_table,
+                                       [&](size_t t) { return ld_g1a_blst(reinterpret_cast<const uint32_t*>(keys + t * 96)); },
+                                       [&]() { atomicOr(seg_bad + it.w, 1u); });
+    st_g1_int(part + (size_t)i * G1W, acc);
+}
+// one lane per set: its last partial - subtracted from its committee's base on the exclusion route - to affine, the record and the status
+// byte as k_aggsets_finish writes them
+__global__ void __launch_bounds__(WAVE) k_aggbits_finish(const uint4* __restrict__ sets, uint32_t k, const uint32_t* __restrict__ part, const uint32_t* __restrict__ seg_bad,
+                                                         const uint8_t* __restrict__ mode, const uint8_t* __restrict__ aggs, size_t agg_stride,
+                                                         const uint32_t* __restrict__ msgs, const uint32_t* __restrict__ sigs, uint32_t* __restrict__ records,
+                                                         uint8_t* __restrict__ status) {
+    uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= k) return;
+    const uint4 st = sets[s];
+    const bool has = st.w != 0xffffffffu;
+    const aggsets_end e = aggbits_finish_item(mode[s], has, seg_bad[s] != 0, has ? ld_g1_int(part + (size_t)st.w * G1W) : jac_inf<fp>(),
+                                              [&]() { return ld_g1a_blst(reinterpret_cast<const uint32_t*>(aggs + (size_t)st.z * agg_stride)); });
     uint32_t* r = records + (size_t)s * 80;
     for (int i = 0; i < 24; i++) r[i] = e.pk[i];
     for (int i = 0; i < 8; i++) r[24 + i] = msgs[(size_t)s * 8 + i];

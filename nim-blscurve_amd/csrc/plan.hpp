@@ -360,6 +360,88 @@ inline void aggsets_fill(const aggsets_plan& p, const size_t* offsets, size_t k,
     }
 }
 
+// Key aggregation by participation bits (mi355_bls_aggregate_sets_bits): m committees in CSR form (committee c = positions [c_offsets[c],
+// c_offsets[c + 1]) of the key sequence) and k sets, set s naming committee which[s] and owning ceil(L / 8) bytes of the packed bit fields
+// (L = its committee's length; SSZ order: position i is bit i % 8 of byte i / 8).  The same levelled one-lane-item segmented sum as
+// aggsets_fill, laid over the committee POSITIONS of every set: the layout depends on the committee lengths alone, never on the bits, so
+// the device form needs no read-back before it.  A level-0 item covers AGGB_P consecutive positions of one set - its src_first is the
+// position of the first one in the key sequence, and, because at level 0 dst is the item's own number, that word carries the offset of the
+// item's first byte in the bit fields instead (partial i is written by item i, as above).  Levels above are aggsets_fill's own: AGG_C
+// partials per item.  Per set the table keeps where its field starts, its length, its committee and final_of (AGG_NONE only for a
+// committee of length 0).
+//   AGGB_P = 8: one byte of the field per lane, the first choice; no other value was tried (32, a word of bits per lane, is the one that
+//   would halve the level-0 partials at four times the serial additions of a lane).
+constexpr uint32_t AGGB_P = 8;
+static_assert(AGGB_P % 8 == 0 && AGGB_P >= 8 && AGGB_P <= 32, "a level-0 item owns whole bytes of a field and selects through one 32-bit word");
+struct aggb_set {
+    uint32_t bits_first, len, committee, final_of;   // first byte of the set's field; committee length; committee; the set's last partial
+};
+struct aggbits_plan {
+    bool ok;                                 // false: offsets decrease, a which[s] >= m, or 2^32 - 1 or more positions, sets, items or field bytes
+    uint32_t levels;
+    size_t level_first[AGG_MAX_LEVELS + 1];
+    size_t items;
+    size_t bits_bytes;                       // the packed fields of all k sets
+};
+inline aggbits_plan aggbits_measure(const size_t* c_offsets, size_t m, const uint32_t* which, size_t k) {
+    aggbits_plan p{};
+    for (size_t c = 0; c < m; c++)
+        if (c_offsets[c + 1] < c_offsets[c]) return p;
+    if (k >= AGG_NONE || (m && c_offsets[m] >= AGG_NONE)) return p;
+    size_t per_level[AGG_MAX_LEVELS] = {};
+    for (size_t s = 0; s < k; s++) {
+        if (which[s] >= m) return p;
+        const size_t len = c_offsets[which[s] + 1] - c_offsets[which[s]];
+        p.bits_bytes += (len + 7) / 8;
+        size_t n = (len + AGGB_P - 1) / AGGB_P;
+        for (uint32_t l = 0; n > 0;) {       // ceil(len / P) partials, then aggsets_measure's levels until there is one
+            per_level[l++] += n;
+            if (l > p.levels) p.levels = l;
+            if (n == 1) break;
+            n = agg_ceil_div(n);
+        }
+        if (per_level[0] >= AGG_NONE || p.bits_bytes >= AGG_NONE) return p;      // (keeps the sums far from wrapping, whatever k is)
+    }
+    for (uint32_t l = 0; l < p.levels; l++) p.level_first[l + 1] = p.level_first[l] + per_level[l];
+    p.items = p.level_first[p.levels];
+    p.ok = p.items < AGG_NONE;
+    return p;
+}
+// the item table (p.items entries) and the set table (k entries), one walk over the sets
+inline void aggbits_fill(const aggbits_plan& p, const size_t* c_offsets, const uint32_t* which, size_t k, agg_item* items, aggb_set* sets) {
+    size_t cur[AGG_MAX_LEVELS];
+    for (uint32_t l = 0; l < AGG_MAX_LEVELS; l++) cur[l] = l < p.levels ? p.level_first[l] : 0;
+    size_t byte = 0;
+    for (size_t s = 0; s < k; s++) {
+        const size_t first = c_offsets[which[s]], len = c_offsets[which[s] + 1] - first;
+        sets[s] = aggb_set{(uint32_t)byte, (uint32_t)len, which[s], AGG_NONE};
+        size_t n = (len + AGGB_P - 1) / AGGB_P, src = 0;
+        for (uint32_t l = 0; n > 0; l++) {
+            const size_t base = cur[l];
+            if (l == 0) {
+                for (size_t j = 0; j < n; j++) {
+                    const size_t left = len - j * AGGB_P;
+                    items[base + j] = agg_item{(uint32_t)(first + j * AGGB_P), (uint32_t)(left < AGGB_P ? left : AGGB_P), (uint32_t)(byte + j * (AGGB_P / 8)), (uint32_t)s};
+                }
+            } else {
+                const size_t below = n;
+                n = agg_ceil_div(below);
+                for (size_t j = 0; j < n; j++) {
+                    const size_t left = below - j * AGG_C;
+                    items[base + j] = agg_item{(uint32_t)(src + j * AGG_C), (uint32_t)(left < AGG_C ? left : AGG_C), (uint32_t)(base + j), (uint32_t)s};
+                }
+            }
+            cur[l] += n;
+            src = base;
+            if (n == 1) {
+                sets[s].final_of = (uint32_t)base;
+                break;
+            }
+        }
+        byte += (len + 7) / 8;
+    }
+}
+
 // Same-message pre-aggregation of k groups (mi355_bls_combine_sets): the members are positions [offsets[0], offsets[k]) of the call's member
 // sequence, renumbered from 0; the two segmented sums run over aggsets_measure / aggsets_fill's tables for the renumbered offsets (level 0
 // reads the per-member products by position).
