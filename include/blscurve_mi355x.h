@@ -425,6 +425,41 @@ int mi355_bls_compress_signatures_device(mi355_bls_ctx* ctx, const void* d_sigs1
 int mi355_bls_deserialize_signatures(mi355_bls_ctx* ctx, const uint8_t* sigs, size_t n, uint32_t flags, void* out_sigs192, uint8_t* status);
 int mi355_bls_deserialize_signatures_device(mi355_bls_ctx* ctx, const void* d_sigs, size_t n, uint32_t flags, void* d_out_sigs192, uint8_t* status,
                                             void* stream);
+/* PublicKey.fromBytes / fromBytesKnownOnCurve (bls_sig_io.nim:81-121) for n keys that arrive without a signature or a message (a validator
+ * key table in its wire form): the key half of mi355_bls_deserialize_sets_ex, by the same decoder.  This is the call that MAKES the
+ * device-resident key table the table-addressed calls take (aggregate_sets[_bits], fast_aggregate_verify_each, aggregate_verify_each, the pop
+ * calls): the _device form's d_out_pks96 is their d_keys / d_pks96 argument as it stands.  pks: n x 48 bytes, or n x 96 with
+ * MI355_BLS_DESER_PK_UNCOMPRESSED; MI355_BLS_DESER_KNOWN_ON_CURVE skips the subgroup check; MI355_BLS_DESER_SIG_UNCOMPRESSED is
+ * MI355_BLS_ERR_ARG (flags are defined with mi355_bls_deserialize_sets_ex, below).  out_pks96: n x 96-byte blst_p1_affine images, all zero
+ * where status[i] is not 0; status[i]: 0 ok, 1 bad encoding, 3 infinity, 2 not in G1, in that precedence, as mi355_bls_deserialize_sets
+ * gives them.  Returns 1 when every status is 0, else 0 (n == 0: 1); negative on failure.  Any n.  The host form's out_pks96 and both
+ * forms' status may be NULL; the _device form reads d_pks and writes d_out_pks96 (4-byte aligned) in device memory, status stays host memory.
+ * COST on one MI355X, device-resident, median of 5 blocking calls (profiles/key_table_bench.json): 1.49 / 1.76 / 23.7 ms at 4 096 / 65 536 / 2^20
+ * keys, against 3.45 / 3.59 / 55.7 ms for mi355_bls_deserialize_sets_ex_device over the same keys with one valid signature repeated in every row. */
+int mi355_bls_deserialize_public_keys(mi355_bls_ctx* ctx, const uint8_t* pks, size_t n, uint32_t flags, void* out_pks96, uint8_t* status);
+int mi355_bls_deserialize_public_keys_device(mi355_bls_ctx* ctx, const void* d_pks, size_t n, uint32_t flags, void* d_out_pks96, uint8_t* status,
+                                             void* stream);
+/* Key admission: what a deposit needs before its key may enter the table - PublicKey.fromBytes, Signature.fromBytes and popVerify
+ * (bls_sig_io.nim:42-58, 81-99; bls_sig_min_pubkey.nim:60-74) - for n (key, proof of possession) rows in their wire forms, one status per row.
+ * pks: n x 48 bytes, or n x 96 with MI355_BLS_DESER_PK_UNCOMPRESSED; proofs: n x 96 bytes, or n x 192 with MI355_BLS_DESER_SIG_UNCOMPRESSED;
+ * MI355_BLS_DESER_KNOWN_ON_CURVE is MI355_BLS_ERR_ARG (admission is the full check).  status[i] is the first that applies of: the key's status
+ * 1, 3 or 2 (mi355_bls_deserialize_public_keys); the proof's status 4 or 5 (mi355_bls_deserialize_signatures); MI355_BLS_KEY_BAD_PROOF when
+ * both decode and popVerify(pk_i, proof_i) is false (the infinity proof included); 0.  status[i] == 0 iff the reference's three calls all
+ * succeed on row i; it depends on row i alone, whatever rnd is (rnd blinds the batch check as in mi355_bls_batch_pop_verify_locate, whose
+ * per-pair pass decides every row of a failing batch).  out_pks96: n x 96-byte images, row i the key where status[i] is 0 and all zero
+ * elsewhere - a table to use as it is.  Only the rows that decode reach the possession check, packed: a row that does not decode costs
+ * the others nothing, and a call in which no row decodes does no pairing work.  Returns 1 when every status is 0, else 0 (n == 0: 1,
+ * nothing written); negative on failure.  Any n (the check runs in slices of the context's capacity).  status and rnd are required; the host
+ * form's out_pks96 may be NULL.  The _device form reads d_pks and d_proofs and writes d_out_pks96 (4-byte aligned) in device memory.
+ * COST on one MI355X, device-resident, median of 5 blocking calls (profiles/key_table_bench.json), at 4 096 / 65 536 / 2^20 rows: 7.0 / 15.4 /
+ * 253 ms all valid, 7.0 / 16.0 / 251 ms with 1 % of the keys undecodable.  mi355_bls_deserialize_sets_ex_device, a host split of the records and
+ * mi355_bls_batch_pop_verify_locate_device over the same rows: 7.3 / 19.8 / 337 ms all valid, 26.6 / 91.1 / 1 461 ms on the 1 % table (its zeroed
+ * rows fail the batch, so every row pays the per-pair pass). */
+#define MI355_BLS_KEY_BAD_PROOF 8
+int mi355_bls_admit_keys(mi355_bls_ctx* ctx, const uint8_t* pks, const uint8_t* proofs, size_t n, uint32_t flags, const uint8_t rnd[32], void* out_pks96,
+                         uint8_t* status);
+int mi355_bls_admit_keys_device(mi355_bls_ctx* ctx, const void* d_pks, const void* d_proofs, size_t n, uint32_t flags, const uint8_t rnd[32],
+                                void* d_out_pks96, uint8_t* status, void* stream);
 /* recover(signs, ids) (blst_recovery.nim:150-156: lagrangeInterpolation, :90-121, at 0 in the exponent) for k groups of threshold-signature
  * shares in one device pass: group g's t_g shares, made with Shamir shares of one secret key, give the signature of that key.
  *   sigs192, n_table, idx, offsets   the addressing of mi355_bls_aggregate_signature_sets: a table of 192-byte blst_p2_affine images, an

@@ -136,6 +136,10 @@ def lib():
         L.mi355_bls_compress_signatures_device.argtypes = [vp, vp, sz, vp, vp]
         L.mi355_bls_deserialize_signatures.argtypes = [vp, ctypes.c_char_p, sz, u32, vp, vp]
         L.mi355_bls_deserialize_signatures_device.argtypes = [vp, vp, sz, u32, vp, vp, vp]
+        L.mi355_bls_deserialize_public_keys.argtypes = [vp, ctypes.c_char_p, sz, u32, vp, vp]
+        L.mi355_bls_deserialize_public_keys_device.argtypes = [vp, vp, sz, u32, vp, vp, vp]
+        L.mi355_bls_admit_keys.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz, u32, ctypes.c_char_p, vp, vp]
+        L.mi355_bls_admit_keys_device.argtypes = [vp, vp, vp, sz, u32, ctypes.c_char_p, vp, vp, vp]
         L.mi355_bls_combine_sets.argtypes = [vp, vp, sz, pu32, psz, sz, ctypes.c_char_p, vp, vp]
         L.mi355_bls_combine_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, ctypes.c_char_p, vp, vp, vp]
         L.mi355_bls_batch_verify_combined.argtypes = [vp, vp, sz, pu32, psz, sz, ctypes.c_char_p, ctypes.c_char_p]
@@ -1144,6 +1148,69 @@ def deserializeSignatures_device(cache, d_sigs, n, d_out192, sig_uncompressed=Fa
     flags = (2 if sig_uncompressed else 0) | (4 if known_on_curve else 0)
     st = ctypes.create_string_buffer(n)
     ok = _check(lib().mi355_bls_deserialize_signatures_device(cache._h, d_sigs, n, flags, d_out192, st, stream))
+    return bool(ok), st.raw
+
+
+def deserializePublicKeys(cache, publicKeys, pk_uncompressed=False, known_on_curve=False):
+    """PublicKey.fromBytes (bls_sig_io.nim:81-99) for n keys without signature or message (mi355_bls_deserialize_public_keys): n x 48 bytes
+    (n x 96 with pk_uncompressed); known_on_curve: fromBytesKnownOnCurve.  -> (all_ok, n x 96-byte images, zeroed on failure, status bytes:
+    0 ok, 1 bad encoding, 3 infinity, 2 not in G1)."""
+    unit = 96 if pk_uncompressed else 48
+    pk = _join(publicKeys, unit, "wire public keys")
+    n = len(pk) // unit
+    if n == 0:
+        return True, b"", b""
+    flags = (1 if pk_uncompressed else 0) | (4 if known_on_curve else 0)       # DESER_PK_UNCOMPRESSED, DESER_KNOWN_ON_CURVE
+    out, st = ctypes.create_string_buffer(96 * n), ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_deserialize_public_keys(cache._h, pk, n, flags, out, st))
+    return bool(ok), out.raw, st.raw
+
+
+def deserializePublicKeys_device(cache, d_pks, n, d_out96, pk_uncompressed=False, known_on_curve=False, stream=0):
+    """Same with the wire bytes and the n x 96 output bytes in device memory (raw pointers): d_out96 is then the key table the table-addressed
+    calls (aggregateSets_device, popVerifyEach_device, ...) take.  -> (all_ok, status bytes)."""
+    if n == 0:
+        return True, b""
+    flags = (1 if pk_uncompressed else 0) | (4 if known_on_curve else 0)
+    st = ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_deserialize_public_keys_device(cache._h, d_pks, n, flags, d_out96, st, stream))
+    return bool(ok), st.raw
+
+
+KEY_BAD_PROOF = 8                    # status byte of admitKeys beyond the decoders' own: both decode, popVerify is false
+
+
+def _wire_keys_and_proofs(publicKeys, proofs, pk_uncompressed, sig_uncompressed):
+    """n wire keys (48 bytes, 96 uncompressed), n wire proofs (96 bytes, 192 uncompressed), lists or concatenated -> (keys, proofs, n)"""
+    ku, pu = (96 if pk_uncompressed else 48), (192 if sig_uncompressed else 96)
+    pk, pr = _join(publicKeys, ku, "wire public keys"), _join(proofs, pu, "wire proofs of possession")
+    if len(pk) // ku != len(pr) // pu:
+        raise ValueError("as many proofs as public keys: got %d keys, %d proofs" % (len(pk) // ku, len(pr) // pu))
+    return pk, pr, len(pk) // ku
+
+
+def admitKeys(cache, publicKeys, proofs, secureRandomBytes, pk_uncompressed=False, sig_uncompressed=False):
+    """PublicKey.fromBytes, Signature.fromBytes and popVerify for n (key, proof) rows on the wire (mi355_bls_admit_keys): the admission of
+    deposits into the key table.  -> (all_ok, n x 96-byte key table: row i is the key where status[i] == 0 and all zero elsewhere, status bytes:
+    0 admitted, 1 / 3 / 2 the key's decoding, 4 / 5 the proof's, KEY_BAD_PROOF).  Only the rows that decode reach the possession check."""
+    pk, pr, n = _wire_keys_and_proofs(publicKeys, proofs, pk_uncompressed, sig_uncompressed)
+    rnd = _rnd32(secureRandomBytes)
+    if n == 0:
+        return True, b"", b""
+    flags = (1 if pk_uncompressed else 0) | (2 if sig_uncompressed else 0)
+    out, st = ctypes.create_string_buffer(96 * n), ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_admit_keys(cache._h, pk, pr, n, flags, rnd, out, st))
+    return bool(ok), out.raw, st.raw
+
+
+def admitKeys_device(cache, d_pks, d_proofs, n, secureRandomBytes, d_out96, pk_uncompressed=False, sig_uncompressed=False, stream=0):
+    """Same with both wire columns and the n x 96-byte table in device memory (raw pointers).  -> (all_ok, status bytes)."""
+    rnd = _rnd32(secureRandomBytes)
+    if n == 0:
+        return True, b""
+    flags = (1 if pk_uncompressed else 0) | (2 if sig_uncompressed else 0)
+    st = ctypes.create_string_buffer(n)
+    ok = _check(lib().mi355_bls_admit_keys_device(cache._h, d_pks, d_proofs, n, flags, rnd, d_out96, st, stream))
     return bool(ok), st.raw
 
 

@@ -237,13 +237,18 @@ BLS_HD uint8_t deserialize_signature(g2_aff& sig, const uint8_t* sigb, uint32_t 
     if (!(flags & DESER_F_KNOWN_ON_CURVE) && !inf && !g2_in_subgroup(sig)) return DESER_SIG_NOT_IN_G2;
     return DESER_OK;
 }
-BLS_HD uint8_t deserialize_tuple(g1_aff& pk, g2_aff& sig, const uint8_t* pkb, const uint8_t* sigb, uint32_t flags) {
+// the key half on its own (mi355_bls_deserialize_public_keys: a key table that arrives without signatures)
+BLS_HD uint8_t deserialize_public_key(g1_aff& pk, const uint8_t* pkb, uint32_t flags) {
     bool inf;
-    bool ok = (flags & DESER_F_PK_UNCOMPRESSED) ? g1_deserialize(pk, inf, pkb) : g1_uncompress(pk, inf, pkb);
+    const bool ok = (flags & DESER_F_PK_UNCOMPRESSED) ? g1_deserialize(pk, inf, pkb) : g1_uncompress(pk, inf, pkb);
     if (!ok) return DESER_PK_BAD_ENCODING;
     if (inf) return DESER_PK_INFINITY;
     if (!(flags & DESER_F_KNOWN_ON_CURVE) && !g1_in_subgroup(pk)) return DESER_PK_NOT_IN_G1;
-    return deserialize_signature(sig, sigb, flags);
+    return DESER_OK;
+}
+BLS_HD uint8_t deserialize_tuple(g1_aff& pk, g2_aff& sig, const uint8_t* pkb, const uint8_t* sigb, uint32_t flags) {
+    const uint8_t st = deserialize_public_key(pk, pkb, flags);
+    return st != DESER_OK ? st : deserialize_signature(sig, sigb, flags);
 }
 
 }  // namespace bls

@@ -1864,6 +1864,116 @@ extern "C" int mi355_bls_deserialize_signatures(mi355_bls_ctx* c, const uint8_t*
     return rc;
 }
 
+// PublicKey.fromBytes (bls_sig_io.nim:81-121) for n keys without signature or message: k_deser's key half.  The device form leaves the images in
+// device memory (d_out_pks96: the key table every table-addressed call takes) and brings the status bytes to the host; 1 when every status is 0.
+extern "C" int mi355_bls_deserialize_public_keys_device(mi355_bls_ctx* c, const void* d_pks, size_t n, uint32_t dflags, void* d_out_pks96, uint8_t* status,
+                                                        void* stream) {
+    if (!c || dflags > 7 || (dflags & DESER_F_SIG_UNCOMPRESSED)) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 1;
+    if (!d_pks || !d_out_pks96 || n > plan::POP_MAX_KEYS || ((uintptr_t)d_out_pks96 & 3)) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;                     // the status bytes' device buffer
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
+    k_deser_pks<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>((const uint8_t*)d_pks, (uint32_t)n, dflags, (uint32_t*)d_out_pks96, c->d_status, c->d_flags);
+    HIPCHK(hipGetLastError());
+    uint32_t fl[4];
+    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
+    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return fl[2] ? 0 : 1;
+}
+extern "C" int mi355_bls_deserialize_public_keys(mi355_bls_ctx* c, const uint8_t* pks, size_t n, uint32_t dflags, void* out_pks96, uint8_t* status) {
+    if (!c || dflags > 7 || (dflags & DESER_F_SIG_UNCOMPRESSED)) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 1;
+    if (!pks || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(c->d_comp, pks, n * ((dflags & DESER_F_PK_UNCOMPRESSED) ? 96 : 48), hipMemcpyHostToDevice, nullptr));
+    int rc = mi355_bls_deserialize_public_keys_device(c, c->d_comp, n, dflags, c->d_sets, status, nullptr);
+    if (rc < 0) return rc;
+    if (out_pks96) HIPCHK(hipMemcpy(out_pks96, c->d_sets, n * 96, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// Key admission: PublicKey.fromBytes, Signature.fromBytes and popVerify (bls_sig_io.nim:42-58, 81-99; bls_sig_min_pubkey.nim:60-74) for n
+// (key, proof) rows on the wire, one status byte per row.  Both columns are decoded where they stand (k_deser_pks, k_deser_sigs); the status
+// bytes come to the host; the rows both decoders accepted (plan::admit_survivors) are packed into popVerify records through a device list of
+// their row numbers (k_admit_records) and only they run the blinded batch check and, if it fails, the per-pair pass (locate_run, pop): a row
+// that does not decode costs the others nothing.  The verdicts go back to their rows (plan::admit_merge) and the refused rows whose key had
+// decoded are zeroed in the table on the device (k_admit_zero_rows).  The context's second staging buffer (cap_io x 320 B) holds, per row: 96 B decoded
+// key (host form only) | 192 B decoded proof | 4 B list entry | 1 B proof status.
+// ------------------------------------------------------------------------------------------
+// d_pks | d_proofs: device memory, wire form; d_out: n x 96 B of device memory; the staging buffers hold n rows (io_reserve)
+static int admit_run(mi355_bls_ctx* c, const uint8_t* d_pks, const uint8_t* d_proofs, size_t n, uint32_t dflags, const uint8_t rnd[32], uint32_t* d_out,
+                     uint8_t* status, hipStream_t st) {
+    uint32_t* d_prf = reinterpret_cast<uint32_t*>(c->d_comp + c->cap_io * 96);
+    uint32_t* d_list = reinterpret_cast<uint32_t*>(c->d_comp + c->cap_io * 288);
+    uint8_t* d_pst = c->d_comp + c->cap_io * 292;
+    const uint32_t n32 = (uint32_t)n;
+    std::vector<uint8_t> key_st(n), proof_st(n);
+    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
+    k_deser_pks<<<plan::waves_for(n32), WAVE, 0, st>>>(d_pks, n32, dflags & DESER_F_PK_UNCOMPRESSED, d_out, c->d_status, c->d_flags);
+    k_deser_sigs<<<plan::waves_for(n32), WAVE, 0, st>>>(d_proofs, n32, dflags & DESER_F_SIG_UNCOMPRESSED, d_prf, d_pst, c->d_flags);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(key_st.data(), c->d_status, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(proof_st.data(), d_pst, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<uint32_t> list(n);
+    const size_t m = plan::admit_survivors(key_st.data(), proof_st.data(), n, list.data());
+    std::vector<uint8_t> verdicts(m);
+    if (m) {                                   // no survivor: no pairing work at all
+        HIPCHK(hipMemcpyAsync(d_list, list.data(), m * 4, hipMemcpyHostToDevice, st));
+        k_admit_records<<<plan::gather_blocks_for(m * 80), plan::GATHER_THREADS, 0, st>>>(d_out, d_prf, d_list, m, reinterpret_cast<uint32_t*>(c->d_sets.p));
+        HIPCHK(hipGetLastError());
+        const int rc = locate_run(c, c->d_sets, nullptr, m, rnd, verdicts.data(), st, true);      // sliced by max_sets like every pop call
+        if (rc < 0) return rc;
+    }
+    std::vector<uint32_t> zero(n);
+    const size_t nz = plan::admit_merge(key_st.data(), proof_st.data(), n, list.data(), verdicts.data(), m, status, zero.data());
+    if (nz) {                                  // the key decoder left an image in these rows
+        HIPCHK(hipMemcpyAsync(d_list, zero.data(), nz * 4, hipMemcpyHostToDevice, st));
+        k_admit_zero_rows<<<plan::gather_blocks_for(nz * 24), plan::GATHER_THREADS, 0, st>>>(d_list, nz, d_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    int all = 1;
+    for (size_t i = 0; i < n; i++) all &= status[i] == 0;
+    return all;
+}
+static int admit_args(mi355_bls_ctx* c, const void* pks, const void* proofs, size_t n, uint32_t dflags, const uint8_t rnd[32], const uint8_t* status) {
+    if (!c || !rnd || !status || dflags > 7 || (dflags & DESER_F_KNOWN_ON_CURVE)) return MI355_BLS_ERR_ARG;      // admission is the full check
+    if (n == 0) return 1;
+    if (!pks || !proofs || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    return 0;
+}
+extern "C" int mi355_bls_admit_keys_device(mi355_bls_ctx* c, const void* d_pks, const void* d_proofs, size_t n, uint32_t dflags, const uint8_t rnd[32],
+                                           void* d_out_pks96, uint8_t* status, void* stream) {
+    if (int rc = admit_args(c, d_pks, d_proofs, n, dflags, rnd, status)) return rc;
+    if (!d_out_pks96 || ((uintptr_t)d_out_pks96 & 3)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return admit_run(c, (const uint8_t*)d_pks, (const uint8_t*)d_proofs, n, dflags, rnd, (uint32_t*)d_out_pks96, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_admit_keys(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t n, uint32_t dflags, const uint8_t rnd[32], void* out_pks96,
+                                    uint8_t* status) {
+    if (int rc = admit_args(c, pks, proofs, n, dflags, rnd, status)) return rc;
+    if (int rc = io_reserve(c, n)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    // the wire forms wait in the record buffer (keys at 0, proofs at cap_io x 96): the decoders have read them before the gather writes there
+    uint8_t* d_wire = c->d_sets;
+    HIPCHK(hipMemcpyAsync(d_wire, pks, n * ((dflags & DESER_F_PK_UNCOMPRESSED) ? 96 : 48), hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(d_wire + c->cap_io * 96, proofs, n * ((dflags & DESER_F_SIG_UNCOMPRESSED) ? 192 : 96), hipMemcpyHostToDevice, nullptr));
+    const int rc = admit_run(c, d_wire, d_wire + c->cap_io * 96, n, dflags, rnd, reinterpret_cast<uint32_t*>(c->d_comp.p), status, nullptr);
+    if (rc < 0) return rc;
+    if (out_pks96) HIPCHK(hipMemcpy(out_pks96, c->d_comp, n * 96, hipMemcpyDeviceToHost));
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------
 // Same-message pre-aggregation: MultiSignatureSet.combine (bls_batch_verifier.nim:47-106, core :570-647) for k groups of SignatureSet records
 // in one device pass.  Group g = positions [offsets[g], offsets[g + 1]) of the member sequence (the record table itself, or table entries

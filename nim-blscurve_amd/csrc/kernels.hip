@@ -40,6 +40,7 @@
 #include "combsets.hpp"
 #include "aggsigs.hpp"
 #include "recover.hpp"
+#include "keytable.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -2720,6 +2721,36 @@ __global__ void __launch_bounds__(WAVE) k_deser_sigs(const uint8_t* __restrict__
     sg = g2_aff{fp2_select(ok, sg.x, fp2_zero()), fp2_select(ok, sg.y, fp2_zero())};
     uint32_t* o = out + (size_t)i * 48;
     st_fp_blst(o, sg.x.c0); st_fp_blst(o + 12, sg.x.c1); st_fp_blst(o + 24, sg.y.c0); st_fp_blst(o + 36, sg.y.c1);
+}
+// PublicKey.fromBytes (bls_sig_io.nim:81-99) for n keys that arrive without signature and message (a validator key table on the wire):
+// k_deser's key half (deser.hpp deserialize_public_key) -> 96-byte images, zeroed where the status is not 0.  k_deser_sigs' twin: one lane
+// per key, the tail wave partial.
+__global__ void __launch_bounds__(WAVE) k_deser_pks(const uint8_t* __restrict__ pks, uint32_t n, uint32_t dflags, uint32_t* __restrict__ out,
+                                                    uint8_t* __restrict__ status, uint32_t* __restrict__ flags) {
+    uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n) return;
+    g1_aff pk;
+    const uint8_t st = deserialize_public_key(pk, pks + (size_t)i * ((dflags & DESER_F_PK_UNCOMPRESSED) ? 96 : 48), dflags);
+    status[i] = st;
+    if (st != DESER_OK) atomicOr(flags + 2, 1u);
+    const bool ok = st == DESER_OK;
+    pk = g1_aff{fp_select(ok, pk.x, fp_zero()), fp_select(ok, pk.y, fp_zero())};
+    uint32_t* o = out + (size_t)i * 24;
+    st_fp_blst(o, pk.x); st_fp_blst(o + 12, pk.y);
+}
+// Key admission (mi355_bls_admit_keys, csrc/keytable.hpp): the decoded keys and proofs of the m surviving rows, through the device list of
+// their row numbers, become m packed popVerify records - k_pop_records with an index in front.  One thread per word.
+__global__ void __launch_bounds__(256) k_admit_records(const uint32_t* __restrict__ pks, const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ list,
+                                                       uint64_t m, uint32_t* __restrict__ recs) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m * ADMIT_RECORD_WORDS) return;
+    recs[j] = admit_record_word(pks, proofs, list, (size_t)(j / ADMIT_RECORD_WORDS), (uint32_t)(j % ADMIT_RECORD_WORDS));
+}
+// the rows whose proof did not decode or was refused by the possession check lose their key: rows list[0 .. m) of the 96-byte table become all zero (a thread per word)
+__global__ void __launch_bounds__(256) k_admit_zero_rows(const uint32_t* __restrict__ list, uint64_t m, uint32_t* __restrict__ pks) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m * 24) return;
+    pks[(size_t)list[j / 24] * 24 + j % 24] = 0u;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -78,6 +78,33 @@ constexpr size_t POP_MAX_KEYS = (size_t)1 << 30;
 constexpr uint32_t POP_RECORD_THREADS = 256;
 inline uint32_t pop_records_grid(size_t n) { return (uint32_t)((n * 80 + POP_RECORD_THREADS - 1) / POP_RECORD_THREADS); }
 
+// Key admission (mi355_bls_admit_keys): the two host decisions between the decoders and the possession check.  key_st / proof_st are the
+// status bytes k_deser_pks / k_deser_sigs wrote for the n rows (0 = decoded).
+//   admit_survivors   the rows both decoders accepted, in row order -> list (room for n entries); returns their number m.  Only these rows
+//                     go to the blinded batch check, packed (k_admit_records: gather_blocks_for(m * 80) workgroups), so a row that failed
+//                     to decode never sends the others to the per-pair pass.
+//   admit_merge       the verdict bytes of the m packed pairs go back to their rows.  status[i] = the key's status if it is not 0, else the
+//                     proof's if it is not 0, else ADMIT_BAD_PROOF when the pair's verdict is not 1, else 0.  zero (room for n entries) takes
+//                     the refused rows whose KEY decoded - a proof that did not decode, or one the check refused: the key decoder left an
+//                     image there, and a refused row of the table is all zero (k_admit_zero_rows).  Returns their number.
+constexpr uint8_t ADMIT_BAD_PROOF = 8;
+inline size_t admit_survivors(const uint8_t* key_st, const uint8_t* proof_st, size_t n, uint32_t* list) {
+    size_t m = 0;
+    for (size_t i = 0; i < n; i++)
+        if (key_st[i] == 0 && proof_st[i] == 0) list[m++] = (uint32_t)i;
+    return m;
+}
+inline size_t admit_merge(const uint8_t* key_st, const uint8_t* proof_st, size_t n, const uint32_t* list, const uint8_t* verdicts, size_t m, uint8_t* status,
+                          uint32_t* zero) {
+    for (size_t i = 0; i < n; i++) status[i] = key_st[i] ? key_st[i] : proof_st[i];
+    for (size_t j = 0; j < m; j++)
+        if (verdicts[j] != 1) status[list[j]] = ADMIT_BAD_PROOF;
+    size_t nz = 0;
+    for (size_t i = 0; i < n; i++)
+        if (status[i] != 0 && key_st[i] == 0) zero[nz++] = (uint32_t)i;
+    return nz;
+}
+
 // cofactor clearing of n32 mapped point pairs: the engine (then k_clear_fix) or k_hash_clear
 inline stage clear_for(uint32_t slots, bool coop, uint32_t n32) {
     return coop && n32 <= team_clear_max(slots) ? team_stage(slots, n32) : one_lane_stage(n32);
