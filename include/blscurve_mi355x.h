@@ -648,6 +648,28 @@ int mi355_bls_batch_verify_combined_device(mi355_bls_ctx* ctx, const void* d_set
                                            size_t k, const uint8_t* rnds, const uint8_t rnd[32], void* stream);
 int mi355_bls_group_by_message(const void* sets, size_t n, uint32_t* idx, size_t* offsets, size_t* k);
 
+/* batchVerify BY MESSAGE: mi355_bls_batch_verify's arguments, scalars, verdict and final value, with hashing and the Miller loop run once per
+ * DISTINCT message of a slice.  The sets that share a 32-byte message are found on the device (an open-addressing table of set indices, all
+ * 32 bytes compared; csrc/bymsg.hpp), and because e([r_1]PK_1, H(m)) e([r_2]PK_2, H(m)) = e([r_1]PK_1 + [r_2]PK_2, H(m)) the blinded keys of
+ * a group are summed into ONE Miller pair.  Set i gets exactly the scalar mi355_bls_batch_verify gives it (same chains, same dispatch), the
+ * signature side is that call's, and the value after the final exponentiation is the same field element: the return value and
+ * mi355_bls_fetch_stage(4) equal mi355_bls_batch_verify's for every input (n == 0: 0; an infinity key: 0).  A group whose summed key is the
+ * point at infinity contributes the factor 1 and does not fail the batch.  Unlike batch_verify_combined it needs no grouping from the host,
+ * no second set of scalars and no G2 multiplication per member.
+ * Any n: a batch beyond max_sets runs in slices cut where mi355_bls_batch_verify cuts them, one after the other; a group that a boundary cuts
+ * is two groups.  A slice whose messages are all distinct runs the ordinary pass.  Blocking (the call waits twice per slice for a few words:
+ * the number of groups and their offsets); there is no submit / wait, sharded or multi-device form.
+ * Stages after the call (last slice): 0 = r_i, n x 8 bytes; 1 = H(m_g) of the k distinct messages in the order each first appears
+ * (mi355_bls_group_by_message's group order); 2 = the k group sums as Jacobian images (compare them as points: the order of additions inside
+ * a group is free); 3, 4, 5 as after mi355_bls_batch_verify.
+ * by_message_device: d_sets in device memory (4-byte aligned), kernels on `stream` and the context's fork streams.
+ * last_message_groups: k of the last such call's last slice; MI355_BLS_ERR_ARG before the first one.
+ * debug_..._scalars: TEST HOOK, mi355_bls_debug_batch_verify_scalars' contract (serial, one slice, host memory, r[i] != 0) for this pass. */
+int mi355_bls_batch_verify_by_message(mi355_bls_ctx* ctx, const void* sets, size_t n, const uint8_t rnd[32]);
+int mi355_bls_batch_verify_by_message_device(mi355_bls_ctx* ctx, const void* d_sets, size_t n, const uint8_t rnd[32], void* stream);
+int mi355_bls_last_message_groups(mi355_bls_ctx* ctx);
+int mi355_bls_debug_batch_verify_by_message_scalars(mi355_bls_ctx* ctx, const void* sets, size_t n, const uint64_t r[]);
+
 /* aggregateVerify(publicKeys, messages, signature) (bls_sig_min_pubkey.nim:153-199; ContextCoreAggregateVerify,
  * blst_min_pubkey_sig_core.nim:305-414): e(G1, sig) == prod_i e(pk_i, H(m_i)) for n (public key, message) pairs
  * with messages of arbitrary length: message i = msgs[msg_offsets[i] .. msg_offsets[i+1]) (n + 1 offsets).

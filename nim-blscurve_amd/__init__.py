@@ -186,6 +186,10 @@ def lib():
         L.mi355_bls_debug_fp_op.argtypes = [vp, i32, cp, cp, sz, cp]
         L.mi355_bls_debug_map_to_g2.argtypes = [vp, cp, sz, cp]
         L.mi355_bls_debug_batch_verify_scalars.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_uint64)]
+        L.mi355_bls_batch_verify_by_message.argtypes = [vp, vp, sz, ctypes.c_char_p]
+        L.mi355_bls_batch_verify_by_message_device.argtypes = [vp, vp, sz, ctypes.c_char_p, vp]
+        L.mi355_bls_last_message_groups.argtypes = [vp]
+        L.mi355_bls_debug_batch_verify_by_message_scalars.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_uint64)]
         L.mi355_bls_debug_multi_enqueue_us.argtypes = [ctypes.POINTER(ctypes.c_float), sz]
         L.mi355_bls_debug_multi_enqueue_us.restype = sz
         L.mi355_bls_fetch_stage.argtypes = [vp, i32, vp, sz]
@@ -484,6 +488,36 @@ def debugBatchVerifyScalars(cache, sets, scalars):
         raise ValueError("one scalar per set: %d sets, %d scalars" % (n, len(scalars)))
     r = (ctypes.c_uint64 * max(n, 1))(*scalars)
     return bool(_check(lib().mi355_bls_debug_batch_verify_scalars(cache._h, rec, n, r)))
+
+
+def batchVerifyByMessage(cache, input_, secureRandomBytes):
+    """mi355_bls_batch_verify_by_message: batchVerifyParallel's verdict (same scalars, same final value) with hashing and the Miller loop run
+    once per distinct message - the sets that share a message are found on the device.  Empty input -> False."""
+    rec = _as_records(input_)
+    n = len(rec) // SIGSET_BYTES
+    if n == 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_verify_by_message(cache._h, rec, n, _rnd32(secureRandomBytes))))
+
+
+def batchVerifyByMessage_device(cache, d_ptr, n, secureRandomBytes, stream=0):
+    """Same with the n records resident in device memory (raw pointer, 4-byte aligned)."""
+    return bool(_check(lib().mi355_bls_batch_verify_by_message_device(cache._h, d_ptr, n, _rnd32(secureRandomBytes), stream)))
+
+
+def lastMessageGroups(cache):
+    """The number of distinct messages the last by-message call found in its (last) slice."""
+    return _check(lib().mi355_bls_last_message_groups(cache._h))
+
+
+def debugBatchVerifyByMessageScalars(cache, sets, scalars):
+    """Test hook (mi355_bls_debug_batch_verify_by_message_scalars): debugBatchVerifyScalars' contract for the by-message pass."""
+    rec = _as_records(sets)
+    n = len(rec) // SIGSET_BYTES
+    if len(scalars) != n:
+        raise ValueError("one scalar per set: %d sets, %d scalars" % (n, len(scalars)))
+    r = (ctypes.c_uint64 * max(n, 1))(*scalars)
+    return bool(_check(lib().mi355_bls_debug_batch_verify_by_message_scalars(cache._h, rec, n, r)))
 
 
 def batchVerifyLocate(cache, input_, secureRandomBytes):

@@ -96,7 +96,16 @@ struct mi355_bls_ctx {
     dev_event ev_s0, ev_l0;       // start of the signature side (on its stream) and of the tuple pairs' Miller lines: the stage timers of forked calls
     float ktimes[4] = {};         // k_hash_map, k_hash_clear, k_lineprod, k_lineprod2 of the last batch call
     uint32_t slots = 1024;        // wave slots at one wave per SIMD: 4 x CUs
-    size_t last_n = 0;
+    // the sets of the last batch slice and the tuple pairs it left in the pair store.  Every path assigns the sets (`last_n = n`), which makes
+    // the pairs as many; the by-message pass then says how many group pairs it left (fetch_stage 1 .. 3 read `pairs`).
+    struct last_count {
+        size_t n = 0, pairs = 0;
+        last_count& operator=(size_t v) {
+            n = pairs = v;
+            return *this;
+        }
+        operator size_t() const { return n; }
+    } last_n;
     bool have_gt = false;
     float timings[8] = {};
     dst_t dst;
@@ -152,6 +161,15 @@ struct mi355_bls_ctx {
     dev_buf<uint32_t> d_aggv_carry;  // the open group's Miller value (a blst_fp12 image), and a second slot for the engine form's part
     dev_buf<uint32_t> d_aggv_work;   // the engine form's block per workgroup
     std::vector<uint32_t> aggv_tab;  // the tables of every slice of the call in flight: the async copies read them
+    // batchVerify by message (mi355_bls_batch_verify_by_message): sized by the slice, grown with the call; the group sums share the item
+    // table and the G1 partials above
+    dev_buf<uint32_t> d_bm_tab;      // the open-addressing table: plan::bymsg_table_slots(n) set indices
+    dev_buf<uint32_t> d_bm_work;     // the word arrays of the grouping (bymsg_arrays)
+    dev_buf<uint4> d_bm_P;           // [r_i]PK_i of all n sets, SoA Jacobian as k_pkmul writes it
+    dev_buf<uint8_t> d_bm_rec;       // the records of the k representatives, for the hashing kernels
+    dev_event ev_bm;                 // the offsets are on the host
+    std::vector<uint32_t> bm_offs;
+    int bm_groups = -1;              // k of the last by-message slice (mi355_bls_last_message_groups)
 
     // the batch workspace's pair store (ctx_build makes it; it never changes) and the per-set path's (each_reserve)
     pair_store batch_pairs() const { return {d_H, d_P, d_lines, stride}; }
@@ -926,6 +944,224 @@ extern "C" int mi355_bls_debug_batch_verify_scalars(mi355_bls_ctx* c, const void
     int rc = verify_enqueue(c, nullptr, (const uint8_t*)sets, n, no_rnd, 1, nullptr, false, r);      // refuses a busy context
     if (rc) return rc;
     return verify_wait(c);
+}
+
+// ------------------------------------------------------------------------------------------
+// batchVerify by message (mi355_bls_batch_verify_by_message): batchVerify's check with batchVerify's scalars, but the sets of a slice that
+// share a message are found on the device (csrc/bymsg.hpp) and their blinded keys summed, e([r_1]PK_1, H(m)) e([r_2]PK_2, H(m)) =
+// e([r_1]PK_1 + [r_2]PK_2, H(m)): hashing, clearing and the Miller loop run for ONE pair per distinct message.  The signature side is
+// run_pairs' own, over all n sets, with its extra pairs behind the k group pairs.  The value after the final exponentiation is the same
+// field element, so verdict and fetch_stage(4) are batchVerify's.  Blocking; any n (slices one after the other on this context's own
+// workspace, cut where run_shard cuts them; a group that a boundary cuts is two groups).
+// ------------------------------------------------------------------------------------------
+// the word arrays of the grouping of n sets, in d_bm_work
+struct bymsg_arrays {
+    uint32_t *slot_of, *rep, *flag, *rank, *gid, *counts, *cursor, *n_inf, *offsets, *members, *reps;
+    static size_t words(size_t n) { return 10 * n + 8; }
+};
+static bymsg_arrays bymsg_view(uint32_t* w, size_t n) {
+    bymsg_arrays a;
+    a.slot_of = w, a.rep = a.slot_of + n, a.flag = a.rep + n, a.rank = a.flag + n;            // rank: n + 1
+    a.gid = a.rank + n + 1;
+    a.counts = a.gid + n, a.cursor = a.counts + n + 1, a.n_inf = a.cursor + n + 1;             // counts | cursor | n_inf: cleared together
+    a.offsets = a.n_inf + 1, a.members = a.offsets + n + 1, a.reps = a.members + n;           // offsets: n + 1
+    return a;
+}
+static int bymsg_reserve(mi355_bls_ctx* c, size_t n) {
+    const size_t tab = (size_t)plan::bymsg_table_slots(n) * 4, work = bymsg_arrays::words(n) * 4, stride = (n + 63) / 64 * 64;
+    int rc = c->d_bm_tab.reserve(tab, 0);
+    if (!rc) rc = c->d_bm_work.reserve(work, work / 4);
+    if (!rc) rc = c->d_bm_P.reserve(stride * 3 * 64, stride * 48);
+    if (!rc && !c->ev_bm) rc = c->ev_bm.create(hipEventDisableTiming);
+    return rc;
+}
+// run_pairs' sibling: everything behind the blinding scalars (d_r[0 .. n) ready on `st`) for a slice whose sets are first grouped by message.
+// Two host waits: the number of groups k (four bytes; k == n hands the slice to run_pairs itself), and the k + 1 offsets the segmented sum's
+// item table is built from (plan.hpp aggsets_fill, as combine_sets builds it) - awaited while the hashing kernels already run.
+static int run_pairs_grouped(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, hipStream_t st) {
+    const uint32_t n32 = (uint32_t)n, nb = plan::waves_for(n32);
+    if (int rc = bymsg_reserve(c, n)) return rc;
+    const bymsg_arrays A = bymsg_view(c->d_bm_work, n);
+    const uint32_t* sets32 = reinterpret_cast<const uint32_t*>(d_sets);
+    const uint32_t slots = plan::bymsg_table_slots(n);
+    // ---- grouping: table, representatives, ranks, counts
+    HIPCHK(hipMemsetAsync(c->d_bm_tab, 0xff, (size_t)slots * 4, st));
+    HIPCHK(hipMemsetAsync(A.counts, 0, (2 * (n + 1) + 1) * 4, st));
+    k_bymsg_insert<<<nb, WAVE, 0, st>>>(sets32, n32, slots, c->d_bm_tab, A.slot_of);
+    k_bymsg_flag<<<nb, WAVE, 0, st>>>(c->d_bm_tab, A.slot_of, n32, A.rep, A.flag);
+    k_bymsg_scan<<<1, WAVE, 0, st>>>(A.flag, n32, A.rank);
+    k_bymsg_group<<<nb, WAVE, 0, st>>>(A.rep, A.rank, A.flag, n32, A.gid, A.counts, A.reps);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_flags + 200, A.rank + n, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t k = c->h_flags[200];
+    const uint32_t k32 = (uint32_t)k;
+    if (k == 0 || k > n) {
+        g_err = "by_message: the grouping returned an impossible group count";
+        return MI355_BLS_ERR_HIP;
+    }
+    c->bm_groups = (int)k;
+    const plan::grouped_plan gp = plan::slice_for_grouped(c->slots, c->coop, c->coop && ensure_side(c), n, k);
+    if (gp.ordinary) return run_pairs(c, d_sets, n, st);
+    // ---- offsets and member lists; the offsets start their way to the host
+    k_bymsg_scan<<<1, WAVE, 0, st>>>(A.counts, k32, A.offsets);
+    k_bymsg_scatter<<<nb, WAVE, 0, st>>>(A.gid, n32, A.offsets, A.cursor, A.members);
+    c->bm_offs.resize(k + 1);
+    HIPCHK(hipMemcpyAsync(c->bm_offs.data(), A.offsets, (k + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(c->ev_bm, st));
+    if (int rc = c->d_bm_rec.reserve(k * 320, k * 80)) return rc;
+    const pair_store ps = c->batch_pairs();
+    HIPCHK(hipEventRecord(c->ev[1], st));
+    const plan::slice_plan& p = gp.sets;
+    const uint32_t cw = p.cw, nwin = p.nwin, total = p.total;
+    const bool fork = p.side == plan::SIDE_FORK, fork_sig = p.side == plan::SIDE_FORK_SIG;
+    const auto stream_of = [&](plan::stream_role r) { return r == plan::STREAM_CALLER ? st : r == plan::STREAM_SIDE2 && c->side2 ? c->side2 : c->side; };
+    hipStream_t sd = stream_of(p.pk_stream);                            // [r]PK and the group sums
+    hipStream_t ss = stream_of(p.sig_stream);                           // signature side
+    if (fork || fork_sig) HIPCHK(hipStreamWaitEvent(c->side, c->ev[1], 0));
+    if (fork && sd != c->side) HIPCHK(hipStreamWaitEvent(sd, c->ev[1], 0));
+    // ---- hashing of the k representatives' messages (caller's stream)
+    k_combsets_gather<<<plan::gather_blocks_for(k * 80), plan::GATHER_THREADS, 0, st>>>(sets32, n, A.reps, k32, reinterpret_cast<uint32_t*>(c->d_bm_rec.p));
+    launch_hash_map(c, c->d_bm_rec, k32, st);
+    HIPCHK(hipEventRecord(c->ev_hm, st));
+    launch_hash_clear(c, ps, k32, st);
+    HIPCHK(hipEventRecord(c->ev[2], st));
+    // ---- [r]PK of all n sets into the pass's own buffer
+    const size_t P_stride = c->d_bm_P.bytes / (3 * 64);
+    if (p.pkmul_spread) k_pkmul_spread<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, c->d_bm_P, P_stride, c->d_flags, c->d_pktab);
+    else k_pkmul<<<nb, WAVE, 0, sd>>>(d_sets, n32, c->d_r, c->d_bm_P, P_stride, c->d_flags, c->d_pktab);
+    // ---- signature side: run_pairs' own, its extra pairs at slots k .. k + total
+    {
+        msm_win W{nwin, cw, 0};
+        uint32_t *hist = c->d_sig_hist, *offs = hist + SIG_SLOTS_MAX, *cursor = offs + SIG_SLOTS_MAX;
+        HIPCHK(hipEventRecord(c->ev_s0, ss));
+        HIPCHK(hipMemsetAsync(hist, 0, (size_t)total * 4, ss));
+        k_sig_convert<<<nb, WAVE, 0, ss>>>(d_sets, n32, c->d_sig_pts);
+        k_msm_hist<<<dim3(nb, nwin), WAVE, 0, ss>>>(reinterpret_cast<const uint8_t*>(c->d_r.p), 8, n32, W, cw, hist);
+        k_msm_scan<<<nwin, WAVE, 0, ss>>>(hist, cw, offs, cursor);
+        k_msm_scatter<<<dim3(nb, nwin), WAVE, 0, ss>>>(reinterpret_cast<const uint8_t*>(c->d_r.p), 8, n32, W, cw, cursor, c->d_sig_sorted);
+        k_sig_bucket<<<p.bucket_grid, WAVE, 0, ss>>>(c->d_sig_pts, c->d_sig_sorted, offs, hist, n32, cw, p.lshift, total,
+                                                     c->d_sig_consts + (cw == 8 ? (size_t)SIG_SLOTS_MAX * G1W : 0), ps.H, ps.P, ps.stride, (size_t)k32);
+        c->sig_c = cw;
+        c->sig_slots = total;
+        c->agg_valid = false;
+    }
+    if (gp.extra_apart) launch_lines_at(ps, gp.extra_lines, k32, total, ss);
+    HIPCHK(hipEventRecord(c->ev[4], ss));
+    // ---- the group sums: item table from the offsets (the device is busy meanwhile), levels, finish into pair slots 0 .. k - 1
+    HIPCHK(hipEventSynchronize(c->ev_bm));
+    {
+        std::vector<size_t> offsets(c->bm_offs.begin(), c->bm_offs.end());
+        const plan::aggsets_plan ap = offsets[k] == n ? plan::aggsets_measure(offsets.data(), k) : plan::aggsets_plan{};
+        if (!ap.ok || ap.items == 0) {
+            g_err = "by_message: the grouping returned offsets that do not cover the slice";
+            (void)hipStreamSynchronize(sd), (void)hipStreamSynchronize(ss), (void)hipStreamSynchronize(st);
+            return MI355_BLS_ERR_HIP;
+        }
+        c->agg_tab.resize(ap.items * 4 + k);
+        plan::aggsets_fill(ap, offsets.data(), k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), c->agg_tab.data() + ap.items * 4);
+        const size_t tb = c->agg_tab.size() * 4;
+        int rc = c->d_agg_part.reserve(ap.items * (size_t)G1W * 4, ap.items * (size_t)G1W);
+        if (!rc) rc = c->d_agg_tab.reserve(tb, tb / 4);
+        if (rc) {
+            (void)hipStreamSynchronize(sd), (void)hipStreamSynchronize(ss), (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), tb, hipMemcpyHostToDevice, sd));
+        const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
+        for (uint32_t l = 0; l < ap.levels; l++) {
+            const uint32_t cnt = (uint32_t)(ap.level_first[l + 1] - ap.level_first[l]);
+            if (l == 0) k_bymsg_l0<<<plan::waves_for(cnt), WAVE, 0, sd>>>(items, cnt, c->d_bm_P, P_stride, A.members, c->d_agg_part);
+            else k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, sd>>>(items + ap.level_first[l], cnt, c->d_agg_part);
+        }
+        k_bymsg_finish<<<gp.grid_k, WAVE, 0, sd>>>(c->d_agg_tab + ap.items * 4, k32, c->d_agg_part, ps.P, ps.stride, A.n_inf);
+    }
+    HIPCHK(hipEventRecord(c->ev[3], sd));
+    // ---- Miller lines and their products per step: k + total pairs
+    const uint32_t npairs = k32 + total;
+    if (fork) {
+        HIPCHK(hipStreamWaitEvent(st, c->ev[4], 0));
+        HIPCHK(hipStreamWaitEvent(st, c->ev[3], 0));
+    }
+    HIPCHK(hipEventRecord(c->ev_l0, st));
+    launch_lines(ps, gp.lines, st);
+    if (fork_sig) HIPCHK(hipStreamWaitEvent(st, c->ev[4], 0));
+    HIPCHK(hipEventRecord(c->ev[5], st));
+    if (int rcp = enqueue_line_products(c, ps, npairs, st, c->ev_lp)) return rcp;
+    c->wide_recorded = true;
+    HIPCHK(hipEventRecord(c->ev[6], st));
+    launch_k_tail(c, st, c->d_L, c->d_states, 1, 1, c->d_gt, c->d_flags + 1, 144, 0);
+    HIPCHK(hipEventRecord(c->ev[7], st));
+    HIPCHK(hipGetLastError());
+    c->last_n = n;
+    c->last_n.pairs = k;                       // fetch_stage(1 .. 3): k group pairs, the extra pairs behind them
+    c->have_gt = false;
+    c->gt_is_fv = false;
+    return 0;
+}
+// the whole call: run_shard's preamble and slice cuts, the slices one after the other on this context's workspace, verify_enqueue's end
+static int bymsg_verify(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, size_t n, const uint8_t rnd[32], int serial, hipStream_t st,
+                        const uint64_t* chosen_r = nullptr) {
+    if (!c || !rnd || (!d_src && !h_src) || n == 0) return MI355_BLS_ERR_ARG;
+    if ((uintptr_t)d_src & 3) {
+        g_err = "by_message: records must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const uint32_t B = (uint32_t)(n < c->num_threads ? n : c->num_threads);
+    std::memcpy(c->h_flags + 4, rnd, 32);
+    HIPCHK(hipMemcpyAsync(c->d_rnd, c->h_flags + 4, 32, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
+    if (serial) {
+        c->h_r.resize(n);
+        if (chosen_r) std::memcpy(c->h_r.data(), chosen_r, n * 8);
+        else host_serial_chain(rnd, n, c->h_r.data());
+    }
+    const size_t nslices = plan::shard_nslices(n, c->cap);
+    c->alone = nslices == 1 && g_in_flight.load(std::memory_order_relaxed) == 0;
+    size_t done = 0;
+    for (uint32_t slice = 0; done < n; slice++) {
+        const size_t cnt = plan::shard_slice_count(n, done, nslices, slice);
+        const uint32_t c_lo = serial ? 0 : plan::chunk_of_tuple(n, B, done), c_hi = serial ? 1 : plan::chunk_of_tuple(n, B, done + cnt - 1) + 1;
+        const uint8_t* d = d_src ? d_src + 320 * done : c->d_sets;
+        if (!d_src) HIPCHK(hipMemcpyAsync(c->d_sets, h_src + 320 * done, cnt * 320, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(c->ev[0], st));
+        if (serial) HIPCHK(hipMemcpyAsync(c->d_r, c->h_r.data() + done, cnt * 8, hipMemcpyHostToDevice, st));
+        else k_blind<<<plan::waves_for(c_hi - c_lo), WAVE, 0, st>>>(c->d_rnd, n, B, c_lo, c_hi - c_lo, done, cnt, c->d_carry + 8 * (slice & 1), c->d_carry + 8 * ((slice + 1) & 1), c->d_r);
+        if (int rc = run_pairs_grouped(c, d, cnt, st)) return rc;
+        if (nslices > 1) k_state_mul<<<1, TAIL_THREADS, 0, st>>>(c->d_states, 1, slice ? 1 : 0, slice ? 0 : -1);      // the running product in slot 1
+        done += cnt;
+    }
+    if (nslices > 1) k_state_mul<<<1, TAIL_THREADS, 0, st>>>(c->d_states, 0, 1, -1);
+    HIPCHK(hipGetLastError());
+    launch_k_tail(c, st, c->d_L, c->d_states, 1, 2, c->d_gt, c->d_flags + 1, 144, 0);
+    HIPCHK(hipEventRecord(c->ev[8], st));
+    HIPCHK(hipMemcpyAsync(c->h_flags, c->d_flags, 8, hipMemcpyDeviceToHost, st));
+    c->pending = true;
+    g_in_flight.fetch_add(1, std::memory_order_relaxed);
+    c->pending_stream = st;
+    return verify_wait(c);
+}
+extern "C" int mi355_bls_batch_verify_by_message_device(mi355_bls_ctx* c, const void* d_sets, size_t n, const uint8_t rnd[32], void* stream) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;                      // batchVerify's rule
+    return bymsg_verify(c, (const uint8_t*)d_sets, nullptr, n, rnd, 0, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_batch_verify_by_message(mi355_bls_ctx* c, const void* sets, size_t n, const uint8_t rnd[32]) {
+    if (!c || !rnd) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!sets) return MI355_BLS_ERR_ARG;
+    return bymsg_verify(c, nullptr, (const uint8_t*)sets, n, rnd, 0, nullptr);
+}
+extern "C" int mi355_bls_last_message_groups(mi355_bls_ctx* c) { return c && c->bm_groups >= 0 ? c->bm_groups : MI355_BLS_ERR_ARG; }
+// TEST HOOK: mi355_bls_debug_batch_verify_scalars' contract (serial, one slice, host memory, no zero scalar) for the by-message pass
+extern "C" int mi355_bls_debug_batch_verify_by_message_scalars(mi355_bls_ctx* c, const void* sets, size_t n, const uint64_t r[]) {
+    if (!c || !sets || !r || n == 0 || n > c->cap) return MI355_BLS_ERR_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (r[i] == 0) return MI355_BLS_ERR_ARG;
+    static const uint8_t no_rnd[32] = {0};
+    return bymsg_verify(c, nullptr, (const uint8_t*)sets, n, no_rnd, 1, nullptr, r);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2567,28 +2803,29 @@ extern "C" int mi355_bls_fetch_stage(mi355_bls_ctx* c, int what, void* out, size
     if (!c || !out) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     size_t n = c->last_n;
-    uint32_t nb = plan::waves_for((uint32_t)n);
+    const size_t np = c->last_n.pairs;       // the tuple pairs in front of the signature side's: n, or the k groups of a by-message slice
+    uint32_t nb = plan::waves_for((uint32_t)np);
     switch (what) {
         case 0:
             if (out_bytes < n * 8) return MI355_BLS_ERR_ARG;
             HIPCHK(hipMemcpy(out, c->d_r, n * 8, hipMemcpyDeviceToHost));
             return 0;
         case 1:
-            if (out_bytes < n * 288 || n == 0) return MI355_BLS_ERR_ARG;
-            k_export_g2<<<nb, WAVE>>>(c->d_H, c->stride, (uint32_t)n, c->d_export);
+            if (out_bytes < np * 288 || np == 0) return MI355_BLS_ERR_ARG;
+            k_export_g2<<<nb, WAVE>>>(c->d_H, c->stride, (uint32_t)np, c->d_export);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpy(out, c->d_export, n * 288, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out, c->d_export, np * 288, hipMemcpyDeviceToHost));
             return 0;
         case 2:
-            if (out_bytes < n * 144 || n == 0) return MI355_BLS_ERR_ARG;
-            k_export_g1<<<nb, WAVE>>>(c->d_P, c->stride, (uint32_t)n, c->d_export);
+            if (out_bytes < np * 144 || np == 0) return MI355_BLS_ERR_ARG;
+            k_export_g1<<<nb, WAVE>>>(c->d_P, c->stride, (uint32_t)np, c->d_export);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpy(out, c->d_export, n * 144, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out, c->d_export, np * 144, hipMemcpyDeviceToHost));
             return 0;
         case 3:
             if (out_bytes < 288) return MI355_BLS_ERR_ARG;
             if (!c->agg_valid && c->sig_slots) {                     // bucket path: fold the bucket sums now
-                k_sig_fold<<<1, WAVE>>>(c->d_H, c->stride, (uint32_t)n, 64 / c->sig_c, c->sig_c, c->d_agg);
+                k_sig_fold<<<1, WAVE>>>(c->d_H, c->stride, (uint32_t)np, 64 / c->sig_c, c->sig_c, c->d_agg);
                 HIPCHK(hipGetLastError());
                 c->agg_valid = true;
             }

@@ -38,6 +38,7 @@
 #include "aggsets.hpp"
 #include "aggbits.hpp"
 #include "combsets.hpp"
+#include "bymsg.hpp"
 #include "aggsigs.hpp"
 #include "recover.hpp"
 #include "keytable.hpp"
@@ -2961,6 +2962,79 @@ __global__ void k_p2_to_affine(const uint32_t* __restrict__ p2, uint32_t* __rest
         fp2 x = fp2_mul(b.x, zi2), y = fp2_mul(b.y, fp2_mul(zi2, zi));
         st_fp_blst(out_sig, x.c0); st_fp_blst(out_sig + 12, x.c1); st_fp_blst(out_sig + 24, y.c0); st_fp_blst(out_sig + 36, y.c1);
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// batchVerify by message (mi355_bls_batch_verify_by_message): the sets that share a message are found on the device and their blinded keys
+// summed, so that hashing and the Miller loop run once per distinct message.  The bodies are csrc/bymsg.hpp; one lane per set, workgroups of
+// one wave, vector atomics only.  The word arrays (n or n + 1 entries each) are the context's (host_api.inc bymsg_reserve).
+// ------------------------------------------------------------------------------------------
+// set i -> the slot of its group in the open-addressing table (`slots` entries, all BYMSG_EMPTY before the launch)
+__global__ void __launch_bounds__(WAVE) k_bymsg_insert(const uint32_t* __restrict__ sets, uint32_t n, uint32_t slots, uint32_t* table, uint32_t* __restrict__ slot_of) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    slot_of[i] = bymsg_insert(i, slots, [&](uint32_t j) { return sets + (size_t)j * 80 + 24; },
+                              [&](uint32_t h, uint32_t expect, uint32_t val) { return atomicCAS(table + h, expect, val); },
+                              [&](uint32_t h, uint32_t val) { atomicMin(table + h, val); });
+}
+// behind every insertion: the representative of set i (the smallest index of its message) and whether it is its own
+__global__ void __launch_bounds__(WAVE) k_bymsg_flag(const uint32_t* __restrict__ table, const uint32_t* __restrict__ slot_of, uint32_t n, uint32_t* __restrict__ rep,
+                                                     uint32_t* __restrict__ flag) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = table[slot_of[i]];
+    rep[i] = r;
+    flag[i] = r == i ? 1u : 0u;
+}
+// one wave: out[0 .. n) = the exclusive scan of in[0 .. n), out[n] = the total (the k_msm_scan shape: a lane sums its part, a shuffle scan
+// over the lanes, a second walk writes)
+__global__ void __launch_bounds__(WAVE) k_bymsg_scan(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t per = bymsg_scan_per(n, WAVE), sum = bymsg_scan_sum(in, n, per, threadIdx.x);
+    uint32_t incl = sum;
+    for (int d = 1; d < WAVE; d <<= 1) {
+        uint32_t o = __shfl_up(incl, d, WAVE);
+        if ((int)threadIdx.x >= d) incl += o;
+    }
+    bymsg_scan_write(in, n, per, threadIdx.x, incl - sum, out);
+    if (threadIdx.x == WAVE - 1) out[n] = incl;
+}
+// set i -> its group (the rank of its representative); the group's member count; a representative puts itself at its group's place in reps
+__global__ void __launch_bounds__(WAVE) k_bymsg_group(const uint32_t* __restrict__ rep, const uint32_t* __restrict__ rank, const uint32_t* __restrict__ flag, uint32_t n,
+                                                      uint32_t* __restrict__ gid, uint32_t* __restrict__ counts, uint32_t* __restrict__ reps) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t g = rank[rep[i]];
+    gid[i] = g;
+    atomicAdd(counts + g, 1u);
+    if (flag[i]) reps[g] = i;
+}
+// the members of group g at [offsets[g], offsets[g + 1]) of the member list, in the order the lanes arrive (cursor: zero before the launch)
+__global__ void __launch_bounds__(WAVE) k_bymsg_scatter(const uint32_t* __restrict__ gid, uint32_t n, const uint32_t* __restrict__ offsets, uint32_t* __restrict__ cursor,
+                                                        uint32_t* __restrict__ members) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t g = gid[i];
+    members[offsets[g] + atomicAdd(cursor + g, 1u)] = i;
+}
+// level 0 of the group sums, one lane per item of plan.hpp aggsets_fill's table over the member list: up to AGG_C of k_pkmul's products -> one
+// partial (the levels above are k_aggsets_ln's).  No message check: the grouping has compared all 32 bytes.
+__global__ void __launch_bounds__(WAVE, 2) k_bymsg_l0(const uint4* __restrict__ items, uint32_t n_items, const uint4* __restrict__ P, size_t stride,
+                                                      const uint32_t* __restrict__ members, uint32_t* __restrict__ part) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    st_g1_int(part + (size_t)it.z * G1W, bymsg_l0_item(it.x, it.y, members, [&](uint32_t j) { return soa_ld_g1(P, stride, j); }));
+}
+// one lane per group: its last partial -> the P of Miller pair g (Jacobian, as k_lines reads it: no inversion); an infinite sum is counted
+// in n_inf[0] and stored as the infinity image, for which every form of the line kernels writes the line 1
+__global__ void __launch_bounds__(WAVE, 2) k_bymsg_finish(const uint32_t* __restrict__ final_of, uint32_t k, const uint32_t* __restrict__ part, uint4* __restrict__ P,
+                                                          size_t stride, uint32_t* __restrict__ n_inf) {
+    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= k) return;
+    bool inf;
+    const g1_jac s = bymsg_finish_item(ld_g1_int(part + (size_t)final_of[g] * G1W), &inf);
+    if (inf) atomicAdd(n_inf, 1u);
+    soa_st_g1(P, stride, g, s);
 }
 
 }  // namespace

@@ -879,5 +879,48 @@ inline uint32_t chunk_of_tuple(size_t n_total, uint32_t B, size_t t) {
     return (uint32_t)(t < cut ? t / (base + 1) : rem + (t - cut) / base);
 }
 
+// ------------------------------------------------------------------------------------------
+// batchVerify by message (mi355_bls_batch_verify_by_message): one slice of n sets that the device grouping found to hold k distinct messages.
+// The per-SET stages - [r]PK, the signature side with its `total` extra pairs, and the streams they take - are slice_for's for n; the
+// per-PAIR stages - hashing, clearing, Miller lines - are the same deciders asked for k (the latency forms where k is small), with the
+// extra pairs behind them at slots k .. k + total.  slice_for itself is not touched.
+//   ordinary: k == n, nothing is shared: the call runs run_pairs as it stands (same result, none of the grouped pass's extra kernels).
+//   BYMSG_MIN_SHARED is the hook for a "not worth grouping" threshold: n - k below it would also take the ordinary path.  UNSET (0):
+//   nobody has measured where the grouped pass stops paying for its sums, and no value is invented here.
+//   table_slots: the open-addressing table of the grouping, a power of two of at least 2 n slots (csrc/bymsg.hpp).
+// ------------------------------------------------------------------------------------------
+constexpr size_t BYMSG_MIN_SHARED = 0;
+constexpr uint32_t bymsg_table_slots(size_t n) {
+    uint32_t s = 2;
+    while (s < 2 * (uint64_t)n) s <<= 1;
+    return s;
+}
+struct grouped_plan {
+    bool ordinary;
+    uint32_t table_slots;
+    uint32_t grid_n, grid_k;           // waves of the one-lane-per-set / one-lane-per-group kernels
+    slice_plan sets;                   // slice_for(n): nb, pkmul_spread, side, the streams, cw / nwin / total, lshift, bucket_grid
+    hash_map_plan hash_map;            // k messages
+    stage clear;
+    bool extra_apart;                  // as in slice_plan, for the pairs of this pass
+    stage extra_lines;
+    lines_plan lines;                  // the caller's stream: the k group pairs (extra_apart) or all k + total pairs
+};
+inline grouped_plan slice_for_grouped(uint32_t slots, bool coop, bool have_side, size_t n, size_t k) {
+    grouped_plan g{};
+    const uint32_t k32 = (uint32_t)k;
+    g.ordinary = k == n || n - k + 1 <= BYMSG_MIN_SHARED;      // (n - k < the hook, written so that 0 switches it off)
+    g.table_slots = bymsg_table_slots(n);
+    g.grid_n = waves_for((uint32_t)n), g.grid_k = waves_for(k32);
+    g.sets = slice_for(slots, coop, have_side, n);
+    g.hash_map = hash_map_for(slots, coop, k32);
+    g.clear = clear_for(slots, coop, k32);
+    const uint32_t total = g.sets.total;
+    g.extra_apart = g.sets.side == SIDE_FORK_SIG || (g.sets.side == SIDE_FORK && total <= team_lines_max(slots));
+    g.extra_lines = total <= team_lines_max(slots) ? team_stage(slots, total) : one_lane_stage(total);
+    g.lines = g.extra_apart ? lines_for(slots, coop, k32, 0) : lines_for(slots, coop, k32 + total, total);
+    return g;
+}
+
 }  // namespace plan
 #endif
