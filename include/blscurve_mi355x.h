@@ -539,6 +539,30 @@ int mi355_bls_p2s_mult_pippenger_device(mi355_bls_ctx* ctx, uint8_t ret_p2[288],
 int mi355_bls_p1s_mult_pippenger_device(mi355_bls_ctx* ctx, uint8_t ret_p1[144], const void* d_points, size_t npoints,
                                         const void* d_scalars, size_t nbits, void* stream);
 
+/* k G1 MSMs in one device pass: ret[j] = the blst_p1 image (Jacobian, 144 B) of MSM j.  A single MSM of a few thousand points costs about as
+ * much as one sixteen times its size (the floor of a device call); k of them here share the stages of one bucket method over k x (windows of
+ * one MSM) virtual windows, with one Horner walk per MSM at the end.  Points, scalars and nbits (1..256) mean what they mean in
+ * mi355_bls_p1s_mult_pippenger_device: 96-byte blst_p1_affine images (all-zero = infinity; subgroup membership is not assumed), 32-byte
+ * little-endian scalar images of which the low nbits count.  Two addressing forms:
+ *   ragged (offsets != NULL)   k + 1 host values, offsets[0] == 0, non-decreasing, offsets[k] == npoints: MSM j is over points and scalars
+ *                              [offsets[j], offsets[j + 1]), point i with scalar i; an empty range gives infinity (144 zero bytes)
+ *   shared base (offsets == NULL)   every MSM is over all npoints points; the scalar array holds k x npoints scalars, MSM j uses
+ *                              [j npoints, (j + 1) npoints); the points are read and converted once
+ * No call is refused for its size - only a single MSM of more than 2^28 points is (MI355_BLS_ERR_ARG before anything is launched), as in
+ * the single call: a call beyond what one pass holds (csrc/plan.hpp MSM_MANY_*) runs as consecutive passes over ranges of
+ * MSMs, a member that alone exceeds a pass takes the single-MSM path, and so does a call with k == 1.  An infinite result is 144 zero bytes
+ * when a pass of this call made it; compare results as points, as with the single call.
+ *   _many          host arrays (contiguous, not pointer lists), results to ret (k x 144 B)
+ *   _many_device   arrays in device memory; results to ret (host, may be NULL) and / or d_out (device, k x 144 B, 4-byte aligned, may be NULL),
+ *                  every pass enqueued on `stream` alone (a member handed to the single path runs as the single call does), and waited
+ *                  for before the call returns
+ * k == 0 returns 0 and touches nothing.  MI355_BLS_ERR_ARG: a NULL context (before any other rule), NULL arrays with work to do, bad
+ * offsets, nbits outside 1..256, no output, an MSM of more than 2^28 points. */
+int mi355_bls_p1s_mult_pippenger_many(mi355_bls_ctx* ctx, uint8_t* ret, const void* points, size_t npoints, const void* scalars, const size_t* offsets,
+                                      size_t k, size_t nbits);
+int mi355_bls_p1s_mult_pippenger_many_device(mi355_bls_ctx* ctx, uint8_t* ret, void* d_out, const void* d_points, size_t npoints, const void* d_scalars,
+                                             const size_t* offsets, size_t k, size_t nbits, void* stream);
+
 /* Point-sharded MSM across the GPUs of one node (blst_p1s_mult_pippenger, blst_abi.nim:336-340, over devices; the bench shape
  * benchmarks/bls12381_msm_g1.nim:47-59): device g computes the full-width partial sum of points [first_g, first_g + count_g)
  * (mi355_bls_msm_shard_range: balanced contiguous blocks), the 144-byte partials are added (blst_p1_add_or_double,

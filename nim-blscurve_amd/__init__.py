@@ -149,6 +149,8 @@ def lib():
         L.mi355_bls_p1s_mult_pippenger_scratch_sizeof.restype = sz
         L.mi355_bls_p1s_mult_pippenger.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), sz, ctypes.POINTER(vp), sz]
         L.mi355_bls_p1s_mult_pippenger_device.argtypes = [vp, ctypes.c_char_p, vp, sz, vp, sz, vp]
+        L.mi355_bls_p1s_mult_pippenger_many.argtypes = [vp, vp, vp, sz, vp, psz, sz, sz]
+        L.mi355_bls_p1s_mult_pippenger_many_device.argtypes = [vp, vp, vp, vp, sz, vp, psz, sz, sz, vp]
         cp = ctypes.c_char_p
         L.mi355_bls_deserialize_sets.argtypes = [vp, cp, cp, cp, sz, vp, vp]
         L.mi355_bls_deserialize_sets_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp]
@@ -1395,6 +1397,54 @@ def p1s_mult_pippenger_device(cache, d_points, n, d_scalars, nbits=255, stream=0
     out = ctypes.create_string_buffer(144)
     _check(lib().mi355_bls_p1s_mult_pippenger_device(cache._h, out, d_points, n, d_scalars, nbits, stream))
     return out.raw
+
+
+def _many_offsets(offsets, npoints):
+    offs = [int(v) for v in offsets]
+    if not offs or offs[0] != 0 or offs[-1] != npoints or any(b < a for a, b in zip(offs, offs[1:])):
+        raise ValueError("offsets: k + 1 non-decreasing values from 0 to the number of points")
+    return offs
+
+
+def p1s_mult_pippenger_many(cache, points, scalars, offsets=None, nbits=255):
+    """k G1 MSMs in one device pass -> a list of k 144-byte blst_p1 (Jacobian) results.  offsets (k + 1 values): MSM j is over points and
+    scalars [offsets[j], offsets[j + 1]).  offsets=None: every MSM is over all n points, scalars = k x n x 32 bytes, MSM j uses scalars
+    [j n, (j + 1) n)."""
+    if len(points) % 96 or len(scalars) % 32:
+        raise ValueError("points: n x 96 bytes, scalars: 32 bytes each")
+    n, ns = len(points) // 96, len(scalars) // 32
+    if offsets is None:
+        if n == 0 or ns % n:
+            if ns:
+                raise ValueError("shared points: scalars must be k x n x 32 bytes")
+            return []
+        k, arr = ns // n, None
+    else:
+        offs = _many_offsets(offsets, n)
+        if ns != n:
+            raise ValueError("ragged: one 32-byte scalar per point")
+        k, arr = len(offs) - 1, (ctypes.c_size_t * len(offs))(*offs)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(144 * k)
+    _check(lib().mi355_bls_p1s_mult_pippenger_many(cache._h, out, bytes(points), n, bytes(scalars), arr, k, nbits))
+    return [out.raw[144 * j:144 * j + 144] for j in range(k)]
+
+
+def p1s_mult_pippenger_many_device(cache, d_points, npoints, d_scalars, offsets, k, nbits=255, d_out=None, stream=0):
+    """The same with both arrays in device memory (pointers as integers); offsets as above or None.  The results come back as a list and,
+    when d_out (a device pointer to k x 144 bytes) is given, are left there as well."""
+    if k == 0:
+        return []
+    arr = None
+    if offsets is not None:
+        offs = _many_offsets(offsets, npoints)
+        if len(offs) != k + 1:
+            raise ValueError("offsets: k + 1 values")
+        arr = (ctypes.c_size_t * len(offs))(*offs)
+    out = ctypes.create_string_buffer(144 * k)
+    _check(lib().mi355_bls_p1s_mult_pippenger_many_device(cache._h, out, d_out, d_points, npoints, d_scalars, arr, k, nbits, stream))
+    return [out.raw[144 * j:144 * j + 144] for j in range(k)]
 
 
 def _split_compressed(pubkeys, messages, signatures):

@@ -19,6 +19,12 @@ struct msm_ws {
     dev_event ev_fork, ev_bucketed, ev_g[2], ev_tail[2];
     dev_buf<uint4> buckets, segout;
 };
+// k MSMs in one pass (mi355_bls_p1s_mult_pippenger_many): buffers of its own, each grown to the call's extent (plan::msm_many_sizes_for)
+struct msm_many_ws {
+    dev_buf<uint8_t> d_pts, d_sc;     // the host entry's staging
+    dev_buf<uint32_t> pts_int, offs_dev, hist, offs, cursor, order, chist, sorted, part, out;
+    dev_buf<uint4> buckets, segout;
+};
 
 // the buffers Miller pairs live in, as the stage launchers take them: a view, it owns nothing
 struct pair_store {
@@ -170,6 +176,9 @@ struct mi355_bls_ctx {
     dev_event ev_bm;                 // the offsets are on the host
     std::vector<uint32_t> bm_offs;
     int bm_groups = -1;              // k of the last by-message slice (mi355_bls_last_message_groups)
+    // k MSMs in one pass (mi355_bls_p1s_mult_pippenger_many): made at the first such call
+    msm_many_ws msm_many;
+    std::vector<uint32_t> many_offs; // the ragged passes' offsets of the call in flight: the async copies read them
 
     // the batch workspace's pair store (ctx_build makes it; it never changes) and the per-set path's (each_reserve)
     pair_store batch_pairs() const { return {d_H, d_P, d_lines, stride}; }
@@ -3219,6 +3228,142 @@ extern "C" int mi355_bls_p2s_mult_pippenger(mi355_bls_ctx* c, uint8_t ret_p2[288
     }
     if (!points || !points[0] || !scalars || !scalars[0] || nbits == 0 || nbits > 256) return MI355_BLS_ERR_ARG;
     return msm_host<fp2>(c, ret_p2, (const uint8_t*)points[0], npoints, scalars[0], 32, nbits);
+}
+
+// ------------------------------------------------------------------------------------------
+// k G1 MSMs in one device pass (mi355_bls_p1s_mult_pippenger_many): a walk over plan::msm_many_for / msm_many_next
+// ------------------------------------------------------------------------------------------
+// The argument rules of both entries, made without looking into the context: 0 go on, 1 nothing to do (k == 0), or the error.
+static int msm_many_check(const mi355_bls_ctx* c, const void* ret, const void* d_out, const void* points, size_t npoints, const void* scalars, const size_t* offsets,
+                          size_t k, size_t nbits) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 1;
+    if ((!ret && !d_out) || nbits == 0 || nbits > 256) return MI355_BLS_ERR_ARG;
+    if (offsets) {
+        if (offsets[0] != 0 || offsets[k] != npoints) return MI355_BLS_ERR_ARG;
+        for (size_t j = 0; j < k; j++)
+            if (offsets[j + 1] < offsets[j] || offsets[j + 1] - offsets[j] > ((size_t)1 << 28)) return MI355_BLS_ERR_ARG;      // (the single call's limit on one MSM)
+    } else if (npoints > ((size_t)1 << 28)) {
+        return MI355_BLS_ERR_ARG;
+    }
+    if (npoints && (!points || !scalars)) return MI355_BLS_ERR_ARG;
+    return 0;
+}
+// Arguments checked (msm_many_check returned 0).  Every pass is enqueued on `st`; the results land in d_out (or the workspace's own k x 144
+// bytes), are copied to ret, and the stream is waited for, as the single call does.
+static int msm_many_run(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const void* d_points, size_t npoints, const void* d_scalars, const size_t* offsets, size_t k,
+                        size_t nbits, hipStream_t st) {
+    msm_many_ws* m = &c->msm_many;
+    const plan::msm_many_plan P = plan::msm_many_for(k, npoints, offsets == nullptr, nbits);
+    const plan::msm_many_sizes sz = plan::msm_many_sizes_for(P, offsets, npoints, k);
+    int rc = 0;
+    const auto grow = [&rc](auto& buf, size_t bytes) { rc = rc ? rc : buf.reserve(bytes, 0); };
+    grow(m->pts_int, sz.pts_int), grow(m->offs_dev, sz.offs_dev), grow(m->hist, sz.hist), grow(m->offs, sz.hist), grow(m->cursor, sz.hist), grow(m->order, sz.hist);
+    grow(m->chist, sz.chist), grow(m->sorted, sz.sorted), grow(m->buckets, sz.buckets), grow(m->segout, sz.segout), grow(m->part, sz.part);
+    if (!d_out) grow(m->out, k * 144);
+    if (rc) return rc;
+    uint32_t* dst = d_out ? (uint32_t*)d_out : m->out.p;
+    const uint8_t* pts = (const uint8_t*)d_points;
+    const uint8_t* sc = (const uint8_t*)d_scalars;
+    const pip_win W{P.W};
+    const uint32_t nw = W.nwin;
+    // the offsets of every ragged pass, relative to its first pair: one array that no pass of the call moves
+    size_t words = 0;
+    if (offsets)
+        for (size_t j = 0; j < k;) {
+            const plan::msm_many_pass s = plan::msm_many_next(P, offsets, npoints, k, j);
+            words += s.single ? 0 : s.j1 - s.j0 + 1;
+            j = s.j1;
+        }
+    c->many_offs.assign(words, 0);
+    size_t used = 0;
+    bool converted = false, timed = false;
+    for (size_t j = 0; j < k;) {
+        const plan::msm_many_pass s = plan::msm_many_next(P, offsets, npoints, k, j);
+        j = s.j1;
+        uint32_t* out = dst + s.j0 * 36;
+        if (s.single) {
+            const size_t n = offsets ? offsets[s.j0 + 1] - offsets[s.j0] : npoints;
+            if (n == 0) {
+                HIPCHK(hipMemsetAsync(out, 0, 144, st));
+                continue;
+            }
+            rc = msm_enqueue<fp>(c, &c->msm, pts + (offsets ? s.pair0 * 96 : 0), n, sc + s.pair0 * 32, 32, nbits, st, false, true);
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(out, c->msm.out, 144, hipMemcpyDeviceToDevice, st));
+            continue;
+        }
+        const uint32_t kp = (uint32_t)(s.j1 - s.j0);
+        if (s.pairs == 0) {
+            HIPCHK(hipMemsetAsync(out, 0, (size_t)kp * 144, st));
+            continue;
+        }
+        const many_addr A{s.pairs, kp, offsets ? 0u : (uint32_t)npoints, nw, W.cbk};
+        if (offsets) {
+            uint32_t* rel = c->many_offs.data() + used;
+            for (uint32_t i = 0; i <= kp; i++) rel[i] = (uint32_t)(offsets[s.j0 + i] - s.pair0);
+            used += kp + 1;
+            HIPCHK(hipMemcpyAsync(m->offs_dev, rel, ((size_t)kp + 1) * 4, hipMemcpyHostToDevice, st));
+        }
+        const uint8_t* psc = sc + s.pair0 * 32;
+        HIPCHK(hipMemsetAsync(m->hist, 0, (size_t)s.total * 4, st));
+        HIPCHK(hipMemsetAsync(m->chist, 0, 256 * 4, st));
+        const bool t = !timed;
+        timed = true;
+        if (t) HIPCHK(hipEventRecord(c->ev[0], st));
+        if (offsets) k_pip_convert<fp><<<plan::waves_for(s.points), WAVE, 0, st>>>(pts + s.pair0 * 96, s.points, m->pts_int);
+        else if (!converted) k_pip_convert<fp><<<plan::waves_for(s.points), WAVE, 0, st>>>(pts, s.points, m->pts_int);      // the shared points: once per call
+        converted = true;
+        k_pipm_hist<<<dim3(s.pair_grid, nw), WAVE, 0, st>>>(psc, A, m->offs_dev, W, m->hist);
+        k_pipm_scan<<<s.nv, WAVE, 0, st>>>(m->hist, A, m->offs_dev, m->offs, m->cursor);
+        k_pipm_scatter<<<dim3(s.pair_grid, nw), WAVE, 0, st>>>(psc, A, m->offs_dev, W, m->cursor, m->sorted);
+        k_msm_order_hist<<<s.order_grid, WAVE, 0, st>>>(m->hist, s.total, m->chist);
+        k_msm_order_scan<<<1, 1, 0, st>>>(m->chist);
+        k_msm_order_scatter<<<s.order_grid, WAVE, 0, st>>>(m->hist, s.total, m->chist, m->order);
+        if (t) HIPCHK(hipEventRecord(c->ev[1], st));
+        // offs holds positions in `sorted` itself (k_pipm_scan): n = 0 takes k_pip_bucket's own window x n out
+        k_pip_bucket<fp><<<s.bucket_grid, WAVE, 0, st>>>(m->pts_int, m->sorted, m->offs, m->hist, m->order, 0, W.cbk, s.total, 0, s.total, m->buckets);
+        if (t) HIPCHK(hipEventRecord(c->ev[2], st));
+        if (s.team == 4) k_pip_segred_team<4><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        else if (s.team == 2) k_pip_segred_team<2><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        else k_pip_segred<fp><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        k_pip_winpart<fp><<<dim3(s.nv, P.nsplit), WAVE, 0, st>>>(m->segout, s.nseg, P.segs_per_win, 0, m->part);
+        if (t) HIPCHK(hipEventRecord(c->ev[3], st));
+        k_pip_rowtail_many<<<kp, P.tail_lanes, 0, st>>>(m->part, P.nsplit, W, out);
+        if (t) HIPCHK(hipEventRecord(c->ev[4], st));
+        HIPCHK(hipGetLastError());
+    }
+    if (ret) HIPCHK(hipMemcpyAsync(ret, dst, k * 144, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (timed) return collect_timings(c, 4);       // the first pass's stages: [0] sort and order, [1] bucket accumulation, [2] reductions, [3] the tails
+    for (float& t : c->timings) t = 0;             // every step took the single path (untimed here): no stale stages of an earlier call
+    return 0;
+}
+extern "C" int mi355_bls_p1s_mult_pippenger_many_device(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const void* d_points, size_t npoints, const void* d_scalars,
+                                                        const size_t* offsets, size_t k, size_t nbits, void* stream) {
+    const int chk = msm_many_check(c, ret, d_out, d_points, npoints, d_scalars, offsets, k, nbits);
+    if (chk) return chk < 0 ? chk : 0;
+    HIPCHK(hipSetDevice(c->device));
+    return msm_many_run(c, ret, d_out, d_points, npoints, d_scalars, offsets, k, nbits, (hipStream_t)stream);
+}
+// host arrays -> staging -> msm_many_run on the null stream
+extern "C" int mi355_bls_p1s_mult_pippenger_many(mi355_bls_ctx* c, uint8_t* ret, const void* points, size_t npoints, const void* scalars, const size_t* offsets,
+                                                 size_t k, size_t nbits) {
+    const int chk = msm_many_check(c, ret, ret, points, npoints, scalars, offsets, k, nbits);
+    if (chk) return chk < 0 ? chk : 0;
+    if (npoints == 0) {
+        memset(ret, 0, k * 144);
+        return 0;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    msm_many_ws* m = &c->msm_many;
+    const size_t nsc = offsets ? npoints : npoints * k;
+    int rc = m->d_pts.reserve(npoints * 96, 0);
+    rc = rc ? rc : m->d_sc.reserve(nsc * 32, 0);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(m->d_pts, points, npoints * 96, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(m->d_sc, scalars, nsc * 32, hipMemcpyHostToDevice, nullptr));
+    return msm_many_run(c, ret, nullptr, m->d_pts, npoints, m->d_sc, offsets, k, nbits, nullptr);
 }
 
 // blst's list convention (blst_p1s_mult_pippenger and friends): list[0] points at element 0; for every following element the

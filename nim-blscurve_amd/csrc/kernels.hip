@@ -42,6 +42,7 @@
 #include "aggsigs.hpp"
 #include "recover.hpp"
 #include "keytable.hpp"
+#include "msmmany.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -1604,6 +1605,8 @@ __device__ __forceinline__ uint32_t pip_off(const pip_win& W, uint32_t w) {
 // The scalar is fetched with two 16-byte loads when it can be (blst_scalar arrays: sbytes = 32, 16-byte aligned) - one load
 // per word behind its own bounds test leaves a lane with eight dependent memory latencies; the two words of k' the window
 // needs are picked while the carry runs (w is uniform: no indexed register array).
+// csrc/msmmany.hpp many_digit / many_win_off restate this arithmetic (and pip_off) as host-runnable bodies for the many-MSM sort: a change here
+// is a change there (tests/test_msm_many_emu.py holds many_digit to the oracle).
 __device__ __forceinline__ int32_t pip_digit(const uint8_t* __restrict__ sc, size_t i, const pip_win& W, uint32_t sbytes, uint32_t w) {
     const uint8_t* p = sc + i * sbytes;
     uint32_t k[8];
@@ -2106,6 +2109,111 @@ __global__ void __launch_bounds__(WAVE) k_pip_final(const uint32_t* __restrict__
         acc = padd(acc, o);
     }
     if (threadIdx.x == 0) st_jac_blst(out, acc);
+}
+
+// ------------------------------------------------------------------------------------------
+// k G1 MSMs in one pass (mi355_bls_p1s_mult_pippenger_many; csrc/msmmany.hpp, plan.hpp msm_many_for): the counting sort over virtual windows
+// v = j x nwin + w and one Horner walk per MSM.  Between them the kernels above run as they are, on k x nwin windows.
+//   k_pipm_hist / k_pipm_scan / k_pipm_scatter   lane per (pair, window of its MSM); the scan adds every virtual window's list start, so
+//                                                offs and cursor hold positions in `sorted` itself (k_pip_bucket then takes n = 0)
+//   k_pip_rowtail_many                           k_pip_rowtail's walk, one workgroup per MSM over its own nwin window parts -> out[j]
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int32_t pipm_digit(const uint8_t* __restrict__ sc, uint32_t p, const pip_win& W, uint32_t w) {
+    const uint8_t* s = sc + (size_t)p * 32;
+    uint32_t k[8];
+    if ((((uintptr_t)sc) & 15) == 0) {
+        const uint4* pv = reinterpret_cast<const uint4*>(s);
+        uint4 a = pv[0], b = pv[1];
+        k[0] = a.x; k[1] = a.y; k[2] = a.z; k[3] = a.w; k[4] = b.x; k[5] = b.y; k[6] = b.z; k[7] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) k[j] = (uint32_t)s[4 * j] | (uint32_t)s[4 * j + 1] << 8 | (uint32_t)s[4 * j + 2] << 16 | (uint32_t)s[4 * j + 3] << 24;
+    }
+    return many_digit(k, W, w);
+}
+__global__ void __launch_bounds__(WAVE) k_pipm_hist(const uint8_t* __restrict__ sc, many_addr A, const uint32_t* __restrict__ moffs, pip_win W, uint32_t* __restrict__ hist) {
+    const uint32_t p = blockIdx.x * WAVE + threadIdx.x, w = blockIdx.y;
+    if (p >= A.pairs) return;
+    const int32_t d = pipm_digit(sc, p, W, w);
+    if (d) atomicAdd(&hist[many_bucket(A, many_owner(A, moffs, p), w, (uint32_t)(d < 0 ? -d : d))], 1u);
+}
+// one wave per virtual window
+__global__ void __launch_bounds__(WAVE) k_pipm_scan(const uint32_t* __restrict__ hist, many_addr A, const uint32_t* __restrict__ moffs, uint32_t* __restrict__ offs,
+                                                    uint32_t* __restrict__ cursor) {
+    const uint32_t v = blockIdx.x, nb = 1u << A.cbk, per = (nb + WAVE - 1) / WAVE;
+    const uint32_t lo = threadIdx.x * per, hi = lo + per < nb ? lo + per : nb;
+    const uint32_t* h = hist + ((size_t)v << A.cbk);
+    uint32_t sum = 0;
+    for (uint32_t b = lo; b < hi; b++) sum += h[b];
+    uint32_t incl = sum;
+    for (int d = 1; d < WAVE; d <<= 1) {
+        uint32_t o = __shfl_up(incl, d, WAVE);
+        if ((int)threadIdx.x >= d) incl += o;
+    }
+    uint32_t run = many_list_start(A, moffs, v) + incl - sum;
+    for (uint32_t b = lo; b < hi; b++) {
+        offs[((size_t)v << A.cbk) | b] = run;
+        cursor[((size_t)v << A.cbk) | b] = run;
+        run += h[b];
+    }
+}
+__global__ void __launch_bounds__(WAVE) k_pipm_scatter(const uint8_t* __restrict__ sc, many_addr A, const uint32_t* __restrict__ moffs, pip_win W, uint32_t* __restrict__ cursor,
+                                                       uint32_t* __restrict__ sorted) {
+    const uint32_t p = blockIdx.x * WAVE + threadIdx.x, w = blockIdx.y;
+    if (p >= A.pairs) return;
+    const int32_t d = pipm_digit(sc, p, W, w);
+    if (d) {
+        const uint32_t j = many_owner(A, moffs, p);
+        const uint32_t pos = atomicAdd(&cursor[many_bucket(A, j, w, (uint32_t)(d < 0 ? -d : d))], 1u);
+        sorted[pos] = many_point(A, p, j) | (d < 0 ? 0x80000000u : 0u);
+    }
+}
+// k_pip_rowtail for MSM j = blockIdx.x of a pass: wave v sums the nsplit parts of the MSM's windows v, v + 16, ... (virtual windows j nwin + w) into
+// LDS, wave 0 walks from window nwin - 1 down to 0 and writes the blst image at out + 36 j words.  An MSM has at most 52 windows, so the 64 sums
+// fit.  An infinite result is stored as 144 zero bytes, what the single call returns for no points.
+__global__ void __launch_bounds__(1024) k_pip_rowtail_many(const uint32_t* __restrict__ part, uint32_t nsplit, pip_win W, uint32_t* __restrict__ out) {
+    __shared__ uint32_t sums[64 * 48];
+    const row_ctx C = row_ctx_make();
+    const uint32_t wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, l16 = threadIdx.x & 15u, nwin = W.nwin;
+    const bool row0 = (threadIdx.x & 63u) < 16u;
+    part += (size_t)blockIdx.x * nwin * nsplit * (3 * FPW);
+    out += (size_t)blockIdx.x * 36;
+#pragma clang loop unroll(disable)
+    for (uint32_t w = wave; w < nwin; w += nwaves) {
+        const uint32_t* base = part + (size_t)w * nsplit * (3 * FPW);
+        row_g1 acc{row_load(base), row_load(base + FPW), row_load(base + 2 * FPW)};
+#pragma clang loop unroll(disable)
+        for (uint32_t j = 1; j < nsplit; j++) {
+            const uint32_t* q = base + (size_t)j * (3 * FPW);
+            acc = row_add(C, acc, row_g1{row_load(q), row_load(q + FPW), row_load(q + 2 * FPW)});
+        }
+        if (row0) {
+            uint32_t* d = sums + w * 48;
+            d[l16] = (uint32_t)acc.x; d[16 + l16] = (uint32_t)acc.y; d[32 + l16] = (uint32_t)acc.z;
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    uint32_t w = nwin - 1;
+    const uint32_t* d0 = sums + w * 48;
+    row_g1 acc{(rw)d0[l16], (rw)d0[16 + l16], (rw)d0[32 + l16]};
+#pragma clang loop unroll(disable)
+    while (w > 0) {
+        w--;
+        const uint32_t sh = pip_off(W, w + 1) - pip_off(W, w);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i < sh; i++) acc = row_dbl(C, acc);
+        const uint32_t* d = sums + w * 48;
+        acc = row_add(C, acc, row_g1{(rw)d[l16], (rw)d[16 + l16], (rw)d[32 + l16]});
+    }
+    const g1_jac r{fp_reduce(row_to_fp(acc.x)), fp_reduce(row_to_fp(acc.y)), fp_reduce(row_to_fp(acc.z))};
+    if (threadIdx.x == 0) {
+        if (jac_is_inf(r)) {
+            for (int i = 0; i < 36; i++) out[i] = 0;
+        } else {
+            st_jac_blst(out, r);
+        }
+    }
 }
 
 // sum of k Jacobian blst images `stride` words apart -> blst image: the merge of the per-device partials of a point-sharded MSM

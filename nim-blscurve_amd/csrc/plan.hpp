@@ -873,6 +873,129 @@ inline msm_sizes msm_extents(const msm_plan& p, bool g2) {
     return s;
 }
 
+// ------------------------------------------------------------------------------------------
+// k G1 MSMs in one device pass (mi355_bls_p1s_mult_pippenger_many): what msm_many_run follows, and what it reserves.
+// Every stage of the bucket method works on VIRTUAL windows v = j x nwin + w (MSM j of the pass, its window w): the counting sort gives each
+// virtual window its buckets' point lists, and from there k_msm_order_*, k_pip_bucket, k_pip_segred(_team) and k_pip_winpart see one MSM of
+// k x nwin windows; k_pip_rowtail_many then walks each MSM's own nwin window parts, one workgroup per MSM.
+//   window width   ONE pip_win per call, whichever way the call is cut into passes: pip_for of the shared npoints, or - ragged - of the MEAN
+//                  member length (npoints / k rounded up, at least 1).  The mean, not the largest: every member pays the reduction of all of its
+//                  windows' buckets, full or empty.  Not measured against the other choices.
+//   one pass       at most MSM_MANY_VWIN_MAX virtual windows (no grid axis of any kernel, whichever it puts them on, exceeds 65 535),
+//                  MSM_MANY_BUCKETS_MAX buckets (the SoA bucket store: 192 bytes each) and MSM_MANY_PAIRS_MAX (point, scalar) pairs (a pass of
+//                  that many pairs already runs at the large single MSM's throughput; list positions stay 32-bit words).  A call beyond that
+//                  runs as consecutive passes over ranges of MSMs; a member that alone exceeds the pair bound is handed to msm_enqueue, and so
+//                  is a call of one MSM.
+//   counting sort  the global-counter form only (k_pipm_hist / k_pipm_scan / k_pipm_scatter).  The LDS-counter sort of large single MSMs is
+//                  left out: its workgroups own (slice of the points, window), and a slice here would straddle members.
+//   team, nsplit   msm_for's rules on the pass's segments / a window's segments.  Not measured for this call.
+// The pass runs on the caller's stream alone (no window groups).
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t MSM_MANY_VWIN_MAX = 65535;
+constexpr uint32_t MSM_MANY_BUCKETS_MAX = 1u << 21;
+constexpr uint32_t MSM_MANY_PAIRS_MAX = 1u << 20;
+static_assert((uint64_t)MSM_MANY_PAIRS_MAX * MSM_WINDOWS_MAX < (1ull << 31), "a list position (pairs x windows) and a point index beside its sign bit fit a word");
+static_assert((uint64_t)MSM_MANY_BUCKETS_MAX * 16 < (1ull << 32), "k_pip_bucket's 16-byte bucket offsets");
+struct msm_many_plan {
+    pip_win W;
+    bool shared;                       // every MSM over all npoints points | MSM j over [offsets[j], offsets[j + 1])
+    uint32_t n_ref;                    // what the window width was taken from
+    uint32_t buckets_per_msm;          // nwin << cbk
+    uint32_t segs_per_win, nsplit;     // as msm_plan's
+    uint32_t tail_waves, tail_lanes;   // k_pip_rowtail_many's workgroup (one per MSM): a wave per window up to MSM_TAIL_WAVES_MAX
+    uint32_t msms_max;                 // MSMs a pass takes at the most (virtual windows, buckets)
+};
+inline msm_many_plan msm_many_for(size_t k, size_t npoints, bool shared, size_t nbits) {
+    msm_many_plan P{};
+    P.shared = shared;
+    const size_t mean = shared || k == 0 ? npoints : (npoints + k - 1) / k;
+    P.n_ref = (uint32_t)(mean < 1 ? 1 : (mean > MSM_MANY_PAIRS_MAX ? MSM_MANY_PAIRS_MAX : mean));
+    P.W = pip_for(P.n_ref, nbits);
+    P.buckets_per_msm = P.W.nwin << P.W.cbk;
+    P.segs_per_win = (1u << P.W.cbk) / MSM_SEG;
+    P.nsplit = P.segs_per_win >= 1024 ? 16 : (P.segs_per_win >= 128 ? 4 : 1);
+    P.tail_waves = P.W.nwin < MSM_TAIL_WAVES_MAX ? P.W.nwin : MSM_TAIL_WAVES_MAX;
+    P.tail_lanes = P.tail_waves * WAVE;
+    const uint32_t by_vwin = MSM_MANY_VWIN_MAX / P.W.nwin, by_buckets = MSM_MANY_BUCKETS_MAX / P.buckets_per_msm;
+    P.msms_max = by_vwin < by_buckets ? by_vwin : by_buckets;      // >= 1: 64 windows of 2^15 buckets are 2^21
+    return P;
+}
+// One step of a call: MSMs [j0, j1).  single: the one MSM j0 goes through msm_enqueue (the call has one MSM, or the member exceeds
+// MSM_MANY_PAIRS_MAX); otherwise the pass below.
+struct msm_many_pass {
+    bool single;
+    size_t j0, j1;
+    size_t pair0;                      // the pass's first pair in the call's scalar array (ragged: in its point array as well)
+    uint32_t pairs;                    // 0: every member is empty, the results are infinity and nothing is launched
+    uint32_t points;                   // what k_pip_convert converts for it: the pass's pairs (ragged), all npoints once per call (shared)
+    uint32_t nv, total, nseg;          // virtual windows, buckets, 16-bucket segments
+    uint32_t pair_grid;                // x of k_pipm_hist / k_pipm_scatter (y: the nwin windows of an MSM): a lane per pair
+    uint32_t order_grid, bucket_grid;  // k_msm_order_hist / _scatter, k_pip_bucket over all buckets of the pass
+    uint32_t team, segred_grid;        // k_pip_segred_team<team> (4, 2) | k_pip_segred (1)
+};
+// offsets: the call's k + 1 (ragged) or nullptr (shared); the caller has checked them
+inline msm_many_pass msm_many_next(const msm_many_plan& P, const size_t* offsets, size_t npoints, size_t k, size_t j0) {
+    msm_many_pass s{};
+    const auto len = [&](size_t j) { return offsets ? offsets[j + 1] - offsets[j] : npoints; };
+    s.j0 = j0, s.j1 = j0 + 1;
+    s.pair0 = offsets ? offsets[j0] : j0 * npoints;
+    if (k == 1 || len(j0) > MSM_MANY_PAIRS_MAX) {
+        s.single = true;
+        return s;
+    }
+    size_t pairs = len(j0);
+    while (s.j1 < k && s.j1 - j0 < P.msms_max && len(s.j1) <= MSM_MANY_PAIRS_MAX && pairs + len(s.j1) <= MSM_MANY_PAIRS_MAX) pairs += len(s.j1++);
+    const uint32_t kp = (uint32_t)(s.j1 - j0);
+    s.pairs = (uint32_t)pairs;
+    s.points = offsets ? s.pairs : (uint32_t)npoints;
+    s.nv = kp * P.W.nwin;
+    s.total = kp * P.buckets_per_msm;
+    s.nseg = s.nv * P.segs_per_win;
+    s.pair_grid = waves_for(s.pairs);
+    s.order_grid = (s.total + WAVE * MSM_ORD_PER - 1) / (WAVE * MSM_ORD_PER);
+    s.bucket_grid = waves_for(s.total);
+    s.team = (size_t)s.nseg * 4 <= MSM_TEAM_LANES_MAX ? 4 : ((size_t)s.nseg * 2 <= MSM_TEAM_LANES_MAX ? 2 : 1);
+    s.segred_grid = waves_for(s.nseg * s.team);
+    return s;
+}
+// The buffers of the workspace in bytes.  msm_many_extents: what the kernels of one pass touch, read off their indexing;
+// msm_many_sizes_for: what msm_many_run grows the workspace to before a call - the largest extent over the call's passes
+// (tests/test_msm_many_plan.py holds every pass to that).
+struct msm_many_sizes {
+    size_t pts_int;                    // k_pip_convert: point i at word i x 2 x FP_WORDS
+    size_t offs_dev;                   // ragged: the pass's k + 1 offsets, relative to its first pair
+    size_t hist;                       // one word per bucket: hist, offs, cursor, order alike
+    size_t chist;                      // k_msm_order_*: 256 bins
+    size_t sorted;                     // virtual window v's list from word msmmany.hpp many_list_start(v): pairs x nwin words in all
+    size_t buckets, segout;            // SoA Jacobian G1 points: rows of `total` / `nseg`
+    size_t part;                       // k_pip_winpart: a Jacobian point at (virtual window x nsplit + part)
+};
+inline msm_many_sizes msm_many_extents(const msm_many_plan& P, const msm_many_pass& s) {
+    msm_many_sizes z{};
+    if (s.single || s.pairs == 0) return z;
+    z.pts_int = (size_t)s.points * 2 * FP_WORDS * 4;
+    z.offs_dev = P.shared ? 0 : (s.j1 - s.j0 + 1) * 4;
+    z.hist = (size_t)s.total * 4;
+    z.chist = 256 * 4;
+    z.sorted = (size_t)s.pairs * P.W.nwin * 4;
+    z.buckets = (size_t)s.total * G1_WORDS * 4;
+    z.segout = (size_t)s.nseg * G1_WORDS * 4;
+    z.part = (size_t)s.nv * P.nsplit * G1_WORDS * 4;
+    return z;
+}
+inline msm_many_sizes msm_many_sizes_for(const msm_many_plan& P, const size_t* offsets, size_t npoints, size_t k) {
+    msm_many_sizes m{};
+    const auto up = [](size_t& a, size_t b) { a = a < b ? b : a; };
+    for (size_t j = 0; j < k;) {
+        const msm_many_pass s = msm_many_next(P, offsets, npoints, k, j);
+        const msm_many_sizes z = msm_many_extents(P, s);
+        up(m.pts_int, z.pts_int), up(m.offs_dev, z.offs_dev), up(m.hist, z.hist), up(m.chist, z.chist), up(m.sorted, z.sorted), up(m.buckets, z.buckets),
+            up(m.segout, z.segout), up(m.part, z.part);
+        j = s.j1;
+    }
+    return m;
+}
+
 // chunk of the parallel_chunks partition (parallel_chunks.nim:42-66) that tuple t of n_total falls into, B chunks
 inline uint32_t chunk_of_tuple(size_t n_total, uint32_t B, size_t t) {
     size_t base = n_total / B, rem = n_total % B, cut = (base + 1) * rem;
