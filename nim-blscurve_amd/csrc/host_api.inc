@@ -26,6 +26,32 @@ struct msm_many_ws {
     dev_buf<uint4> buckets, segout;
 };
 
+// What the "k groups in one device pass" calls share: every buffer is sized by the call, never by max_sets, grown on demand with a quarter of
+// slack (grouped_upload, stage_inputs), and free again when the call returns - each of them drains its stream first.  Who uses what:
+//   items / d_items, d_flag     every one: aggregate_sets, aggregate_sets_bits (items | sets; two route counters behind the k flag words),
+//                               combine_sets, aggregate_signature_sets, recover_signature_sets, by_message (table only); aggregate_verify_each
+//                               has tables of its own and takes the flag words alone
+//   d_status, status_h          all but by_message and aggregate_verify_each
+//   d_g1_part                   aggregate_sets, aggregate_sets_bits, combine_sets (key side), by_message
+//   d_g2_prod                   combine_sets ([s_j]S_j), recover_signature_sets ([l_j]S_j)
+//   d_g2_part                   combine_sets (signature side), aggregate_signature_sets, recover_signature_sets
+//   d_rec                       aggregate_sets, aggregate_sets_bits, combine_sets: the forms that verify their records, and the host forms
+//   d_in                        the host forms of all but by_message
+//   d_g2_out                    the host forms of aggregate_signature_sets and recover_signature_sets
+struct grouped_ws {
+    std::vector<uint32_t> items;     // the item table of the call in flight (the feature's words behind it): the async copy reads it
+    dev_buf<uint32_t> d_items;       // ... on the device
+    dev_buf<uint32_t> d_g1_part;     // the plan's G1 partials, G1W words each
+    dev_buf<uint32_t> d_g2_prod;     // a G2 product per member, G2W words each
+    dev_buf<uint32_t> d_g2_part;     // the plan's G2 partials, G2W words each
+    dev_buf<uint32_t> d_flag;        // per group: an index was out of range (or what else the feature's kernels raise)
+    dev_buf<uint8_t> d_status;       // per group: the status byte
+    std::vector<uint8_t> status_h;   // ... on the host, for the forms that gate a verification on it
+    dev_buf<uint8_t> d_rec;          // k 320-byte records
+    dev_buf<uint8_t> d_in;           // host inputs staged (plan.hpp pack_for)
+    dev_buf<uint8_t> d_g2_out;       // k x 192 bytes | k x 96 bytes: aggregated or recovered signatures on their way to the host
+};
+
 // the buffers Miller pairs live in, as the stage launchers take them: a view, it owns nothing
 struct pair_store {
     uint4 *H, *P, *lines;
@@ -131,44 +157,28 @@ struct mi355_bls_ctx {
     dev_buf<uint32_t> d_each_work;   // the engine form's step values and results, one block per workgroup
     size_t each_stride = 0;
     int each_passes = 0;             // per-set passes made on this context (mi355_bls_debug_verify_each_passes)
-    // per-set key aggregation (mi355_bls_aggregate_sets): sized by the call, grown on demand (reserve with a quarter of slack), never by max_sets
-    dev_buf<uint32_t> d_agg_part;    // the plan's partials, G1W words each
-    dev_buf<uint32_t> d_agg_tab;     // item table | final_of, as agg_tab holds them
-    dev_buf<uint32_t> d_agg_bad;     // per segment: an index was out of range
-    dev_buf<uint8_t> d_agg_status;   // per segment: the status byte
-    dev_buf<uint8_t> d_agg_rec;      // the records of the forms that verify them (and of the host form)
-    dev_buf<uint8_t> d_agg_in;       // host inputs staged: keys | signatures | messages | indices
-    std::vector<uint32_t> agg_tab;   // the table of the call in flight: the async copy reads it
-    std::vector<uint8_t> agg_status_h;
-    // key aggregation by participation bits (mi355_bls_aggregate_sets_bits): shares the buffers above (the flag words carry the two route
-    // counters behind the k per-set words, the table is items | sets)
+    grouped_ws grp;                  // what the grouped calls share (above)
+    // key aggregation by participation bits (mi355_bls_aggregate_sets_bits)
     dev_buf<uint8_t> d_aggb_mode;    // per set: the mode byte (aggbits.hpp AGGB_*)
     uint32_t aggb_routes[2] = {0, 0};      // sets of the last bits call summed directly / by exclusion (mi355_bls_debug_aggregate_bits_routes)
-    // same-message pre-aggregation (mi355_bls_combine_sets): sized by the call like the buffers above, which it shares (item table, G1
-    // partials, flag words, status bytes, records, staged inputs)
+    // same-message pre-aggregation (mi355_bls_combine_sets): sized by the call
     dev_buf<uint64_t> d_comb_s;      // s_j by position: blinding material, cleared before every return
     dev_buf<uint8_t> d_comb_rnd;     // the groups' random bytes (cleared likewise)
     dev_buf<uint32_t> d_comb_gather; // the member records by position, when the call addresses them through indices
     dev_buf<uint4> d_comb_P;         // [s_j]PK_j, SoA Jacobian as k_pkmul writes it
-    dev_buf<uint32_t> d_comb_g2;     // [s_j]S_j, G2W words each
-    dev_buf<uint32_t> d_comb_part2;  // the plan's G2 partials
     dev_buf<uint8_t> d_comb_pktab;   // the window tables of one chunk of members: k_pkmul's ...
     dev_buf<uint4> d_comb_g2tab;     // ... and k_combsets_g2mul's
     dev_buf<uint32_t> d_comb_pkflag; // k_pkmul's infinity-key word (the check items report such a key per group)
     std::vector<uint64_t> comb_s_h;  // the chains the host walks, until the call's synchronisation
-    // per-group signature aggregation (mi355_bls_aggregate_signature_sets): sized by the call (plan.hpp aggsigs_sizes_for), made at the first
-    // such call; it shares the item table, flag words, status bytes and staged inputs above and combine_sets' G2 partials (d_comb_part2)
-    dev_buf<uint8_t> d_aggsig_out;   // the host form's outputs: k x 192 bytes | k x 96 bytes
     // per-group aggregateVerify (mi355_bls_aggregate_verify_each): sized by the largest SLICE of a call (plan.hpp aggveach_*), grown on demand;
-    // it shares the per-set path's pair store, verdict bytes and values, the flag words above and, for the host form, the staged inputs
+    // it runs in the per-set path's pair store, verdict bytes and values
     dev_buf<uint32_t> d_aggv_part;   // the partials of a slice: per Miller step an Fp12 each
     dev_buf<uint32_t> d_aggv_step;   // the step values of a slice's groups: N_LINES x F12W words per group
     dev_buf<uint32_t> d_aggv_tab;    // a slice's groups | items
     dev_buf<uint32_t> d_aggv_carry;  // the open group's Miller value (a blst_fp12 image), and a second slot for the engine form's part
     dev_buf<uint32_t> d_aggv_work;   // the engine form's block per workgroup
     std::vector<uint32_t> aggv_tab;  // the tables of every slice of the call in flight: the async copies read them
-    // batchVerify by message (mi355_bls_batch_verify_by_message): sized by the slice, grown with the call; the group sums share the item
-    // table and the G1 partials above
+    // batchVerify by message (mi355_bls_batch_verify_by_message): sized by the slice, grown with the call
     dev_buf<uint32_t> d_bm_tab;      // the open-addressing table: plan::bymsg_table_slots(n) set indices
     dev_buf<uint32_t> d_bm_work;     // the word arrays of the grouping (bymsg_arrays)
     dev_buf<uint4> d_bm_P;           // [r_i]PK_i of all n sets, SoA Jacobian as k_pkmul writes it
@@ -197,6 +207,67 @@ struct mi355_bls_ctx {
 static bool ctx_busy(const mi355_bls_ctx* c) {
     if (c->pending) g_err = "a batch submitted on this context has not been waited for";
     return c->pending;
+}
+
+// ---- the grouped calls' plumbing (grouped_ws)
+// The levels of a segmented sum laid out by plan.hpp (aggsets_plan, aggbits_plan, aggveach_tab): level 0 reads the feature's operands,
+// every higher level the partials of the one below.  Each callable launches `cnt` items that start at `it`.
+template <class Plan, class L0, class Ln>
+static void launch_levels(const Plan& p, const uint4* items, L0 level0, Ln higher) {
+    for (uint32_t l = 0; l < p.levels; l++) {
+        const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
+        if (l == 0) level0(items, cnt);
+        else higher(items + p.level_first[l], cnt);
+    }
+}
+// The table the feature has laid out in grp.items goes to the device on `st`, with the flag words cleared in front of it.  Table, flag words
+// and status bytes grow with a quarter of slack; a count of zero leaves its buffer alone.
+static int grouped_upload(mi355_bls_ctx* c, size_t tab_bytes, size_t flag_bytes, size_t status_bytes, hipStream_t st) {
+    grouped_ws& g = c->grp;
+    int rc = g.d_items.reserve(tab_bytes, tab_bytes / 4);
+    if (!rc) rc = g.d_flag.reserve(flag_bytes, flag_bytes / 4);
+    if (!rc) rc = g.d_status.reserve(status_bytes, status_bytes / 4);
+    if (rc) return rc;
+    if (flag_bytes) HIPCHK(hipMemsetAsync(g.d_flag, 0, flag_bytes, st));
+    HIPCHK(hipMemcpyAsync(g.d_items, g.items.data(), tab_bytes, hipMemcpyHostToDevice, st));
+    return 0;
+}
+// A host array of a call.  row != 0: rows of `row` bytes that lie `pitch` bytes apart at the source and are packed on the device.
+struct host_part {
+    const void* p;      // null: the call has no such part
+    size_t bytes;
+    size_t row = 0, pitch = 0;
+};
+// The host forms' inputs -> grp.d_in at the places plan::pack_for names (every part 4-byte aligned: a byte-aligned part goes last), one copy
+// per non-empty part on `st`.  d[i]: where part i is on the device, null for a part the call does not have.
+template <size_t N>
+static int stage_inputs(mi355_bls_ctx* c, const host_part (&parts)[N], hipStream_t st, const uint8_t* (&d)[N]) {
+    static_assert(N <= plan::PACK_PARTS_MAX, "plan::pack_layout holds that many offsets");
+    size_t len[N];
+    for (size_t i = 0; i < N; i++) len[i] = parts[i].p ? parts[i].bytes : 0;
+    const plan::pack_layout L = plan::pack_for(len, N);
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = c->grp.d_in.reserve(L.total, L.total / 4)) return rc;
+    for (size_t i = 0; i < N; i++) {
+        uint8_t* at = c->grp.d_in + L.at[i];
+        d[i] = parts[i].p ? at : nullptr;
+        if (!len[i]) continue;
+        if (parts[i].row) HIPCHK(hipMemcpy2DAsync(at, parts[i].row, parts[i].p, parts[i].pitch, parts[i].row, len[i] / parts[i].row, hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemcpyAsync(at, parts[i].p, len[i], hipMemcpyHostToDevice, st));
+    }
+    return 0;
+}
+// offsets: k + 1 entries that never decrease
+static bool agg_offsets_ok(const size_t* offsets, size_t k) {
+    for (size_t s = 0; s < k; s++)
+        if (offsets[s + 1] < offsets[s]) return false;
+    return true;
+}
+// a sequence addressed without an index array is the table itself: it holds offsets[k] positions, or the call is refused with `msg`
+static bool table_holds(bool have_idx, const size_t* offsets, size_t k, size_t n_table, const char* msg) {
+    if (have_idx || offsets[k] <= n_table) return true;
+    g_err = msg;
+    return false;
 }
 
 constexpr size_t PKTAB_BYTES = 8 * 5 * 64;   // per set: 8 table entries x (X, Y, Z, Z^2, Z^3) x 64 bytes (tools/gen_pkmul_asm.py LANE_BYTES)
@@ -1067,23 +1138,19 @@ static int run_pairs_grouped(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n, 
             (void)hipStreamSynchronize(sd), (void)hipStreamSynchronize(ss), (void)hipStreamSynchronize(st);
             return MI355_BLS_ERR_HIP;
         }
-        c->agg_tab.resize(ap.items * 4 + k);
-        plan::aggsets_fill(ap, offsets.data(), k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), c->agg_tab.data() + ap.items * 4);
-        const size_t tb = c->agg_tab.size() * 4;
-        int rc = c->d_agg_part.reserve(ap.items * (size_t)G1W * 4, ap.items * (size_t)G1W);
-        if (!rc) rc = c->d_agg_tab.reserve(tb, tb / 4);
+        c->grp.items.resize(ap.items * 4 + k);
+        plan::aggsets_fill(ap, offsets.data(), k, reinterpret_cast<plan::agg_item*>(c->grp.items.data()), c->grp.items.data() + ap.items * 4);
+        int rc = c->grp.d_g1_part.reserve(ap.items * (size_t)G1W * 4, ap.items * (size_t)G1W);
+        if (!rc) rc = grouped_upload(c, c->grp.items.size() * 4, 0, 0, sd);      // the table alone: this pass has no flag words and no status bytes
         if (rc) {
             (void)hipStreamSynchronize(sd), (void)hipStreamSynchronize(ss), (void)hipStreamSynchronize(st);
             return rc;
         }
-        HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), tb, hipMemcpyHostToDevice, sd));
-        const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
-        for (uint32_t l = 0; l < ap.levels; l++) {
-            const uint32_t cnt = (uint32_t)(ap.level_first[l + 1] - ap.level_first[l]);
-            if (l == 0) k_bymsg_l0<<<plan::waves_for(cnt), WAVE, 0, sd>>>(items, cnt, c->d_bm_P, P_stride, A.members, c->d_agg_part);
-            else k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, sd>>>(items + ap.level_first[l], cnt, c->d_agg_part);
-        }
-        k_bymsg_finish<<<gp.grid_k, WAVE, 0, sd>>>(c->d_agg_tab + ap.items * 4, k32, c->d_agg_part, ps.P, ps.stride, A.n_inf);
+        uint32_t* part = c->grp.d_g1_part;
+        launch_levels(ap, reinterpret_cast<const uint4*>(c->grp.d_items.p),
+                      [&](const uint4* it, uint32_t cnt) { k_bymsg_l0<<<plan::waves_for(cnt), WAVE, 0, sd>>>(it, cnt, c->d_bm_P, P_stride, A.members, part); },
+                      [&](const uint4* it, uint32_t cnt) { k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, sd>>>(it, cnt, part); });
+        k_bymsg_finish<<<gp.grid_k, WAVE, 0, sd>>>(c->grp.d_items + ap.items * 4, k32, c->grp.d_g1_part, ps.P, ps.stride, A.n_inf);
     }
     HIPCHK(hipEventRecord(c->ev[3], sd));
     // ---- Miller lines and their products per step: k + total pairs
@@ -1369,18 +1436,13 @@ extern "C" int mi355_bls_compress_public_keys(mi355_bls_ctx* c, const void* pks9
 // operands, no item across two lists) and sends the table with one copy; a kernel per level and k_aggsets_finish follow on the caller's stream.
 // ------------------------------------------------------------------------------------------
 static_assert(sizeof(plan::agg_item) == 16, "k_aggsets_l0 / k_aggsets_ln load an item as one uint4");
-static bool agg_offsets_ok(const size_t* offsets, size_t k) {
-    for (size_t s = 0; s < k; s++)
-        if (offsets[s + 1] < offsets[s]) return false;
-    return true;
-}
 // device addresses of a call's inputs
 struct agg_in {
     const uint8_t* keys;
     const uint32_t* idx;
     const uint8_t *msgs, *sigs;
 };
-// aggregation of k > 0 lists enqueued on st: records at d_out, status bytes in c->d_agg_status
+// aggregation of k > 0 lists enqueued on st: records at d_out, status bytes in c->grp.d_status
 static int aggsets_enqueue(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, uint8_t* d_out, hipStream_t st) {
     if (!in.keys || !in.msgs || !in.sigs || !offsets || !d_out) return MI355_BLS_ERR_ARG;
     if (((uintptr_t)in.keys | (uintptr_t)in.msgs | (uintptr_t)in.sigs | (uintptr_t)in.idx | (uintptr_t)d_out) & 3) {
@@ -1393,56 +1455,76 @@ static int aggsets_enqueue(mi355_bls_ctx* c, const agg_in& in, size_t n_table, c
         g_err = "aggregate_sets: offsets decrease, or more than 2^32 - 2 keys or lists";
         return MI355_BLS_ERR_ARG;
     }
-    if (!in.idx && offsets[k] > n_table) {
-        g_err = "aggregate_sets: offsets[k] exceeds the number of keys";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (!table_holds(in.idx, offsets, k, n_table, "aggregate_sets: offsets[k] exceeds the number of keys")) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    c->agg_tab.resize(p.items * 4 + k);
-    plan::aggsets_fill(p, offsets, k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), c->agg_tab.data() + p.items * 4);
-    // grown with a quarter of slack; every entry point that used the old buffers has drained its stream before returning
-    const size_t pb = (p.items ? p.items : 1) * (size_t)G1W * 4, tb = c->agg_tab.size() * 4;
-    int rc = c->d_agg_part.reserve(pb, pb / 4);
-    if (!rc) rc = c->d_agg_tab.reserve(tb, tb / 4);
-    if (!rc) rc = c->d_agg_bad.reserve(k * 4, k);
-    if (!rc) rc = c->d_agg_status.reserve(k, k / 4);
+    c->grp.items.resize(p.items * 4 + k);
+    plan::aggsets_fill(p, offsets, k, reinterpret_cast<plan::agg_item*>(c->grp.items.data()), c->grp.items.data() + p.items * 4);
+    const size_t pb = (p.items ? p.items : 1) * (size_t)G1W * 4;
+    int rc = c->grp.d_g1_part.reserve(pb, pb / 4);
+    if (!rc) rc = grouped_upload(c, c->grp.items.size() * 4, k * 4, k, st);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, k * 4, st));
-    HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), c->agg_tab.size() * 4, hipMemcpyHostToDevice, st));
-    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
-    for (uint32_t l = 0; l < p.levels; l++) {
-        const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
-        if (l == 0) k_aggsets_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, in.keys, n_table, in.idx, c->d_agg_part, c->d_agg_bad);
-        else k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + p.level_first[l], cnt, c->d_agg_part);
-    }
-    k_aggsets_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(c->d_agg_tab + p.items * 4, (uint32_t)k, c->d_agg_part, c->d_agg_bad,
+    uint32_t* part = c->grp.d_g1_part;
+    launch_levels(p, reinterpret_cast<const uint4*>(c->grp.d_items.p),
+                  [&](const uint4* it, uint32_t cnt) { k_aggsets_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, in.keys, n_table, in.idx, part, c->grp.d_flag); },
+                  [&](const uint4* it, uint32_t cnt) { k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, part); });
+    k_aggsets_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(c->grp.d_items + p.items * 4, (uint32_t)k, part, c->grp.d_flag,
                                                                    reinterpret_cast<const uint32_t*>(in.msgs), reinterpret_cast<const uint32_t*>(in.sigs),
-                                                                   reinterpret_cast<uint32_t*>(d_out), c->d_agg_status);
+                                                                   reinterpret_cast<uint32_t*>(d_out), c->grp.d_status);
     HIPCHK(hipGetLastError());
     return 0;
 }
-// the status bytes back (the call's synchronisation): 1 when every list gave a key
-static int aggsets_status(mi355_bls_ctx* c, size_t k, uint8_t* status, hipStream_t st) {
-    HIPCHK(hipMemcpyAsync(status, c->d_agg_status, k, hipMemcpyDeviceToHost, st));
+// The status bytes back (a grouped call's synchronisation): 1 when every group's is 0.  The chains combine_sets walked on the host are blinding
+// material: they are wiped and dropped here, on every way out, so a call that left none (every other feature's) has nothing to fill.
+static int grouped_status(mi355_bls_ctx* c, size_t k, uint8_t* status, hipStream_t st) {
+    struct wipe {
+        std::vector<uint64_t>& v;
+        ~wipe() { std::fill(v.begin(), v.end(), 0), v.clear(); }
+    } at_return{c->comb_s_h};
+    HIPCHK(hipMemcpyAsync(status, c->grp.d_status, k, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     int all = 1;
     for (size_t s = 0; s < k; s++) all &= status[s] == 0;
     return all;
 }
-// host inputs -> d_agg_in (keys | signatures | messages | indices: every part 4-byte aligned)
-static int agg_stage(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k, const void* msgs, const void* sigs,
-                     hipStream_t st, agg_in* out) {
-    if (!keys || !offsets || !msgs || !sigs || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
-    const size_t n_idx = idx ? offsets[k] : 0, kb = n_table * 96, sb = k * 192, mb = k * 32, all = kb + sb + mb + n_idx * 4 + 4;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->d_agg_in.reserve(all, all / 4);
+// What is done with the k records of aggregate_sets, aggregate_sets_bits and combine_sets.  enqueue(d_out, st): the feature's pass, k records to
+// d_out on st, status bytes to grp.d_status.
+template <class Enqueue>
+static int records_enqueue(mi355_bls_ctx* c, size_t k, hipStream_t st, Enqueue enqueue) {
+    if (int rc = c->grp.d_rec.reserve(k * 320, k * 80)) return rc;
+    return enqueue(c->grp.d_rec.p, st);
+}
+// the host forms: records and status bytes to the host
+template <class Enqueue>
+static int records_to_host(mi355_bls_ctx* c, size_t k, void* out_records, uint8_t* status, Enqueue enqueue) {
+    if (int rc = records_enqueue(c, k, nullptr, enqueue)) return rc;
+    HIPCHK(hipMemcpyAsync(out_records, c->grp.d_rec, k * 320, hipMemcpyDeviceToHost, nullptr));
+    return grouped_status(c, k, status, nullptr);
+}
+// verify (fastAggregateVerify, bls_sig_min_pubkey.nim:234-258) per record: the per-set pass on them.  A group that gave no key (no member, an
+// index out of range, the sum at infinity) has the infinity key in its record: verdict 0.
+template <class Enqueue>
+static int records_each(mi355_bls_ctx* c, size_t k, uint8_t* out, hipStream_t st, Enqueue enqueue) {
+    if (int rc = records_enqueue(c, k, st, enqueue)) return rc;
+    return each_run(c, c->grp.d_rec, nullptr, k, out, nullptr, st);
+}
+// batchVerify over the records: a group that gives none (any status but 0) ends the call with 0 before any verification pass - the
+// reference's caller would not have obtained a SignatureSet for it.
+template <class Enqueue>
+static int records_batch(mi355_bls_ctx* c, size_t k, const uint8_t rnd[32], hipStream_t st, Enqueue enqueue) {
+    int rc = records_enqueue(c, k, st, enqueue);
     if (rc) return rc;
-    uint8_t* d = c->d_agg_in;
-    if (kb) HIPCHK(hipMemcpyAsync(d, keys, kb, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d + kb, sigs, sb, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d + kb + sb, msgs, mb, hipMemcpyHostToDevice, st));
-    if (n_idx) HIPCHK(hipMemcpyAsync(d + kb + sb + mb, idx, n_idx * 4, hipMemcpyHostToDevice, st));
-    *out = agg_in{d, idx ? reinterpret_cast<const uint32_t*>(d + kb + sb + mb) : nullptr, d + kb + sb, d + kb};
+    c->grp.status_h.resize(k);
+    rc = grouped_status(c, k, c->grp.status_h.data(), st);
+    if (rc != 1) return rc;
+    return verify_common(c, c->grp.d_rec, nullptr, k, rnd, 0, st);
+}
+// host inputs -> the staged inputs: keys | signatures | messages | indices (every part 4-byte aligned)
+static int agg_stage(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k, const void* msgs, size_t msg_bytes,
+                     const void* sigs, hipStream_t st, agg_in* out) {
+    if (!keys || !offsets || !msgs || !sigs || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
+    const uint8_t* d[4];
+    if (int rc = stage_inputs(c, {{keys, n_table * 96}, {sigs, k * 192}, {msgs, msg_bytes}, {idx, offsets[k] * 4}}, st, d)) return rc;
+    *out = agg_in{d[0], reinterpret_cast<const uint32_t*>(d[3]), d[2], d[1]};
     return 0;
 }
 extern "C" int mi355_bls_aggregate_sets_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k,
@@ -1453,7 +1535,7 @@ extern "C" int mi355_bls_aggregate_sets_device(mi355_bls_ctx* c, const void* d_k
     const agg_in in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192};
     int rc = aggsets_enqueue(c, in, n_table, offsets, k, (uint8_t*)d_out_records, (hipStream_t)stream);
     if (rc) return rc;
-    return aggsets_status(c, k, status, (hipStream_t)stream);
+    return grouped_status(c, k, status, (hipStream_t)stream);
 }
 extern "C" int mi355_bls_aggregate_sets(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
                                         const void* msgs32, const void* sigs192, void* out_records, uint8_t* status) {
@@ -1461,28 +1543,18 @@ extern "C" int mi355_bls_aggregate_sets(mi355_bls_ctx* c, const void* keys, size
     if (k == 0) return 0;
     if (!out_records || !status) return MI355_BLS_ERR_ARG;
     agg_in in;
-    int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
-    if (!rc) rc = c->d_agg_rec.reserve(k * 320, k * 80);
-    if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out_records, c->d_agg_rec, k * 320, hipMemcpyDeviceToHost, nullptr));
-    return aggsets_status(c, k, status, nullptr);
+    if (int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, k * 32, sigs192, nullptr, &in)) return rc;
+    return records_to_host(c, k, out_records, status, [&](uint8_t* d_out, hipStream_t st) { return aggsets_enqueue(c, in, n_table, offsets, k, d_out, st); });
 }
-// fastAggregateVerify (bls_sig_min_pubkey.nim:234-258) for every list: the records into the context's own buffer, then the per-set pass
-// on them.  A list without a key, with an out-of-range index or with the sum at infinity has the infinity key in its record: verdict 0.
-static int agg_each(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, uint8_t* out, hipStream_t st) {
-    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
-    if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, st);
-    if (rc) return rc;
-    return each_run(c, c->d_agg_rec, nullptr, k, out, nullptr, st);
-}
+// fastAggregateVerify for every list (records_each)
 extern "C" int mi355_bls_fast_aggregate_verify_each_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
                                                            size_t k, const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream) {
     if (!c) return MI355_BLS_ERR_ARG;
     if (k == 0) return 0;
     if (!out) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    return agg_each(c, agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, n_table, offsets, k, out, (hipStream_t)stream);
+    const agg_in in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192};
+    return records_each(c, k, out, (hipStream_t)stream, [&](uint8_t* d_out, hipStream_t st) { return aggsets_enqueue(c, in, n_table, offsets, k, d_out, st); });
 }
 extern "C" int mi355_bls_fast_aggregate_verify_each(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
                                                     const void* msgs32, const void* sigs192, uint8_t* out) {
@@ -1490,36 +1562,25 @@ extern "C" int mi355_bls_fast_aggregate_verify_each(mi355_bls_ctx* c, const void
     if (k == 0) return 0;
     if (!out) return MI355_BLS_ERR_ARG;
     agg_in in;
-    int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
-    if (rc) return rc;
-    return agg_each(c, in, n_table, offsets, k, out, nullptr);
+    if (int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, k * 32, sigs192, nullptr, &in)) return rc;
+    return records_each(c, k, out, nullptr, [&](uint8_t* d_out, hipStream_t st) { return aggsets_enqueue(c, in, n_table, offsets, k, d_out, st); });
 }
-// batchVerify over the sets (aggregateAll(keys_s), msg_s, sig_s): a list that gives no key (any status but 0) ends the call with 0 before
-// any verification pass - the reference's caller would not have obtained a SignatureSet for it.
-static int agg_batch(mi355_bls_ctx* c, const agg_in& in, size_t n_table, const size_t* offsets, size_t k, const uint8_t rnd[32], hipStream_t st) {
-    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
-    if (!rc) rc = aggsets_enqueue(c, in, n_table, offsets, k, c->d_agg_rec, st);
-    if (rc) return rc;
-    c->agg_status_h.resize(k);
-    rc = aggsets_status(c, k, c->agg_status_h.data(), st);
-    if (rc != 1) return rc;
-    return verify_common(c, c->d_agg_rec, nullptr, k, rnd, 0, st);
-}
+// batchVerify over the sets (aggregateAll(keys_s), msg_s, sig_s) (records_batch)
 extern "C" int mi355_bls_batch_fast_aggregate_verify_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
                                                             size_t k, const void* d_msgs32, const void* d_sigs192, const uint8_t rnd[32], void* stream) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if (k == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    return agg_batch(c, agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, n_table, offsets, k, rnd, (hipStream_t)stream);
+    const agg_in in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192};
+    return records_batch(c, k, rnd, (hipStream_t)stream, [&](uint8_t* d_out, hipStream_t st) { return aggsets_enqueue(c, in, n_table, offsets, k, d_out, st); });
 }
 extern "C" int mi355_bls_batch_fast_aggregate_verify(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
                                                      const void* msgs32, const void* sigs192, const uint8_t rnd[32]) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if (k == 0) return 0;
     agg_in in;
-    int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, sigs192, nullptr, &in);
-    if (rc) return rc;
-    return agg_batch(c, in, n_table, offsets, k, rnd, nullptr);
+    if (int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, k * 32, sigs192, nullptr, &in)) return rc;
+    return records_batch(c, k, rnd, nullptr, [&](uint8_t* d_out, hipStream_t st) { return aggsets_enqueue(c, in, n_table, offsets, k, d_out, st); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1554,7 +1615,7 @@ static bool aggb_args_ok(size_t n_table, bool have_idx, const size_t* c_offsets,
         }
     return true;
 }
-// aggregation of k > 0 sets enqueued on st: records at d_out, status bytes in c->d_agg_status, the route census on its way to c->aggb_routes
+// aggregation of k > 0 sets enqueued on st: records at d_out, status bytes in c->grp.d_status, the route census on its way to c->aggb_routes
 static int aggbits_enqueue(mi355_bls_ctx* c, const aggb_in& in, size_t n_table, const size_t* c_offsets, size_t m, const uint32_t* which, size_t k, uint8_t* d_out,
                            hipStream_t st) {
     if (!in.a.keys || !in.a.msgs || !in.a.sigs || !in.bits || !d_out) return MI355_BLS_ERR_ARG;
@@ -1570,34 +1631,31 @@ static int aggbits_enqueue(mi355_bls_ctx* c, const aggb_in& in, size_t n_table, 
         return MI355_BLS_ERR_ARG;
     }
     HIPCHK(hipSetDevice(c->device));
-    c->agg_tab.resize((p.items + k) * 4);
-    plan::aggbits_fill(p, c_offsets, which, k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), reinterpret_cast<plan::aggb_set*>(c->agg_tab.data() + p.items * 4));
-    const size_t pb = (p.items ? p.items : 1) * (size_t)G1W * 4, tb = c->agg_tab.size() * 4;
-    int rc = c->d_agg_part.reserve(pb, pb / 4);
-    if (!rc) rc = c->d_agg_tab.reserve(tb, tb / 4);
-    if (!rc) rc = c->d_agg_bad.reserve((k + 2) * 4, k);
-    if (!rc) rc = c->d_agg_status.reserve(k, k / 4);
+    c->grp.items.resize((p.items + k) * 4);
+    plan::aggbits_fill(p, c_offsets, which, k, reinterpret_cast<plan::agg_item*>(c->grp.items.data()), reinterpret_cast<plan::aggb_set*>(c->grp.items.data() + p.items * 4));
+    const size_t pb = (p.items ? p.items : 1) * (size_t)G1W * 4;
+    int rc = c->grp.d_g1_part.reserve(pb, pb / 4);
     if (!rc) rc = c->d_aggb_mode.reserve(k, k / 4);
+    if (!rc) rc = c->grp.d_flag.reserve((k + 2) * 4, k);      // the two route counters behind the k flag words take no part in the slack
+    if (!rc) rc = grouped_upload(c, c->grp.items.size() * 4, (k + 2) * 4, k, st);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, (k + 2) * 4, st));
-    HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), tb, hipMemcpyHostToDevice, st));
-    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
+    const uint4* items = reinterpret_cast<const uint4*>(c->grp.d_items.p);
     const uint4* sets = items + p.items;
-    uint32_t* routes = c->d_agg_bad + k;
+    uint32_t *part = c->grp.d_g1_part, *routes = c->grp.d_flag + k;
     k_aggbits_mode<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(sets, (uint32_t)k, in.bits, in.aggs, in.agg_stride, c->d_aggb_mode, routes);
-    for (uint32_t l = 0; l < p.levels; l++) {
-        const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
-        if (l == 0) k_aggbits_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, in.a.keys, n_table, in.a.idx, in.bits, c->d_aggb_mode, c->d_agg_part, c->d_agg_bad);
-        else k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + p.level_first[l], cnt, c->d_agg_part);
-    }
-    k_aggbits_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(sets, (uint32_t)k, c->d_agg_part, c->d_agg_bad, c->d_aggb_mode, in.aggs, in.agg_stride,
+    launch_levels(p, items,
+                  [&](const uint4* it, uint32_t cnt) {
+                      k_aggbits_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, in.a.keys, n_table, in.a.idx, in.bits, c->d_aggb_mode, part, c->grp.d_flag);
+                  },
+                  [&](const uint4* it, uint32_t cnt) { k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, part); });
+    k_aggbits_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(sets, (uint32_t)k, c->grp.d_g1_part, c->grp.d_flag, c->d_aggb_mode, in.aggs, in.agg_stride,
                                                                    reinterpret_cast<const uint32_t*>(in.a.msgs), reinterpret_cast<const uint32_t*>(in.a.sigs),
-                                                                   reinterpret_cast<uint32_t*>(d_out), c->d_agg_status);
+                                                                   reinterpret_cast<uint32_t*>(d_out), c->grp.d_status);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->aggb_routes, routes, 8, hipMemcpyDeviceToHost, st));      // there when aggsets_status has synchronised
+    HIPCHK(hipMemcpyAsync(c->aggb_routes, routes, 8, hipMemcpyDeviceToHost, st));      // there when grouped_status has synchronised
     return 0;
 }
-// host inputs -> d_agg_in (keys | signatures | messages | indices | committee aggregates, packed | bits: the byte-aligned part last)
+// host inputs -> the staged inputs: keys | signatures | messages | indices | committee aggregates, packed | bits (the byte-aligned part, last)
 static int aggb_stage(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m, const void* aggs, size_t agg_stride,
                       const uint32_t* which, const void* bits, size_t k, const void* msgs, const void* sigs, hipStream_t st, aggb_in* out) {
     if (!keys || !msgs || !sigs || !bits || !aggb_args_ok(n_table, idx != nullptr, c_offsets, m, aggs, agg_stride, which, k)) return MI355_BLS_ERR_ARG;
@@ -1606,21 +1664,15 @@ static int aggb_stage(mi355_bls_ctx* c, const void* keys, size_t n_table, const 
         g_err = "aggregate_sets_bits: more than 2^32 - 2 positions, sets or level-0 items";
         return MI355_BLS_ERR_ARG;
     }
-    const size_t n_idx = idx ? c_offsets[m] : 0, kb = n_table * 96, sb = k * 192, mb = k * 32, ib = n_idx * 4, ab = aggs ? m * 96 : 0;
-    const size_t all = kb + sb + mb + ib + ab + p.bits_bytes + 4;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->d_agg_in.reserve(all, all / 4);
-    if (rc) return rc;
-    uint8_t* d = c->d_agg_in;
-    if (kb) HIPCHK(hipMemcpyAsync(d, keys, kb, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d + kb, sigs, sb, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d + kb + sb, msgs, mb, hipMemcpyHostToDevice, st));
-    if (ib) HIPCHK(hipMemcpyAsync(d + kb + sb + mb, idx, ib, hipMemcpyHostToDevice, st));
-    uint8_t* da = d + kb + sb + mb + ib;
-    if (ab) HIPCHK(hipMemcpy2DAsync(da, 96, aggs, agg_stride, 96, m, hipMemcpyHostToDevice, st));
-    if (p.bits_bytes) HIPCHK(hipMemcpyAsync(da + ab, bits, p.bits_bytes, hipMemcpyHostToDevice, st));
-    *out = aggb_in{agg_in{d, idx ? reinterpret_cast<const uint32_t*>(d + kb + sb + mb) : nullptr, d + kb + sb, d + kb}, aggs ? da : nullptr, 96, da + ab};
+    const uint8_t* d[6];
+    if (int rc = stage_inputs(c, {{keys, n_table * 96}, {sigs, k * 192}, {msgs, k * 32}, {idx, c_offsets[m] * 4}, {aggs, m * 96, 96, agg_stride}, {bits, p.bits_bytes}}, st, d))
+        return rc;
+    *out = aggb_in{agg_in{d[0], reinterpret_cast<const uint32_t*>(d[3]), d[2], d[1]}, d[4], 96, d[5]};
     return 0;
+}
+// the device forms' inputs
+static aggb_in aggb_device_in(const void* d_keys, const uint32_t* d_idx, const void* d_aggs, size_t agg_stride, const void* d_bits, const void* d_msgs, const void* d_sigs) {
+    return aggb_in{agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs, (const uint8_t*)d_sigs}, (const uint8_t*)d_aggs, agg_stride, (const uint8_t*)d_bits};
 }
 extern "C" int mi355_bls_aggregate_sets_bits_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets, size_t m,
                                                     const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits, size_t k,
@@ -1628,11 +1680,10 @@ extern "C" int mi355_bls_aggregate_sets_bits_device(mi355_bls_ctx* c, const void
     if (!c) return MI355_BLS_ERR_ARG;
     if (k == 0) return 0;                      // nothing aggregated, nothing written
     if (!status) return MI355_BLS_ERR_ARG;
-    const aggb_in in{agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, (const uint8_t*)d_committee_aggs, agg_stride,
-                     (const uint8_t*)d_bits};
+    const aggb_in in = aggb_device_in(d_keys, d_idx, d_committee_aggs, agg_stride, d_bits, d_msgs32, d_sigs192);
     int rc = aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, (uint8_t*)d_out_records, (hipStream_t)stream);
     if (rc) return rc;
-    return aggsets_status(c, k, status, (hipStream_t)stream);
+    return grouped_status(c, k, status, (hipStream_t)stream);
 }
 extern "C" int mi355_bls_aggregate_sets_bits(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
                                              const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k, const void* msgs32,
@@ -1641,21 +1692,11 @@ extern "C" int mi355_bls_aggregate_sets_bits(mi355_bls_ctx* c, const void* keys,
     if (k == 0) return 0;
     if (!out_records || !status) return MI355_BLS_ERR_ARG;
     aggb_in in;
-    int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in);
-    if (!rc) rc = c->d_agg_rec.reserve(k * 320, k * 80);
-    if (!rc) rc = aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, c->d_agg_rec, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out_records, c->d_agg_rec, k * 320, hipMemcpyDeviceToHost, nullptr));
-    return aggsets_status(c, k, status, nullptr);
+    if (int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in)) return rc;
+    return records_to_host(c, k, out_records, status,
+                           [&](uint8_t* d_out, hipStream_t st) { return aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, d_out, st); });
 }
-// the records into the context's own buffer, then the per-set pass on them, as agg_each
-static int aggb_each(mi355_bls_ctx* c, const aggb_in& in, size_t n_table, const size_t* c_offsets, size_t m, const uint32_t* which, size_t k, uint8_t* out,
-                     hipStream_t st) {
-    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
-    if (!rc) rc = aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, c->d_agg_rec, st);
-    if (rc) return rc;
-    return each_run(c, c->d_agg_rec, nullptr, k, out, nullptr, st);
-}
+// fastAggregateVerify for every set, as for key lists (records_each)
 extern "C" int mi355_bls_fast_aggregate_verify_each_bits_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets,
                                                                 size_t m, const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits,
                                                                 size_t k, const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream) {
@@ -1663,9 +1704,9 @@ extern "C" int mi355_bls_fast_aggregate_verify_each_bits_device(mi355_bls_ctx* c
     if (k == 0) return 0;
     if (!out) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    const aggb_in in{agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, (const uint8_t*)d_committee_aggs, agg_stride,
-                     (const uint8_t*)d_bits};
-    return aggb_each(c, in, n_table, c_offsets, m, which, k, out, (hipStream_t)stream);
+    const aggb_in in = aggb_device_in(d_keys, d_idx, d_committee_aggs, agg_stride, d_bits, d_msgs32, d_sigs192);
+    return records_each(c, k, out, (hipStream_t)stream,
+                        [&](uint8_t* d_out, hipStream_t st) { return aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, d_out, st); });
 }
 extern "C" int mi355_bls_fast_aggregate_verify_each_bits(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
                                                          const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k,
@@ -1674,30 +1715,19 @@ extern "C" int mi355_bls_fast_aggregate_verify_each_bits(mi355_bls_ctx* c, const
     if (k == 0) return 0;
     if (!out) return MI355_BLS_ERR_ARG;
     aggb_in in;
-    int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in);
-    if (rc) return rc;
-    return aggb_each(c, in, n_table, c_offsets, m, which, k, out, nullptr);
+    if (int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in)) return rc;
+    return records_each(c, k, out, nullptr, [&](uint8_t* d_out, hipStream_t st) { return aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, d_out, st); });
 }
-// batchVerify over the records, as agg_batch: any status but 0 ends the call with 0 before any verification pass
-static int aggb_batch(mi355_bls_ctx* c, const aggb_in& in, size_t n_table, const size_t* c_offsets, size_t m, const uint32_t* which, size_t k, const uint8_t rnd[32],
-                      hipStream_t st) {
-    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
-    if (!rc) rc = aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, c->d_agg_rec, st);
-    if (rc) return rc;
-    c->agg_status_h.resize(k);
-    rc = aggsets_status(c, k, c->agg_status_h.data(), st);
-    if (rc != 1) return rc;
-    return verify_common(c, c->d_agg_rec, nullptr, k, rnd, 0, st);
-}
+// batchVerify over the records, as for key lists (records_batch)
 extern "C" int mi355_bls_batch_fast_aggregate_verify_bits_device(mi355_bls_ctx* c, const void* d_keys, size_t n_table, const uint32_t* d_idx, const size_t* c_offsets,
                                                                  size_t m, const void* d_committee_aggs, size_t agg_stride, const uint32_t* which, const void* d_bits,
                                                                  size_t k, const void* d_msgs32, const void* d_sigs192, const uint8_t rnd[32], void* stream) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if (k == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    const aggb_in in{agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, (const uint8_t*)d_committee_aggs, agg_stride,
-                     (const uint8_t*)d_bits};
-    return aggb_batch(c, in, n_table, c_offsets, m, which, k, rnd, (hipStream_t)stream);
+    const aggb_in in = aggb_device_in(d_keys, d_idx, d_committee_aggs, agg_stride, d_bits, d_msgs32, d_sigs192);
+    return records_batch(c, k, rnd, (hipStream_t)stream,
+                         [&](uint8_t* d_out, hipStream_t st) { return aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, d_out, st); });
 }
 extern "C" int mi355_bls_batch_fast_aggregate_verify_bits(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* c_offsets, size_t m,
                                                           const void* committee_aggs, size_t agg_stride, const uint32_t* which, const void* bits, size_t k,
@@ -1705,9 +1735,8 @@ extern "C" int mi355_bls_batch_fast_aggregate_verify_bits(mi355_bls_ctx* c, cons
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if (k == 0) return 0;
     aggb_in in;
-    int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in);
-    if (rc) return rc;
-    return aggb_batch(c, in, n_table, c_offsets, m, which, k, rnd, nullptr);
+    if (int rc = aggb_stage(c, keys, n_table, idx, c_offsets, m, committee_aggs, agg_stride, which, bits, k, msgs32, sigs192, nullptr, &in)) return rc;
+    return records_batch(c, k, rnd, nullptr, [&](uint8_t* d_out, hipStream_t st) { return aggbits_enqueue(c, in, n_table, c_offsets, m, which, k, d_out, st); });
 }
 extern "C" int mi355_bls_debug_aggregate_bits_routes(mi355_bls_ctx* c, uint32_t out[2]) {
     if (!c || !out) return MI355_BLS_ERR_ARG;
@@ -1736,10 +1765,7 @@ static int aggveach_run(mi355_bls_ctx* c, const agg_in& in, size_t n_table, cons
         g_err = "aggregate_verify_each: offsets decrease, or more than 2^32 - 2 pairs or groups";
         return MI355_BLS_ERR_ARG;
     }
-    if (!in.idx && offsets[k] > n_table) {
-        g_err = "aggregate_verify_each: offsets[k] exceeds the number of keys";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (!table_holds(in.idx, offsets, k, n_table, "aggregate_verify_each: offsets[k] exceeds the number of keys")) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     // pass 1: the slices and their tables (groups | items, slice after slice), and what the largest slice needs
     struct slice_rec {
@@ -1768,7 +1794,7 @@ static int aggveach_run(mi355_bls_ctx* c, const agg_in& in, size_t n_table, cons
     }
     int rc = each_reserve(c, k, gt_out != nullptr);
     const size_t pw = plan::aggveach_part_words(max_part) * 4, sw = plan::aggveach_step_words(max_ng) * 4;
-    if (!rc) rc = c->d_agg_bad.reserve(k * 4, k);
+    if (!rc) rc = c->grp.d_flag.reserve(k * 4, k);
     if (!rc) rc = c->d_aggv_part.reserve(pw, pw / 4);
     if (!rc) rc = c->d_aggv_step.reserve(sw, sw / 4);
     if (!rc) rc = c->d_aggv_tab.reserve(max_tab * 4 + 16, max_tab);
@@ -1777,7 +1803,7 @@ static int aggveach_run(mi355_bls_ctx* c, const agg_in& in, size_t n_table, cons
     if (rc) return rc;
     const pair_store ps = c->each_pairs();
     HIPCHK(hipEventRecord(c->ev[0], st));
-    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, k * 4, st));
+    HIPCHK(hipMemsetAsync(c->grp.d_flag, 0, k * 4, st));
     HIPCHK(hipMemsetAsync(c->d_each_v, 0, k, st));                     // an empty group has no lane: its verdict is 0, its value zero bytes
     if (gt_out) HIPCHK(hipMemsetAsync(c->d_each_gt, 0, k * 576, st));
     uint32_t* dg = gt_out ? c->d_each_gt.p : nullptr;
@@ -1790,21 +1816,21 @@ static int aggveach_run(mi355_bls_ctx* c, const agg_in& in, size_t n_table, cons
         const uint4* items = gtab + s.ng;
         k_aggveach_records<<<p.setup_grid, WAVE, 0, st>>>(in.keys, n_table, in.idx, s.pos0, P, reinterpret_cast<const uint32_t*>(in.msgs), gtab, s.ng, nsig,
                                                           reinterpret_cast<const uint32_t*>(in.sigs), reinterpret_cast<uint32_t*>(c->d_sets.p), ps.H, ps.P,
-                                                          ps.stride, c->d_agg_bad);
+                                                          ps.stride, c->grp.d_flag);
         launch_hash_map(c, c->d_sets, P, st);                              // H(msg_i) -> pair slot i, in the forms the batch path takes for P messages
         launch_hash_clear(c, ps, P, st);
         launch_lines(ps, p.lines, st);
         const uint32_t n_part = (uint32_t)(sr.t.partials ? sr.t.partials : 1);
-        for (uint32_t l = 0; l < sr.t.levels; l++) {
-            const uint32_t cnt = (uint32_t)(sr.t.level_first[l + 1] - sr.t.level_first[l]);
-            const dim3 grid(plan::waves_for(cnt), N_LINES);
-            if (l == 0) k_aggveach_l0<<<grid, WAVE, 0, st>>>(items, cnt, ps.lines, ps.stride, P, c->d_aggv_part, n_part, c->d_aggv_step);
-            else k_aggveach_ln<<<grid, WAVE, 0, st>>>(items + sr.t.level_first[l], cnt, c->d_aggv_part, n_part, c->d_aggv_step);
-        }
+        uint32_t *part = c->d_aggv_part, *step = c->d_aggv_step;
+        launch_levels(sr.t, items,
+                      [&](const uint4* it, uint32_t cnt) {
+                          k_aggveach_l0<<<dim3(plan::waves_for(cnt), N_LINES), WAVE, 0, st>>>(it, cnt, ps.lines, ps.stride, P, part, n_part, step);
+                      },
+                      [&](const uint4* it, uint32_t cnt) { k_aggveach_ln<<<dim3(plan::waves_for(cnt), N_LINES), WAVE, 0, st>>>(it, cnt, part, n_part, step); });
         if (!p.tail_engine) {
-            k_aggveach_tail<<<p.tail_grid, WAVE, 0, st>>>(c->d_aggv_step, gtab, s.ng, c->d_agg_bad, c->d_aggv_carry, c->d_each_v, dg);
+            k_aggveach_tail<<<p.tail_grid, WAVE, 0, st>>>(c->d_aggv_step, gtab, s.ng, c->grp.d_flag, c->d_aggv_carry, c->d_each_v, dg);
         } else {
-            k_aggveach_engine_rows<<<p.tail_grid, K_TAIL_THREADS, 0, st>>>(c->d_aggv_step, gtab, s.ng, c->d_agg_bad, c->d_aggv_carry, c->d_each_v, dg, c->d_aggv_work);
+            k_aggveach_engine_rows<<<p.tail_grid, K_TAIL_THREADS, 0, st>>>(c->d_aggv_step, gtab, s.ng, c->grp.d_flag, c->d_aggv_carry, c->d_each_v, dg, c->d_aggv_work);
             if (s.open_in && s.open_out) k_state_mul<<<1, TAIL_THREADS, 0, st>>>(c->d_aggv_carry, 0, 0, 1);      // the part's value into the carried one
         }
     }
@@ -1830,7 +1856,7 @@ extern "C" int mi355_bls_aggregate_verify_each_device(mi355_bls_ctx* c, const vo
     return aggveach_run(c, agg_in{(const uint8_t*)d_keys, d_idx, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs192}, n_table, offsets, k, out, nullptr,
                         (hipStream_t)stream);
 }
-// host inputs -> d_agg_in (keys | signatures | messages by position | indices: every part 4-byte aligned), then the device form
+// host inputs staged as aggregate_sets stages them (the messages follow the positions), then the device form
 static int aggveach_host(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k, const void* msgs32,
                          const void* sigs192, uint8_t* out, uint8_t* gt_out) {
     if (!c) return MI355_BLS_ERR_ARG;
@@ -1841,16 +1867,8 @@ static int aggveach_host(mi355_bls_ctx* c, const void* keys, size_t n_table, con
         return MI355_BLS_ERR_ARG;
     }
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    const size_t n_pos = offsets[k], kb = n_table * 96, sb = k * 192, mb = n_pos * 32, all = kb + sb + mb + (idx ? n_pos * 4 : 0) + 4;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->d_agg_in.reserve(all, all / 4);
-    if (rc) return rc;
-    uint8_t* d = c->d_agg_in;
-    if (kb) HIPCHK(hipMemcpyAsync(d, keys, kb, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(d + kb, sigs192, sb, hipMemcpyHostToDevice, nullptr));
-    if (mb) HIPCHK(hipMemcpyAsync(d + kb + sb, msgs32, mb, hipMemcpyHostToDevice, nullptr));
-    if (idx && n_pos) HIPCHK(hipMemcpyAsync(d + kb + sb + mb, idx, n_pos * 4, hipMemcpyHostToDevice, nullptr));
-    const agg_in in{d, idx ? reinterpret_cast<const uint32_t*>(d + kb + sb + mb) : nullptr, d + kb + sb, d + kb};
+    agg_in in;
+    if (int rc = agg_stage(c, keys, n_table, idx, offsets, k, msgs32, offsets[k] * 32, sigs192, nullptr, &in)) return rc;
     return aggveach_run(c, in, n_table, offsets, k, out, gt_out, nullptr);
 }
 extern "C" int mi355_bls_aggregate_verify_each(mi355_bls_ctx* c, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
@@ -1871,7 +1889,7 @@ extern "C" int mi355_bls_debug_aggregate_verify_each_gt(mi355_bls_ctx* c, const 
 // of the signature sequence: the table itself, or table entries picked by index); level 0 is k_aggsigs_l0, higher levels k_combsets_g2_sum,
 // then k_aggsigs_finish, all on the caller's stream.
 // ------------------------------------------------------------------------------------------
-// aggregation of k > 0 groups enqueued on st: images at d_out192, wire forms at d_out96 (either may be null), status bytes in c->d_agg_status
+// aggregation of k > 0 groups enqueued on st: images at d_out192, wire forms at d_out96 (either may be null), status bytes in c->grp.d_status
 static int aggsigs_enqueue(mi355_bls_ctx* c, const uint8_t* d_sigs, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k, uint8_t* d_out192,
                            uint8_t* d_out96, hipStream_t st) {
     if (!d_sigs || !offsets || (!d_out192 && !d_out96)) return MI355_BLS_ERR_ARG;
@@ -1885,32 +1903,22 @@ static int aggsigs_enqueue(mi355_bls_ctx* c, const uint8_t* d_sigs, size_t n_tab
         g_err = "aggregate_signature_sets: offsets decrease, or more than 2^32 - 2 signatures or groups";
         return MI355_BLS_ERR_ARG;
     }
-    if (!d_idx && offsets[k] > n_table) {
-        g_err = "aggregate_signature_sets: offsets[k] exceeds the number of signatures";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (!table_holds(d_idx, offsets, k, n_table, "aggregate_signature_sets: offsets[k] exceeds the number of signatures")) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    c->agg_tab.resize(p.items * 4 + k);
-    plan::aggsets_fill(p, offsets, k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), c->agg_tab.data() + p.items * 4);
-    // grown with a quarter of slack; every entry point that used the old buffers has drained its stream before returning
+    c->grp.items.resize(p.items * 4 + k);
+    plan::aggsets_fill(p, offsets, k, reinterpret_cast<plan::agg_item*>(c->grp.items.data()), c->grp.items.data() + p.items * 4);
     const plan::aggsigs_sizes sz = plan::aggsigs_sizes_for(p, k);
-    int rc = c->d_comb_part2.reserve(sz.part, sz.part / 4);
-    if (!rc) rc = c->d_agg_tab.reserve(sz.tab, sz.tab / 4);
-    if (!rc) rc = c->d_agg_bad.reserve(sz.bad, sz.bad / 4);
-    if (!rc) rc = c->d_agg_status.reserve(sz.status, sz.status / 4);
+    int rc = c->grp.d_g2_part.reserve(sz.part, sz.part / 4);
+    if (!rc) rc = grouped_upload(c, sz.tab, sz.bad, sz.status, st);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, sz.bad, st));
-    HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), sz.tab, hipMemcpyHostToDevice, st));
-    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
-    for (uint32_t l = 0; l < p.levels; l++) {
-        const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
-        if (l == 0)
-            k_aggsigs_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, reinterpret_cast<const uint32_t*>(d_sigs), n_table, d_idx, c->d_comb_part2, c->d_agg_bad);
-        else
-            k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + p.level_first[l], cnt, c->d_comb_part2, c->d_comb_part2);
-    }
-    k_aggsigs_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(c->d_agg_tab + p.items * 4, (uint32_t)k, c->d_comb_part2, c->d_agg_bad,
-                                                                   reinterpret_cast<uint32_t*>(d_out192), reinterpret_cast<uint32_t*>(d_out96), c->d_agg_status);
+    uint32_t* part = c->grp.d_g2_part;
+    launch_levels(p, reinterpret_cast<const uint4*>(c->grp.d_items.p),
+                  [&](const uint4* it, uint32_t cnt) {
+                      k_aggsigs_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, reinterpret_cast<const uint32_t*>(d_sigs), n_table, d_idx, part, c->grp.d_flag);
+                  },
+                  [&](const uint4* it, uint32_t cnt) { k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, part, part); });
+    k_aggsigs_finish<<<plan::waves_for((uint32_t)k), WAVE, 0, st>>>(c->grp.d_items + p.items * 4, (uint32_t)k, c->grp.d_g2_part, c->grp.d_flag,
+                                                                   reinterpret_cast<uint32_t*>(d_out192), reinterpret_cast<uint32_t*>(d_out96), c->grp.d_status);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1921,7 +1929,7 @@ extern "C" int mi355_bls_aggregate_signature_sets_device(mi355_bls_ctx* c, const
     if (!status) return MI355_BLS_ERR_ARG;
     int rc = aggsigs_enqueue(c, (const uint8_t*)d_sigs192, n_table, d_idx, offsets, k, (uint8_t*)d_out_sigs192, (uint8_t*)d_out_sigs96, (hipStream_t)stream);
     if (rc) return rc;
-    return aggsets_status(c, k, status, (hipStream_t)stream);
+    return grouped_status(c, k, status, (hipStream_t)stream);
 }
 extern "C" int mi355_bls_aggregate_signature_sets(mi355_bls_ctx* c, const void* sigs192, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
                                                   void* out_sigs192, void* out_sigs96, uint8_t* status) {
@@ -1929,21 +1937,16 @@ extern "C" int mi355_bls_aggregate_signature_sets(mi355_bls_ctx* c, const void* 
     if (k == 0) return 0;
     if (!sigs192 || !offsets || !status || (!out_sigs192 && !out_sigs96) || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    // signatures | indices -> d_agg_in (both parts 4-byte aligned)
-    const size_t n_idx = idx ? offsets[k] : 0, sb = n_table * 192, all = sb + n_idx * 4 + 4;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->d_agg_in.reserve(all, all / 4);
-    if (!rc) rc = c->d_aggsig_out.reserve(k * 288, k * 72);
+    const uint8_t* d[2];      // signatures | indices
+    int rc = stage_inputs(c, {{sigs192, n_table * 192}, {idx, offsets[k] * 4}}, nullptr, d);
+    if (!rc) rc = c->grp.d_g2_out.reserve(k * 288, k * 72);
     if (rc) return rc;
-    uint8_t *d = c->d_agg_in, *o192 = c->d_aggsig_out, *o96 = o192 + k * 192;
-    if (sb) HIPCHK(hipMemcpyAsync(d, sigs192, sb, hipMemcpyHostToDevice, nullptr));
-    if (n_idx) HIPCHK(hipMemcpyAsync(d + sb, idx, n_idx * 4, hipMemcpyHostToDevice, nullptr));
-    rc = aggsigs_enqueue(c, d, n_table, idx ? reinterpret_cast<const uint32_t*>(d + sb) : nullptr, offsets, k, out_sigs192 ? o192 : nullptr,
-                         out_sigs96 ? o96 : nullptr, nullptr);
+    uint8_t *o192 = c->grp.d_g2_out, *o96 = o192 + k * 192;
+    rc = aggsigs_enqueue(c, d[0], n_table, reinterpret_cast<const uint32_t*>(d[1]), offsets, k, out_sigs192 ? o192 : nullptr, out_sigs96 ? o96 : nullptr, nullptr);
     if (rc) return rc;
     if (out_sigs192) HIPCHK(hipMemcpyAsync(out_sigs192, o192, k * 192, hipMemcpyDeviceToHost, nullptr));
     if (out_sigs96) HIPCHK(hipMemcpyAsync(out_sigs96, o96, k * 96, hipMemcpyDeviceToHost, nullptr));
-    return aggsets_status(c, k, status, nullptr);
+    return grouped_status(c, k, status, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1951,11 +1954,10 @@ extern "C" int mi355_bls_aggregate_signature_sets(mi355_bls_ctx* c, const void* 
 // in one device pass.  The addressing is aggregate_signature_sets' (a table of blst_p2_affine images, optional indices, k + 1 host offsets);
 // ids holds 32 bytes per sequence position.  The call runs in the chunks of plan.hpp recover_chunk_end: per chunk k_recover_mul (a lane per
 // member), the segmented sum (k_combsets_g2_sum at every level, level 0 over the products) and k_recover_finish, all on the caller's stream,
-// then the chunk's status bytes come back (its synchronisation: the host table of the next chunk reuses the vector).  It shares combine_sets'
-// product and partial buffers (d_comb_g2, d_comb_part2) and aggregate_sets' table, flag and status buffers.
+// then the chunk's status bytes come back (its synchronisation: the host table of the next chunk reuses the vector).
 // ------------------------------------------------------------------------------------------
 static_assert(sizeof(plan::rec_item) == 16, "k_recover_mul loads an item as one uint4");
-// h_out192 / h_out96: the host form - the device outputs are then the chunk's own (d_aggsig_out) and copied out chunk by chunk
+// h_out192 / h_out96: the host form - the device outputs are then the chunk's own (grp.d_g2_out) and copied out chunk by chunk
 static int recover_run(mi355_bls_ctx* c, const uint8_t* d_sigs, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k, const uint8_t* d_ids,
                        uint8_t* d_out192, uint8_t* d_out96, uint8_t* h_out192, uint8_t* h_out96, uint8_t* status, hipStream_t st) {
     const bool host_out = h_out192 || h_out96;
@@ -1970,13 +1972,10 @@ static int recover_run(mi355_bls_ctx* c, const uint8_t* d_sigs, size_t n_table, 
         g_err = "recover_signature_sets: offsets decrease, or 2^32 - 1 positions or groups, or more";
         return MI355_BLS_ERR_ARG;
     }
-    if (!d_idx && offsets[k] > n_table) {
-        g_err = "recover_signature_sets: offsets[k] exceeds the number of signatures";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (!table_holds(d_idx, offsets, k, n_table, "recover_signature_sets: offsets[k] exceeds the number of signatures")) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     if (host_out) {
-        if (int rc = c->d_aggsig_out.reserve(rp.max_groups * 288, rp.max_groups * 72)) return rc;
+        if (int rc = c->grp.d_g2_out.reserve(rp.max_groups * 288, rp.max_groups * 72)) return rc;
     }
     std::vector<size_t> ro;
     int all = 1;
@@ -1987,37 +1986,33 @@ static int recover_run(mi355_bls_ctx* c, const uint8_t* d_sigs, size_t n_table, 
         const plan::aggsets_plan p = plan::aggsets_measure(ro.data(), kc);
         if (!p.ok) return MI355_BLS_ERR_ARG;           // cannot happen below 2^32 - 1 positions
         const plan::recover_sizes sz = plan::recover_sizes_for(p, m, kc);
-        c->agg_tab.resize(sz.tab / 4);
-        uint32_t* tab = c->agg_tab.data();
+        c->grp.items.resize(sz.tab / 4);
+        uint32_t* tab = c->grp.items.data();
         const size_t t_items = m * 4, t_final = t_items + p.items * 4, t_len = t_final + kc;
         plan::recover_fill(offsets, g0, g1, reinterpret_cast<plan::rec_item*>(tab));
         plan::aggsets_fill(p, ro.data(), kc, reinterpret_cast<plan::agg_item*>(tab + t_items), tab + t_final);
         for (size_t i = 0; i < kc; i++) tab[t_len + i] = (uint32_t)(ro[i + 1] - ro[i]);
-        // grown with a quarter of slack, never beyond what the largest chunk needs; the previous chunk has drained the stream
-        int rc = c->d_comb_g2.reserve(sz.prod, sz.prod / 4);
-        if (!rc) rc = c->d_comb_part2.reserve(sz.part, sz.part / 4);
-        if (!rc) rc = c->d_agg_tab.reserve(sz.tab, sz.tab / 4);
-        if (!rc) rc = c->d_agg_bad.reserve(sz.flags, sz.flags / 4);
-        if (!rc) rc = c->d_agg_status.reserve(sz.status, sz.status / 4);
+        // never beyond what the largest chunk needs; the previous chunk has drained the stream
+        int rc = c->grp.d_g2_prod.reserve(sz.prod, sz.prod / 4);
+        if (!rc) rc = c->grp.d_g2_part.reserve(sz.part, sz.part / 4);
+        if (!rc) rc = grouped_upload(c, sz.tab, sz.flags, sz.status, st);
         if (rc) return rc;
-        HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, sz.flags, st));
-        HIPCHK(hipMemcpyAsync(c->d_agg_tab, tab, sz.tab, hipMemcpyHostToDevice, st));
-        const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
+        const uint4* items = reinterpret_cast<const uint4*>(c->grp.d_items.p);
+        uint32_t *prod = c->grp.d_g2_prod, *part = c->grp.d_g2_part;
         if (m)
             k_recover_mul<<<plan::waves_for((uint32_t)m), WAVE, 0, st>>>(items, (uint32_t)m, reinterpret_cast<const uint32_t*>(d_sigs), n_table, d_idx,
-                                                                        reinterpret_cast<const uint32_t*>(d_ids), (uint32_t)base, c->d_comb_g2, c->d_agg_bad);
-        for (uint32_t l = 0; l < p.levels; l++) {
-            const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
-            k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + m + p.level_first[l], cnt, l == 0 ? c->d_comb_g2.p : c->d_comb_part2.p, c->d_comb_part2);
-        }
-        uint8_t* o192 = host_out ? (h_out192 ? c->d_aggsig_out.p : nullptr) : (d_out192 ? d_out192 + g0 * 192 : nullptr);
-        uint8_t* o96 = host_out ? (h_out96 ? c->d_aggsig_out.p + kc * 192 : nullptr) : (d_out96 ? d_out96 + g0 * 96 : nullptr);
-        k_recover_finish<<<plan::waves_for((uint32_t)kc), WAVE, 0, st>>>(c->d_agg_tab + t_final, c->d_agg_tab + t_len, (uint32_t)kc, c->d_comb_part2, c->d_agg_bad,
-                                                                        reinterpret_cast<uint32_t*>(o192), reinterpret_cast<uint32_t*>(o96), c->d_agg_status);
+                                                                        reinterpret_cast<const uint32_t*>(d_ids), (uint32_t)base, prod, c->grp.d_flag);
+        launch_levels(p, items + m,      // one kernel at every level: level 0 sums the products, the levels above it the partials
+                      [&](const uint4* it, uint32_t cnt) { k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, prod, part); },
+                      [&](const uint4* it, uint32_t cnt) { k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, part, part); });
+        uint8_t* o192 = host_out ? (h_out192 ? c->grp.d_g2_out.p : nullptr) : (d_out192 ? d_out192 + g0 * 192 : nullptr);
+        uint8_t* o96 = host_out ? (h_out96 ? c->grp.d_g2_out.p + kc * 192 : nullptr) : (d_out96 ? d_out96 + g0 * 96 : nullptr);
+        k_recover_finish<<<plan::waves_for((uint32_t)kc), WAVE, 0, st>>>(c->grp.d_items + t_final, c->grp.d_items + t_len, (uint32_t)kc, c->grp.d_g2_part, c->grp.d_flag,
+                                                                        reinterpret_cast<uint32_t*>(o192), reinterpret_cast<uint32_t*>(o96), c->grp.d_status);
         HIPCHK(hipGetLastError());
         if (h_out192) HIPCHK(hipMemcpyAsync(h_out192 + g0 * 192, o192, kc * 192, hipMemcpyDeviceToHost, st));
         if (h_out96) HIPCHK(hipMemcpyAsync(h_out96 + g0 * 96, o96, kc * 96, hipMemcpyDeviceToHost, st));
-        const int ok = aggsets_status(c, kc, status + g0, st);
+        const int ok = grouped_status(c, kc, status + g0, st);
         if (ok < 0) return ok;
         all &= ok;
         g0 = g1;
@@ -2037,16 +2032,10 @@ extern "C" int mi355_bls_recover_signature_sets(mi355_bls_ctx* c, const void* si
     if (k == 0) return 0;
     if (!sigs192 || !offsets || !ids32 || !status || (!out_sigs192 && !out_sigs96) || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    // signatures | ids | indices -> d_agg_in (every part 4-byte aligned)
-    const size_t n_idx = idx ? offsets[k] : 0, sb = n_table * 192, ib = offsets[k] * 32, all = sb + ib + n_idx * 4 + 4;
-    HIPCHK(hipSetDevice(c->device));
-    if (int rc = c->d_agg_in.reserve(all, all / 4)) return rc;
-    uint8_t* d = c->d_agg_in;
-    if (sb) HIPCHK(hipMemcpyAsync(d, sigs192, sb, hipMemcpyHostToDevice, nullptr));
-    if (ib) HIPCHK(hipMemcpyAsync(d + sb, ids32, ib, hipMemcpyHostToDevice, nullptr));
-    if (n_idx) HIPCHK(hipMemcpyAsync(d + sb + ib, idx, n_idx * 4, hipMemcpyHostToDevice, nullptr));
-    return recover_run(c, d, n_table, idx ? reinterpret_cast<const uint32_t*>(d + sb + ib) : nullptr, offsets, k, d + sb, nullptr, nullptr, (uint8_t*)out_sigs192,
-                       (uint8_t*)out_sigs96, status, nullptr);
+    const uint8_t* d[3];      // signatures | ids | indices
+    if (int rc = stage_inputs(c, {{sigs192, n_table * 192}, {ids32, offsets[k] * 32}, {idx, offsets[k] * 4}}, nullptr, d)) return rc;
+    return recover_run(c, d[0], n_table, reinterpret_cast<const uint32_t*>(d[2]), offsets, k, d[1], nullptr, nullptr, (uint8_t*)out_sigs192, (uint8_t*)out_sigs96, status,
+                       nullptr);
 }
 
 // serialize for n signatures (bls_sig_io.nim:225-234).  The device form leaves the bytes in device memory and returns when they are there.
@@ -2227,7 +2216,7 @@ extern "C" int mi355_bls_admit_keys(mi355_bls_ctx* c, const uint8_t* pks, const 
 // the plan's item tables and a finish lane (kernels.hip, csrc/combsets.hpp); the key side on the caller's stream, the signature side on
 // the context's fork stream beside it.  The scalars and the random bytes are cleared on the device before the call returns.
 // ------------------------------------------------------------------------------------------
-// combination of k > 0 groups enqueued on st: records at d_out, status bytes in c->d_agg_status
+// combination of k > 0 groups enqueued on st: records at d_out, status bytes in c->grp.d_status
 static int combsets_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k, const uint8_t* rnds,
                             uint8_t* d_out, hipStream_t st) {
     if (!d_sets || !offsets || !rnds || !d_out) return MI355_BLS_ERR_ARG;
@@ -2241,10 +2230,7 @@ static int combsets_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_se
         g_err = "combine_sets: offsets decrease, or more than 2^26 members or 2^32 - 2 groups";
         return MI355_BLS_ERR_ARG;
     }
-    if (!d_idx && offsets[k] > n_sets) {
-        g_err = "combine_sets: offsets[k] exceeds the number of records";
-        return MI355_BLS_ERR_ARG;
-    }
+    if (!table_holds(d_idx, offsets, k, n_sets, "combine_sets: offsets[k] exceeds the number of records")) return MI355_BLS_ERR_ARG;
     const size_t N = cp.members;
     std::vector<size_t> rel(k + 1);
     for (size_t g = 0; g <= k; g++) rel[g] = offsets[g] - cp.lo;
@@ -2255,31 +2241,28 @@ static int combsets_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_se
     }
     HIPCHK(hipSetDevice(c->device));
     // item table | final_of | first position | length of every group
-    c->agg_tab.resize(p.items * 4 + 3 * k);
-    uint32_t *h_final = c->agg_tab.data() + p.items * 4, *h_first = h_final + k, *h_len = h_first + k;
-    plan::aggsets_fill(p, rel.data(), k, reinterpret_cast<plan::agg_item*>(c->agg_tab.data()), h_final);
+    c->grp.items.resize(p.items * 4 + 3 * k);
+    uint32_t *h_final = c->grp.items.data() + p.items * 4, *h_first = h_final + k, *h_len = h_first + k;
+    plan::aggsets_fill(p, rel.data(), k, reinterpret_cast<plan::agg_item*>(c->grp.items.data()), h_final);
     for (size_t g = 0; g < k; g++) h_first[g] = (uint32_t)rel[g], h_len[g] = (uint32_t)(rel[g + 1] - rel[g]);
-    const size_t n1 = N ? N : 1, it1 = p.items ? p.items : 1, tb = c->agg_tab.size() * 4, stride = (n1 + 63) / 64 * 64, tcap = cp.chunk_cap ? cp.chunk_cap : WAVE;
-    int rc = c->d_agg_part.reserve(it1 * (size_t)G1W * 4, it1 * (size_t)G1W);
-    if (!rc) rc = c->d_comb_part2.reserve(it1 * (size_t)G2W * 4, it1 * (size_t)G2W);
-    if (!rc) rc = c->d_agg_tab.reserve(tb, tb / 4);
-    if (!rc) rc = c->d_agg_bad.reserve(k * 4, k);
-    if (!rc) rc = c->d_agg_status.reserve(k, k / 4);
+    const size_t n1 = N ? N : 1, it1 = p.items ? p.items : 1, stride = (n1 + 63) / 64 * 64, tcap = cp.chunk_cap ? cp.chunk_cap : WAVE;
+    int rc = c->grp.d_g1_part.reserve(it1 * (size_t)G1W * 4, it1 * (size_t)G1W);
+    if (!rc) rc = c->grp.d_g2_part.reserve(it1 * (size_t)G2W * 4, it1 * (size_t)G2W);
     if (!rc) rc = c->d_comb_s.reserve(n1 * 8, n1 * 2);
     if (!rc) rc = c->d_comb_rnd.reserve(k * 32, k * 8);
     if (!rc) rc = c->d_comb_P.reserve(stride * 3 * 64, stride * 48);
-    if (!rc) rc = c->d_comb_g2.reserve(n1 * (size_t)G2W * 4, n1 * (size_t)G2W);
+    if (!rc) rc = c->grp.d_g2_prod.reserve(n1 * (size_t)G2W * 4, n1 * (size_t)G2W);
     if (!rc) rc = c->d_comb_pktab.reserve(tcap * PKTAB_BYTES, 0);
     if (!rc) rc = c->d_comb_g2tab.reserve(tcap * 8 * 6 * 64, 0);
     if (!rc) rc = c->d_comb_pkflag.reserve(4, 0);
     if (!rc && d_idx) rc = c->d_comb_gather.reserve(n1 * 320, n1 * 80);
+    if (!rc) rc = grouped_upload(c, c->grp.items.size() * 4, k * 4, k, st);
     if (rc) return rc;
     const size_t P_stride = c->d_comb_P.bytes / (3 * 64), g2tcap = c->d_comb_g2tab.bytes / (8 * 6 * 64);      // what the buffers hold (they may be larger than this call needs)
-    HIPCHK(hipMemsetAsync(c->d_agg_bad, 0, k * 4, st));
-    HIPCHK(hipMemcpyAsync(c->d_agg_tab, c->agg_tab.data(), tb, hipMemcpyHostToDevice, st));
+    uint32_t *g1_part = c->grp.d_g1_part, *g2_part = c->grp.d_g2_part;
     HIPCHK(hipMemcpyAsync(c->d_comb_rnd, rnds, k * 32, hipMemcpyHostToDevice, st));
-    const uint4* items = reinterpret_cast<const uint4*>(c->d_agg_tab.p);
-    const uint32_t *d_final = c->d_agg_tab + p.items * 4, *d_first = d_final + k, *d_len = d_first + k;
+    const uint4* items = reinterpret_cast<const uint4*>(c->grp.d_items.p);
+    const uint32_t *d_final = c->grp.d_items + p.items * 4, *d_first = d_final + k, *d_len = d_first + k;
     const uint32_t* idx = d_idx ? d_idx + cp.lo : nullptr;
     const uint32_t* recs = reinterpret_cast<const uint32_t*>(d_sets) + (d_idx ? 0 : cp.lo * 80);
     const uint32_t k32 = (uint32_t)k, N32 = (uint32_t)N;
@@ -2312,12 +2295,11 @@ static int combsets_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_se
         }
         for (size_t a = 0; a < N; a += plan::COMB_MUL_CHUNK) {
             const uint32_t m = (uint32_t)(N - a < plan::COMB_MUL_CHUNK ? N - a : plan::COMB_MUL_CHUNK);
-            k_combsets_g2mul<<<plan::waves_for(m), WAVE, 0, s2>>>(recs + a * 80, m, c->d_comb_s + a, c->d_comb_g2tab, g2tcap, c->d_comb_g2 + a * (size_t)G2W);
+            k_combsets_g2mul<<<plan::waves_for(m), WAVE, 0, s2>>>(recs + a * 80, m, c->d_comb_s + a, c->d_comb_g2tab, g2tcap, c->grp.d_g2_prod + a * (size_t)G2W);
         }
-        for (uint32_t l = 0; l < p.levels; l++) {
-            const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
-            k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, s2>>>(items + p.level_first[l], cnt, l == 0 ? c->d_comb_g2.p : c->d_comb_part2.p, c->d_comb_part2);
-        }
+        launch_levels(p, items,      // one kernel at every level: level 0 sums the products, the levels above it the partials
+                      [&](const uint4* it, uint32_t cnt) { k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, s2>>>(it, cnt, c->grp.d_g2_prod, g2_part); },
+                      [&](const uint4* it, uint32_t cnt) { k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, s2>>>(it, cnt, g2_part, g2_part); });
         if (s2 != st) HIPCHK(hipEventRecord(c->ev[2], s2));
         HIPCHK(hipMemsetAsync(c->d_comb_pkflag, 0, 4, st));
         for (size_t a = 0; a < N; a += plan::COMB_MUL_CHUNK) {
@@ -2325,39 +2307,28 @@ static int combsets_enqueue(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_se
             k_pkmul<<<plan::waves_for(m), WAVE, 0, st>>>(reinterpret_cast<const uint8_t*>(recs + a * 80), m, c->d_comb_s + a, c->d_comb_P + a, P_stride, c->d_comb_pkflag,
                                                          c->d_comb_pktab);
         }
-        for (uint32_t l = 0; l < p.levels; l++) {
-            const uint32_t cnt = (uint32_t)(p.level_first[l + 1] - p.level_first[l]);
-            if (l == 0) k_combsets_g1_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(items, cnt, c->d_comb_P, P_stride, recs, idx, n_sets, d_first, c->d_agg_part, c->d_agg_bad);
-            else k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(items + p.level_first[l], cnt, c->d_agg_part);
-        }
+        launch_levels(p, items,
+                      [&](const uint4* it, uint32_t cnt) {
+                          k_combsets_g1_l0<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, c->d_comb_P, P_stride, recs, idx, n_sets, d_first, g1_part, c->grp.d_flag);
+                      },
+                      [&](const uint4* it, uint32_t cnt) { k_aggsets_ln<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, g1_part); });
         if (s2 != st) HIPCHK(hipStreamWaitEvent(st, c->ev[2], 0));
     }
-    k_combsets_finish<<<plan::waves_for(k32), WAVE, 0, st>>>(d_final, d_first, d_len, k32, c->d_agg_part, c->d_comb_part2, c->d_agg_bad, recs, idx, n_sets,
-                                                             reinterpret_cast<uint32_t*>(d_out), c->d_agg_status);
+    k_combsets_finish<<<plan::waves_for(k32), WAVE, 0, st>>>(d_final, d_first, d_len, k32, c->grp.d_g1_part, c->grp.d_g2_part, c->grp.d_flag, recs, idx, n_sets,
+                                                             reinterpret_cast<uint32_t*>(d_out), c->grp.d_status);
     HIPCHK(hipGetLastError());
     // the scalars are blinding material: nothing of them stays on the device
     if (N) HIPCHK(hipMemsetAsync(c->d_comb_s, 0, N * 8, st));
     HIPCHK(hipMemsetAsync(c->d_comb_rnd, 0, k * 32, st));
     return 0;
 }
-// the status bytes back (the call's synchronisation): 1 when every group gave a record; the host's chains go with it
-static int combsets_status(mi355_bls_ctx* c, size_t k, uint8_t* status, hipStream_t st) {
-    const int rc = aggsets_status(c, k, status, st);
-    std::fill(c->comb_s_h.begin(), c->comb_s_h.end(), 0);
-    return rc;
-}
-// host records (and indices) -> d_agg_in
+// host records (and indices) -> the staged inputs
 static int combsets_stage(mi355_bls_ctx* c, const void* sets, size_t n_sets, const uint32_t* idx, const size_t* offsets, size_t k, hipStream_t st,
                           const uint8_t** d_sets, const uint32_t** d_idx) {
     if (!sets || !offsets || !agg_offsets_ok(offsets, k)) return MI355_BLS_ERR_ARG;
-    const size_t n_idx = idx ? offsets[k] : 0, sb = n_sets * 320, all = sb + n_idx * 4 + 4;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->d_agg_in.reserve(all, all / 4);
-    if (rc) return rc;
-    uint8_t* d = c->d_agg_in;
-    if (sb) HIPCHK(hipMemcpyAsync(d, sets, sb, hipMemcpyHostToDevice, st));
-    if (n_idx) HIPCHK(hipMemcpyAsync(d + sb, idx, n_idx * 4, hipMemcpyHostToDevice, st));
-    *d_sets = d, *d_idx = idx ? reinterpret_cast<const uint32_t*>(d + sb) : nullptr;
+    const uint8_t* d[2];
+    if (int rc = stage_inputs(c, {{sets, n_sets * 320}, {idx, offsets[k] * 4}}, st, d)) return rc;
+    *d_sets = d[0], *d_idx = reinterpret_cast<const uint32_t*>(d[1]);
     return 0;
 }
 extern "C" int mi355_bls_combine_sets_device(mi355_bls_ctx* c, const void* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k,
@@ -2367,7 +2338,7 @@ extern "C" int mi355_bls_combine_sets_device(mi355_bls_ctx* c, const void* d_set
     if (!status) return MI355_BLS_ERR_ARG;
     int rc = combsets_enqueue(c, (const uint8_t*)d_sets, n_sets, d_idx, offsets, k, rnds, (uint8_t*)d_out_records, (hipStream_t)stream);
     if (rc) return rc;
-    return combsets_status(c, k, status, (hipStream_t)stream);
+    return grouped_status(c, k, status, (hipStream_t)stream);
 }
 extern "C" int mi355_bls_combine_sets(mi355_bls_ctx* c, const void* sets, size_t n_sets, const uint32_t* idx, const size_t* offsets, size_t k, const uint8_t* rnds,
                                       void* out_records, uint8_t* status) {
@@ -2376,30 +2347,19 @@ extern "C" int mi355_bls_combine_sets(mi355_bls_ctx* c, const void* sets, size_t
     if (!out_records || !status) return MI355_BLS_ERR_ARG;
     const uint8_t* d_sets;
     const uint32_t* d_idx;
-    int rc = combsets_stage(c, sets, n_sets, idx, offsets, k, nullptr, &d_sets, &d_idx);
-    if (!rc) rc = c->d_agg_rec.reserve(k * 320, k * 80);
-    if (!rc) rc = combsets_enqueue(c, d_sets, n_sets, d_idx, offsets, k, rnds, c->d_agg_rec, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out_records, c->d_agg_rec, k * 320, hipMemcpyDeviceToHost, nullptr));
-    return combsets_status(c, k, status, nullptr);
+    if (int rc = combsets_stage(c, sets, n_sets, idx, offsets, k, nullptr, &d_sets, &d_idx)) return rc;
+    return records_to_host(c, k, out_records, status,
+                           [&](uint8_t* d_out, hipStream_t st) { return combsets_enqueue(c, d_sets, n_sets, d_idx, offsets, k, rnds, d_out, st); });
 }
-// batchVerify over the k combined records: a group that gives no record (any status but 0) ends the call with 0 before any verification pass
-static int combsets_batch(mi355_bls_ctx* c, const uint8_t* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k, const uint8_t* rnds,
-                          const uint8_t rnd[32], hipStream_t st) {
-    int rc = c->d_agg_rec.reserve(k * 320, k * 80);
-    if (!rc) rc = combsets_enqueue(c, d_sets, n_sets, d_idx, offsets, k, rnds, c->d_agg_rec, st);
-    if (rc) return rc;
-    c->agg_status_h.resize(k);
-    rc = combsets_status(c, k, c->agg_status_h.data(), st);
-    if (rc != 1) return rc;
-    return verify_common(c, c->d_agg_rec, nullptr, k, rnd, 0, st);
-}
+// batchVerify over the k combined records (records_batch)
 extern "C" int mi355_bls_batch_verify_combined_device(mi355_bls_ctx* c, const void* d_sets, size_t n_sets, const uint32_t* d_idx, const size_t* offsets, size_t k,
                                                       const uint8_t* rnds, const uint8_t rnd[32], void* stream) {
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if (k == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    return combsets_batch(c, (const uint8_t*)d_sets, n_sets, d_idx, offsets, k, rnds, rnd, (hipStream_t)stream);
+    return records_batch(c, k, rnd, (hipStream_t)stream, [&](uint8_t* d_out, hipStream_t st) {
+        return combsets_enqueue(c, (const uint8_t*)d_sets, n_sets, d_idx, offsets, k, rnds, d_out, st);
+    });
 }
 extern "C" int mi355_bls_batch_verify_combined(mi355_bls_ctx* c, const void* sets, size_t n_sets, const uint32_t* idx, const size_t* offsets, size_t k,
                                                const uint8_t* rnds, const uint8_t rnd[32]) {
@@ -2407,9 +2367,8 @@ extern "C" int mi355_bls_batch_verify_combined(mi355_bls_ctx* c, const void* set
     if (k == 0) return 0;
     const uint8_t* d_sets;
     const uint32_t* d_idx;
-    int rc = combsets_stage(c, sets, n_sets, idx, offsets, k, nullptr, &d_sets, &d_idx);
-    if (rc) return rc;
-    return combsets_batch(c, d_sets, n_sets, d_idx, offsets, k, rnds, rnd, nullptr);
+    if (int rc = combsets_stage(c, sets, n_sets, idx, offsets, k, nullptr, &d_sets, &d_idx)) return rc;
+    return records_batch(c, k, rnd, nullptr, [&](uint8_t* d_out, hipStream_t st) { return combsets_enqueue(c, d_sets, n_sets, d_idx, offsets, k, rnds, d_out, st); });
 }
 // Host only, no GPU: the records of a flat batch grouped by their 32-byte message, stably - groups in the order their message first appears,
 // members in input order.  idx: n positions, offsets: n + 1 entries of which k + 1 are written.

@@ -1045,5 +1045,26 @@ inline grouped_plan slice_for_grouped(uint32_t slots, bool coop, bool have_side,
     return g;
 }
 
+// The host inputs of a grouped call in ONE staging buffer: the parts in the order given, each at the next multiple of 4 bytes behind the one
+// before (the kernels load words, and hand a part on as a table of its own).  A part of zero bytes takes no room.  total: what to reserve -
+// the end of the last part and a word, so that the word a byte-aligned last part ends in lies inside and an empty call still has an address.
+constexpr size_t PACK_PARTS_MAX = 6;
+struct pack_layout {
+    size_t at[PACK_PARTS_MAX];
+    size_t total;
+};
+// n <= PACK_PARTS_MAX; more parts than the layout can name give total == 0, which no call with parts has
+inline pack_layout pack_for(const size_t* bytes, size_t n) {
+    pack_layout p{};
+    if (n > PACK_PARTS_MAX) return p;
+    size_t end = 0;
+    for (size_t i = 0; i < n; i++) {
+        p.at[i] = (end + 3) & ~(size_t)3;
+        end = p.at[i] + bytes[i];
+    }
+    p.total = end + 4;
+    return p;
+}
+
 }  // namespace plan
 #endif
