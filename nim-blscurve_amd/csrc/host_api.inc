@@ -5,6 +5,7 @@
 #include "plan.hpp"      // which kernel, what grid, which stream: every size decision of this file
 #include "devres.hpp"    // the owners of device buffers, events, streams and pinned memory
 using plan::SIG_SLOTS_MAX;
+namespace cols = plan::cols;      // the columns of the per-row calls' staging
 static_assert(plan::WAVE == (uint32_t)WAVE && plan::N_LINES == (uint32_t)N_LINES, "plan.hpp restates the wave size and the Miller loop's step count");
 static_assert(plan::FP_WORDS == (uint32_t)FPW && plan::G1_WORDS == (uint32_t)G1W && plan::G2_WORDS == (uint32_t)G2W && plan::F12_WORDS == (uint32_t)F12W,
               "plan.hpp restates the words of an element in device buffers");
@@ -87,7 +88,7 @@ struct mi355_bls_ctx {
     dev_buf<uint32_t> d_agg;
     dev_buf<uint32_t> d_agg1;        // G1 aggregate (blst_p1 image)
     dev_buf<uint8_t> d_msg;          // message (<= 4096 B) + signature staging
-    dev_buf<uint8_t> d_comp;         // compressed wire-format staging: cap x (48 + 32 + 96) bytes
+    dev_buf<uint8_t> d_comp;         // staging of the per-row calls: cap_io rows of plan::ROW_BYTES, in columns (plan.hpp cols, col_at)
     dev_buf<uint8_t> d_status;       // per-tuple deserialisation status
     dev_event ev_deser0, ev_deser1;
     float deser_ms = 0.f;
@@ -356,7 +357,7 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     c->mstride = sz.mstride;
     int rc = 0;                                    // the first failure: nothing is created behind it
     const auto alloc = [&rc](auto& buf, size_t bytes) { rc = rc ? rc : buf.alloc(bytes); };
-    alloc(c->d_sets, max_sets * 320);
+    alloc(c->d_sets, max_sets * plan::ROW_BYTES);   // records, or rows of staging columns (plan.hpp cols)
     alloc(c->d_rnd, 32);
     alloc(c->d_r, c->stride * 8);
     alloc(c->d_H, c->stride * 6 * 64);
@@ -371,7 +372,7 @@ static int ctx_build(mi355_bls_ctx* c, int device, size_t max_sets) {
     alloc(c->d_agg, 288);
     alloc(c->d_agg1, 144);
     alloc(c->d_msg, 4096 + 192 + 64 + 288);      // message | affine signature | pad | Jacobian signature (AggregateSignature overloads)
-    alloc(c->d_comp, max_sets * 320);          // wire-format staging: keys (<= 96 B) | messages (32 B) | signatures (<= 192 B)
+    alloc(c->d_comp, max_sets * plan::ROW_BYTES);   // rows of staging columns
     alloc(c->d_status, max_sets);
     alloc(c->d_lpart, sz.lpart_words * 4);         // per-lane partial products of k_lineprod (+ k_fold's first-level results)
     alloc(c->d_L, (size_t)N_LINES * F12W * 4);
@@ -425,8 +426,8 @@ static int io_reserve(mi355_bls_ctx* c, size_t n) {
     // device-resident input never come through here and would otherwise launch on null pointers)
     dev_buf<uint8_t> sets, comp, status;
     dev_buf<uint64_t> r;
-    int rc = sets.alloc(want * 320);
-    if (!rc) rc = comp.alloc(want * 320);
+    int rc = sets.alloc(want * plan::ROW_BYTES);
+    if (!rc) rc = comp.alloc(want * plan::ROW_BYTES);
     if (!rc) rc = status.alloc(want);
     if (!rc) rc = r.alloc((want > c->stride ? want : c->stride) * 8);
     if (rc) return rc;
@@ -440,6 +441,33 @@ static int io_reserve(mi355_bls_ctx* c, size_t n) {
     c->d_sets.swap(sets), c->d_comp.swap(comp), c->d_status.swap(status), c->d_r.swap(r);      // the old ones go with the locals
     c->cap_io = want;
     return 0;
+}
+// where a column of the staging layout (plan.hpp cols) starts: it moves whenever io_reserve grows the buffers, so it is asked for after that
+static uint8_t* col_at(const mi355_bls_ctx* c, plan::row_col col) { return (col.buf == plan::ROW_SETS ? c->d_sets : c->d_comp) + c->cap_io * col.start; }
+// The status pass a per-row call ends in, on `st`: [ev0,] the flag words cleared, what `enqueue` launches, [ev1,] then d_flags, `bytes` from d_also to `also`
+// and the n status bytes (each where the caller asked) to the host, and the stream drained.  1: every row's status is 0; 0: some row failed; < 0: an error.
+template <class Enqueue>
+static int status_pass(mi355_bls_ctx* c, hipStream_t st, size_t n, uint8_t* status, hipEvent_t ev0, hipEvent_t ev1, Enqueue enqueue, void* also = nullptr,
+                       const void* d_also = nullptr, size_t bytes = 0) {
+    if (ev0) HIPCHK(hipEventRecord(ev0, st));
+    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
+    enqueue();
+    HIPCHK(hipGetLastError());
+    if (ev1) HIPCHK(hipEventRecord(ev1, st));
+    uint32_t fl[4];
+    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
+    if (also) HIPCHK(hipMemcpyAsync(also, d_also, bytes, hipMemcpyDeviceToHost, st));
+    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return fl[2] ? 0 : 1;
+}
+// the timings of a call that was one stage, between ev[0] and ev[1], and is waited for: the stage in slot 0 and the total, 0 elsewhere; rc: the stage's result
+static int one_stage_timings(mi355_bls_ctx* c, int rc = 0) {
+    if (rc < 0) return rc;
+    for (int i = 0; i < 8; i++) c->timings[i] = 0;
+    HIPCHK(hipEventElapsedTime(&c->timings[0], c->ev[0], c->ev[1]));
+    c->timings[7] = c->timings[0];
+    return rc;
 }
 
 // 320-byte records -> d_M: the two mapped points of every message (two lanes per message)
@@ -1348,16 +1376,16 @@ extern "C" int mi355_bls_batch_verify_locate_device(mi355_bls_ctx* c, const void
 // buffer (k_pop_records); the per-set pass, the blinded batch pass and the locate form then run on them with `pop` set, i.e. with the PoP
 // forms of the hash-map kernels and nothing else changed: slicing, stages, verdict bytes as for SignatureSets.
 // ------------------------------------------------------------------------------------------
-// keys | proofs (host memory when `host`, staged through d_comp; else device memory) -> n records at c->d_sets, enqueued on `st`
+// keys | proofs (host memory when `host`, staged through their columns; else device memory) -> n records at c->d_sets, enqueued on `st`
 static int pop_stage(mi355_bls_ctx* c, const void* pks, const void* proofs, size_t n, bool host, hipStream_t st) {
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     if (int rc = io_reserve(c, n)) return rc;
     HIPCHK(hipSetDevice(c->device));
     const uint8_t *dk = (const uint8_t*)pks, *dp = (const uint8_t*)proofs;
     if (host) {
-        HIPCHK(hipMemcpyAsync(c->d_comp, pks, n * 96, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(c->d_comp + c->cap_io * 96, proofs, n * 192, hipMemcpyHostToDevice, st));
-        dk = c->d_comp, dp = c->d_comp + c->cap_io * 96;
+        HIPCHK(hipMemcpyAsync(col_at(c, cols::POP_KEYS), pks, n * 96, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(col_at(c, cols::POP_PROOFS), proofs, n * 192, hipMemcpyHostToDevice, st));
+        dk = col_at(c, cols::POP_KEYS), dp = col_at(c, cols::POP_PROOFS);
     }
     k_pop_records<<<plan::pop_records_grid(n), 256, 0, st>>>(reinterpret_cast<const uint32_t*>(dk), reinterpret_cast<const uint32_t*>(dp), n,
                                                              reinterpret_cast<uint32_t*>(c->d_sets.p));
@@ -1401,30 +1429,44 @@ extern "C" int mi355_bls_batch_pop_verify_locate_device(mi355_bls_ctx* c, const 
                                                         uint8_t verdicts[], void* stream) {
     return pop_batch(c, d_pks96, d_proofs192, n, rnd, verdicts, true, false, (hipStream_t)stream);
 }
-// rawFromPublic / serialize for n keys (bls_sig_io.nim:203-211).  The device form leaves the bytes in device memory and returns when they are there.
-extern "C" int mi355_bls_compress_public_keys_device(mi355_bls_ctx* c, const void* d_pks96, size_t n, void* d_out48, void* stream) {
+// The two compressors: rawFromPublic / serialize for n keys (bls_sig_io.nim:203-211), serialize for n signatures (:225-234).  The device form leaves the
+// bytes in device memory and returns when they are there.  aligned: an input or output off a multiple of 4 bytes is refused (the signatures' is, the keys' not).
+template <class In>
+static int compress_device(mi355_bls_ctx* c, void (*kernel)(const In*, uint32_t, uint32_t*), bool aligned, const void* d_in, size_t n, void* d_out, hipStream_t st) {
     if (!c) return MI355_BLS_ERR_ARG;
     if (n == 0) return 0;
-    if (!d_pks96 || !d_out48 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (!d_in || !d_out || n > plan::POP_MAX_KEYS || (aligned && (((uintptr_t)d_in | (uintptr_t)d_out) & 3))) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    k_compress_pks<<<plan::waves_for((uint32_t)n), WAVE, 0, (hipStream_t)stream>>>((const uint8_t*)d_pks96, (uint32_t)n, (uint32_t*)d_out48);
+    kernel<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>((const In*)d_in, (uint32_t)n, (uint32_t*)d_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
-extern "C" int mi355_bls_compress_public_keys(mi355_bls_ctx* c, const void* pks96, size_t n, uint8_t out48[]) {
+static int compress_host(mi355_bls_ctx* c, int (*device_form)(mi355_bls_ctx*, const void*, size_t, void*, void*), plan::row_col in_col, plan::row_col out_col,
+                         const void* in, size_t n, uint8_t* out) {
     if (!c) return MI355_BLS_ERR_ARG;
     if (n == 0) return 0;
-    if (!pks96 || !out48 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+    if (!in || !out || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     if (int rc = io_reserve(c, n)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_comp, pks96, n * 96, hipMemcpyHostToDevice, nullptr));
-    int rc = mi355_bls_compress_public_keys_device(c, c->d_comp, n, c->d_comp + c->cap_io * 96, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out48, c->d_comp + c->cap_io * 96, n * 48, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpyAsync(col_at(c, in_col), in, n * in_col.width, hipMemcpyHostToDevice, nullptr));
+    if (int rc = device_form(c, col_at(c, in_col), n, col_at(c, out_col), nullptr)) return rc;
+    HIPCHK(hipMemcpy(out, col_at(c, out_col), n * out_col.width, hipMemcpyDeviceToHost));
     return 0;
+}
+extern "C" int mi355_bls_compress_public_keys_device(mi355_bls_ctx* c, const void* d_pks96, size_t n, void* d_out48, void* stream) {
+    return compress_device(c, k_compress_pks, false, d_pks96, n, d_out48, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_compress_public_keys(mi355_bls_ctx* c, const void* pks96, size_t n, uint8_t out48[]) {
+    return compress_host(c, mi355_bls_compress_public_keys_device, cols::CPK_IN, cols::CPK_OUT, pks96, n, out48);
+}
+extern "C" int mi355_bls_compress_signatures_device(mi355_bls_ctx* c, const void* d_sigs192, size_t n, void* d_out96, void* stream) {
+    return compress_device(c, k_compress_sigs, true, d_sigs192, n, d_out96, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_compress_signatures(mi355_bls_ctx* c, const void* sigs192, size_t n, uint8_t out96[]) {
+    return compress_host(c, mi355_bls_compress_signatures_device, cols::CSIG_IN, cols::CSIG_OUT, sigs192, n, out96);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2038,98 +2080,50 @@ extern "C" int mi355_bls_recover_signature_sets(mi355_bls_ctx* c, const void* si
                        nullptr);
 }
 
-// serialize for n signatures (bls_sig_io.nim:225-234).  The device form leaves the bytes in device memory and returns when they are there.
-extern "C" int mi355_bls_compress_signatures_device(mi355_bls_ctx* c, const void* d_sigs192, size_t n, void* d_out96, void* stream) {
-    if (!c) return MI355_BLS_ERR_ARG;
-    if (n == 0) return 0;
-    if (!d_sigs192 || !d_out96 || n > plan::POP_MAX_KEYS || (((uintptr_t)d_sigs192 | (uintptr_t)d_out96) & 3)) return MI355_BLS_ERR_ARG;
+// The two decoders, k_deser's halves: Signature.fromBytes (bls_sig_io.nim:42-58) for n signatures without key or message, PublicKey.fromBytes (:81-121)
+// for n keys without signature or message.  The device form leaves the images in device memory (n x 192 bytes; n x 96, the key table every
+// table-addressed call takes) and brings the status bytes to the host; 1 when every status is 0.  refused: the other decoder's DESER_F_* bit.
+using deser_kernel = void (*)(const uint8_t*, uint32_t, uint32_t, uint32_t*, uint8_t*, uint32_t*);
+static int deser_rows_device(mi355_bls_ctx* c, deser_kernel kernel, uint32_t refused, const void* d_wire, size_t n, uint32_t dflags, void* d_out, uint8_t* status,
+                             hipStream_t st) {
+    if (!c || dflags > 7 || (dflags & refused)) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 1;
+    if (!d_wire || !d_out || n > plan::POP_MAX_KEYS || ((uintptr_t)d_out & 3)) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    if (int rc = io_reserve(c, n)) return rc;                     // the status bytes' device buffer
     HIPCHK(hipSetDevice(c->device));
-    k_compress_sigs<<<plan::waves_for((uint32_t)n), WAVE, 0, (hipStream_t)stream>>>((const uint32_t*)d_sigs192, (uint32_t)n, (uint32_t*)d_out96);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    return 0;
+    return status_pass(c, st, n, status, nullptr, nullptr, [&] {
+        kernel<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>((const uint8_t*)d_wire, (uint32_t)n, dflags, (uint32_t*)d_out, c->d_status, c->d_flags);
+    });
 }
-extern "C" int mi355_bls_compress_signatures(mi355_bls_ctx* c, const void* sigs192, size_t n, uint8_t out96[]) {
-    if (!c) return MI355_BLS_ERR_ARG;
-    if (n == 0) return 0;
-    if (!sigs192 || !out96 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
+// wire: the column the host's bytes wait in, as wide as an image; uncompressed: the DESER_F_* bit under which a row on the wire is that wide, not half
+static int deser_rows_host(mi355_bls_ctx* c, deser_kernel kernel, uint32_t refused, plan::row_col wire, uint32_t uncompressed, const uint8_t* in, size_t n,
+                           uint32_t dflags, void* out, uint8_t* status) {
+    if (!c || dflags > 7 || (dflags & refused)) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 1;
+    if (!in || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     if (int rc = io_reserve(c, n)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_comp, sigs192, n * 192, hipMemcpyHostToDevice, nullptr));
-    int rc = mi355_bls_compress_signatures_device(c, c->d_comp, n, c->d_comp + c->cap_io * 192, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out96, c->d_comp + c->cap_io * 192, n * 96, hipMemcpyDeviceToHost));
-    return 0;
+    HIPCHK(hipMemcpyAsync(col_at(c, wire), in, n * ((dflags & uncompressed) ? wire.width : wire.width / 2), hipMemcpyHostToDevice, nullptr));
+    int rc = deser_rows_device(c, kernel, refused, col_at(c, wire), n, dflags, c->d_sets, status, nullptr);
+    if (rc < 0) return rc;
+    if (out) HIPCHK(hipMemcpy(out, c->d_sets, n * wire.width, hipMemcpyDeviceToHost));
+    return rc;
 }
-
-// Signature.fromBytes (bls_sig_io.nim:42-58) for n signatures without key or message: k_deser's signature half.  The device form leaves the
-// images in device memory (d_out_sigs192) and brings the status bytes to the host; 1 when every status is 0.
 extern "C" int mi355_bls_deserialize_signatures_device(mi355_bls_ctx* c, const void* d_sigs, size_t n, uint32_t dflags, void* d_out_sigs192, uint8_t* status,
                                                        void* stream) {
-    if (!c || dflags > 7 || (dflags & DESER_F_PK_UNCOMPRESSED)) return MI355_BLS_ERR_ARG;
-    if (n == 0) return 1;
-    if (!d_sigs || !d_out_sigs192 || n > plan::POP_MAX_KEYS || ((uintptr_t)d_out_sigs192 & 3)) return MI355_BLS_ERR_ARG;
-    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    if (int rc = io_reserve(c, n)) return rc;                     // the status bytes' device buffer
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
-    k_deser_sigs<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>((const uint8_t*)d_sigs, (uint32_t)n, dflags, (uint32_t*)d_out_sigs192, c->d_status, c->d_flags);
-    HIPCHK(hipGetLastError());
-    uint32_t fl[4];
-    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return fl[2] ? 0 : 1;
+    return deser_rows_device(c, k_deser_sigs, DESER_F_PK_UNCOMPRESSED, d_sigs, n, dflags, d_out_sigs192, status, (hipStream_t)stream);
 }
 extern "C" int mi355_bls_deserialize_signatures(mi355_bls_ctx* c, const uint8_t* sigs, size_t n, uint32_t dflags, void* out_sigs192, uint8_t* status) {
-    if (!c || dflags > 7 || (dflags & DESER_F_PK_UNCOMPRESSED)) return MI355_BLS_ERR_ARG;
-    if (n == 0) return 1;
-    if (!sigs || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
-    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    if (int rc = io_reserve(c, n)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_comp, sigs, n * ((dflags & DESER_F_SIG_UNCOMPRESSED) ? 192 : 96), hipMemcpyHostToDevice, nullptr));
-    int rc = mi355_bls_deserialize_signatures_device(c, c->d_comp, n, dflags, c->d_sets, status, nullptr);
-    if (rc < 0) return rc;
-    if (out_sigs192) HIPCHK(hipMemcpy(out_sigs192, c->d_sets, n * 192, hipMemcpyDeviceToHost));
-    return rc;
+    return deser_rows_host(c, k_deser_sigs, DESER_F_PK_UNCOMPRESSED, cols::DSIG_WIRE, DESER_F_SIG_UNCOMPRESSED, sigs, n, dflags, out_sigs192, status);
 }
-
-// PublicKey.fromBytes (bls_sig_io.nim:81-121) for n keys without signature or message: k_deser's key half.  The device form leaves the images in
-// device memory (d_out_pks96: the key table every table-addressed call takes) and brings the status bytes to the host; 1 when every status is 0.
 extern "C" int mi355_bls_deserialize_public_keys_device(mi355_bls_ctx* c, const void* d_pks, size_t n, uint32_t dflags, void* d_out_pks96, uint8_t* status,
                                                         void* stream) {
-    if (!c || dflags > 7 || (dflags & DESER_F_SIG_UNCOMPRESSED)) return MI355_BLS_ERR_ARG;
-    if (n == 0) return 1;
-    if (!d_pks || !d_out_pks96 || n > plan::POP_MAX_KEYS || ((uintptr_t)d_out_pks96 & 3)) return MI355_BLS_ERR_ARG;
-    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    if (int rc = io_reserve(c, n)) return rc;                     // the status bytes' device buffer
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
-    k_deser_pks<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>((const uint8_t*)d_pks, (uint32_t)n, dflags, (uint32_t*)d_out_pks96, c->d_status, c->d_flags);
-    HIPCHK(hipGetLastError());
-    uint32_t fl[4];
-    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return fl[2] ? 0 : 1;
+    return deser_rows_device(c, k_deser_pks, DESER_F_SIG_UNCOMPRESSED, d_pks, n, dflags, d_out_pks96, status, (hipStream_t)stream);
 }
 extern "C" int mi355_bls_deserialize_public_keys(mi355_bls_ctx* c, const uint8_t* pks, size_t n, uint32_t dflags, void* out_pks96, uint8_t* status) {
-    if (!c || dflags > 7 || (dflags & DESER_F_SIG_UNCOMPRESSED)) return MI355_BLS_ERR_ARG;
-    if (n == 0) return 1;
-    if (!pks || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
-    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    if (int rc = io_reserve(c, n)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_comp, pks, n * ((dflags & DESER_F_PK_UNCOMPRESSED) ? 96 : 48), hipMemcpyHostToDevice, nullptr));
-    int rc = mi355_bls_deserialize_public_keys_device(c, c->d_comp, n, dflags, c->d_sets, status, nullptr);
-    if (rc < 0) return rc;
-    if (out_pks96) HIPCHK(hipMemcpy(out_pks96, c->d_sets, n * 96, hipMemcpyDeviceToHost));
-    return rc;
+    return deser_rows_host(c, k_deser_pks, DESER_F_SIG_UNCOMPRESSED, cols::DPK_WIRE, DESER_F_PK_UNCOMPRESSED, pks, n, dflags, out_pks96, status);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2138,15 +2132,14 @@ extern "C" int mi355_bls_deserialize_public_keys(mi355_bls_ctx* c, const uint8_t
 // bytes come to the host; the rows both decoders accepted (plan::admit_survivors) are packed into popVerify records through a device list of
 // their row numbers (k_admit_records) and only they run the blinded batch check and, if it fails, the per-pair pass (locate_run, pop): a row
 // that does not decode costs the others nothing.  The verdicts go back to their rows (plan::admit_merge) and the refused rows whose key had
-// decoded are zeroed in the table on the device (k_admit_zero_rows).  The context's second staging buffer (cap_io x 320 B) holds, per row: 96 B decoded
-// key (host form only) | 192 B decoded proof | 4 B list entry | 1 B proof status.
+// decoded are zeroed in the table on the device (k_admit_zero_rows).  What a row holds in the staging buffers meanwhile: plan.hpp cols::ADMIT_*.
 // ------------------------------------------------------------------------------------------
 // d_pks | d_proofs: device memory, wire form; d_out: n x 96 B of device memory; the staging buffers hold n rows (io_reserve)
 static int admit_run(mi355_bls_ctx* c, const uint8_t* d_pks, const uint8_t* d_proofs, size_t n, uint32_t dflags, const uint8_t rnd[32], uint32_t* d_out,
                      uint8_t* status, hipStream_t st) {
-    uint32_t* d_prf = reinterpret_cast<uint32_t*>(c->d_comp + c->cap_io * 96);
-    uint32_t* d_list = reinterpret_cast<uint32_t*>(c->d_comp + c->cap_io * 288);
-    uint8_t* d_pst = c->d_comp + c->cap_io * 292;
+    uint32_t* d_prf = reinterpret_cast<uint32_t*>(col_at(c, cols::ADMIT_PROOFS));
+    uint32_t* d_list = reinterpret_cast<uint32_t*>(col_at(c, cols::ADMIT_LIST));
+    uint8_t* d_pst = col_at(c, cols::ADMIT_PROOF_ST);
     const uint32_t n32 = (uint32_t)n;
     std::vector<uint8_t> key_st(n), proof_st(n);
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
@@ -2198,13 +2191,13 @@ extern "C" int mi355_bls_admit_keys(mi355_bls_ctx* c, const uint8_t* pks, const 
     if (int rc = admit_args(c, pks, proofs, n, dflags, rnd, status)) return rc;
     if (int rc = io_reserve(c, n)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    // the wire forms wait in the record buffer (keys at 0, proofs at cap_io x 96): the decoders have read them before the gather writes there
-    uint8_t* d_wire = c->d_sets;
-    HIPCHK(hipMemcpyAsync(d_wire, pks, n * ((dflags & DESER_F_PK_UNCOMPRESSED) ? 96 : 48), hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(d_wire + c->cap_io * 96, proofs, n * ((dflags & DESER_F_SIG_UNCOMPRESSED) ? 192 : 96), hipMemcpyHostToDevice, nullptr));
-    const int rc = admit_run(c, d_wire, d_wire + c->cap_io * 96, n, dflags, rnd, reinterpret_cast<uint32_t*>(c->d_comp.p), status, nullptr);
+    // the wire forms wait in the record buffer: the decoders have read them before the gather writes there
+    uint8_t *d_wk = col_at(c, cols::ADMIT_WIRE_KEYS), *d_wp = col_at(c, cols::ADMIT_WIRE_PROOFS), *d_keys = col_at(c, cols::ADMIT_KEYS);
+    HIPCHK(hipMemcpyAsync(d_wk, pks, n * ((dflags & DESER_F_PK_UNCOMPRESSED) ? 96 : 48), hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(d_wp, proofs, n * ((dflags & DESER_F_SIG_UNCOMPRESSED) ? 192 : 96), hipMemcpyHostToDevice, nullptr));
+    const int rc = admit_run(c, d_wk, d_wp, n, dflags, rnd, reinterpret_cast<uint32_t*>(d_keys), status, nullptr);
     if (rc < 0) return rc;
-    if (out_pks96) HIPCHK(hipMemcpy(out_pks96, c->d_comp, n * 96, hipMemcpyDeviceToHost));
+    if (out_pks96) HIPCHK(hipMemcpy(out_pks96, d_keys, n * 96, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -2843,10 +2836,7 @@ extern "C" int mi355_bls_g1_aggregate_device(mi355_bls_ctx* c, const void* d_pks
     HIPCHK(hipEventRecord(c->ev[1], st));
     HIPCHK(hipMemcpyAsync(out_p1, c->d_agg1, 144, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < 8; i++) c->timings[i] = 0;
-    HIPCHK(hipEventElapsedTime(&c->timings[0], c->ev[0], c->ev[1]));
-    c->timings[7] = c->timings[0];
-    return 0;
+    return one_stage_timings(c);
 }
 
 extern "C" int mi355_bls_g2_aggregate_device(mi355_bls_ctx* c, const void* d_sigs, size_t n, void* stream, uint8_t out_p2[288]) {
@@ -2862,10 +2852,7 @@ extern "C" int mi355_bls_g2_aggregate_device(mi355_bls_ctx* c, const void* d_sig
     HIPCHK(hipEventRecord(c->ev[1], st));
     HIPCHK(hipMemcpyAsync(out_p2, c->d_agg, 288, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < 8; i++) c->timings[i] = 0;
-    HIPCHK(hipEventElapsedTime(&c->timings[0], c->ev[0], c->ev[1]));
-    c->timings[7] = c->timings[0];
-    return 0;
+    return one_stage_timings(c);
 }
 extern "C" int mi355_bls_g2_aggregate(mi355_bls_ctx* c, const void* sigs, size_t n, uint8_t out_p2[288]) {
     if (!c || !sigs || !out_p2 || n == 0) return MI355_BLS_ERR_ARG;
@@ -3392,16 +3379,14 @@ extern "C" void mi355_p2s_mult_pippenger(void* ret, const void* const points[], 
 // ------------------------------------------------------------------------------------------
 // Wire-format entry points: batched fromBytes (+ batchVerify)
 // ------------------------------------------------------------------------------------------
-static int deser_enqueue(mi355_bls_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint8_t* d_sigs, size_t n, uint32_t dflags, hipStream_t st) {
-    {
-        int rcr = io_reserve(c, n);
-        if (rcr) return rcr;
-    }
+// k_deser over n rows of device memory -> the records at d_sets (and at out_sets, where the caller gave it), as a status pass between ev0 and ev1
+static int deser_pass(mi355_bls_ctx* c, const void* d_pks, const void* d_msgs, const void* d_sigs, size_t n, uint32_t dflags, hipStream_t st, void* out_sets,
+                      uint8_t* status, hipEvent_t ev0, hipEvent_t ev1) {
+    if (int rc = io_reserve(c, n)) return rc;
     if (dflags > 7) return MI355_BLS_ERR_ARG;
-    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
-    k_deser<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>(d_pks, d_msgs, d_sigs, (uint32_t)n, dflags, c->d_sets, c->d_status, c->d_flags);
-    HIPCHK(hipGetLastError());
-    return 0;
+    const uint8_t *pk = (const uint8_t*)d_pks, *ms = (const uint8_t*)d_msgs, *sg = (const uint8_t*)d_sigs;
+    const auto enqueue = [&] { k_deser<<<plan::waves_for((uint32_t)n), WAVE, 0, st>>>(pk, ms, sg, (uint32_t)n, dflags, c->d_sets, c->d_status, c->d_flags); };
+    return status_pass(c, st, n, status, ev0, ev1, enqueue, out_sets, c->d_sets, n * 320);
 }
 
 extern "C" int mi355_bls_deserialize_sets_ex_device(mi355_bls_ctx* c, const void* d_pks48, const void* d_msgs32, const void* d_sigs96, size_t n, uint32_t dflags,
@@ -3409,57 +3394,35 @@ extern "C" int mi355_bls_deserialize_sets_ex_device(mi355_bls_ctx* c, const void
     if (!c) return MI355_BLS_ERR_ARG;
     if (n == 0) return 1;
     if (!d_pks48 || !d_msgs32 || !d_sigs96) return MI355_BLS_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventRecord(c->ev[0], st));
-    int rc = deser_enqueue(c, (const uint8_t*)d_pks48, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs96, n, dflags, st);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(c->ev[1], st));
-    uint32_t fl[4];
-    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
-    if (out_sets) HIPCHK(hipMemcpyAsync(out_sets, c->d_sets, n * 320, hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < 8; i++) c->timings[i] = 0;
-    HIPCHK(hipEventElapsedTime(&c->timings[0], c->ev[0], c->ev[1]));
-    c->timings[7] = c->timings[0];
-    return fl[2] ? 0 : 1;
-}
-
-// host wire-format arrays -> d_comp: keys at 0, messages at cap * 96, signatures at cap * 128
-static int stage_compressed(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint32_t dflags) {
-    {
-        int rcr = io_reserve(c, n);
-        if (rcr) return rcr;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_comp, pks, n * ((dflags & DESER_F_PK_UNCOMPRESSED) ? 96 : 48), hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(c->d_comp + c->cap_io * 96, msgs, n * 32, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(c->d_comp + c->cap_io * 128, sigs, n * ((dflags & DESER_F_SIG_UNCOMPRESSED) ? 192 : 96), hipMemcpyHostToDevice, nullptr));
-    return 0;
+    return one_stage_timings(c, deser_pass(c, d_pks48, d_msgs32, d_sigs96, n, dflags, (hipStream_t)stream, out_sets, status, c->ev[0], c->ev[1]));
 }
 extern "C" int mi355_bls_deserialize_sets_device(mi355_bls_ctx* c, const void* d_pks48, const void* d_msgs32, const void* d_sigs96, size_t n, void* stream,
                                                  void* out_sets, uint8_t* status) {
     return mi355_bls_deserialize_sets_ex_device(c, d_pks48, d_msgs32, d_sigs96, n, 0, stream, out_sets, status);
+}
+
+// host wire-format arrays -> their columns
+static int stage_compressed(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs, size_t n, uint32_t dflags) {
+    if (int rc = io_reserve(c, n)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(col_at(c, cols::SETS_KEYS), pks, n * ((dflags & DESER_F_PK_UNCOMPRESSED) ? 96 : 48), hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(col_at(c, cols::SETS_MSGS), msgs, n * 32, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(col_at(c, cols::SETS_SIGS), sigs, n * ((dflags & DESER_F_SIG_UNCOMPRESSED) ? 192 : 96), hipMemcpyHostToDevice, nullptr));
+    return 0;
 }
 extern "C" int mi355_bls_deserialize_sets_ex(mi355_bls_ctx* c, const uint8_t* pks, const uint8_t* msgs32, const uint8_t* sigs, size_t n, uint32_t dflags,
                                              void* out_sets, uint8_t* status) {
     if (!c || dflags > 7) return MI355_BLS_ERR_ARG;
     if (n == 0) return 1;
     if (!pks || !msgs32 || !sigs) return MI355_BLS_ERR_ARG;
-    int rc = stage_compressed(c, pks, msgs32, sigs, n, dflags);
-    if (rc) return rc;
-    return mi355_bls_deserialize_sets_ex_device(c, c->d_comp, c->d_comp + c->cap_io * 96, c->d_comp + c->cap_io * 128, n, dflags, nullptr, out_sets, status);
+    if (int rc = stage_compressed(c, pks, msgs32, sigs, n, dflags)) return rc;
+    return mi355_bls_deserialize_sets_ex_device(c, col_at(c, cols::SETS_KEYS), col_at(c, cols::SETS_MSGS), col_at(c, cols::SETS_SIGS), n, dflags, nullptr, out_sets,
+                                                status);
 }
-
 extern "C" int mi355_bls_deserialize_sets(mi355_bls_ctx* c, const uint8_t* pks48, const uint8_t* msgs32, const uint8_t* sigs96, size_t n, void* out_sets,
                                           uint8_t* status) {
-    if (!c) return MI355_BLS_ERR_ARG;
-    if (n == 0) return 1;
-    if (!pks48 || !msgs32 || !sigs96) return MI355_BLS_ERR_ARG;
-    int rc = stage_compressed(c, pks48, msgs32, sigs96, n, 0);
-    if (rc) return rc;
-    return mi355_bls_deserialize_sets_device(c, c->d_comp, c->d_comp + c->cap_io * 96, c->d_comp + c->cap_io * 128, n, nullptr, out_sets, status);
+    return mi355_bls_deserialize_sets_ex(c, pks48, msgs32, sigs96, n, 0, out_sets, status);
 }
 
 extern "C" int mi355_bls_batch_verify_compressed_device(mi355_bls_ctx* c, const void* d_pks48, const void* d_msgs32, const void* d_sigs96, size_t n,
@@ -3469,16 +3432,10 @@ extern "C" int mi355_bls_batch_verify_compressed_device(mi355_bls_ctx* c, const 
     if (!d_pks48 || !d_msgs32 || !d_sigs96) return MI355_BLS_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventRecord(c->ev_deser0, st));
-    int rc = deser_enqueue(c, (const uint8_t*)d_pks48, (const uint8_t*)d_msgs32, (const uint8_t*)d_sigs96, n, 0, st);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(c->ev_deser1, st));
-    uint32_t fl[4];
-    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    const int ok = deser_pass(c, d_pks48, d_msgs32, d_sigs96, n, 0, st, nullptr, status, c->ev_deser0, c->ev_deser1);
+    if (ok < 0) return ok;
     HIPCHK(hipEventElapsedTime(&c->deser_ms, c->ev_deser0, c->ev_deser1));
-    if (fl[2]) return 0;                                   // some fromBytes failed: the caller never gets to batchVerify
+    if (!ok) return 0;                                     // some fromBytes failed: the caller never gets to batchVerify
     return verify_common(c, c->d_sets, nullptr, n, rnd, 0, st);
 }
 
@@ -3487,9 +3444,8 @@ extern "C" int mi355_bls_batch_verify_compressed(mi355_bls_ctx* c, const uint8_t
     if (!c || !rnd) return MI355_BLS_ERR_ARG;
     if (n == 0) return 0;
     if (!pks48 || !msgs32 || !sigs96) return MI355_BLS_ERR_ARG;
-    int rc = stage_compressed(c, pks48, msgs32, sigs96, n, 0);
-    if (rc) return rc;
-    return mi355_bls_batch_verify_compressed_device(c, c->d_comp, c->d_comp + c->cap_io * 96, c->d_comp + c->cap_io * 128, n, rnd, nullptr, status);
+    if (int rc = stage_compressed(c, pks48, msgs32, sigs96, n, 0)) return rc;
+    return mi355_bls_batch_verify_compressed_device(c, col_at(c, cols::SETS_KEYS), col_at(c, cols::SETS_MSGS), col_at(c, cols::SETS_SIGS), n, rnd, nullptr, status);
 }
 
 extern "C" float mi355_bls_last_deser_ms(mi355_bls_ctx* c) { return c ? c->deser_ms : 0.f; }
@@ -3502,44 +3458,29 @@ extern "C" int mi355_bls_sign_sets_device(mi355_bls_ctx* c, const void* d_sks32,
     if (!c) return MI355_BLS_ERR_ARG;
     if (n == 0) return 1;
     if (!d_sks32 || !d_msgs32 || !d_out_sets) return MI355_BLS_ERR_ARG;
-    {
-        int rcr = io_reserve(c, n);
-        if (rcr) return rcr;
-    }
+    if (int rc = io_reserve(c, n)) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
-    HIPCHK(hipEventRecord(c->ev[0], st));
-    uint32_t nb = plan::waves_for((uint32_t)n);
-    k_sign_pk<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, (const uint8_t*)d_msgs32, (uint32_t)n, (uint8_t*)d_out_sets, c->d_status, c->d_flags);
-    k_sign_sig<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, (const uint8_t*)d_msgs32, (uint32_t)n, c->dst, (uint8_t*)d_out_sets);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev[1], st));
-    uint32_t fl[4];
-    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < 8; i++) c->timings[i] = 0;
-    HIPCHK(hipEventElapsedTime(&c->timings[0], c->ev[0], c->ev[1]));
-    c->timings[7] = c->timings[0];
-    return fl[2] ? 0 : 1;
+    const uint32_t nb = plan::waves_for((uint32_t)n);
+    return one_stage_timings(c, status_pass(c, st, n, status, c->ev[0], c->ev[1], [&] {
+        k_sign_pk<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, (const uint8_t*)d_msgs32, (uint32_t)n, (uint8_t*)d_out_sets, c->d_status, c->d_flags);
+        k_sign_sig<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, (const uint8_t*)d_msgs32, (uint32_t)n, c->dst, (uint8_t*)d_out_sets);
+    }));
 }
 
 extern "C" int mi355_bls_sign_sets(mi355_bls_ctx* c, const uint8_t* sks32, const uint8_t* msgs32, size_t n, void* out_sets, uint8_t* status) {
     if (!c) return MI355_BLS_ERR_ARG;
     if (n == 0) return 1;
     if (!sks32 || !msgs32 || !out_sets) return MI355_BLS_ERR_ARG;
-    {
-        int rcr = io_reserve(c, n);
-        if (rcr) return rcr;
-    }
+    if (int rc = io_reserve(c, n)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_comp, sks32, n * 32, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(c->d_comp + c->cap_io * 48, msgs32, n * 32, hipMemcpyHostToDevice, nullptr));
-    int rc = mi355_bls_sign_sets_device(c, c->d_comp, c->d_comp + c->cap_io * 48, n, c->d_sets, nullptr, status);
+    uint8_t *d_sk = col_at(c, cols::SIGN_SKS), *d_msg = col_at(c, cols::SIGN_MSGS);
+    HIPCHK(hipMemcpyAsync(d_sk, sks32, n * 32, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(d_msg, msgs32, n * 32, hipMemcpyHostToDevice, nullptr));
+    int rc = mi355_bls_sign_sets_device(c, d_sk, d_msg, n, c->d_sets, nullptr, status);
     if (rc < 0) return rc;
     HIPCHK(hipMemcpy(out_sets, c->d_sets, n * 320, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemsetAsync(c->d_comp, 0, n * 32, nullptr));          // do not leave the scalars in the staging buffer
+    HIPCHK(hipMemsetAsync(d_sk, 0, n * 32, nullptr));               // do not leave the scalars in the staging buffer
     HIPCHK(hipStreamSynchronize(nullptr));
     return rc;
 }
@@ -3551,40 +3492,29 @@ extern "C" int mi355_bls_pop_prove_device(mi355_bls_ctx* c, const void* d_sks32,
     if (n == 0) return 1;
     if (!d_sks32 || !d_out_pks96 || !d_out_proofs192 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    if (int rcr = io_reserve(c, n)) return rcr;
+    if (int rc = io_reserve(c, n)) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
-    uint8_t* d_zero = c->d_comp + c->cap_io * 96;                  // n x 32 zero bytes: k_sign_pk copies a message into every record.  (The host form's
-                                                                   // proofs land here afterwards, behind k_sign_pk on the same stream.)
-    HIPCHK(hipMemsetAsync(c->d_flags, 0, 12, st));
+    uint8_t* d_zero = col_at(c, cols::PROVE_ZERO_MSGS);            // n x 32 zero bytes: k_sign_pk copies a message into every record
     HIPCHK(hipMemsetAsync(d_zero, 0, n * 32, st));
-    HIPCHK(hipEventRecord(c->ev[0], st));
-    uint32_t nb = plan::waves_for((uint32_t)n);
-    k_sign_pk<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, d_zero, (uint32_t)n, c->d_sets, c->d_status, c->d_flags);
-    k_pop_prove_sig<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, c->d_sets, (uint32_t)n, c->dst_pop, (uint8_t*)d_out_pks96, (uint8_t*)d_out_proofs192);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev[1], st));
-    uint32_t fl[4];
-    HIPCHK(hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < 8; i++) c->timings[i] = 0;
-    HIPCHK(hipEventElapsedTime(&c->timings[0], c->ev[0], c->ev[1]));
-    c->timings[7] = c->timings[0];
-    return fl[2] ? 0 : 1;
+    const uint32_t nb = plan::waves_for((uint32_t)n);
+    return one_stage_timings(c, status_pass(c, st, n, status, c->ev[0], c->ev[1], [&] {
+        k_sign_pk<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, d_zero, (uint32_t)n, c->d_sets, c->d_status, c->d_flags);
+        k_pop_prove_sig<<<nb, WAVE, 0, st>>>((const uint8_t*)d_sks32, c->d_sets, (uint32_t)n, c->dst_pop, (uint8_t*)d_out_pks96, (uint8_t*)d_out_proofs192);
+    }));
 }
 extern "C" int mi355_bls_pop_prove(mi355_bls_ctx* c, const uint8_t* sks32, size_t n, void* out_pks96, void* out_proofs192, uint8_t* status) {
     if (!c) return MI355_BLS_ERR_ARG;
     if (n == 0) return 1;
     if (!sks32 || !out_pks96 || !out_proofs192 || n > plan::POP_MAX_KEYS) return MI355_BLS_ERR_ARG;
-    if (int rcr = io_reserve(c, n)) return rcr;
+    if (int rc = io_reserve(c, n)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    uint8_t* d_sk = c->d_comp + c->cap_io * 288;                   // d_comp (cap_io x 320 B): keys out at 0, proofs out at cap_io x 96, the scalars behind them
+    uint8_t *d_sk = col_at(c, cols::PROVE_SKS), *d_keys = col_at(c, cols::PROVE_KEYS), *d_proofs = col_at(c, cols::PROVE_PROOFS);
     HIPCHK(hipMemcpyAsync(d_sk, sks32, n * 32, hipMemcpyHostToDevice, nullptr));
-    int rc = mi355_bls_pop_prove_device(c, d_sk, n, c->d_comp, c->d_comp + c->cap_io * 96, nullptr, status);
+    int rc = mi355_bls_pop_prove_device(c, d_sk, n, d_keys, d_proofs, nullptr, status);
     if (rc < 0) return rc;
-    HIPCHK(hipMemcpy(out_pks96, c->d_comp, n * 96, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_proofs192, c->d_comp + c->cap_io * 96, n * 192, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_pks96, d_keys, n * 96, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_proofs192, d_proofs, n * 192, hipMemcpyDeviceToHost));
     HIPCHK(hipMemsetAsync(d_sk, 0, n * 32, nullptr));               // do not leave the scalars in the staging buffer
     HIPCHK(hipStreamSynchronize(nullptr));
     return rc;

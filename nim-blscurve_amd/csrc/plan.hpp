@@ -1066,5 +1066,74 @@ inline pack_layout pack_for(const size_t* bytes, size_t n) {
     return p;
 }
 
+// The per-row calls' staging.  The context's two staging buffers hold cap_io rows of ROW_BYTES each (io_reserve); an array a call stages is a
+// COLUMN: `width` bytes per row (its widest form: a compressed key takes 48 of a key column's 96), starting at buffer + cap_io * start, so columns
+// apart in a row are apart in the buffer whatever cap_io is.  Calls that use a buffer from offset 0 as one array (records, the decoders' output,
+// fastAggregateVerify, combine, the MSM host forms) have none.  X(name, call, column, buffer, start, width, the column of that call it shares bytes with):
+constexpr size_t ROW_BYTES = 320;
+enum row_buf { ROW_COMP, ROW_SETS };         // d_comp, d_sets
+struct row_col {
+    row_buf buf;
+    uint32_t start, width;
+};
+#define BLS_ROW_COLUMNS(X)                                                                      \
+    X(CPK_IN, "compress_public_keys", "keys in", ROW_COMP, 0, 96, nullptr)                      \
+    X(CPK_OUT, "compress_public_keys", "out", ROW_COMP, 96, 48, nullptr)                        \
+    X(CSIG_IN, "compress_signatures", "signatures in", ROW_COMP, 0, 192, nullptr)               \
+    X(CSIG_OUT, "compress_signatures", "out", ROW_COMP, 192, 96, nullptr)                       \
+    X(DSIG_WIRE, "deserialize_signatures", "wire", ROW_COMP, 0, 192, nullptr)                   \
+    X(DPK_WIRE, "deserialize_public_keys", "wire", ROW_COMP, 0, 96, nullptr)                    \
+    X(POP_KEYS, "pop_verify", "keys", ROW_COMP, 0, 96, nullptr) /* the host forms: pop_stage */ \
+    X(POP_PROOFS, "pop_verify", "proofs", ROW_COMP, 96, 192, nullptr)                           \
+    X(ADMIT_KEYS, "admit_keys", "decoded keys", ROW_COMP, 0, 96, nullptr) /* host form only */  \
+    X(ADMIT_PROOFS, "admit_keys", "decoded proofs", ROW_COMP, 96, 192, nullptr)                 \
+    X(ADMIT_LIST, "admit_keys", "row list", ROW_COMP, 288, 4, nullptr)                          \
+    X(ADMIT_PROOF_ST, "admit_keys", "proof status", ROW_COMP, 292, 1, nullptr)                  \
+    X(ADMIT_WIRE_KEYS, "admit_keys", "wire keys", ROW_SETS, 0, 96, nullptr) /* host form */     \
+    X(ADMIT_WIRE_PROOFS, "admit_keys", "wire proofs", ROW_SETS, 96, 192, nullptr)               \
+    X(SETS_KEYS, "deserialize_sets", "keys", ROW_COMP, 0, 96, nullptr) /* and _ex, batch_verify_compressed */ \
+    X(SETS_MSGS, "deserialize_sets", "messages", ROW_COMP, 96, 32, nullptr)                     \
+    X(SETS_SIGS, "deserialize_sets", "signatures", ROW_COMP, 128, 192, nullptr)                 \
+    X(SIGN_SKS, "sign_sets", "scalars", ROW_COMP, 0, 32, nullptr)                               \
+    X(SIGN_MSGS, "sign_sets", "messages", ROW_COMP, 48, 32, nullptr)                            \
+    X(PROVE_KEYS, "pop_prove", "keys out", ROW_COMP, 0, 96, nullptr)                            \
+    X(PROVE_PROOFS, "pop_prove", "proofs out", ROW_COMP, 96, 192, nullptr)                      \
+    X(PROVE_SKS, "pop_prove", "scalars", ROW_COMP, 288, 32, nullptr)                            \
+    X(PROVE_ZERO_MSGS, "pop_prove", "zero messages", ROW_COMP, 96, 32, "proofs out")
+// The one sharing: the zero messages k_sign_pk copies into pop_prove's records (device form) lie in the proofs' column; k_pop_prove_sig writes
+// the host form's proofs there behind k_sign_pk, the zero bytes' only reader, on the same stream.
+namespace cols {
+#define X(name, call, column, buf, start, width, shares) constexpr row_col name{buf, start, width};
+BLS_ROW_COLUMNS(X)
+#undef X
+}  // namespace cols
+// the same by call, for the check below and tests/test_pack_plan.py: the columns of one call in one buffer are live together
+struct row_col_entry {
+    const char *call, *column;
+    row_col col;
+    const char* shares;
+};
+#define X(name, call, column, buf, start, width, shares) {call, column, cols::name, shares},
+constexpr row_col_entry ROW_COLUMNS[] = {BLS_ROW_COLUMNS(X)};
+#undef X
+constexpr size_t ROW_COLUMN_COUNT = sizeof(ROW_COLUMNS) / sizeof(ROW_COLUMNS[0]);
+constexpr bool same_text(const char* a, const char* b) {
+    while (a && b && *a && *a == *b) a++, b++;
+    return a && b && *a == *b;
+}
+constexpr bool row_columns_ok() {
+    for (size_t i = 0; i < ROW_COLUMN_COUNT; i++) {
+        const row_col_entry& a = ROW_COLUMNS[i];
+        if (a.col.width == 0 || a.col.start + a.col.width > ROW_BYTES) return false;
+        for (size_t j = 0; j < i; j++) {
+            const row_col_entry& b = ROW_COLUMNS[j];
+            const bool apart = a.col.start + a.col.width <= b.col.start || b.col.start + b.col.width <= a.col.start;
+            if (same_text(a.call, b.call) && a.col.buf == b.col.buf && !apart && !same_text(a.shares, b.column) && !same_text(b.shares, a.column)) return false;
+        }
+    }
+    return true;
+}
+static_assert(row_columns_ok(), "a column of the per-row staging ends behind its 320-byte row, or two columns of one call overlap undeclared");
+
 }  // namespace plan
 #endif

@@ -1,7 +1,8 @@
 """The staging layout of the grouped calls' host inputs (csrc/plan.hpp pack_for), called from the product's header through
 tests/host_emu/plan_pack.cpp: every part starts on a multiple of 4 bytes, the parts keep their order and do not overlap, the total covers the
 last one, and for the part lists the host forms pass (every length a multiple of 4 except the last) the offsets are the running sums the
-entry points used to add up by hand."""
+entry points used to add up by hand.  And the per-row calls' staging (csrc/plan.hpp cols, ROW_COLUMNS): every column where the entry points
+used to write it as a bare number, no two columns of a call overlapping but for the one declared sharing, every column inside its 320-byte row."""
 import ctypes
 import itertools
 import os
@@ -21,6 +22,9 @@ def lib():
         sz, szp = ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)
         L.plan_pack_parts_max.restype = sz
         L.plan_pack_for.restype, L.plan_pack_for.argtypes = sz, [szp, sz, szp]
+        L.plan_row_bytes.restype = L.plan_row_column_count.restype = sz
+        strp, u32p = ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint32)
+        L.plan_row_column.restype, L.plan_row_column.argtypes = ctypes.c_int, [sz, strp, strp, strp, u32p, u32p, u32p]
         _lib = L
     return _lib
 
@@ -107,3 +111,79 @@ def test_the_host_forms_part_lists_land_where_they_did():
     for name, (lengths, want_at, want_total) in cases.items():
         assert running_sums(lengths) == (want_at, want_total), name      # the figures written out above are the old sums
         assert pack(lengths) == (want_at, want_total), name
+
+
+# ---- the per-row calls' staging columns
+
+def row_columns():
+    """[(call, buffer, column, start, width, shares)] as csrc/plan.hpp lists them"""
+    out = []
+    for i in range(lib().plan_row_column_count()):
+        call, column, shares = ctypes.c_char_p(), ctypes.c_char_p(), ctypes.c_char_p()
+        buf, start, width = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        assert lib().plan_row_column(i, call, column, shares, buf, start, width) == 1
+        out.append((call.value.decode(), ("d_comp", "d_sets")[buf.value], column.value.decode(), start.value, width.value,
+                    shares.value.decode() if shares.value else None))
+    return out
+
+
+# (call, buffer, column): (start, width) - the figures the entry points carried as `cap_io * K` and `n * W` before there was a table
+ROW_COLUMNS = {
+    ("compress_public_keys", "d_comp", "keys in"): (0, 96),
+    ("compress_public_keys", "d_comp", "out"): (96, 48),
+    ("compress_signatures", "d_comp", "signatures in"): (0, 192),
+    ("compress_signatures", "d_comp", "out"): (192, 96),
+    ("deserialize_signatures", "d_comp", "wire"): (0, 192),
+    ("deserialize_public_keys", "d_comp", "wire"): (0, 96),
+    ("pop_verify", "d_comp", "keys"): (0, 96),
+    ("pop_verify", "d_comp", "proofs"): (96, 192),
+    ("admit_keys", "d_comp", "decoded keys"): (0, 96),
+    ("admit_keys", "d_comp", "decoded proofs"): (96, 192),
+    ("admit_keys", "d_comp", "row list"): (288, 4),
+    ("admit_keys", "d_comp", "proof status"): (292, 1),
+    ("admit_keys", "d_sets", "wire keys"): (0, 96),
+    ("admit_keys", "d_sets", "wire proofs"): (96, 192),
+    ("deserialize_sets", "d_comp", "keys"): (0, 96),
+    ("deserialize_sets", "d_comp", "messages"): (96, 32),
+    ("deserialize_sets", "d_comp", "signatures"): (128, 192),
+    ("sign_sets", "d_comp", "scalars"): (0, 32),
+    ("sign_sets", "d_comp", "messages"): (48, 32),
+    ("pop_prove", "d_comp", "keys out"): (0, 96),
+    ("pop_prove", "d_comp", "proofs out"): (96, 192),
+    ("pop_prove", "d_comp", "scalars"): (288, 32),
+    ("pop_prove", "d_comp", "zero messages"): (96, 32),           # the device form's: they share the proofs' column
+}
+ROW_SHARINGS = {("pop_prove", "d_comp", frozenset(("zero messages", "proofs out")))}
+
+
+def test_the_row_is_320_bytes():
+    assert lib().plan_row_bytes() == 320
+    assert lib().plan_row_column(lib().plan_row_column_count(), *([None] * 6)) == 0
+
+
+def test_every_row_column_lands_where_it_did():
+    got = {(call, buf, column): (start, width) for call, buf, column, start, width, _ in row_columns()}
+    assert len(got) == lib().plan_row_column_count()         # no (call, buffer, column) twice
+    assert got == ROW_COLUMNS
+
+
+def test_row_columns_of_a_call_do_not_overlap():
+    cols = row_columns()
+    declared = set()
+    for call, buf, column, _, _, shares in cols:
+        if shares is not None:
+            assert any(c == call and b == buf and name == shares for c, b, name, _, _, _ in cols), (call, column, shares)
+            declared.add((call, buf, frozenset((column, shares))))
+    assert declared == ROW_SHARINGS
+    overlapping = set()
+    for (c1, b1, n1, s1, w1, _), (c2, b2, n2, s2, w2, _) in itertools.combinations(cols, 2):
+        if (c1, b1) == (c2, b2) and s1 < s2 + w2 and s2 < s1 + w1:
+            overlapping.add((c1, b1, frozenset((n1, n2))))
+    assert overlapping == ROW_SHARINGS                       # the declared sharing is a real one, and the only overlap
+
+
+def test_every_row_column_ends_inside_the_row():
+    for call, buf, column, start, width, _ in row_columns():
+        assert width > 0 and start + width <= 320, (call, buf, column)
+    # the two that end exactly at the row's end
+    assert sum(ROW_COLUMNS[("pop_prove", "d_comp", "scalars")]) == 320 and sum(ROW_COLUMNS[("deserialize_sets", "d_comp", "signatures")]) == 320
