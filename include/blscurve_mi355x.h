@@ -125,11 +125,52 @@ int mi355_bls_batch_wait(mi355_bls_ctx* ctx);
  * separate calls, only the speed-up is lost.  Draw one fresh rnd per batch.
  * COST: a passing call is one whole-chip pass.  A call in which some batch fails costs that pass PLUS k single-batch calls (about
  * twice the latency; the calls are synchronous): an adversary who can place one bad signature per call forces the slow path for all
- * k batches - hosts that expect failures should keep k small or verify suspicious batches separately.
+ * k batches - hosts that expect failures should keep k small or verify suspicious batches separately.  mi355_bls_batch_verify_many_locate
+ * (below) answers a failing call with ONE per-batch pass instead of the k calls.
 */
 int mi355_bls_batch_verify_many(mi355_bls_ctx* ctx, const void* sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[]);
 int mi355_bls_batch_verify_many_device(mi355_bls_ctx* ctx, const void* d_sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
                                        void* stream);
+
+/* Per-batch verdicts for many batches in ONE device pass: what the failing case of mi355_bls_batch_verify_many finds with k single-batch
+ * calls.  Arguments and layout are those of mi355_bls_batch_verify_many (records laid end to end; counts, rnds and the k verdict bytes in host
+ * memory).
+ *   many_each:   verdicts[b] = what mi355_bls_batch_verify_once(batch b, rnds[b], num_threads) returns, computed as batch b's OWN product:
+ *                prod_i e([r_i]PK_i, H(m_i)) * e(-G1, sum_i [r_i]S_i) over the sets of batch b, r_i the scalar set i has in its own batch
+ *                (chain partition B = min(n_b, num_threads), serial chain for n_b < 3 or num_threads = 1).  An empty batch gives 0 and
+ *                takes no lane; a batch that holds an infinity public key gives 0 and the other batches are not affected; an infinity
+ *                signature adds nothing to its batch's sum.  Nothing is sticky across batches, and since NO PRODUCT IS SHARED between
+ *                batches, two batches with the same 32 random bytes need no special case: errors cannot cancel across batches here.
+ *                Returns 1 iff every verdict is 1 (k == 0 or every batch empty: 0, every verdict 0), negative on a runtime failure,
+ *                MI355_BLS_ERR_ARG under the rules of mi355_bls_batch_verify_many (a context with a submitted batch pending among them).
+ *   many_locate: the merged pass of mi355_bls_batch_verify_many first, under its conditions (distinct rnds, union within the capacity,
+ *                k <= 65 536).  If it passes: every non-empty batch 1 and no per-batch pass.  If it fails or cannot run: one many_each pass.
+ * No input is refused for its size: the call runs in slices of whole consecutive batches, as many as fit max_sets sets and, sets plus one
+ * signature slot per batch, the per-set path's pair store; a batch that alone does not fit takes the single-batch path, which slices
+ * internally.  The blinding scalars and the random bytes are cleared from device memory before the call returns.  Synchronous.
+ * COST on one MI355X against mi355_bls_batch_verify_many_device on the same input in the same run (profiles/verify_many_each_bench.json,
+ * nim-blscurve_amd/tools/bench_verify_many_each.py: 65 536 device-resident sets on a 65 536-set context, median of 5 blocking calls, every
+ * min .. max within 4 % of its median), at 16 x 4 096 / 64 x 1 024 / 256 x 256 / 1 024 x 64 batches x sets:
+ *   failing case (one forged batch): many_each 21.6 / 19.9 / 19.1 / 21.8 ms and many_locate 33.8 / 32.0 / 31.0 / 33.8 ms against the k-call
+ *   fallback's 66.7 / 199 / 615 / 2 250 ms: 3.1 / 10 / 32 / 103 times and 2.0 / 6.2 / 20 / 67 times faster - the new calls lose at none
+ *   of the four shapes;
+ *   passing case (all valid): many_each 21.3 / 19.8 / 19.0 / 21.9 ms against the merged pass's 11.9 / 12.2 / 12.2 / 12.3 ms - asking "which
+ *   one?" up front costs 1.79 / 1.63 / 1.56 / 1.78 times the merged pass, its time does not depend on the input - and many_locate IS the
+ *   merged pass there (0.98 - 1.00 of it).
+ * So: many_locate where failures are rare, many_each where a bad batch per call is to be expected (it beats many_locate's failing case by
+ * the merged pass).  Nothing inside the library switches on these numbers. */
+int mi355_bls_batch_verify_many_each(mi355_bls_ctx* ctx, const void* sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[]);
+int mi355_bls_batch_verify_many_each_device(mi355_bls_ctx* ctx, const void* d_sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                                            void* stream);
+int mi355_bls_batch_verify_many_locate(mi355_bls_ctx* ctx, const void* sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[]);
+int mi355_bls_batch_verify_many_locate_device(mi355_bls_ctx* ctx, const void* d_sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                                              void* stream);
+/* TEST HOOKS: the host form of many_each with, for every batch, the 576-byte blst_fp12 image of the value after the final exponentiation
+ * (gt_out: k x 576 bytes; an empty batch: zero bytes) - the per-batch counterpart of mi355_bls_fetch_stage(4); the number of per-batch passes
+ * this context has made. */
+int mi355_bls_debug_batch_verify_many_each_gt(mi355_bls_ctx* ctx, const void* sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                                              uint8_t* gt_out);
+int mi355_bls_debug_batch_verify_many_each_passes(mi355_bls_ctx* ctx);
 
 /* Per-set verdicts in one device pass: verdicts[i] = verify(pk_i, msg_i, sig_i) (bls_sig_min_pubkey.nim:108-125 ->
  * coreVerifyNoGroupCheck, blst_min_pubkey_sig_core.nim:269-297) for every 320-byte SignatureSet record of the input - what a host does

@@ -59,6 +59,11 @@ def lib():
         L.mi355_bls_batch_wait.argtypes = [vp]
         L.mi355_bls_batch_verify_many.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_char_p]
         L.mi355_bls_batch_verify_many_device.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_char_p, vp]
+        for name in ("mi355_bls_batch_verify_many_each", "mi355_bls_batch_verify_many_locate"):
+            getattr(L, name).argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_char_p]
+            getattr(L, name + "_device").argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_char_p, vp]
+        L.mi355_bls_debug_batch_verify_many_each_gt.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_char_p, ctypes.c_char_p]
+        L.mi355_bls_debug_batch_verify_many_each_passes.argtypes = [vp]
         L.mi355_bls_verify_each.argtypes = [vp, vp, sz, ctypes.c_char_p]
         L.mi355_bls_verify_each_device.argtypes = [vp, vp, sz, ctypes.c_char_p, vp]
         L.mi355_bls_batch_verify_locate.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p]
@@ -412,6 +417,82 @@ def batchVerifyMany_device(cache, d_ptr, counts, secureRandomBytes_list, stream=
     out = ctypes.create_string_buffer(k)
     _check(lib().mi355_bls_batch_verify_many_device(cache._h, d_ptr, carr, rnds, k, out, stream))
     return [bool(v) for v in out.raw]
+
+
+def _many_host(inputs, secureRandomBytes_list):
+    """the batches of a k-batch call -> (records end to end, counts array, rnds, k)"""
+    recs = [_as_records(x) for x in inputs]
+    if len(recs) != len(secureRandomBytes_list):
+        raise ValueError("one secureRandomBytes per batch")
+    k = len(recs)
+    counts = (ctypes.c_size_t * max(k, 1))(*[len(r) // SIGSET_BYTES for r in recs])
+    return b"".join(recs) or b"\0", counts, b"".join(_rnd32(r) for r in secureRandomBytes_list), k
+
+
+def _many_device(counts, secureRandomBytes_list):
+    k = len(counts)
+    if k != len(secureRandomBytes_list):
+        raise ValueError("one secureRandomBytes per batch")
+    return (ctypes.c_size_t * max(k, 1))(*counts), b"".join(_rnd32(r) for r in secureRandomBytes_list), k
+
+
+def batchVerifyManyEach(cache, inputs, secureRandomBytes_list):
+    """Per-batch verdicts for k batches in ONE device pass (mi355_bls_batch_verify_many_each): arguments as batchVerifyMany.  -> [bool] * k,
+    each what batchVerify(cache, inputs[b], rnd[b]) returns, computed as batch b's own product - one bad batch costs the others nothing."""
+    rec, counts, rnds, k = _many_host(inputs, secureRandomBytes_list)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_batch_verify_many_each(cache._h, rec, counts, rnds, k, out))
+    return [v == 1 for v in out.raw]
+
+
+def batchVerifyManyEach_device(cache, d_ptr, counts, secureRandomBytes_list, stream=0):
+    """Same with the records of all batches contiguous in device memory."""
+    carr, rnds, k = _many_device(counts, secureRandomBytes_list)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_batch_verify_many_each_device(cache._h, d_ptr, carr, rnds, k, out, stream))
+    return [v == 1 for v in out.raw]
+
+
+def batchVerifyManyLocate(cache, inputs, secureRandomBytes_list):
+    """batchVerifyMany's merged pass first; only if it fails (or cannot run) one batchVerifyManyEach pass (mi355_bls_batch_verify_many_locate).
+    -> [bool] * k, the verdicts of batchVerifyMany."""
+    rec, counts, rnds, k = _many_host(inputs, secureRandomBytes_list)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_batch_verify_many_locate(cache._h, rec, counts, rnds, k, out))
+    return [v == 1 for v in out.raw]
+
+
+def batchVerifyManyLocate_device(cache, d_ptr, counts, secureRandomBytes_list, stream=0):
+    """Same with the records of all batches contiguous in device memory."""
+    carr, rnds, k = _many_device(counts, secureRandomBytes_list)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_batch_verify_many_locate_device(cache._h, d_ptr, carr, rnds, k, out, stream))
+    return [v == 1 for v in out.raw]
+
+
+def batchVerifyManyEachValues(cache, inputs, secureRandomBytes_list):
+    """Test hook (mi355_bls_debug_batch_verify_many_each_gt): -> ([bool], [576-byte blst_fp12 image of batch b's value after the final
+    exponentiation]); an empty batch's value is 576 zero bytes."""
+    rec, counts, rnds, k = _many_host(inputs, secureRandomBytes_list)
+    if k == 0:
+        return [], []
+    out, gt = ctypes.create_string_buffer(k), ctypes.create_string_buffer(k * 576)
+    _check(lib().mi355_bls_debug_batch_verify_many_each_gt(cache._h, rec, counts, rnds, k, out, gt))
+    raw = gt.raw
+    return [v == 1 for v in out.raw], [raw[576 * i:576 * i + 576] for i in range(k)]
+
+
+def batchVerifyManyEachPasses(cache):
+    """per-batch passes the cache's context has made (test hook)"""
+    return _check(lib().mi355_bls_debug_batch_verify_many_each_passes(cache._h))
 
 
 def verifyEach(cache, input_):

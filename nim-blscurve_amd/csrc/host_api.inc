@@ -190,6 +190,13 @@ struct mi355_bls_ctx {
     // k MSMs in one pass (mi355_bls_p1s_mult_pippenger_many): made at the first such call
     msm_many_ws msm_many;
     std::vector<uint32_t> many_offs; // the ragged passes' offsets of the call in flight: the async copies read them
+    // per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): sized by the largest slice of a call; it runs in the per-set path's
+    // pair store with the per-group path's tables, partials and step values (d_aggv_*) and combine_sets' G2 products and tables (grp, d_comb_*)
+    dev_buf<uint8_t> d_me_meta;      // k_blind_many's table of a slice's parallel batches
+    std::vector<many_meta> me_meta;  // ... of every slice of the call in flight: the async copies read them
+    std::vector<uint8_t> me_rr;      // those batches' random bytes, and
+    std::vector<uint64_t> me_r;      // the serial batches' chains by set: blinding material, wiped before the call returns
+    int me_passes = 0;               // per-batch passes made on this context (mi355_bls_debug_batch_verify_many_each_passes)
 
     // the batch workspace's pair store (ctx_build makes it; it never changes) and the per-set path's (each_reserve)
     pair_store batch_pairs() const { return {d_H, d_P, d_lines, stride}; }
@@ -2394,18 +2401,13 @@ extern "C" int mi355_bls_group_by_message(const void* sets, size_t n, uint32_t* 
 // verdict is true (the common case, at whole-chip throughput); if it fails, the batches are verified one by one to find the
 // culprits - the optimistic scheme clients already wrap around batchVerify.  Verdicts are exactly those of k separate calls.
 // ------------------------------------------------------------------------------------------
-static int verify_many(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
-                       hipStream_t st) {
-    if (!c || !counts || !rnds || !verdicts || (!d_src && !h_src)) return MI355_BLS_ERR_ARG;
-    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
-    size_t total = 0;
-    for (size_t b = 0; b < k; b++) {
-        verdicts[b] = 0;
-        total += counts[b];
-    }
-    if (total == 0) return 0;                                     // every batch empty: every verdict false (bls_batch_verifier.nim:137-139)
-    HIPCHK(hipSetDevice(c->device));
+// The merged pass over the union of `total` > 0 sets, where it may run: *passed = the union's product is one and no key is at infinity.
+// It does not run (and *passed stays false) when two non-empty batches carry the same random bytes, when the union exceeds the workspace or
+// when k > 65 536.  0, or a negative error.
+static int many_merged_pass(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, const size_t counts[], const uint8_t* rnds, size_t k, size_t total,
+                            hipStream_t st, bool* passed) {
     bool merged_ok = false;
+    *passed = false;
     // The merged check is sound only if the batches' blinding scalars are independent.  They are a deterministic SHA-256 chain of
     // (rnd_b, chain id): two batches with the SAME secureRandomBytes and the same count get identical r_i at identical indices, and a
     // forger who knows that can make errors cancel across them (sig + D at index i of one, sig' - D at index i of the other: the
@@ -2475,14 +2477,39 @@ static int verify_many(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_
         (void)collect_timings(c, 7);
         merged_ok = fl[0] == 0 && fl[1] == 1;
     }
-    if (merged_ok) {
-        int all = 1;
-        for (size_t b = 0; b < k; b++) {
-            verdicts[b] = counts[b] ? 1 : 0;
-            all &= verdicts[b];
-        }
-        return all;
+    *passed = merged_ok;
+    return 0;
+}
+// the arguments every k-batch call checks, its verdicts cleared: the sets of the call, or a negative error
+static int many_args(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                     size_t* total) {
+    if (!c || !counts || !rnds || !verdicts || (!d_src && !h_src)) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    *total = 0;
+    for (size_t b = 0; b < k; b++) {
+        verdicts[b] = 0;
+        *total += counts[b];
     }
+    return 0;
+}
+// every non-empty batch verified: 1 iff there is no empty one
+static int many_all_pass(const size_t counts[], size_t k, uint8_t verdicts[]) {
+    int all = 1;
+    for (size_t b = 0; b < k; b++) {
+        verdicts[b] = counts[b] ? 1 : 0;
+        all &= verdicts[b];
+    }
+    return all;
+}
+static int verify_many(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                       hipStream_t st) {
+    size_t total = 0;
+    if (int rc = many_args(c, d_src, h_src, counts, rnds, k, verdicts, &total)) return rc;
+    if (total == 0) return 0;                                     // every batch empty: every verdict false (bls_batch_verifier.nim:137-139)
+    HIPCHK(hipSetDevice(c->device));
+    bool merged_ok = false;
+    if (int rc = many_merged_pass(c, d_src, h_src, counts, rnds, k, total, st, &merged_ok)) return rc;
+    if (merged_ok) return many_all_pass(counts, k, verdicts);
     // ---- some batch fails (or the union exceeds the workspace): one by one, exactly as k separate batchVerify calls
     int all = 1;
     size_t first = 0;
@@ -2506,6 +2533,253 @@ extern "C" int mi355_bls_batch_verify_many(mi355_bls_ctx* c, const void* sets, c
 extern "C" int mi355_bls_batch_verify_many_device(mi355_bls_ctx* c, const void* d_sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
                                                   void* stream) {
     return verify_many(c, (const uint8_t*)d_sets, nullptr, counts, rnds, k, verdicts, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-batch verdicts for many batches in ONE device pass: what verify_many's fallback finds with k single-batch calls.  Batch b is one group
+// of the per-group path (aggveach_run): its pairs are ([r_i]PK_i, H(m_i)), r_i the scalar set i has in its own batch (k_blind_many for
+// the parallel batches, host_serial_chain for the serial ones: verify_many's rule), its signature pair (-G1, sum [r_i]S_i).  The call runs in
+// slices of whole batches (plan.hpp manyeach_cut); per slice one copy of its tables, the scalars, hashing and [r]PK into the per-set
+// path's pair store on the caller's stream and, beside them on the context's fork stream, one 64-bit G2 multiplication per set
+// (k_combsets_g2mul) and the segmented sum per batch (k_combsets_g2_sum); k_manyeach_setup joins the two, then the Miller lines, the
+// segmented line product and the tail of the per-group path.  A batch that fits no slice takes verify_common, in its turn.  No product is
+// shared between batches, so equal random bytes in two batches need no special case.  The verdict bytes of all slices collect in d_each_v
+// and come back in one copy; the scalars and the random bytes are cleared on the device before the call returns.
+// ------------------------------------------------------------------------------------------
+static int manyeach_run(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                        uint8_t* gt_out, hipStream_t st) {
+    size_t total = 0;
+    if (int rc = many_args(c, d_src, h_src, counts, rnds, k, verdicts, &total)) return rc;
+    if (k >= plan::AGG_NONE || ((uintptr_t)d_src & 3)) {
+        g_err = "batch_verify_many_each: more than 2^32 - 2 batches, or records that are not 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (gt_out) std::memset(gt_out, 0, k * 576);
+    if (total == 0) return 0;                                     // every batch empty: every verdict false
+    HIPCHK(hipSetDevice(c->device));
+    int rc = each_reserve(c, k, gt_out != nullptr);               // the verdict bytes, the values, and the pair store at its first use
+    if (rc) return rc;
+    const pair_store ps = c->each_pairs();
+    // pass 1: the slices, their tables (groups | line-product items in aggv_tab; G2 sum items | final_of in grp.items), the scalars' sources
+    struct slice_rec {
+        plan::manyeach_slice s;
+        plan::aggveach_tab t;
+        plan::aggsets_plan sum;
+        size_t tab_at, sum_at, meta_at, n_meta;
+        uint32_t lanes;
+        bool any_serial;
+    };
+    std::vector<slice_rec> slices;
+    std::vector<size_t> offs(k + 1), rel;
+    offs[0] = 0;
+    for (size_t b = 0; b < k; b++) offs[b + 1] = offs[b] + counts[b];
+    c->aggv_tab.clear(), c->grp.items.clear(), c->me_meta.clear(), c->me_rr.clear();
+    c->me_r.assign(total, 0);
+    size_t max_sets = 0, max_part = 0, max_ng = 0, max_tab = 0, max_sum_tab = 0, max_sum_items = 0, max_meta = 0;
+    for (size_t b = 0; b < k;) {
+        slice_rec sr{};
+        sr.s = plan::manyeach_cut(counts, k, b, offs[b], c->cap, ps.stride);
+        const plan::manyeach_slice& s = sr.s;
+        b = s.b1;
+        if (s.nb == 0) continue;                                  // empty batches alone
+        if (!s.single) {
+            const uint32_t ng = s.nb;
+            sr.tab_at = c->aggv_tab.size();
+            c->aggv_tab.resize(sr.tab_at + (size_t)ng * 4);
+            plan::aggveach_groups(offs.data(), plan::manyeach_as_groups(s), reinterpret_cast<plan::aggv_group*>(c->aggv_tab.data() + sr.tab_at));
+            sr.t = plan::aggveach_measure(reinterpret_cast<const plan::aggv_group*>(c->aggv_tab.data() + sr.tab_at), ng);
+            c->aggv_tab.resize(sr.tab_at + ((size_t)ng + sr.t.items) * 4);
+            const plan::aggv_group* gr = reinterpret_cast<const plan::aggv_group*>(c->aggv_tab.data() + sr.tab_at);
+            plan::aggveach_fill(sr.t, gr, ng, reinterpret_cast<plan::agg_item*>(c->aggv_tab.data() + sr.tab_at + (size_t)ng * 4));
+            rel.resize((size_t)ng + 1);
+            plan::manyeach_sum_offsets(gr, ng, rel.data());
+            sr.sum = plan::aggsets_measure(rel.data(), ng);
+            if (!sr.sum.ok) return MI355_BLS_ERR_ARG;             // (a slice is far below 2^32 sets)
+            sr.sum_at = c->grp.items.size();
+            c->grp.items.resize(sr.sum_at + sr.sum.items * 4 + ng);
+            plan::aggsets_fill(sr.sum, rel.data(), ng, reinterpret_cast<plan::agg_item*>(c->grp.items.data() + sr.sum_at),
+                               c->grp.items.data() + sr.sum_at + sr.sum.items * 4);
+            // the scalars: batchVerify's dispatch per batch (bls_batch_verifier.nim:440), addressed within the slice
+            sr.meta_at = c->me_meta.size();
+            for (uint32_t l = 0; l < ng; l++) {
+                const size_t nb_ = gr[l].count;
+                const uint8_t* rnd = rnds + 32 * (size_t)gr[l].g;
+                if (c->num_threads > 1 && nb_ >= 3) {
+                    const uint32_t B = (uint32_t)(nb_ < c->num_threads ? nb_ : c->num_threads);
+                    c->me_meta.push_back(many_meta{gr[l].first, nb_, B, sr.lanes});
+                    c->me_rr.insert(c->me_rr.end(), rnd, rnd + 32);
+                    sr.lanes += B;
+                } else {
+                    host_serial_chain(rnd, nb_, c->me_r.data() + s.set0 + gr[l].first);
+                    sr.any_serial = true;
+                }
+            }
+            sr.n_meta = c->me_meta.size() - sr.meta_at;
+            if (s.sets > max_sets) max_sets = s.sets;
+            if (sr.t.partials > max_part) max_part = sr.t.partials;
+            if (ng > max_ng) max_ng = ng;
+            if (((size_t)ng + sr.t.items) * 4 > max_tab) max_tab = ((size_t)ng + sr.t.items) * 4;
+            if (sr.sum.items * 4 + ng > max_sum_tab) max_sum_tab = sr.sum.items * 4 + ng;
+            if (sr.sum.items > max_sum_items) max_sum_items = sr.sum.items;
+            if (sr.n_meta > max_meta) max_meta = sr.n_meta;
+        }
+        slices.push_back(sr);
+    }
+    const size_t n1 = max_sets ? max_sets : 1, it1 = max_sum_items ? max_sum_items : 1, m1 = max_meta ? max_meta : 1;
+    const size_t tcap = n1 < plan::COMB_MUL_CHUNK ? (n1 + WAVE - 1) / WAVE * WAVE : plan::COMB_MUL_CHUNK;
+    const size_t pw = plan::aggveach_part_words(max_part) * 4, sw = plan::aggveach_step_words(max_ng) * 4;
+    rc = c->grp.d_flag.reserve(k * 4, k);
+    if (!rc) rc = c->grp.d_items.reserve(max_sum_tab * 4 + 16, max_sum_tab);
+    if (!rc) rc = c->grp.d_g2_prod.reserve(n1 * (size_t)G2W * 4, n1 * (size_t)G2W);
+    if (!rc) rc = c->grp.d_g2_part.reserve(it1 * (size_t)G2W * 4, it1 * (size_t)G2W);
+    if (!rc) rc = c->d_comb_g2tab.reserve(tcap * 8 * 6 * 64, 0);
+    if (!rc) rc = c->d_comb_pkflag.reserve(4, 0);
+    if (!rc) rc = c->d_comb_rnd.reserve(m1 * 32, m1 * 8);
+    if (!rc) rc = c->d_me_meta.reserve(m1 * sizeof(many_meta), m1 * sizeof(many_meta) / 4);
+    if (!rc) rc = c->d_aggv_part.reserve(pw, pw / 4);
+    if (!rc) rc = c->d_aggv_step.reserve(sw, sw / 4);
+    if (!rc) rc = c->d_aggv_tab.reserve(max_tab * 4 + 16, max_tab);
+    if (!rc) rc = c->d_aggv_carry.reserve(2 * 576, 0);
+    if (!rc) rc = c->d_aggv_work.reserve((size_t)plan::each_engine_grid_max(c->slots) * AGGV_WORK_WORDS * 4, 0);
+    if (rc) return rc;
+    const size_t g2tcap = c->d_comb_g2tab.bytes / (8 * 6 * 64);      // what the buffer holds (it may be larger than this call needs)
+    HIPCHK(hipEventRecord(c->ev[0], st));
+    HIPCHK(hipMemsetAsync(c->grp.d_flag, 0, k * 4, st));
+    HIPCHK(hipMemsetAsync(c->d_each_v, 0, k, st));                     // an empty batch has no lane: its verdict is 0, its value zero bytes
+    if (gt_out) HIPCHK(hipMemsetAsync(c->d_each_gt, 0, k * 576, st));
+    uint32_t* dg = gt_out ? c->d_each_gt.p : nullptr;
+    struct single_rec {
+        size_t b;
+        int v;
+        uint8_t gt[576];
+    };
+    std::vector<single_rec> singles;
+    // pass 2: slice after slice on the caller's stream
+    for (const slice_rec& sr : slices) {
+        const plan::manyeach_slice& s = sr.s;
+        if (s.single) {                                                // the single-batch path, which slices internally; blocking
+            size_t b = s.b0;
+            while (counts[b] == 0) b++;
+            const int serial = (c->num_threads > 1 && s.sets >= 3) ? 0 : 1;
+            single_rec r{b, 0, {}};
+            r.v = verify_common(c, d_src ? d_src + 320 * s.set0 : nullptr, d_src ? nullptr : h_src + 320 * s.set0, s.sets, rnds + 32 * b, serial, st);
+            if (r.v < 0) return r.v;
+            if (gt_out) HIPCHK(hipMemcpy(r.gt, c->d_gt, 576, hipMemcpyDeviceToHost));      // stage 4 of that call
+            singles.push_back(r);
+            continue;
+        }
+        const uint32_t n32 = (uint32_t)s.sets, ng = s.nb;
+        const plan::aggveach_plan p = plan::aggveach_for(c->slots, c->coop, n32, ng, ng);
+        const uint8_t* src = d_src ? d_src + s.set0 * 320 : c->d_sets;
+        if (!d_src) HIPCHK(hipMemcpyAsync(c->d_sets, h_src + s.set0 * 320, s.sets * 320, hipMemcpyHostToDevice, st));      // behind the last slice's kernels
+        HIPCHK(hipMemcpyAsync(c->d_aggv_tab, c->aggv_tab.data() + sr.tab_at, ((size_t)ng + sr.t.items) * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(c->grp.d_items, c->grp.items.data() + sr.sum_at, (sr.sum.items * 4 + ng) * 4, hipMemcpyHostToDevice, st));
+        const uint4* gtab = reinterpret_cast<const uint4*>(c->d_aggv_tab.p);
+        const uint4* items = gtab + ng;
+        const uint4* sum_items = reinterpret_cast<const uint4*>(c->grp.d_items.p);
+        const uint32_t* d_final = c->grp.d_items + sr.sum.items * 4;
+        // ---- scalars (verify_many's): the serial batches' from the host, zeros elsewhere, then the parallel batches' chains over them
+        if (sr.any_serial) HIPCHK(hipMemcpyAsync(c->d_r, c->me_r.data() + s.set0, s.sets * 8, hipMemcpyHostToDevice, st));
+        if (sr.lanes) {
+            many_meta* d_meta = reinterpret_cast<many_meta*>(c->d_me_meta.p);
+            HIPCHK(hipMemcpyAsync(d_meta, c->me_meta.data() + sr.meta_at, sr.n_meta * sizeof(many_meta), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(c->d_comb_rnd, c->me_rr.data() + sr.meta_at * 32, sr.n_meta * 32, hipMemcpyHostToDevice, st));
+            k_blind_many<<<plan::waves_for(sr.lanes), WAVE, 0, st>>>(c->d_comb_rnd, d_meta, (uint32_t)sr.n_meta, sr.lanes, c->d_r);
+        }
+        // ---- fork: the signature side on the context's first fork stream, hashing and [r]PK here
+        hipStream_t s2 = ensure_side(c) ? (hipStream_t)c->side : st;
+        if (s2 != st) {
+            HIPCHK(hipEventRecord(c->ev[2], st));
+            HIPCHK(hipStreamWaitEvent(s2, c->ev[2], 0));
+        }
+        const uint32_t* recs = reinterpret_cast<const uint32_t*>(src);
+        for (size_t a = 0; a < s.sets; a += plan::COMB_MUL_CHUNK) {
+            const uint32_t m = (uint32_t)(s.sets - a < plan::COMB_MUL_CHUNK ? s.sets - a : plan::COMB_MUL_CHUNK);
+            k_combsets_g2mul<<<plan::waves_for(m), WAVE, 0, s2>>>(recs + a * 80, m, c->d_r + a, c->d_comb_g2tab, g2tcap, c->grp.d_g2_prod + a * (size_t)G2W);
+        }
+        uint32_t* g2_part = c->grp.d_g2_part;
+        launch_levels(sr.sum, sum_items,
+                      [&](const uint4* it, uint32_t cnt) { k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, s2>>>(it, cnt, c->grp.d_g2_prod, g2_part); },
+                      [&](const uint4* it, uint32_t cnt) { k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, s2>>>(it, cnt, g2_part, g2_part); });
+        if (s2 != st) HIPCHK(hipEventRecord(c->ev[3], s2));
+        launch_hash_map(c, src, n32, st);                                  // H(m_i) -> pair slot i, in the forms the batch path takes for n messages
+        launch_hash_clear(c, ps, n32, st);
+        HIPCHK(hipMemsetAsync(c->d_comb_pkflag, 0, 4, st));               // k_pkmul's one word for all keys: the batches' own words are k_manyeach_setup's
+        if (plan::pkmul_spread_for(c->slots, c->coop, n32))
+            k_pkmul_spread<<<plan::waves_for(n32), WAVE, 0, st>>>(src, n32, c->d_r, ps.P, ps.stride, c->d_comb_pkflag, c->d_pktab);
+        else k_pkmul<<<plan::waves_for(n32), WAVE, 0, st>>>(src, n32, c->d_r, ps.P, ps.stride, c->d_comb_pkflag, c->d_pktab);
+        if (s2 != st) HIPCHK(hipStreamWaitEvent(st, c->ev[3], 0));        // join
+        k_manyeach_setup<<<p.setup_grid, WAVE, 0, st>>>(recs, n32, gtab, ng, d_final, g2_part, ps.H, ps.P, ps.stride, c->grp.d_flag);
+        launch_lines(ps, p.lines, st);
+        const uint32_t n_part = (uint32_t)(sr.t.partials ? sr.t.partials : 1);
+        uint32_t *part = c->d_aggv_part, *step = c->d_aggv_step;
+        launch_levels(sr.t, items,
+                      [&](const uint4* it, uint32_t cnt) {
+                          k_aggveach_l0<<<dim3(plan::waves_for(cnt), N_LINES), WAVE, 0, st>>>(it, cnt, ps.lines, ps.stride, n32, part, n_part, step);
+                      },
+                      [&](const uint4* it, uint32_t cnt) { k_aggveach_ln<<<dim3(plan::waves_for(cnt), N_LINES), WAVE, 0, st>>>(it, cnt, part, n_part, step); });
+        if (!p.tail_engine) k_aggveach_tail<<<p.tail_grid, WAVE, 0, st>>>(step, gtab, ng, c->grp.d_flag, c->d_aggv_carry, c->d_each_v, dg);
+        else k_aggveach_engine_rows<<<p.tail_grid, K_TAIL_THREADS, 0, st>>>(step, gtab, ng, c->grp.d_flag, c->d_aggv_carry, c->d_each_v, dg, c->d_aggv_work);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(c->ev[1], st));
+    HIPCHK(hipMemcpyAsync(verdicts, c->d_each_v, k, hipMemcpyDeviceToHost, st));
+    if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, c->d_each_gt, k * 576, hipMemcpyDeviceToHost, st));
+    // the scalars and the random bytes are blinding material: nothing of them stays on the device, or in the context's host vectors
+    if (max_sets) HIPCHK(hipMemsetAsync(c->d_r, 0, max_sets * 8, st));
+    if (max_meta) HIPCHK(hipMemsetAsync(c->d_comb_rnd, 0, max_meta * 32, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::fill(c->me_r.begin(), c->me_r.end(), 0);
+    std::fill(c->me_rr.begin(), c->me_rr.end(), 0);
+    for (const single_rec& r : singles) {
+        verdicts[r.b] = (uint8_t)r.v;
+        if (gt_out) std::memcpy(gt_out + r.b * 576, r.gt, 576);
+    }
+    c->me_passes++;
+    c->last_n = 0;                             // fetch_stage shows the last call, and this one left no batch stages
+    c->sig_slots = 0;
+    c->agg_valid = false;
+    c->have_gt = false;
+    rc = collect_timings(c, 1);
+    if (rc) return rc;
+    int all = 1;
+    for (size_t b = 0; b < k; b++) all &= verdicts[b] == 1;
+    return all;
+}
+extern "C" int mi355_bls_batch_verify_many_each(mi355_bls_ctx* c, const void* sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[]) {
+    return manyeach_run(c, nullptr, (const uint8_t*)sets, counts, rnds, k, verdicts, nullptr, nullptr);
+}
+extern "C" int mi355_bls_batch_verify_many_each_device(mi355_bls_ctx* c, const void* d_sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                                                       void* stream) {
+    return manyeach_run(c, (const uint8_t*)d_sets, nullptr, counts, rnds, k, verdicts, nullptr, (hipStream_t)stream);
+}
+// TEST HOOKS: the host form with the 576-byte value of every batch (zero bytes for an empty one; stage 4 of the single-batch call for a
+// batch that took that path); the number of per-batch passes this context has made
+extern "C" int mi355_bls_debug_batch_verify_many_each_gt(mi355_bls_ctx* c, const void* sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                                                         uint8_t* gt_out) {
+    if (k && !gt_out) return MI355_BLS_ERR_ARG;
+    return manyeach_run(c, nullptr, (const uint8_t*)sets, counts, rnds, k, verdicts, gt_out, nullptr);
+}
+extern "C" int mi355_bls_debug_batch_verify_many_each_passes(mi355_bls_ctx* c) { return c ? c->me_passes : MI355_BLS_ERR_ARG; }
+
+// The merged pass of batch_verify_many first, where it may run; only a call in which it fails (or cannot run) pays for the per-batch pass
+static int many_locate(mi355_bls_ctx* c, const uint8_t* d_src, const uint8_t* h_src, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[],
+                       hipStream_t st) {
+    size_t total = 0;
+    if (int rc = many_args(c, d_src, h_src, counts, rnds, k, verdicts, &total)) return rc;
+    if (total == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    bool merged_ok = false;
+    if (int rc = many_merged_pass(c, d_src, h_src, counts, rnds, k, total, st, &merged_ok)) return rc;
+    if (merged_ok) return many_all_pass(counts, k, verdicts);
+    return manyeach_run(c, d_src, h_src, counts, rnds, k, verdicts, nullptr, st);      // (1 where the merged pass could not run and every batch verifies)
+}
+extern "C" int mi355_bls_batch_verify_many_locate(mi355_bls_ctx* c, const void* sets, const size_t counts[], const uint8_t* rnds, size_t k, uint8_t verdicts[]) {
+    return many_locate(c, nullptr, (const uint8_t*)sets, counts, rnds, k, verdicts, nullptr);
+}
+extern "C" int mi355_bls_batch_verify_many_locate_device(mi355_bls_ctx* c, const void* d_sets, const size_t counts[], const uint8_t* rnds, size_t k,
+                                                         uint8_t verdicts[], void* stream) {
+    return many_locate(c, (const uint8_t*)d_sets, nullptr, counts, rnds, k, verdicts, (hipStream_t)stream);
 }
 
 static int shard_enqueue(mi355_bls_ctx* c, const void* d_sets, const uint8_t* h_sets, size_t n_total, uint32_t chunk_lo, uint32_t chunk_hi, const uint8_t rnd[32],

@@ -38,6 +38,7 @@
 #include "aggsets.hpp"
 #include "aggbits.hpp"
 #include "combsets.hpp"
+#include "manyeach.hpp"
 #include "bymsg.hpp"
 #include "aggsigs.hpp"
 #include "recover.hpp"
@@ -2596,6 +2597,30 @@ __global__ void __launch_bounds__(K_TAIL_THREADS) k_aggveach_engine_rows(const u
                                                                          const uint32_t* __restrict__ bad, uint32_t* __restrict__ carry, uint8_t* __restrict__ verdicts,
                                                                          uint32_t* __restrict__ gt, uint32_t* __restrict__ work) {
     aggveach_engine_body(step, gtab, ng, bad, carry, verdicts, gt, work);
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): batch b of a slice is group b of the per-group path above, so the
+// levels and the tail are k_aggveach_l0 / k_aggveach_ln / k_aggveach_tail / k_aggveach_engine_rows as they stand; the pairs come from the batch
+// path's kernels ([r_i]PK_i: k_pkmul into the P column, H(m_i): the hashing kernels into the H column), the per-batch signature sums from
+// k_combsets_g2mul and k_combsets_g2_sum.  This kernel joins them (csrc/manyeach.hpp).
+// ------------------------------------------------------------------------------------------
+// One lane per pair slot of a slice of n sets in ng batches (gtab: plan::aggv_group, first = the batch's first set in the slice).  i < n: the
+// key of record i checked - the all-zero image raises the word of the set's batch in `bad` (indexed by the batch's number in the call),
+// which forces the verdict to 0 in the tail as update() would; a lane per SET, like k_aggveach_records: one lane per batch would walk a
+// batch of thousands of keys alone.  n <= i < n + ng: (-G1, the signature sum of batch i - n: partial final_of[i - n] of `g2_part`) into
+// pair slot i, where k_aggveach_l0 looks for the group's signature line.
+__global__ void __launch_bounds__(WAVE) k_manyeach_setup(const uint32_t* __restrict__ recs, uint32_t n, const uint4* __restrict__ gtab, uint32_t ng,
+                                                         const uint32_t* __restrict__ final_of, const uint32_t* __restrict__ g2_part, uint4* __restrict__ H,
+                                                         uint4* __restrict__ Pst, size_t stride, uint32_t* __restrict__ bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        if (manyeach_key_is_inf(recs + (size_t)i * 80)) atomicOr(bad + gtab[manyeach_group_of(i, ng, [&](uint32_t l) { return gtab[l].y; })].x, 1u);
+    } else if (i < n + ng) {
+        const manyeach_pair pr = manyeach_sig_pair(ld_g2_int(g2_part + (size_t)final_of[i - n] * G2W));
+        soa_st_g1(Pst, stride, i, pr.p);
+        soa_st_g2(H, stride, i, pr.q);
+    }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -139,6 +139,8 @@ inline lines_plan lines_for(uint32_t slots, bool coop, uint32_t npairs, uint32_t
 //   SIDE_FORK      a small batch in latency mode: [r]PK on a fork stream of its own, the signature side on the other, beside the hashing;
 //   SIDE_FORK_SIG  a whole-device batch of one caller: only the signature side (and its extra pairs' lines) beside the hashing.
 enum side_mode { SIDE_NONE, SIDE_FORK, SIDE_FORK_SIG };
+// [r]PK of n sets: k_pkmul_spread (one wave per SIMD) while the grid is at most a wave per slot in latency mode | k_pkmul
+inline bool pkmul_spread_for(uint32_t slots, bool coop, uint32_t n) { return coop && waves_for(n) <= slots; }
 enum stream_role { STREAM_CALLER, STREAM_SIDE, STREAM_SIDE2 };
 struct slice_plan {
     uint32_t nb;                       // waves of the one-lane-per-set kernels ([r]PK, the signature side's conversion, histogram, scatter)
@@ -164,7 +166,7 @@ inline slice_plan slice_for(uint32_t slots, bool coop, bool have_side, size_t n)
     p.sig_stream = (fork || fork_sig) ? STREAM_SIDE : STREAM_CALLER;
     p.hash_map = hash_map_for(slots, coop, n32);
     p.clear = clear_for(slots, coop, n32);
-    p.pkmul_spread = coop && p.nb <= slots;
+    p.pkmul_spread = pkmul_spread_for(slots, coop, n32);
     // the signature side as a bucket fold: `total` extra Miller pairs n .. n + total - 1 (every batch size: for a handful of tuples the
     // 256 nearly empty buckets are still cheaper than one 64-bit G2 multiplication per tuple)
     p.cw = n >= SIG_WIDE_MIN ? 8 : 4, p.nwin = 64 / p.cw, p.total = p.nwin << p.cw;
@@ -702,6 +704,51 @@ inline aggveach_plan aggveach_for(uint32_t slots, bool coop, uint32_t pairs, uin
 // (s x partials + p) x F12_WORDS; group i's step s at (i x N_LINES + s) x F12_WORDS, the 68 values the tail walks side by side)
 inline size_t aggveach_part_words(size_t partials) { return (partials ? partials : 1) * (size_t)N_LINES * F12_WORDS; }
 inline size_t aggveach_step_words(size_t ng) { return (ng ? ng : 1) * (size_t)N_LINES * F12_WORDS; }
+
+// Per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): k batches of counts[b] sets, laid end to end.  Batch b is one
+// GROUP of the per-group path above: its pairs are ([r_i]PK_i, H(m_i)) for its sets, its signature pair (-G1, sum [r_i]S_i), so the group
+// tables, the item levels and the tail are aggveach_groups / aggveach_measure / aggveach_fill / aggveach_for as they stand; the per-batch
+// signature sums are a segmented G2 sum over aggsets_measure / aggsets_fill's tables (manyeach_sum_offsets).
+//   Cutting (manyeach_cut): a slice is a run of WHOLE consecutive batches.  It holds at most cap_sets sets (the hashing workspace, the
+//   scalars and k_pkmul's tables are sized by the context's max_sets) and its sets plus one signature slot per non-empty batch fit
+//   cap_pairs, the slots of the per-set path's pair store.  No batch is ever cut, so no group is open at a slice boundary.  A batch that
+//   does not fit an empty slice (more than cap_sets sets, or sets + 1 > cap_pairs) is a slice by itself and is marked `single`: the host
+//   layer gives it to the single-batch path, which slices internally.  Empty batches ride in the slice that meets them: no pair, no slot,
+//   no lane; their verdict is 0.
+struct manyeach_slice {
+    size_t b0, b1;                     // batches [b0, b1) of the call
+    size_t set0, sets;                 // their sets: [set0, set0 + sets) of the call's record sequence
+    uint32_t nb;                       // non-empty batches among them = signature slots = groups
+    bool single;                       // one batch that fits no slice: the single-batch path, alone (nb == 1)
+    size_t pairs() const { return sets + nb; }
+};
+inline bool manyeach_fits_alone(size_t n, size_t cap_sets, size_t cap_pairs) { return n <= cap_sets && n + 1 <= cap_pairs; }
+// the slice that starts at batch b, whose first set is set0 of the call (b == k: b1 == b0, nothing is left)
+inline manyeach_slice manyeach_cut(const size_t* counts, size_t k, size_t b, size_t set0, size_t cap_sets, size_t cap_pairs) {
+    manyeach_slice s{};
+    s.b0 = s.b1 = b, s.set0 = set0;
+    for (; b < k; b++) {
+        const size_t n = counts[b];
+        if (n == 0) {
+            s.b1 = b + 1;
+            continue;
+        }
+        if (!manyeach_fits_alone(n, cap_sets, cap_pairs)) {
+            if (s.nb == 0) s.sets = n, s.nb = 1, s.b1 = b + 1, s.single = true;      // alone; behind whole batches it starts the next slice
+            break;
+        }
+        if (s.sets + n > cap_sets || s.sets + n + s.nb + 1 > cap_pairs) break;
+        s.sets += n, s.nb++, s.b1 = b + 1;
+    }
+    return s;
+}
+// the slice as the per-group path takes it: offsets = the k + 1 prefix sums of counts; no group is open at either end
+inline aggv_slice manyeach_as_groups(const manyeach_slice& s) { return aggv_slice{s.b0, s.b1, s.set0, s.set0 + s.sets, s.nb, false, false}; }
+// the signature sums' segments: group l of the slice = products [rel[l], rel[l + 1]) (rel: nb + 1 entries), from the slice's group table
+inline void manyeach_sum_offsets(const aggv_group* gr, uint32_t nb, size_t* rel) {
+    for (uint32_t l = 0; l < nb; l++) rel[l] = gr[l].first;
+    rel[nb] = nb ? (size_t)gr[nb - 1].first + gr[nb - 1].count : 0;
+}
 
 // ------------------------------------------------------------------------------------------
 // Pippenger MSM (blst_p1s_mult_pippenger / blst_p2s_mult_pippenger): what msm_enqueue follows, and what msm_reserve allocates.
