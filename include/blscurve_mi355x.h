@@ -604,6 +604,54 @@ int mi355_bls_p1s_mult_pippenger_many(mi355_bls_ctx* ctx, uint8_t* ret, const vo
 int mi355_bls_p1s_mult_pippenger_many_device(mi355_bls_ctx* ctx, uint8_t* ret, void* d_out, const void* d_points, size_t npoints, const void* d_scalars,
                                              const size_t* offsets, size_t k, size_t nbits, void* stream);
 
+/* Fixed-base G1 MSM over a precomputed window table: blst_p1s_mult_wbits_precompute(_sizeof) and blst_p1s_mult_wbits (blst_abi.nim:327-335)
+ * for callers whose point set does not change - k commitments over one SRS or Lagrange table.  A table is a library-owned handle that keeps, in
+ * device memory, the rows [2^(w wbits)] P_i for w = 0 .. W - 1, W = ceil((nbits + 1) / wbits), W x npoints x 128 bytes
+ * (mi355_bls_p1s_table_sizeof), and carries its parameters.  An MSM is then sum_i sum_w d_(i,w) T[w][i] over the signed wbits-bit digits d of
+ * the scalars: no window needs a doubling chain, and the W windows of an MSM share S <= W bucket sets (csrc/plan.hpp fixed_for), so the
+ * reductions shrink by W / S.  Points, scalars, nbits and results mean what they mean in mi355_bls_p1s_mult_pippenger_device: 96-byte
+ * blst_p1_affine images (all-zero = infinity, contributes nothing; subgroup membership is not assumed), 32-byte little-endian scalar images of
+ * which the low nbits count, nbits in 1..256, results blst_p1 (Jacobian, 144 B), an infinite one 144 zero bytes; compare results as points.
+ *   wbits     5 .. 16 (at least one 16-bucket segment, at most 2^15 buckets per set), or 0: the plan chooses from npoints (8 below 2^14 points,
+ *             16 from there on: csrc/plan.hpp fixed_wbits_for).  Choose a width that leaves the top window, (nbits + 1) - (W - 1) wbits bits, about as
+ *             wide as the others: a narrow one crowds every point into its few buckets (12-bit windows on 255-bit scalars: 4x slower than the generic call).
+ *             Windows are uniform; digits are the signed digits of the Pippenger sort over nbits + 1 bits.
+ *   reuse     a table made for nbits serves every mult call with nbits at most the table's; a larger nbits is MI355_BLS_ERR_ARG.  The table is
+ *             memory of the creating context's device and usable through any context on that device: the ctx of a mult call supplies
+ *             workspace and streams only.  Destroying the context that made a table does not free it; mi355_bls_p1s_table_destroy does
+ *             (NULL: a no-op).
+ *   _create / _mult_table / _mult_table_many          host arrays (contiguous), staged and run on the null stream
+ *   _create_device / _mult_table(_many)_device        arrays in device memory; everything is enqueued on `stream` and waited for once
+ *   _many     k MSMs over the one table - the shared-base form of mi355_bls_p1s_mult_pippenger_many: scalars k x npoints x 32 bytes, MSM j uses
+ *             [j npoints, (j + 1) npoints); results to ret (host, k x 144 B, may be NULL in the device form) and / or d_out (device, 4-byte
+ *             aligned, may be NULL).  k == 0 returns 0 and touches nothing; k == 1 is the single call.
+ * MI355_BLS_ERR_ARG, before anything is launched: NULL arguments, npoints == 0 at create, wbits outside {0, 5..16}, nbits outside 1..256, more
+ * than 2^31 table entries (W x npoints; csrc/plan.hpp FIXED_ENTRIES_MAX: a sorted index word names an entry in 31 bits beside the digit's sign),
+ * a table of another device.  No other call is refused for its size: a call beyond one pass runs as consecutive passes over ranges of MSMs
+ * inside the library.  Variable time, like every MSM here.
+ * Cost (one MI355X, device-resident, 255 bits, median of 5 blocking calls, against the generic call in the same run, the plan's own wbits;
+ * nim-blscurve_amd/tools/bench_msm_table.py, profiles/msm_table_bench.json): FASTER at 4 096 points (0.99 against 1.34 ms), at 2^16 (1.14
+ * against 1.58) and for k = 8 / 64 / 512 MSMs over 4 096 points (1.09 / 2.45 / 14.5 against 1.42 / 2.64 / 17.9 ms); SLOWER at 2^20 points (5.00
+ * against 4.36 ms).  Create: 2.1 - 2.6 ms up to 2^16 points, 28 ms at 2^20 (2 GB); paid for after 5 - 12 uses where the call wins. */
+typedef struct mi355_bls_p1s_table mi355_bls_p1s_table;
+size_t mi355_bls_p1s_table_sizeof(size_t npoints, size_t wbits, size_t nbits);      /* device bytes a table takes; 0 for arguments create refuses */
+int mi355_bls_p1s_table_create(mi355_bls_ctx* ctx, mi355_bls_p1s_table** out, const void* points96, size_t npoints, size_t wbits, size_t nbits);
+int mi355_bls_p1s_table_create_device(mi355_bls_ctx* ctx, mi355_bls_p1s_table** out, const void* d_points96, size_t npoints, size_t wbits, size_t nbits,
+                                      void* stream);
+void mi355_bls_p1s_table_destroy(mi355_bls_p1s_table* tab);
+int mi355_bls_p1s_mult_table(mi355_bls_ctx* ctx, uint8_t ret_p1[144], const mi355_bls_p1s_table* tab, const void* scalars32, size_t nbits);
+int mi355_bls_p1s_mult_table_device(mi355_bls_ctx* ctx, uint8_t ret_p1[144], const mi355_bls_p1s_table* tab, const void* d_scalars32, size_t nbits,
+                                    void* stream);
+int mi355_bls_p1s_mult_table_many(mi355_bls_ctx* ctx, uint8_t* ret, const mi355_bls_p1s_table* tab, const void* scalars32, size_t k, size_t nbits);
+int mi355_bls_p1s_mult_table_many_device(mi355_bls_ctx* ctx, uint8_t* ret, void* d_out, const mi355_bls_p1s_table* tab, const void* d_scalars32, size_t k,
+                                         size_t nbits, void* stream);
+/* TEST HOOKS: rows [w0, w0 + nw) x points [i0, i0 + ni) of the table as 96-byte blst_p1_affine images (all-zero = infinity), row-major; the
+ * (W, S, buckets per set) the last mult call on this context ran with; and the plan's parameters for the following mult calls on this context:
+ * force_sets bucket sets per MSM (capped at W) and at most pairs_max (point, scalar) pairs per pass beyond a pass's first MSM (0: the plan's own). */
+int mi355_bls_debug_p1s_table_rows(const mi355_bls_p1s_table* tab, size_t w0, size_t nw, size_t i0, size_t ni, uint8_t* out96);
+int mi355_bls_debug_p1s_table_last_plan(mi355_bls_ctx* ctx, uint32_t out[3]);
+int mi355_bls_debug_p1s_table_set_plan(mi355_bls_ctx* ctx, uint32_t force_sets, uint32_t pairs_max);
+
 /* Point-sharded MSM across the GPUs of one node (blst_p1s_mult_pippenger, blst_abi.nim:336-340, over devices; the bench shape
  * benchmarks/bls12381_msm_g1.nim:47-59): device g computes the full-width partial sum of points [first_g, first_g + count_g)
  * (mi355_bls_msm_shard_range: balanced contiguous blocks), the 144-byte partials are added (blst_p1_add_or_double,

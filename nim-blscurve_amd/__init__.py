@@ -156,6 +156,19 @@ def lib():
         L.mi355_bls_p1s_mult_pippenger_device.argtypes = [vp, ctypes.c_char_p, vp, sz, vp, sz, vp]
         L.mi355_bls_p1s_mult_pippenger_many.argtypes = [vp, vp, vp, sz, vp, psz, sz, sz]
         L.mi355_bls_p1s_mult_pippenger_many_device.argtypes = [vp, vp, vp, vp, sz, vp, psz, sz, sz, vp]
+        L.mi355_bls_p1s_table_sizeof.argtypes = [sz, sz, sz]
+        L.mi355_bls_p1s_table_sizeof.restype = sz
+        L.mi355_bls_p1s_table_create.argtypes = [vp, vp, vp, sz, sz, sz]
+        L.mi355_bls_p1s_table_create_device.argtypes = [vp, vp, vp, sz, sz, sz, vp]
+        L.mi355_bls_p1s_table_destroy.argtypes = [vp]
+        L.mi355_bls_p1s_table_destroy.restype = None
+        L.mi355_bls_p1s_mult_table.argtypes = [vp, vp, vp, vp, sz]
+        L.mi355_bls_p1s_mult_table_device.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.mi355_bls_p1s_mult_table_many.argtypes = [vp, vp, vp, vp, sz, sz]
+        L.mi355_bls_p1s_mult_table_many_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp]
+        L.mi355_bls_debug_p1s_table_rows.argtypes = [vp, sz, sz, sz, sz, vp]
+        L.mi355_bls_debug_p1s_table_last_plan.argtypes = [vp, pu32]
+        L.mi355_bls_debug_p1s_table_set_plan.argtypes = [vp, u32, u32]
         cp = ctypes.c_char_p
         L.mi355_bls_deserialize_sets.argtypes = [vp, cp, cp, cp, sz, vp, vp]
         L.mi355_bls_deserialize_sets_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp]
@@ -1526,6 +1539,103 @@ def p1s_mult_pippenger_many_device(cache, d_points, npoints, d_scalars, offsets,
     out = ctypes.create_string_buffer(144 * k)
     _check(lib().mi355_bls_p1s_mult_pippenger_many_device(cache._h, out, d_out, d_points, npoints, d_scalars, arr, k, nbits, stream))
     return [out.raw[144 * j:144 * j + 144] for j in range(k)]
+
+
+class P1sTable:
+    """A fixed-base window table (mi355_bls_p1s_table_create): the handle and the parameters it was asked for.  It outlives the cache that
+    made it; p1s_table_destroy (or destroy()) releases it."""
+
+    def __init__(self, handle, npoints, wbits, nbits):
+        self._h, self.npoints, self.wbits, self.nbits = handle, npoints, wbits, nbits
+
+    def destroy(self):
+        if self._h:
+            lib().mi355_bls_p1s_table_destroy(self._h)
+            self._h = None
+
+
+def p1s_table_sizeof(npoints, wbits=0, nbits=255):
+    """device bytes a table takes; 0 for arguments p1s_table_create refuses"""
+    return lib().mi355_bls_p1s_table_sizeof(npoints, wbits, nbits)
+
+
+def p1s_table_create(cache, points, wbits=0, nbits=255):
+    """blst_p1s_mult_wbits_precompute: the rows [2^(w wbits)] P_i of n 96-byte affine points -> P1sTable.  wbits 5..16, or 0: the plan's rule."""
+    if len(points) % 96:
+        raise ValueError("points: n x 96 bytes")
+    n = len(points) // 96
+    h = ctypes.c_void_p()
+    _check(lib().mi355_bls_p1s_table_create(cache._h, ctypes.byref(h), bytes(points), n, wbits, nbits))
+    return P1sTable(h, n, wbits, nbits)
+
+
+def p1s_table_create_device(cache, d_points, npoints, wbits=0, nbits=255, stream=0):
+    """the same with the points in device memory (a pointer as an integer)"""
+    h = ctypes.c_void_p()
+    _check(lib().mi355_bls_p1s_table_create_device(cache._h, ctypes.byref(h), d_points, npoints, wbits, nbits, stream))
+    return P1sTable(h, npoints, wbits, nbits)
+
+
+def p1s_table_destroy(table):
+    if table is not None:
+        table.destroy()
+
+
+def p1s_mult_table(cache, table, scalars, nbits=255):
+    """blst_p1s_mult_wbits: sum_i [k_i mod 2^nbits] P_i over the table's points -> the 144-byte blst_p1; scalars: n x 32 bytes"""
+    if len(scalars) != 32 * table.npoints:
+        raise ValueError("scalars: one 32-byte scalar per point of the table")
+    out = ctypes.create_string_buffer(144)
+    _check(lib().mi355_bls_p1s_mult_table(cache._h, out, table._h, bytes(scalars), nbits))
+    return out.raw
+
+
+def p1s_mult_table_device(cache, table, d_scalars, nbits=255, stream=0):
+    out = ctypes.create_string_buffer(144)
+    _check(lib().mi355_bls_p1s_mult_table_device(cache._h, out, table._h, d_scalars, nbits, stream))
+    return out.raw
+
+
+def p1s_mult_table_many(cache, table, scalars, nbits=255):
+    """k MSMs over the one table -> a list of k 144-byte blst_p1 results; scalars: k x n x 32 bytes, MSM j uses [j n, (j + 1) n)"""
+    if len(scalars) % (32 * table.npoints):
+        raise ValueError("scalars: k x n x 32 bytes")
+    k = len(scalars) // (32 * table.npoints)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(144 * k)
+    _check(lib().mi355_bls_p1s_mult_table_many(cache._h, out, table._h, bytes(scalars), k, nbits))
+    return [out.raw[144 * j:144 * j + 144] for j in range(k)]
+
+
+def p1s_mult_table_many_device(cache, table, d_scalars, k, nbits=255, d_out=None, stream=0):
+    """The same with the scalars in device memory; the results come back as a list and, when d_out (a device pointer to k x 144 bytes) is
+    given, are left there as well."""
+    if k == 0:
+        _check(lib().mi355_bls_p1s_mult_table_many_device(cache._h, None, d_out, table._h, d_scalars, 0, nbits, stream))
+        return []
+    out = ctypes.create_string_buffer(144 * k)
+    _check(lib().mi355_bls_p1s_mult_table_many_device(cache._h, out, d_out, table._h, d_scalars, k, nbits, stream))
+    return [out.raw[144 * j:144 * j + 144] for j in range(k)]
+
+
+def debug_p1s_table_rows(table, w0, nw, i0, ni):
+    """TEST HOOK: rows [w0, w0 + nw) x points [i0, i0 + ni) as a list of nw lists of ni 96-byte affine images"""
+    out = ctypes.create_string_buffer(max(1, 96 * nw * ni))
+    _check(lib().mi355_bls_debug_p1s_table_rows(table._h, w0, nw, i0, ni, out))
+    return [[out.raw[96 * (r * ni + c):96 * (r * ni + c + 1)] for c in range(ni)] for r in range(nw)]
+
+
+def debug_p1s_table_last_plan(cache):
+    """TEST HOOK: (W, S, buckets per set) of the last table mult call on this cache"""
+    out = (ctypes.c_uint32 * 3)()
+    _check(lib().mi355_bls_debug_p1s_table_last_plan(cache._h, out))
+    return tuple(out)
+
+
+def debug_p1s_table_set_plan(cache, force_sets=0, pairs_max=0):
+    """TEST HOOK: bucket sets per MSM and pairs per pass of the following table mult calls on this cache (0: the plan's own)"""
+    _check(lib().mi355_bls_debug_p1s_table_set_plan(cache._h, force_sets, pairs_max))
 
 
 def _split_compressed(pubkeys, messages, signatures):

@@ -41,6 +41,18 @@ struct dev_buf {
     int reserve(size_t n, size_t slack) { return n <= bytes ? 0 : alloc(n + slack); }
 };
 
+// A fixed-base window table (mi355_bls_p1s_table_create): the rows in device memory and the parameters they were made with.  It belongs to its
+// caller, not to the context that made it: mi355_bls_p1s_table_destroy releases it, on its own device.
+struct mi355_bls_p1s_table {
+    int device = 0;
+    size_t npoints = 0;
+    uint32_t wbits = 0, nbits = 0, nwin = 0;     // nwin = plan::fixed_nwin(wbits, nbits) rows of npoints entries
+    dev_buf<uint32_t> rows;                      // entry w x npoints + i: k_pip_convert's 32-word record of [2^(w wbits)] P_i
+    ~mi355_bls_p1s_table() {
+        if (rows) (void)hipSetDevice(device);
+    }
+};
+
 // H: the handle; Destroy: what releases it
 template <class H, hipError_t (*Destroy)(H)>
 struct dev_handle {

@@ -26,6 +26,14 @@ struct msm_many_ws {
     dev_buf<uint32_t> pts_int, offs_dev, hist, offs, cursor, order, chist, sorted, part, out;
     dev_buf<uint4> buckets, segout;
 };
+// MSMs over a fixed-base window table (mi355_bls_p1s_mult_table*): each buffer grown to the call's largest pass (plan::fixed_sizes_for); the
+// scratch columns of k_ptab_rows (mi355_bls_p1s_table_create)
+struct ptab_ws {
+    dev_buf<uint32_t> scratch, hist, offs, cursor, order, chist, sorted, part, out;
+    dev_buf<uint4> buckets, segout;
+    uint32_t last_plan[3] = {0, 0, 0};              // (W, S, buckets per set) of the last mult call (mi355_bls_debug_p1s_table_last_plan)
+    uint32_t force_S = 0, pairs_max = 0;            // test hook (mi355_bls_debug_p1s_table_set_plan); 0: the plan's own
+};
 
 // What the "k groups in one device pass" calls share: every buffer is sized by the call, never by max_sets, grown on demand with a quarter of
 // slack (grouped_upload, stage_inputs), and free again when the call returns - each of them drains its stream first.  Who uses what:
@@ -190,6 +198,7 @@ struct mi355_bls_ctx {
     // k MSMs in one pass (mi355_bls_p1s_mult_pippenger_many): made at the first such call
     msm_many_ws msm_many;
     std::vector<uint32_t> many_offs; // the ragged passes' offsets of the call in flight: the async copies read them
+    ptab_ws ptab;                    // MSMs over a fixed-base window table: made at the first such call
     // per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): sized by the largest slice of a call; it runs in the per-set path's
     // pair store with the per-group path's tables, partials and step values (d_aggv_*) and combine_sets' G2 products and tables (grp, d_comb_*)
     dev_buf<uint8_t> d_me_meta;      // k_blind_many's table of a slice's parallel batches
@@ -3584,6 +3593,146 @@ extern "C" int mi355_bls_p1s_mult_pippenger_many(mi355_bls_ctx* c, uint8_t* ret,
     HIPCHK(hipMemcpyAsync(m->d_pts, points, npoints * 96, hipMemcpyHostToDevice, nullptr));
     HIPCHK(hipMemcpyAsync(m->d_sc, scalars, nsc * 32, hipMemcpyHostToDevice, nullptr));
     return msm_many_run(c, ret, nullptr, m->d_pts, npoints, m->d_sc, offsets, k, nbits, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Fixed-base G1 MSM over a precomputed window table (blst_p1s_mult_wbits_precompute / blst_p1s_mult_wbits, blst_abi.nim:327-335): a walk
+// over plan::fixed_for / fixed_next
+// ------------------------------------------------------------------------------------------
+extern "C" size_t mi355_bls_p1s_table_sizeof(size_t npoints, size_t wbits, size_t nbits) { return plan::fixed_table_bytes(npoints, wbits, nbits); }
+extern "C" void mi355_bls_p1s_table_destroy(mi355_bls_p1s_table* tab) { delete tab; }
+extern "C" int mi355_bls_p1s_table_create_device(mi355_bls_ctx* c, mi355_bls_p1s_table** out, const void* d_points, size_t npoints, size_t wbits, size_t nbits,
+                                                 void* stream) {
+    if (!c || !out || !d_points || !plan::fixed_args_ok(npoints, wbits, nbits)) return MI355_BLS_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    std::unique_ptr<mi355_bls_p1s_table> t(new mi355_bls_p1s_table());
+    t->device = c->device, t->npoints = npoints, t->nbits = (uint32_t)nbits;
+    t->wbits = wbits ? (uint32_t)wbits : plan::fixed_wbits_for(npoints);
+    t->nwin = plan::fixed_nwin(t->wbits, nbits);
+    const uint32_t chunk = plan::fixed_rows_chunk(npoints, t->nwin);
+    int rc = t->rows.alloc(plan::fixed_table_bytes(npoints, t->wbits, nbits));
+    rc = rc ? rc : c->ptab.scratch.reserve((size_t)chunk * t->nwin * plan::FIXED_ENTRY_BYTES, 0);
+    if (rc) return rc;
+    for (size_t i0 = 0; i0 < npoints; i0 += chunk) {
+        const uint32_t cnt = (uint32_t)(npoints - i0 < chunk ? npoints - i0 : chunk);
+        k_ptab_rows<<<plan::waves_for(cnt), WAVE, 0, st>>>((const uint8_t*)d_points, (uint32_t)npoints, (uint32_t)i0, cnt, t->nwin, t->wbits, t->rows, c->ptab.scratch);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    *out = t.release();
+    return 0;
+}
+// host array -> staging -> create_device on the null stream
+extern "C" int mi355_bls_p1s_table_create(mi355_bls_ctx* c, mi355_bls_p1s_table** out, const void* points96, size_t npoints, size_t wbits, size_t nbits) {
+    if (!c || !out || !points96 || !plan::fixed_args_ok(npoints, wbits, nbits)) return MI355_BLS_ERR_ARG;
+    const uint8_t* d[1];
+    if (int rc = stage_inputs(c, {{points96, npoints * 96}}, nullptr, d)) return rc;
+    return mi355_bls_p1s_table_create_device(c, out, d[0], npoints, wbits, nbits, nullptr);
+}
+// The argument rules of the mult entries, made without looking into the context: 0 go on, 1 nothing to do (k == 0), or the error.
+static int ptab_check(const mi355_bls_ctx* c, const void* ret, const void* d_out, const mi355_bls_p1s_table* tab, const void* scalars, size_t k, size_t nbits) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 1;
+    if (!tab || !scalars || (!ret && !d_out) || nbits == 0 || nbits > 256 || nbits > tab->nbits || tab->device != c->device) return MI355_BLS_ERR_ARG;
+    return 0;
+}
+// Arguments checked (ptab_check returned 0).  Every pass is enqueued on `st`; the results land in d_out (or the workspace's own k x 144 bytes),
+// are copied to ret, and the stream is waited for once.
+static int ptab_run(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const mi355_bls_p1s_table* tab, const void* d_scalars, size_t k, size_t nbits, hipStream_t st) {
+    ptab_ws* m = &c->ptab;
+    const plan::fixed_plan P = plan::fixed_for(tab->npoints, plan::fixed_win(tab->wbits, nbits), k, c->slots, m->pairs_max ? m->pairs_max : plan::FIXED_PAIRS_MAX, m->force_S);
+    const plan::fixed_sizes sz = plan::fixed_sizes_for(P, k);
+    int rc = 0;
+    const auto grow = [&rc](auto& buf, size_t bytes) { rc = rc ? rc : buf.reserve(bytes, 0); };
+    grow(m->hist, sz.hist), grow(m->offs, sz.hist), grow(m->cursor, sz.hist), grow(m->order, sz.hist), grow(m->chist, sz.chist), grow(m->sorted, sz.sorted);
+    grow(m->buckets, sz.buckets), grow(m->segout, sz.segout), grow(m->part, sz.part);
+    if (!d_out) grow(m->out, k * 144);
+    if (rc) return rc;
+    m->last_plan[0] = P.W.nwin, m->last_plan[1] = P.S, m->last_plan[2] = 1u << P.W.cbk;
+    uint32_t* dst = d_out ? (uint32_t*)d_out : m->out.p;
+    const uint8_t* sc = (const uint8_t*)d_scalars;
+    const pip_win W{P.W};
+    pip_win Wsum{};                                      // S windows of width 0: k_pip_rowtail_many's walk adds an MSM's S parts and doubles nothing
+    Wsum.nwin = P.S;
+    bool timed = false;
+    for (size_t j = 0; j < k;) {
+        const plan::fixed_pass s = plan::fixed_next(P, k, j);
+        j = s.j1;
+        const uint32_t kp = (uint32_t)(s.j1 - s.j0);
+        const fixed_addr A{s.pairs, P.n, W.nwin, P.S, W.cbk};
+        const uint8_t* psc = sc + s.pair0 * 32;
+        HIPCHK(hipMemsetAsync(m->hist, 0, (size_t)s.total * 4, st));
+        HIPCHK(hipMemsetAsync(m->chist, 0, 256 * 4, st));
+        const bool t = !timed;
+        timed = true;
+        if (t) HIPCHK(hipEventRecord(c->ev[0], st));
+        k_ptab_hist<<<dim3(s.pair_grid, W.nwin), WAVE, 0, st>>>(psc, A, W, m->hist);
+        k_ptab_scan<<<s.nv, WAVE, 0, st>>>(m->hist, A, m->offs, m->cursor);
+        k_ptab_scatter<<<dim3(s.pair_grid, W.nwin), WAVE, 0, st>>>(psc, A, W, m->cursor, m->sorted);
+        k_msm_order_hist<<<s.order_grid, WAVE, 0, st>>>(m->hist, s.total, m->chist);
+        k_msm_order_scan<<<1, 1, 0, st>>>(m->chist);
+        k_msm_order_scatter<<<s.order_grid, WAVE, 0, st>>>(m->hist, s.total, m->chist, m->order);
+        if (t) HIPCHK(hipEventRecord(c->ev[1], st));
+        // the records are the table's rows; offs holds positions in `sorted` itself (k_ptab_scan): n = 0 takes k_pip_bucket's own window x n out
+        k_pip_bucket<fp><<<s.bucket_grid, WAVE, 0, st>>>(tab->rows, m->sorted, m->offs, m->hist, m->order, 0, W.cbk, s.total, 0, s.total, m->buckets);
+        if (t) HIPCHK(hipEventRecord(c->ev[2], st));
+        if (s.team == 4) k_pip_segred_team<4><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        else if (s.team == 2) k_pip_segred_team<2><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        else k_pip_segred<fp><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        k_pip_winpart<fp><<<dim3(s.nv, P.nsplit), WAVE, 0, st>>>(m->segout, s.nseg, P.segs_per_set, 0, m->part);
+        if (t) HIPCHK(hipEventRecord(c->ev[3], st));
+        k_pip_rowtail_many<<<kp, P.tail_lanes, 0, st>>>(m->part, P.nsplit, Wsum, dst + s.j0 * 36);
+        if (t) HIPCHK(hipEventRecord(c->ev[4], st));
+        HIPCHK(hipGetLastError());
+    }
+    if (ret) HIPCHK(hipMemcpyAsync(ret, dst, k * 144, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return collect_timings(c, 4);       // the first pass's stages: [0] sort and order, [1] bucket accumulation, [2] reductions, [3] the sums
+}
+extern "C" int mi355_bls_p1s_mult_table_many_device(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const mi355_bls_p1s_table* tab, const void* d_scalars, size_t k,
+                                                    size_t nbits, void* stream) {
+    const int chk = ptab_check(c, ret, d_out, tab, d_scalars, k, nbits);
+    if (chk) return chk < 0 ? chk : 0;
+    HIPCHK(hipSetDevice(c->device));
+    return ptab_run(c, ret, d_out, tab, d_scalars, k, nbits, (hipStream_t)stream);
+}
+// host array -> staging -> ptab_run on the null stream
+extern "C" int mi355_bls_p1s_mult_table_many(mi355_bls_ctx* c, uint8_t* ret, const mi355_bls_p1s_table* tab, const void* scalars32, size_t k, size_t nbits) {
+    const int chk = ptab_check(c, ret, nullptr, tab, scalars32, k, nbits);
+    if (chk) return chk < 0 ? chk : 0;
+    const uint8_t* d[1];
+    if (int rc = stage_inputs(c, {{scalars32, k * tab->npoints * 32}}, nullptr, d)) return rc;
+    return ptab_run(c, ret, nullptr, tab, d[0], k, nbits, nullptr);
+}
+extern "C" int mi355_bls_p1s_mult_table_device(mi355_bls_ctx* c, uint8_t ret_p1[144], const mi355_bls_p1s_table* tab, const void* d_scalars, size_t nbits, void* stream) {
+    if (!ret_p1) return MI355_BLS_ERR_ARG;
+    return mi355_bls_p1s_mult_table_many_device(c, ret_p1, nullptr, tab, d_scalars, 1, nbits, stream);
+}
+extern "C" int mi355_bls_p1s_mult_table(mi355_bls_ctx* c, uint8_t ret_p1[144], const mi355_bls_p1s_table* tab, const void* scalars32, size_t nbits) {
+    if (!ret_p1) return MI355_BLS_ERR_ARG;
+    return mi355_bls_p1s_mult_table_many(c, ret_p1, tab, scalars32, 1, nbits);
+}
+extern "C" int mi355_bls_debug_p1s_table_rows(const mi355_bls_p1s_table* tab, size_t w0, size_t nw, size_t i0, size_t ni, uint8_t* out96) {
+    if (!tab || !out96 || w0 > tab->nwin || nw > tab->nwin - w0 || i0 > tab->npoints || ni > tab->npoints - i0 || nw * ni > ((size_t)1 << 24)) return MI355_BLS_ERR_ARG;
+    if (nw * ni == 0) return 0;
+    HIPCHK(hipSetDevice(tab->device));
+    dev_buf<uint32_t> d;
+    if (int rc = d.alloc(nw * ni * 96)) return rc;
+    k_debug_ptab_rows<<<plan::waves_for((uint32_t)(nw * ni)), WAVE, 0, nullptr>>>(tab->rows, (uint32_t)tab->npoints, (uint32_t)w0, (uint32_t)nw, (uint32_t)i0, (uint32_t)ni, d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out96, d, nw * ni * 96, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int mi355_bls_debug_p1s_table_last_plan(mi355_bls_ctx* c, uint32_t out[3]) {
+    if (!c || !out) return MI355_BLS_ERR_ARG;
+    for (int i = 0; i < 3; i++) out[i] = c->ptab.last_plan[i];
+    return 0;
+}
+extern "C" int mi355_bls_debug_p1s_table_set_plan(mi355_bls_ctx* c, uint32_t force_sets, uint32_t pairs_max) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    c->ptab.force_S = force_sets, c->ptab.pairs_max = pairs_max;
+    return 0;
 }
 
 // blst's list convention (blst_p1s_mult_pippenger and friends): list[0] points at element 0; for every following element the

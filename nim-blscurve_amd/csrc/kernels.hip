@@ -44,6 +44,7 @@
 #include "recover.hpp"
 #include "keytable.hpp"
 #include "msmmany.hpp"
+#include "msmtable.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -2214,6 +2215,72 @@ __global__ void __launch_bounds__(1024) k_pip_rowtail_many(const uint32_t* __res
         } else {
             st_jac_blst(out, r);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Fixed-base G1 MSM over a precomputed window table (mi355_bls_p1s_table_* / mi355_bls_p1s_mult_table*; csrc/msmtable.hpp, plan.hpp fixed_for).
+//   k_ptab_rows                                  lane per point: its W rows [2^(w wbits)] P_i, one inversion per lane (msmtable.hpp ptab_rows_lane)
+//   k_ptab_hist / k_ptab_scan / k_ptab_scatter   k_pipm_*'s counting sort, lane per (pair, window): the W windows of MSM j fold into its S bucket
+//                                                sets (window w -> set j S + w mod S), the sorted word names table entry w n + i
+// Between the sort and the sum of an MSM's S window parts the kernels above run as they are, on (MSMs of the pass) x S windows; the sum is
+// k_pip_rowtail_many under a window plan of S windows of width 0 (no doubling).
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(WAVE) k_ptab_rows(const uint8_t* __restrict__ pts, uint32_t n, uint32_t i0, uint32_t cnt, uint32_t nwin, uint32_t wbits,
+                                                    uint32_t* __restrict__ tab, uint32_t* __restrict__ scratch) {
+    const uint32_t l = blockIdx.x * WAVE + threadIdx.x;
+    if (l >= cnt) return;
+    const uint32_t i = i0 + l;
+    ptab_rows_lane(ld_g1a_blst(reinterpret_cast<const uint32_t*>(pts + (size_t)i * 96)), i, n, l, cnt, nwin, wbits, tab, scratch);
+}
+__global__ void __launch_bounds__(WAVE) k_ptab_hist(const uint8_t* __restrict__ sc, fixed_addr A, pip_win W, uint32_t* __restrict__ hist) {
+    const uint32_t p = blockIdx.x * WAVE + threadIdx.x, w = blockIdx.y;
+    if (p >= A.pairs) return;
+    const int32_t d = pipm_digit(sc, p, W, w);
+    if (d) atomicAdd(&hist[fixed_bucket(A, fixed_owner(A, p), w, (uint32_t)(d < 0 ? -d : d))], 1u);
+}
+// one wave per bucket set
+__global__ void __launch_bounds__(WAVE) k_ptab_scan(const uint32_t* __restrict__ hist, fixed_addr A, uint32_t* __restrict__ offs, uint32_t* __restrict__ cursor) {
+    const uint32_t v = blockIdx.x, nb = 1u << A.cbk, per = (nb + WAVE - 1) / WAVE;
+    const uint32_t lo = threadIdx.x * per, hi = lo + per < nb ? lo + per : nb;
+    const uint32_t* h = hist + ((size_t)v << A.cbk);
+    uint32_t sum = 0;
+    for (uint32_t b = lo; b < hi; b++) sum += h[b];
+    uint32_t incl = sum;
+    for (int d = 1; d < WAVE; d <<= 1) {
+        uint32_t o = __shfl_up(incl, d, WAVE);
+        if ((int)threadIdx.x >= d) incl += o;
+    }
+    uint32_t run = fixed_list_start(A, v) + incl - sum;
+    for (uint32_t b = lo; b < hi; b++) {
+        offs[((size_t)v << A.cbk) | b] = run;
+        cursor[((size_t)v << A.cbk) | b] = run;
+        run += h[b];
+    }
+}
+__global__ void __launch_bounds__(WAVE) k_ptab_scatter(const uint8_t* __restrict__ sc, fixed_addr A, pip_win W, uint32_t* __restrict__ cursor, uint32_t* __restrict__ sorted) {
+    const uint32_t p = blockIdx.x * WAVE + threadIdx.x, w = blockIdx.y;
+    if (p >= A.pairs) return;
+    const int32_t d = pipm_digit(sc, p, W, w);
+    if (d) {
+        const uint32_t j = fixed_owner(A, p);
+        const uint32_t pos = atomicAdd(&cursor[fixed_bucket(A, j, w, (uint32_t)(d < 0 ? -d : d))], 1u);
+        sorted[pos] = fixed_entry(A, w, fixed_point(A, p, j)) | (d < 0 ? 0x80000000u : 0u);
+    }
+}
+// TEST HOOK (mi355_bls_debug_p1s_table_rows): rows [w0, w0 + nw) x points [i0, i0 + ni) of a table as blst_p1_affine images, row-major
+__global__ void __launch_bounds__(WAVE) k_debug_ptab_rows(const uint32_t* __restrict__ tab, uint32_t n, uint32_t w0, uint32_t nw, uint32_t i0, uint32_t ni,
+                                                          uint32_t* __restrict__ out) {
+    const uint32_t t = blockIdx.x * WAVE + threadIdx.x;
+    if (t >= nw * ni) return;
+    const uint32_t w = w0 + t / ni, i = i0 + t % ni;
+    const uint32_t* e = tab + ((size_t)w * n + i) * (2 * FPW);
+    uint32_t* o = out + (size_t)t * 24;
+    if (e[FP_N]) {
+        for (int q = 0; q < 24; q++) o[q] = 0;
+    } else {
+        st_fp_blst(o, ld_fp_int(e));
+        st_fp_blst(o + 12, ld_fp_int(e + FPW));
     }
 }
 

@@ -1043,6 +1043,160 @@ inline msm_many_sizes msm_many_sizes_for(const msm_many_plan& P, const size_t* o
     return m;
 }
 
+// ------------------------------------------------------------------------------------------
+// Fixed-base G1 MSM over a precomputed window table (mi355_bls_p1s_table_* / mi355_bls_p1s_mult_table*): what ptab_run follows and reserves.
+// The table holds, for point i and window w, the affine row T[w][i] = [2^(w wbits)] P_i at entry w x npoints + i (k_pip_convert's record).
+// An MSM is sum_i sum_w d_(i,w) T[w][i] over the signed digits d of the existing sort: no window needs a Horner step, so all W windows of
+// an MSM may share buckets.  MSM j of a pass owns S bucket SETS (1 <= S <= W), window w falls into set j S + w mod S; from the sort on,
+// k_msm_order_*, k_pip_bucket, k_pip_segred(_team) and k_pip_winpart see one MSM of (MSMs of the pass) x S windows, and k_pip_rowtail_many,
+// given a window plan of S windows of width 0, adds each MSM's S window parts without a doubling.
+//   windows        UNIFORM: W = ceil((nbits + 1) / wbits) windows of wbits bits (fixed_win: wrem = 0, wbase = wbits), 2^(wbits - 1) buckets per
+//                  set.  A table made for nbits serves every smaller nbits: its first W' <= W rows.
+//   wbits          5 .. 16 (pip_for's limits), or the rule fixed_wbits_for: changed once after the first measurement, see there.
+//   S              fixed_for: the fewest sets with which the buckets of one pass give k_pip_bucket two waves per SIMD.  A first choice: the
+//                  benchmark has run with it, no other rule was tried.
+//   one pass       a range of whole MSMs: at least one, further ones while the pairs stay within pairs_max (FIXED_PAIRS_MAX; a parameter so
+//                  that a test can cut a small call) and the sets and buckets within msm_many's limits.  One MSM always fits: a table has at
+//                  most FIXED_ENTRIES_MAX entries, so its W lists hold at most 2^31 positions.
+// Measured with nim-blscurve_amd/tools/bench_msm_table.py (profiles/msm_table_bench.json; DESIGN.md 3.2.9 says where the call wins and loses).
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t FIXED_WBITS_MIN = 5, FIXED_WBITS_MAX = 16;
+// k_pip_bucket reads a sorted word as (record index & 0x7fffffff, sign = bit 31) and addresses the record at 128 x index in 64 bits: a table
+// may hold at most 2^31 entries (W x npoints).
+constexpr uint64_t FIXED_ENTRIES_MAX = 1ull << 31;
+constexpr size_t FIXED_ENTRY_BYTES = 2 * FP_WORDS * 4;
+constexpr uint32_t FIXED_PAIRS_MAX = MSM_MANY_PAIRS_MAX;
+constexpr size_t FIXED_SCRATCH_BYTES = (size_t)256 << 20;      // k_ptab_rows: Z and prefix-product columns of one chunk of points
+inline uint32_t fixed_nwin(size_t wbits, size_t nbits) { return (uint32_t)((nbits + 1 + wbits - 1) / wbits); }
+// 8 bits below 2^14 points, 16 from there on.  Uniform windows leave the TOP window (nbits + 1) - (W - 1) wbits bits; where that is much less
+// than wbits, all n points of that window crowd into its few buckets and k_pip_bucket's one lane per bucket adds them serially.  The first
+// rule here, about log2(n) bits, chose 12 at 4 096 points: 255-bit scalars then have a 4-bit top window, and the bucket kernel took 4.9 ms of
+// a 5.4 ms call (1.34 ms generic); 1.18 s at 2^20 points.  For 255- and 256-bit scalars the widths whose top window is full are 8 and 16;
+// measured (profiles/msm_table_bench.json), 8 wins every 4 096-point shape and 16 wins at 2^16 points, where 8 has too few buckets (32 x 128)
+// to fill the chip.  The hand-over between them, 2^14, is not measured.
+constexpr size_t FIXED_WBITS_WIDE_FROM = (size_t)1 << 14;
+inline uint32_t fixed_wbits_for(size_t npoints) { return npoints < FIXED_WBITS_WIDE_FROM ? 8 : 16; }
+// what create accepts (wbits 0: the rule)
+inline bool fixed_args_ok(size_t npoints, size_t wbits, size_t nbits) {
+    if (npoints == 0 || nbits == 0 || nbits > 256 || (wbits != 0 && (wbits < FIXED_WBITS_MIN || wbits > FIXED_WBITS_MAX))) return false;
+    if (npoints > FIXED_ENTRIES_MAX) return false;
+    const uint64_t W = fixed_nwin(wbits ? wbits : fixed_wbits_for(npoints), nbits);
+    return W * (uint64_t)npoints <= FIXED_ENTRIES_MAX;
+}
+// device bytes of a table; 0 for arguments create refuses
+inline size_t fixed_table_bytes(size_t npoints, size_t wbits, size_t nbits) {
+    if (!fixed_args_ok(npoints, wbits, nbits)) return 0;
+    return (size_t)fixed_nwin(wbits ? wbits : fixed_wbits_for(npoints), nbits) * npoints * FIXED_ENTRY_BYTES;
+}
+// the windows of a call as the kernels take them; wbits in 5 .. 16, nbits in 1 .. 256
+inline pip_win fixed_win(size_t wbits, size_t nbits) {
+    pip_win W{};
+    W.nbits = (uint32_t)nbits;
+    W.nwin = fixed_nwin(wbits, nbits);
+    W.wbase = (uint32_t)wbits, W.wrem = 0;
+    W.cbk = (uint32_t)wbits - 1;
+    for (uint32_t w = 0; w + 1 < W.nwin; w++) {
+        const uint32_t bit = w * W.wbase + W.wbase - 1;      // + 2^(wbits - 1) at every window but the top one; bit < 272
+        W.H[bit >> 5] |= 1u << (bit & 31);
+    }
+    return W;
+}
+// k_ptab_rows: points per launch, so that the two scratch columns of a chunk stay within FIXED_SCRATCH_BYTES (at least a wave)
+inline uint32_t fixed_rows_chunk(size_t npoints, uint32_t nwin) {
+    size_t c = FIXED_SCRATCH_BYTES / ((size_t)nwin * FIXED_ENTRY_BYTES);
+    c = c / WAVE * WAVE;
+    if (c < WAVE) c = WAVE;
+    return (uint32_t)(c < npoints ? c : npoints);
+}
+struct fixed_plan {
+    pip_win W;                         // of the CALL's nbits (the table's wbits)
+    uint32_t n;                        // points = pairs per MSM
+    uint32_t S;                        // bucket sets per MSM
+    uint32_t buckets_per_msm;          // S << cbk
+    uint32_t segs_per_set, nsplit;     // as msm_plan's per window
+    uint32_t tail_waves, tail_lanes;   // k_pip_rowtail_many's workgroup (one per MSM): a wave per set up to MSM_TAIL_WAVES_MAX
+    uint32_t pairs_max, msms_max;      // what a pass takes at the most (it always takes one MSM)
+};
+// W: fixed_win of the table's wbits and the call's nbits; slots: the device's wave slots at one wave per SIMD; force_S: a test's choice (0: the rule)
+inline fixed_plan fixed_for(size_t npoints, const pip_win& W, size_t k, uint32_t slots, uint32_t pairs_max = FIXED_PAIRS_MAX, uint32_t force_S = 0) {
+    fixed_plan P{};
+    P.W = W;
+    P.n = (uint32_t)npoints;
+    P.pairs_max = pairs_max;
+    size_t fit = npoints ? pairs_max / npoints : 1;      // MSMs of a pass by the pair bound
+    if (fit < 1) fit = 1;
+    if (fit > k && k) fit = k;
+    // two waves per SIMD of one-lane-per-bucket work: 2 x slots x WAVE buckets in the pass
+    const uint64_t want = 2ull * slots * WAVE, have = (uint64_t)fit << W.cbk;
+    uint64_t S = (want + have - 1) / have;
+    if (S < 1) S = 1;
+    if (S > W.nwin) S = W.nwin;
+    if (force_S) S = force_S > W.nwin ? W.nwin : force_S;
+    P.S = (uint32_t)S;
+    P.buckets_per_msm = P.S << W.cbk;
+    P.segs_per_set = (1u << W.cbk) / MSM_SEG;
+    P.nsplit = P.segs_per_set >= 1024 ? 16 : (P.segs_per_set >= 128 ? 4 : 1);
+    P.tail_waves = P.S < MSM_TAIL_WAVES_MAX ? P.S : MSM_TAIL_WAVES_MAX;
+    P.tail_lanes = P.tail_waves * WAVE;
+    const uint32_t by_sets = MSM_MANY_VWIN_MAX / P.S, by_buckets = MSM_MANY_BUCKETS_MAX / P.buckets_per_msm;      // >= 1: 52 sets of 2^4, 17 of 2^15
+    P.msms_max = by_sets < by_buckets ? by_sets : by_buckets;
+    return P;
+}
+// One pass of a call: MSMs [j0, j1) of k
+struct fixed_pass {
+    size_t j0, j1;
+    size_t pair0;                      // the pass's first pair in the call's scalar array
+    uint32_t pairs;
+    uint32_t nv, total, nseg;          // bucket sets, buckets, 16-bucket segments
+    uint32_t pair_grid;                // x of k_ptab_hist / k_ptab_scatter (y: the W windows): a lane per pair
+    uint32_t order_grid, bucket_grid;  // k_msm_order_hist / _scatter, k_pip_bucket over all buckets of the pass
+    uint32_t team, segred_grid;        // k_pip_segred_team<team> (4, 2) | k_pip_segred (1)
+};
+inline fixed_pass fixed_next(const fixed_plan& P, size_t k, size_t j0) {
+    fixed_pass s{};
+    s.j0 = j0, s.j1 = j0 + 1;
+    s.pair0 = j0 * (size_t)P.n;
+    size_t pairs = P.n;
+    while (s.j1 < k && s.j1 - j0 < P.msms_max && pairs + P.n <= P.pairs_max) pairs += P.n, s.j1++;
+    const uint32_t kp = (uint32_t)(s.j1 - j0);
+    s.pairs = (uint32_t)pairs;
+    s.nv = kp * P.S;
+    s.total = kp * P.buckets_per_msm;
+    s.nseg = s.nv * P.segs_per_set;
+    s.pair_grid = waves_for(s.pairs);
+    s.order_grid = (s.total + WAVE * MSM_ORD_PER - 1) / (WAVE * MSM_ORD_PER);
+    s.bucket_grid = waves_for(s.total);
+    s.team = (size_t)s.nseg * 4 <= MSM_TEAM_LANES_MAX ? 4 : ((size_t)s.nseg * 2 <= MSM_TEAM_LANES_MAX ? 2 : 1);
+    s.segred_grid = waves_for(s.nseg * s.team);
+    return s;
+}
+// The buffers of the workspace in bytes.  fixed_extents: what the kernels of one pass touch, read off their indexing; fixed_sizes_for: what
+// ptab_run grows the workspace to before a call - the largest extent over the call's passes (tests/test_msm_table_plan.py holds every pass
+// to that).
+struct fixed_sizes {
+    size_t hist;                       // one word per bucket: hist, offs, cursor, order alike
+    size_t chist;                      // k_msm_order_*: 256 bins
+    size_t sorted;                     // set v's list from word msmtable.hpp fixed_list_start(v): pairs x W words in all
+    size_t buckets, segout;            // SoA Jacobian G1 points: rows of `total` / `nseg`
+    size_t part;                       // k_pip_winpart: a Jacobian point at (set x nsplit + part)
+    size_t out;                        // a blst_p1 image per MSM of the pass
+};
+inline fixed_sizes fixed_extents(const fixed_plan& P, const fixed_pass& s) {
+    fixed_sizes z{};
+    z.hist = (size_t)s.total * 4;
+    z.chist = 256 * 4;
+    z.sorted = (size_t)s.pairs * P.W.nwin * 4;
+    z.buckets = (size_t)s.total * G1_WORDS * 4;
+    z.segout = (size_t)s.nseg * G1_WORDS * 4;
+    z.part = (size_t)s.nv * P.nsplit * G1_WORDS * 4;
+    z.out = (s.j1 - s.j0) * 144;
+    return z;
+}
+inline fixed_sizes fixed_sizes_for(const fixed_plan& P, size_t k) {
+    // every pass takes as many MSMs as the first one, but the last, which takes the rest: the first pass bounds them all
+    return k ? fixed_extents(P, fixed_next(P, k, 0)) : fixed_sizes{};
+}
+
 // chunk of the parallel_chunks partition (parallel_chunks.nim:42-66) that tuple t of n_total falls into, B chunks
 inline uint32_t chunk_of_tuple(size_t n_total, uint32_t B, size_t t) {
     size_t base = n_total / B, rem = n_total % B, cut = (base + 1) * rem;
