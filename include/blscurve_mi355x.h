@@ -449,6 +449,64 @@ int mi355_bls_aggregate_verify_each_device(mi355_bls_ctx* ctx, const void* d_key
                                            const void* d_msgs32, const void* d_sigs192, uint8_t* out, void* stream);
 int mi355_bls_debug_aggregate_verify_each_gt(mi355_bls_ctx* ctx, const void* keys, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
                                              const void* msgs32, const void* sigs192, uint8_t* out, uint8_t* gt_out);
+/* PAIRING-PRODUCT CHECKS over pairs the caller already holds, k at once: the batched device counterpart of blst_miller_loop_n + blst_final_exp +
+ * blst_fp12_finalverify with blst_p1_affine_in_g1 / blst_p2_affine_in_g2 in front (blst_abi.nim:294,317,453-461).  Every verifier above builds
+ * its own pairs, (pk, H(m)) and (-G1, sig); these calls take any (P, Q) - what a caller who commits on the device (mi355_bls_p1s_mult_table_many)
+ * needs to verify openings, e.g. e(C - [y]G1, G2) * e(-pi, [tau - z]G2) == 1.
+ *   p1s96     n x 96-byte blst_p1_affine images;  q2s192: n x 192-byte blst_p2_affine images.  All zero: the point at infinity.  Pair i is
+ *             (p1s96[i], q2s192[i]).  Coordinates are canonical Montgomery images, as blst writes them.
+ *   offsets   k + 1 entries in HOST memory, non-decreasing, offsets[0] == 0, offsets[k] == n: group g is pairs [offsets[g], offsets[g+1]).
+ *   flags     0: the caller vouches that every operand is on its curve and in G1 / G2 - the precondition of every verifier of this library.
+ *             MI355_BLS_PAIR_VALIDATE: the device checks every finite operand for both (the comparison and the endomorphism tests of the
+ *             uncompressed decoders); a failing pair never reaches the Miller loop with its own coordinates (it is given infinite operands)
+ *             and forces the verdict of its group to 0.
+ *   status    n bytes, host memory: MI355_BLS_PAIR_* per pair (P is checked first).  May be NULL when flags == 0 (all zero if given); required
+ *             under MI355_BLS_PAIR_VALIDATE.
+ * pairing_check_each:  out[g] = [ final_exp( prod_j miller(P_gj, Q_gj) ) == 1 ], k bytes of host memory.  A pair with an operand at infinity
+ *             contributes 1 (blst_miller_loop_n skips it).  An EMPTY group is the empty product: verdict 1 - on purpose unlike the
+ *             signature-level calls above, whose 0 for empty input is the reference's scheme-level rule (bls_sig_min_pubkey.nim:167-169), not
+ *             arithmetic.  Returns 1 iff every out[g] is 1; k == 0: 0, nothing written.
+ * pairing_products:    the same, and gt_out (k x 576 bytes, host memory) receives the blst_fp12 image of every group's value after the final
+ *             exponentiation - the library's fixed exponent, the one oracle/bls12381_py.py final_exp defines and every other path of
+ *             this library uses, so two values are comparable with each other and with the debug hooks' values.  An empty group: the image of one.  Compare e(A, B) with e(C, D) through it.
+ * batch_pairing_check: ONE verdict for all k checks: [ final_exp( prod_g prod_j miller([r_g]P_gj, Q_gj) ) == 1 ], r_g the g-th 64-bit scalar of
+ *             the serial blinding chain from rnd32 (the chain mi355_bls_batch_verify_serial gives set g; nonzero by construction).  The G1
+ *             side is multiplied; G2 is not touched.  Empty groups contribute nothing; every group empty: 1; k == 0: 0.  The scalars are
+ *             cleared from host and device memory before the call returns.  SOUNDNESS: a false check passes with probability 2^-64 only when
+ *             every operand is in G1 / G2 - vouched for (flags == 0) or checked (MI355_BLS_PAIR_VALIDATE); a failing pair makes the verdict 0.
+ * batch_pairing_check_locate: batch_pairing_check first; out (k bytes) is all 1 when it passes, else pairing_check_each fills it.  Returns the
+ *             first call's verdict.
+ * debug_batch_pairing_check_scalars: TEST HOOK, batch_pairing_check with k scalars of the test's choice and the 576-byte value in gt_out.
+ * No call is refused for its size: a call runs in slices of at most max_sets pairs - whole groups while they fit, a longer group in parts
+ * whose Miller values are multiplied together on the device.  MI355_BLS_ERR_ARG, before anything is launched, for a NULL context (first),
+ * NULL arrays with work to do, offsets that decrease or do not start at 0, a device pointer that is not 4-byte aligned, unknown flag bits,
+ * status == NULL under MI355_BLS_PAIR_VALIDATE.  The _device forms take p1s96 / q2s192 in device memory, enqueue on `stream` and synchronise
+ * it once.  The width of the per-step line products (AGGV_C = 8) and the tail hand-over are inherited from aggregate_verify_each and were not
+ * re-measured.  COST: nim-blscurve_amd/tools/bench_pairing_check.py writes profiles/pairing_check_bench.json; README.md says whether it has run. */
+#define MI355_BLS_PAIR_VALIDATE 1u
+#define MI355_BLS_PAIR_OK 0
+#define MI355_BLS_PAIR_P_OFF_CURVE 1
+#define MI355_BLS_PAIR_P_NOT_IN_G1 2
+#define MI355_BLS_PAIR_Q_OFF_CURVE 3
+#define MI355_BLS_PAIR_Q_NOT_IN_G2 4
+int mi355_bls_pairing_check_each(mi355_bls_ctx* ctx, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags, uint8_t* out,
+                                 uint8_t* status);
+int mi355_bls_pairing_check_each_device(mi355_bls_ctx* ctx, const void* d_p1s96, const void* d_q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                        uint8_t* out, uint8_t* status, void* stream);
+int mi355_bls_pairing_products(mi355_bls_ctx* ctx, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags, uint8_t* out,
+                               uint8_t* status, uint8_t* gt_out);
+int mi355_bls_pairing_products_device(mi355_bls_ctx* ctx, const void* d_p1s96, const void* d_q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                      uint8_t* out, uint8_t* status, uint8_t* gt_out, void* stream);
+int mi355_bls_batch_pairing_check(mi355_bls_ctx* ctx, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                  const uint8_t rnd32[32], uint8_t* status);
+int mi355_bls_batch_pairing_check_device(mi355_bls_ctx* ctx, const void* d_p1s96, const void* d_q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                         const uint8_t rnd32[32], uint8_t* status, void* stream);
+int mi355_bls_batch_pairing_check_locate(mi355_bls_ctx* ctx, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                         const uint8_t rnd32[32], uint8_t* status, uint8_t* out);
+int mi355_bls_batch_pairing_check_locate_device(mi355_bls_ctx* ctx, const void* d_p1s96, const void* d_q2s192, const size_t* offsets, size_t k,
+                                                uint32_t flags, const uint8_t rnd32[32], uint8_t* status, uint8_t* out, void* stream);
+int mi355_bls_debug_batch_pairing_check_scalars(mi355_bls_ctx* ctx, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                                const uint64_t* r, uint8_t* status, uint8_t* gt_out);
 /* serialize(Signature) (bls_sig_io.nim:225-234), i.e. blst_p2_affine_compress, for n signatures: 192-byte blst_p2_affine images in, 96 bytes
  * each out (ZCash form: big-endian x.c1 then x.c0, bit 7 of byte 0 set, bit 5 set when y is the lexicographically larger root - decided by
  * y.c1 unless it is zero, then by y.c0; the all-zero infinity image gives 0xc0 and 95 zero bytes).  The device form writes device memory

@@ -133,6 +133,15 @@ def lib():
         L.mi355_bls_aggregate_verify_each.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp]
         L.mi355_bls_aggregate_verify_each_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_debug_aggregate_verify_each_gt.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp, vp]
+        L.mi355_bls_pairing_check_each.argtypes = [vp, vp, vp, psz, sz, u32, vp, vp]
+        L.mi355_bls_pairing_check_each_device.argtypes = [vp, vp, vp, psz, sz, u32, vp, vp, vp]
+        L.mi355_bls_pairing_products.argtypes = [vp, vp, vp, psz, sz, u32, vp, vp, vp]
+        L.mi355_bls_pairing_products_device.argtypes = [vp, vp, vp, psz, sz, u32, vp, vp, vp, vp]
+        L.mi355_bls_batch_pairing_check.argtypes = [vp, vp, vp, psz, sz, u32, vp, vp]
+        L.mi355_bls_batch_pairing_check_device.argtypes = [vp, vp, vp, psz, sz, u32, vp, vp, vp]
+        L.mi355_bls_batch_pairing_check_locate.argtypes = [vp, vp, vp, psz, sz, u32, vp, vp, vp]
+        L.mi355_bls_batch_pairing_check_locate_device.argtypes = [vp, vp, vp, psz, sz, u32, vp, vp, vp, vp]
+        L.mi355_bls_debug_batch_pairing_check_scalars.argtypes = [vp, vp, vp, psz, sz, u32, ctypes.POINTER(ctypes.c_uint64), vp, vp]
         L.mi355_bls_aggregate_signature_sets.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp]
         L.mi355_bls_aggregate_signature_sets_device.argtypes = [vp, vp, sz, vp, psz, sz, vp, vp, vp, vp]
         L.mi355_bls_recover_signature_sets.argtypes = [vp, vp, sz, pu32, psz, sz, vp, vp, vp, vp]
@@ -1119,6 +1128,145 @@ def aggregateVerifyEachValues(cache, keys, messages, signatures):
     _check(lib().mi355_bls_debug_aggregate_verify_each_gt(cache._h, table or b"\0", n_table, idx, offs, k, ms or b"\0", sg, out, gt))
     raw = gt.raw
     return [v == 1 for v in out.raw], [raw[576 * i:576 * i + 576] for i in range(k)]
+
+
+PAIR_VALIDATE = 1
+PAIR_OK, PAIR_P_OFF_CURVE, PAIR_P_NOT_IN_G1, PAIR_Q_OFF_CURVE, PAIR_Q_NOT_IN_G2 = range(5)
+
+
+def _pair_groups(groups, flags):
+    """groups: a list of groups, each a list of (96-byte blst_p1_affine image, 192-byte blst_p2_affine image) pairs (all zero: infinity)
+    -> (p1s, q2s, offsets array, k, n, status buffer or None).  The pairs are laid end to end."""
+    if flags & ~PAIR_VALIDATE:
+        raise ValueError("unknown flag bits: %#x" % flags)
+    offs, ps, qs = [0], [], []
+    for g in groups:
+        for p, q in g:
+            if len(p) != 96 or len(q) != 192:
+                raise ValueError("a pair is a 96-byte blst_p1_affine and a 192-byte blst_p2_affine image, got %d and %d bytes" % (len(p), len(q)))
+            ps.append(bytes(p))
+            qs.append(bytes(q))
+        offs.append(len(ps))
+    k, n = len(offs) - 1, len(ps)
+    return b"".join(ps), b"".join(qs), (ctypes.c_size_t * (k + 1))(*offs), k, n, ctypes.create_string_buffer(max(n, 1))
+
+
+def _pair_scalars(r, k):
+    if len(r) != k:
+        raise ValueError("one scalar per group: %d scalars for %d groups" % (len(r), k))
+    if any(not 0 <= x < 1 << 64 for x in r):
+        raise ValueError("a scalar is an unsigned 64-bit integer")
+    return (ctypes.c_uint64 * max(k, 1))(*r)
+
+
+def pairingCheckEach(cache, groups, flags=0, with_status=False):
+    """k pairing-product checks in one device pass (mi355_bls_pairing_check_each): -> [bool], one per group: final_exp(prod miller(P, Q)) == 1.
+    A pair with an operand at infinity contributes 1; an EMPTY group is the empty product, True.  flags = PAIR_VALIDATE: the device checks every
+    finite operand (on the curve, in G1 / G2); a group holding a failing pair is False.  with_status: -> ([bool], [PAIR_* per pair])."""
+    p1, q2, offs, k, n, st = _pair_groups(groups, flags)
+    if k == 0:
+        return ([], []) if with_status else []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_pairing_check_each(cache._h, p1 or None, q2 or None, offs, k, flags, out, st))
+    v = [x == 1 for x in out.raw]
+    return (v, list(st.raw[:n])) if with_status else v
+
+
+def pairingProducts(cache, groups, flags=0, with_status=False):
+    """The same pass with every group's value (mi355_bls_pairing_products): -> ([bool], [576-byte blst_fp12 image of the group's product after
+    the final exponentiation]); an empty group's value is the image of one.  Two products are equal iff their images are."""
+    p1, q2, offs, k, n, st = _pair_groups(groups, flags)
+    if k == 0:
+        return ([], [], []) if with_status else ([], [])
+    out, gt = ctypes.create_string_buffer(k), ctypes.create_string_buffer(k * 576)
+    _check(lib().mi355_bls_pairing_products(cache._h, p1 or None, q2 or None, offs, k, flags, out, st, gt))
+    raw = gt.raw
+    v, g = [x == 1 for x in out.raw], [raw[576 * i:576 * i + 576] for i in range(k)]
+    return (v, g, list(st.raw[:n])) if with_status else (v, g)
+
+
+def batchPairingCheck(cache, groups, secureRandomBytes, flags=0, with_status=False):
+    """One verdict for all k checks (mi355_bls_batch_pairing_check): P of every pair of group g is multiplied by the g-th 64-bit scalar of the
+    serial blinding chain from secureRandomBytes, and one product is formed.  Sound only for operands in G1 / G2: vouched for, or checked with
+    flags = PAIR_VALIDATE.  No group: False."""
+    rnd = _rnd32(secureRandomBytes)
+    p1, q2, offs, k, n, st = _pair_groups(groups, flags)
+    if k == 0:
+        return (False, []) if with_status else False
+    ok = bool(_check(lib().mi355_bls_batch_pairing_check(cache._h, p1 or None, q2 or None, offs, k, flags, rnd, st)))
+    return (ok, list(st.raw[:n])) if with_status else ok
+
+
+def batchPairingCheckLocate(cache, groups, secureRandomBytes, flags=0):
+    """batchPairingCheck first; only behind a failure the per-group pass (mi355_bls_batch_pairing_check_locate) -> (bool, [bool] per group)."""
+    rnd = _rnd32(secureRandomBytes)
+    p1, q2, offs, k, n, st = _pair_groups(groups, flags)
+    if k == 0:
+        return False, []
+    out = ctypes.create_string_buffer(k)
+    ok = bool(_check(lib().mi355_bls_batch_pairing_check_locate(cache._h, p1 or None, q2 or None, offs, k, flags, rnd, st, out)))
+    return ok, [x == 1 for x in out.raw]
+
+
+def batchPairingCheckScalars(cache, groups, scalars, flags=0):
+    """Test hook (mi355_bls_debug_batch_pairing_check_scalars): the blinded form with one scalar per group of the test's choice
+    -> (bool, the 576-byte value of the one product)."""
+    p1, q2, offs, k, n, st = _pair_groups(groups, flags)
+    r = _pair_scalars(scalars, k)
+    if k == 0:
+        return False, b""
+    gt = ctypes.create_string_buffer(576)
+    ok = bool(_check(lib().mi355_bls_debug_batch_pairing_check_scalars(cache._h, p1 or None, q2 or None, offs, k, flags, r, st, gt)))
+    return ok, gt.raw
+
+
+def _pair_device_args(offsets, flags, n_status):
+    if flags & ~PAIR_VALIDATE:
+        raise ValueError("unknown flag bits: %#x" % flags)
+    k = len(offsets) - 1
+    if k >= 0 and (offsets[0] != 0 or any(b < a for a, b in zip(offsets, offsets[1:]))):
+        raise ValueError("offsets start at 0 and never decrease")
+    return k, ctypes.create_string_buffer(max(n_status, 1))
+
+
+def pairingCheckEach_device(cache, d_p1s, d_q2s, offsets, flags=0, stream=0):
+    """pairingCheckEach with the two arrays in device memory (raw pointers, 4-byte aligned); offsets stay on the host -> ([bool], [status])."""
+    k, st = _pair_device_args(offsets, flags, offsets[-1] if offsets else 0)
+    if k <= 0:
+        return [], []
+    out = ctypes.create_string_buffer(k)
+    _check(lib().mi355_bls_pairing_check_each_device(cache._h, d_p1s or None, d_q2s or None, (ctypes.c_size_t * (k + 1))(*offsets), k, flags, out, st, stream))
+    return [x == 1 for x in out.raw], list(st.raw[:offsets[-1]])
+
+
+def pairingProducts_device(cache, d_p1s, d_q2s, offsets, flags=0, stream=0):
+    k, st = _pair_device_args(offsets, flags, offsets[-1] if offsets else 0)
+    if k <= 0:
+        return [], []
+    out, gt = ctypes.create_string_buffer(k), ctypes.create_string_buffer(k * 576)
+    _check(lib().mi355_bls_pairing_products_device(cache._h, d_p1s or None, d_q2s or None, (ctypes.c_size_t * (k + 1))(*offsets), k, flags, out, st, gt, stream))
+    raw = gt.raw
+    return [x == 1 for x in out.raw], [raw[576 * i:576 * i + 576] for i in range(k)]
+
+
+def batchPairingCheck_device(cache, d_p1s, d_q2s, offsets, secureRandomBytes, flags=0, stream=0):
+    rnd = _rnd32(secureRandomBytes)
+    k, st = _pair_device_args(offsets, flags, offsets[-1] if offsets else 0)
+    if k <= 0:
+        return False
+    return bool(_check(lib().mi355_bls_batch_pairing_check_device(cache._h, d_p1s or None, d_q2s or None, (ctypes.c_size_t * (k + 1))(*offsets), k, flags, rnd, st,
+                                                                   stream)))
+
+
+def batchPairingCheckLocate_device(cache, d_p1s, d_q2s, offsets, secureRandomBytes, flags=0, stream=0):
+    rnd = _rnd32(secureRandomBytes)
+    k, st = _pair_device_args(offsets, flags, offsets[-1] if offsets else 0)
+    if k <= 0:
+        return False, []
+    out = ctypes.create_string_buffer(k)
+    ok = bool(_check(lib().mi355_bls_batch_pairing_check_locate_device(cache._h, d_p1s or None, d_q2s or None, (ctypes.c_size_t * (k + 1))(*offsets), k, flags, rnd,
+                                                                        st, out, stream)))
+    return ok, [x == 1 for x in out.raw]
 
 
 def _signature_lists(signatures):

@@ -206,6 +206,11 @@ struct mi355_bls_ctx {
     std::vector<uint8_t> me_rr;      // those batches' random bytes, and
     std::vector<uint64_t> me_r;      // the serial batches' chains by set: blinding material, wiped before the call returns
     int me_passes = 0;               // per-batch passes made on this context (mi355_bls_debug_batch_verify_many_each_passes)
+    // pairing-product checks (mi355_bls_pairing_check_each, _products, batch_pairing_check): sized by the call (plan::pairprod_sizes_for); they
+    // run in the per-set path's pair store with the per-group path's tables, partials and step values (d_aggv_*) and the grouped calls' flag words
+    dev_buf<uint8_t> d_pp_status;    // a status byte per pair of the call
+    dev_buf<uint64_t> d_pp_r;        // the blinded form's k group scalars: blinding material, cleared before every return
+    std::vector<uint64_t> pp_r;      // ... on the host, until the call's synchronisation
 
     // the batch workspace's pair store (ctx_build makes it; it never changes) and the per-set path's (each_reserve)
     pair_store batch_pairs() const { return {d_H, d_P, d_lines, stride}; }
@@ -1938,6 +1943,253 @@ extern "C" int mi355_bls_debug_aggregate_verify_each_gt(mi355_bls_ctx* c, const 
                                                         const void* msgs32, const void* sigs192, uint8_t* out, uint8_t* gt_out) {
     if (k && !gt_out) return MI355_BLS_ERR_ARG;
     return aggveach_host(c, keys, n_table, idx, offsets, k, msgs32, sigs192, out, gt_out);
+}
+
+// ------------------------------------------------------------------------------------------
+// Pairing-product checks over caller-supplied pairs (blst_miller_loop_n + blst_final_exp + blst_fp12_finalverify, blst_abi.nim:294,317,453-461,
+// for k groups in one device pass).  Group g = pairs [offsets[g], offsets[g + 1]) of two packed arrays of affine images.  One driver:
+//   r == nullptr   pairing_check_each / pairing_products: the groups are groups of the per-group path without a signature pair (plan.hpp
+//                  aggveach_cut over `cap` pairs, aggveach_fill with_sig = false); verdict bytes and values by the group's number in the call
+//   r != nullptr   the blinded form: ALL pairs are one group of that path (plan::pairprod_blind_cut), P of every pair multiplied by its own
+//                  group's scalar (k_pairprod_setup expands r to the pair slots and lays the keys out for k_pkmul); one verdict, one value
+// Per slice: one copy of its tables, k_pairprod_setup, [k_pkmul,] the Miller lines, the line product level by level, the tail.  No hashing
+// kernel runs.  Verdicts, values and status bytes come back behind the last slice: the call's only synchronisation.  The empty groups, which
+// have no lane, are fixed up on the host: verdict 1, the image of one.
+// ------------------------------------------------------------------------------------------
+// the rules that are decided before the context is looked into (c != nullptr and k != 0 are the caller's)
+static int pairprod_args(const void* p1, const void* q2, const size_t* offsets, size_t k, uint32_t flags, const uint8_t* status, bool device) {
+    if (!offsets || offsets[0] != 0 || !agg_offsets_ok(offsets, k)) {
+        g_err = "pairing_check: offsets are missing, do not start at 0, or decrease";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (offsets[k] && (!p1 || !q2)) return MI355_BLS_ERR_ARG;
+    if (flags & ~(uint32_t)MI355_BLS_PAIR_VALIDATE) {
+        g_err = "pairing_check: unknown flag bits";
+        return MI355_BLS_ERR_ARG;
+    }
+    if ((flags & MI355_BLS_PAIR_VALIDATE) && !status) {
+        g_err = "pairing_check: MI355_BLS_PAIR_VALIDATE needs the status array";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (device && (((uintptr_t)p1 | (uintptr_t)q2) & 3)) {
+        g_err = "pairing_check: device pointers must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (k >= plan::AGG_NONE || offsets[k] >= plan::AGG_NONE) {
+        g_err = "pairing_check: more than 2^32 - 2 pairs or groups (the tables are 32-bit)";
+        return MI355_BLS_ERR_ARG;
+    }
+    return 0;
+}
+static_assert(MI355_BLS_PAIR_VALIDATE == plan::PAIRPROD_VALIDATE && MI355_BLS_PAIR_Q_NOT_IN_G2 == PAIRPROD_Q_NOT_IN_G2, "the header restates pairprod.hpp's codes");
+// out: k verdict bytes (r == nullptr) or one; gt_out (may be null): as many 576-byte values.  d_p1 / d_q2: device memory (null when there is no pair).
+static int pairprod_run(mi355_bls_ctx* c, const uint8_t* d_p1, const uint8_t* d_q2, const size_t* offsets, size_t k, uint32_t flags, uint8_t* status,
+                        uint8_t* out, uint8_t* gt_out, const uint64_t* r, hipStream_t st) {
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const bool blinded = r != nullptr;
+    const size_t n = offsets[k], nres = blinded ? 1 : k;
+    // pass 1: the slices and their tables (groups | items | the blinded form's real groups, slice after slice), and what the largest needs
+    struct slice_rec {
+        plan::aggv_slice s;
+        plan::aggveach_tab t;
+        size_t tab_at;
+        uint32_t real;
+    };
+    std::vector<slice_rec> slices;
+    c->aggv_tab.clear();
+    size_t max_part = 0, max_ng = 0, max_tab = 0, max_pairs = 0;
+    const size_t one[2] = {0, n};
+    for (size_t g = 0, pos = 0;;) {
+        const plan::aggv_slice s = blinded ? plan::pairprod_blind_cut(n, pos, c->cap) : plan::aggveach_cut(offsets, k, g, pos, c->cap);
+        if (s.pairs() == 0) break;
+        const size_t at = c->aggv_tab.size();
+        c->aggv_tab.resize(at + (size_t)s.ng * 4);
+        plan::aggveach_groups(blinded ? one : offsets, s, reinterpret_cast<plan::aggv_group*>(c->aggv_tab.data() + at));
+        const plan::aggveach_tab t = plan::aggveach_measure(reinterpret_cast<const plan::aggv_group*>(c->aggv_tab.data() + at), s.ng);
+        c->aggv_tab.resize(at + ((size_t)s.ng + t.items) * 4);
+        plan::aggveach_fill(t, reinterpret_cast<const plan::aggv_group*>(c->aggv_tab.data() + at), s.ng,
+                            reinterpret_cast<plan::agg_item*>(c->aggv_tab.data() + at + (size_t)s.ng * 4), plan::AGGV_C, false);
+        uint32_t real = 0;
+        if (blinded) {
+            const plan::aggv_slice rs = plan::pairprod_real_groups(offsets, k, s.pos0, s.pos1);
+            real = rs.ng;
+            const size_t rat = c->aggv_tab.size();
+            c->aggv_tab.resize(rat + (size_t)real * 4);
+            plan::aggveach_groups(offsets, rs, reinterpret_cast<plan::aggv_group*>(c->aggv_tab.data() + rat));
+        }
+        slices.push_back({s, t, at, real});
+        const size_t entries = plan::pairprod_tab_entries(s.ng, t.items, real);
+        if (t.partials > max_part) max_part = t.partials;
+        if (s.ng > max_ng) max_ng = s.ng;
+        if (entries * 4 > max_tab) max_tab = entries * 4;
+        if (s.pairs() > max_pairs) max_pairs = s.pairs();
+        g = s.next_g(), pos = s.pos1;
+    }
+    const plan::pairprod_sizes sz = plan::pairprod_sizes_for(n, k, blinded);
+    int rc = each_reserve(c, nres, gt_out != nullptr);
+    const size_t pw = plan::aggveach_part_words(max_part) * 4, sw = plan::aggveach_step_words(max_ng) * 4;
+    if (!rc) rc = c->grp.d_flag.reserve(sz.flags, sz.flags / 4);
+    if (!rc) rc = c->d_pp_status.reserve(sz.status, sz.status / 4);
+    if (!rc && blinded) rc = c->d_pp_r.reserve(sz.scalars, sz.scalars / 4);
+    if (!rc && blinded) rc = c->d_comb_pkflag.reserve(4, 0);
+    if (!rc) rc = c->d_aggv_part.reserve(pw, pw / 4);
+    if (!rc) rc = c->d_aggv_step.reserve(sw, sw / 4);
+    if (!rc) rc = c->d_aggv_tab.reserve(max_tab * 4 + 16, max_tab);
+    if (!rc) rc = c->d_aggv_carry.reserve(2 * 576, 0);
+    if (!rc) rc = c->d_aggv_work.reserve((size_t)plan::each_engine_grid_max(c->slots) * AGGV_WORK_WORDS * 4, 0);
+    if (rc) return rc;
+    const pair_store ps = c->each_pairs();
+    HIPCHK(hipEventRecord(c->ev[0], st));
+    HIPCHK(hipMemsetAsync(c->grp.d_flag, 0, sz.flags, st));
+    HIPCHK(hipMemsetAsync(c->d_each_v, 0, nres, st));                  // a group without pairs has no lane: fixed up on the host below
+    if (gt_out) HIPCHK(hipMemsetAsync(c->d_each_gt, 0, nres * 576, st));
+    if (blinded) HIPCHK(hipMemcpyAsync(c->d_pp_r, r, k * 8, hipMemcpyHostToDevice, st));
+    uint32_t* dg = gt_out ? c->d_each_gt.p : nullptr;
+    uint8_t* d_status = status ? c->d_pp_status.p : nullptr;
+    for (const slice_rec& sr : slices) {
+        const plan::aggv_slice& s = sr.s;
+        const uint32_t P = (uint32_t)s.pairs();
+        const plan::pairprod_plan p = plan::pairprod_for(c->slots, c->coop, P, s.ng, blinded);
+        HIPCHK(hipMemcpyAsync(c->d_aggv_tab, c->aggv_tab.data() + sr.tab_at, plan::pairprod_tab_entries(s.ng, sr.t.items, sr.real) * 16, hipMemcpyHostToDevice, st));
+        const uint4* gtab = reinterpret_cast<const uint4*>(c->d_aggv_tab.p);
+        const uint4* items = gtab + s.ng;
+        const uint4* real = blinded ? items + sr.t.items : gtab;
+        k_pairprod_setup<<<p.setup_grid, WAVE, 0, st>>>(reinterpret_cast<const uint32_t*>(d_p1), reinterpret_cast<const uint32_t*>(d_q2), s.pos0, P, real,
+                                                        blinded ? sr.real : s.ng, flags, blinded ? c->d_pp_r.p : nullptr, reinterpret_cast<uint32_t*>(c->d_sets.p),
+                                                        c->d_r, ps.H, ps.P, ps.stride, d_status, c->grp.d_flag);
+        if (blinded) {
+            HIPCHK(hipMemsetAsync(c->d_comb_pkflag, 0, 4, st));           // k_pkmul's word for an infinity key: such a pair contributes 1 here, nothing reads it
+            if (p.pkmul_spread) k_pkmul_spread<<<plan::waves_for(P), WAVE, 0, st>>>(c->d_sets, P, c->d_r, ps.P, ps.stride, c->d_comb_pkflag, c->d_pktab);
+            else k_pkmul<<<plan::waves_for(P), WAVE, 0, st>>>(c->d_sets, P, c->d_r, ps.P, ps.stride, c->d_comb_pkflag, c->d_pktab);
+        }
+        launch_lines(ps, p.lines, st);
+        const uint32_t n_part = (uint32_t)(sr.t.partials ? sr.t.partials : 1);
+        uint32_t *part = c->d_aggv_part, *step = c->d_aggv_step;
+        launch_levels(sr.t, items,
+                      [&](const uint4* it, uint32_t cnt) {
+                          k_aggveach_l0<<<dim3(plan::waves_for(cnt), N_LINES), WAVE, 0, st>>>(it, cnt, ps.lines, ps.stride, P, part, n_part, step);
+                      },
+                      [&](const uint4* it, uint32_t cnt) { k_aggveach_ln<<<dim3(plan::waves_for(cnt), N_LINES), WAVE, 0, st>>>(it, cnt, part, n_part, step); });
+        if (!p.tail_engine) {
+            k_aggveach_tail<<<p.tail_grid, WAVE, 0, st>>>(step, gtab, s.ng, c->grp.d_flag, c->d_aggv_carry, c->d_each_v, dg);
+        } else {
+            k_aggveach_engine_rows<<<p.tail_grid, K_TAIL_THREADS, 0, st>>>(step, gtab, s.ng, c->grp.d_flag, c->d_aggv_carry, c->d_each_v, dg, c->d_aggv_work);
+            if (s.open_in && s.open_out) k_state_mul<<<1, TAIL_THREADS, 0, st>>>(c->d_aggv_carry, 0, 0, 1);      // the part's value into the carried one
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev[1], st));
+    HIPCHK(hipMemcpyAsync(out, c->d_each_v, nres, hipMemcpyDeviceToHost, st));
+    if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, c->d_each_gt, nres * 576, hipMemcpyDeviceToHost, st));
+    if (status && n) HIPCHK(hipMemcpyAsync(status, c->d_pp_status, n, hipMemcpyDeviceToHost, st));
+    if (blinded) {                                                     // blinding material: nothing of it stays on the device
+        HIPCHK(hipMemsetAsync(c->d_pp_r, 0, k * 8, st));
+        if (max_pairs) HIPCHK(hipMemsetAsync(c->d_r, 0, max_pairs * 8, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    c->last_n = 0;                             // fetch_stage shows the last call, and this one left no batch stages
+    c->sig_slots = 0;
+    c->agg_valid = false;
+    c->have_gt = false;
+    rc = collect_timings(c, 1);
+    if (rc) return rc;
+    // the empty product: a group without pairs (the blinded form: a call without pairs) has verdict 1 and the value one
+    uint8_t one_image[576];
+    if (gt_out) fp12_store_le(one_image, fp12_one());
+    for (size_t g = 0; g < nres; g++) {
+        if (blinded ? n != 0 : offsets[g + 1] != offsets[g]) continue;
+        out[g] = 1;
+        if (gt_out) std::memcpy(gt_out + g * 576, one_image, 576);
+    }
+    int all = 1;
+    for (size_t g = 0; g < nres; g++) all &= out[g] == 1;
+    return all;
+}
+// the two arrays of a host form staged (the existing stager: p1s96 | q2s192 in grp.d_in), or the device form's pointers as they are
+static int pairprod_stage(mi355_bls_ctx* c, const void* p1, const void* q2, size_t n, bool host, const uint8_t** d_p1, const uint8_t** d_q2) {
+    if (!host || n == 0) {
+        *d_p1 = n ? (const uint8_t*)p1 : nullptr, *d_q2 = n ? (const uint8_t*)q2 : nullptr;
+        return 0;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const host_part parts[2] = {{p1, n * 96}, {q2, n * 192}};
+    const uint8_t* d[2];
+    if (int rc = stage_inputs(c, parts, nullptr, d)) return rc;
+    *d_p1 = d[0], *d_q2 = d[1];
+    return 0;
+}
+static int pairprod_each(mi355_bls_ctx* c, const void* p1, const void* q2, const size_t* offsets, size_t k, uint32_t flags, uint8_t* out, uint8_t* status,
+                         uint8_t* gt_out, bool want_gt, bool host, hipStream_t st) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing checked, nothing written
+    if (!out || (want_gt && !gt_out)) return MI355_BLS_ERR_ARG;
+    if (int rc = pairprod_args(p1, q2, offsets, k, flags, status, !host)) return rc;
+    const uint8_t *d_p1, *d_q2;
+    if (int rc = pairprod_stage(c, p1, q2, offsets[k], host, &d_p1, &d_q2)) return rc;
+    return pairprod_run(c, d_p1, d_q2, offsets, k, flags, status, out, gt_out, nullptr, st);
+}
+// The blinded driver.  r: the k scalars (the hook's), or null: the serial chain from rnd32.  out != nullptr: the locate form.
+static int pairprod_blind(mi355_bls_ctx* c, const void* p1, const void* q2, const size_t* offsets, size_t k, uint32_t flags, const uint8_t* rnd32,
+                          const uint64_t* r, uint8_t* status, uint8_t* out, bool locate, uint8_t* gt_out, bool host, hipStream_t st) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if ((!rnd32 && !r) || (locate && !out)) return MI355_BLS_ERR_ARG;
+    if (int rc = pairprod_args(p1, q2, offsets, k, flags, status, !host)) return rc;
+    const uint8_t *d_p1, *d_q2;
+    if (int rc = pairprod_stage(c, p1, q2, offsets[k], host, &d_p1, &d_q2)) return rc;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    c->pp_r.resize(k);
+    if (r) std::memcpy(c->pp_r.data(), r, k * 8);
+    else host_serial_chain(rnd32, k, c->pp_r.data());
+    uint8_t verdict = 0;
+    int rc = pairprod_run(c, d_p1, d_q2, offsets, k, flags, status, &verdict, gt_out, c->pp_r.data(), st);
+    std::fill(c->pp_r.begin(), c->pp_r.end(), 0);      // pairprod_run has drained the stream: the copy that read them is done
+    if (rc < 0 || !locate) return rc;
+    if (rc == 1) {
+        std::memset(out, 1, k);
+        return 1;
+    }
+    rc = pairprod_run(c, d_p1, d_q2, offsets, k, flags, status, out, nullptr, nullptr, st);      // only behind a failure
+    return rc < 0 ? rc : 0;
+}
+extern "C" int mi355_bls_pairing_check_each(mi355_bls_ctx* c, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags, uint8_t* out,
+                                            uint8_t* status) {
+    return pairprod_each(c, p1s96, q2s192, offsets, k, flags, out, status, nullptr, false, true, nullptr);
+}
+extern "C" int mi355_bls_pairing_check_each_device(mi355_bls_ctx* c, const void* d_p1s96, const void* d_q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                                   uint8_t* out, uint8_t* status, void* stream) {
+    return pairprod_each(c, d_p1s96, d_q2s192, offsets, k, flags, out, status, nullptr, false, false, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_pairing_products(mi355_bls_ctx* c, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags, uint8_t* out,
+                                          uint8_t* status, uint8_t* gt_out) {
+    return pairprod_each(c, p1s96, q2s192, offsets, k, flags, out, status, gt_out, true, true, nullptr);
+}
+extern "C" int mi355_bls_pairing_products_device(mi355_bls_ctx* c, const void* d_p1s96, const void* d_q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                                 uint8_t* out, uint8_t* status, uint8_t* gt_out, void* stream) {
+    return pairprod_each(c, d_p1s96, d_q2s192, offsets, k, flags, out, status, gt_out, true, false, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_batch_pairing_check(mi355_bls_ctx* c, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                             const uint8_t rnd32[32], uint8_t* status) {
+    return pairprod_blind(c, p1s96, q2s192, offsets, k, flags, rnd32, nullptr, status, nullptr, false, nullptr, true, nullptr);
+}
+extern "C" int mi355_bls_batch_pairing_check_device(mi355_bls_ctx* c, const void* d_p1s96, const void* d_q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                                    const uint8_t rnd32[32], uint8_t* status, void* stream) {
+    return pairprod_blind(c, d_p1s96, d_q2s192, offsets, k, flags, rnd32, nullptr, status, nullptr, false, nullptr, false, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_batch_pairing_check_locate(mi355_bls_ctx* c, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                                    const uint8_t rnd32[32], uint8_t* status, uint8_t* out) {
+    return pairprod_blind(c, p1s96, q2s192, offsets, k, flags, rnd32, nullptr, status, out, true, nullptr, true, nullptr);
+}
+extern "C" int mi355_bls_batch_pairing_check_locate_device(mi355_bls_ctx* c, const void* d_p1s96, const void* d_q2s192, const size_t* offsets, size_t k,
+                                                           uint32_t flags, const uint8_t rnd32[32], uint8_t* status, uint8_t* out, void* stream) {
+    return pairprod_blind(c, d_p1s96, d_q2s192, offsets, k, flags, rnd32, nullptr, status, out, true, nullptr, false, (hipStream_t)stream);
+}
+// TEST HOOK: the blinded form with the test's k scalars and the 576-byte value of the one product
+extern "C" int mi355_bls_debug_batch_pairing_check_scalars(mi355_bls_ctx* c, const void* p1s96, const void* q2s192, const size_t* offsets, size_t k, uint32_t flags,
+                                                           const uint64_t* r, uint8_t* status, uint8_t* gt_out) {
+    if (c && k && (!r || !gt_out)) return MI355_BLS_ERR_ARG;
+    return pairprod_blind(c, p1s96, q2s192, offsets, k, flags, nullptr, r, status, nullptr, false, gt_out, true, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -39,6 +39,7 @@
 #include "aggbits.hpp"
 #include "combsets.hpp"
 #include "manyeach.hpp"
+#include "pairprod.hpp"
 #include "bymsg.hpp"
 #include "aggsigs.hpp"
 #include "recover.hpp"
@@ -2687,6 +2688,45 @@ __global__ void __launch_bounds__(WAVE) k_manyeach_setup(const uint32_t* __restr
         const manyeach_pair pr = manyeach_sig_pair(ld_g2_int(g2_part + (size_t)final_of[i - n] * G2W));
         soa_st_g1(Pst, stride, i, pr.p);
         soa_st_g2(H, stride, i, pr.q);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Pairing-product checks over caller-supplied pairs (mi355_bls_pairing_check_each, mi355_bls_pairing_products, mi355_bls_batch_pairing_check):
+// group g of a slice is a group of the per-group path with NO signature pair (plan.hpp aggveach_fill, with_sig = false), so the lines, the
+// levels and the tails are launch_lines / k_aggveach_l0 / k_aggveach_ln / k_aggveach_tail / k_aggveach_engine_rows as they stand.  What is new
+// is the lane that fills a pair slot (csrc/pairprod.hpp).
+// ------------------------------------------------------------------------------------------
+// One lane per pair slot i < P of a slice that starts at position pos0 of the call: the 96-byte blst_p1_affine and the 192-byte
+// blst_p2_affine image of position pos0 + i (all zero: infinity), validated when `vflags` has plan::PAIRPROD_VALIDATE (on the curve, in
+// G1 / G2: the heavy part - two 64-bit multiplications in G1 and one in G2 per pair, through deser.hpp's out-of-line bodies), the status
+// byte to status[pos0 + i] (status may be null without validation), a failure raises a word of `bad`, and the pair (both operands infinite
+// behind a failure) into slot i of the pair store.  gtab: the groups with pairs in the slice (plan::aggv_group: g, first, count, flags).
+//   r_group == nullptr   Q -> H, P -> the P column; bad is indexed by the group's number in the call
+//   r_group != nullptr   the blinded form: Q -> H; the P image into record i of `recs` where k_pkmul reads a key (320-byte records, key at 0)
+//                        and r_group[group's number] -> r_pair[i], k_pkmul's scalar of the slot; the one product's word is bad[0]
+__global__ void __launch_bounds__(WAVE) k_pairprod_setup(const uint32_t* __restrict__ p1s, const uint32_t* __restrict__ q2s, size_t pos0, uint32_t P,
+                                                         const uint4* __restrict__ gtab, uint32_t ng, uint32_t vflags, const uint64_t* __restrict__ r_group,
+                                                         uint32_t* __restrict__ recs, uint64_t* __restrict__ r_pair, uint4* __restrict__ H,
+                                                         uint4* __restrict__ Pst, size_t stride, uint8_t* __restrict__ status, uint32_t* __restrict__ bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const size_t pos = pos0 + i;
+    const uint32_t* pw = p1s + pos * 24;
+    const g1_aff p = ld_g1a_blst(pw);
+    const g2_aff q = ld_g2a_blst(q2s + pos * 48);
+    const uint8_t st = (vflags & plan::PAIRPROD_VALIDATE) ? pairprod_validate(p, q) : (uint8_t)PAIRPROD_OK;
+    if (status) status[pos] = st;
+    const auto first = [&](uint32_t l) { return gtab[l].y; };
+    if (st != PAIRPROD_OK) atomicOr(bad + (r_group ? 0u : gtab[manyeach_group_of(i, ng, first)].x), 1u);
+    const pairprod_pair pr = pairprod_operands(p, q, st);
+    soa_st_g2(H, stride, i, pr.q);
+    if (r_group) {
+        uint32_t* rec = recs + (size_t)i * 80;
+        for (int j = 0; j < 24; j++) rec[j] = pairprod_key_word(pw, j, st);
+        r_pair[i] = pairprod_scalar_of(i, ng, first, [&](uint32_t l) { return gtab[l].x; }, r_group);
+    } else {
+        soa_st_g1(Pst, stride, i, pr.p);
     }
 }
 

@@ -663,8 +663,9 @@ inline aggveach_tab aggveach_measure(const aggv_group* gr, uint32_t ng, uint32_t
     return t;
 }
 // the item table (t.items entries): src_first = a pair of the slice (level 0) or a partial (above), count = the operands | AGGV_FINAL |
-// AGGV_SIG, dst = a partial, or the group's number in the slice for a FINAL item, seg = that number
-inline void aggveach_fill(const aggveach_tab& t, const aggv_group* gr, uint32_t ng, agg_item* items, uint32_t C = AGGV_C) {
+// AGGV_SIG, dst = a partial, or the group's number in the slice for a FINAL item, seg = that number.  with_sig = false: the groups have
+// no signature pair (the pairing-product calls below), so no item carries AGGV_SIG; everything else is the same table.
+inline void aggveach_fill(const aggveach_tab& t, const aggv_group* gr, uint32_t ng, agg_item* items, uint32_t C = AGGV_C, bool with_sig = true) {
     size_t cur[AGGV_MAX_LEVELS], pcur = 0;
     for (uint32_t l = 0; l < AGGV_MAX_LEVELS; l++) cur[l] = l < t.levels ? t.level_first[l] : 0;
     for (uint32_t i = 0; i < ng; i++) {
@@ -673,7 +674,7 @@ inline void aggveach_fill(const aggveach_tab& t, const aggv_group* gr, uint32_t 
             const size_t m = (n + C - 1) / C, base = cur[l];
             for (size_t j = 0; j < m; j++) {
                 const size_t left = n - j * C;
-                const uint32_t sig = l == 0 && j == 0 && !(gr[i].flags & AGGV_OPEN_OUT) ? AGGV_SIG : 0u;
+                const uint32_t sig = with_sig && l == 0 && j == 0 && !(gr[i].flags & AGGV_OPEN_OUT) ? AGGV_SIG : 0u;
                 items[base + j] = agg_item{(uint32_t)(src + j * C), (uint32_t)(left < C ? left : C) | sig | (m == 1 ? AGGV_FINAL : 0u),
                                            (uint32_t)(m == 1 ? i : pcur + j), i};
             }
@@ -704,6 +705,57 @@ inline aggveach_plan aggveach_for(uint32_t slots, bool coop, uint32_t pairs, uin
 // (s x partials + p) x F12_WORDS; group i's step s at (i x N_LINES + s) x F12_WORDS, the 68 values the tail walks side by side)
 inline size_t aggveach_part_words(size_t partials) { return (partials ? partials : 1) * (size_t)N_LINES * F12_WORDS; }
 inline size_t aggveach_step_words(size_t ng) { return (ng ? ng : 1) * (size_t)N_LINES * F12_WORDS; }
+
+// Pairing-product checks over caller-supplied pairs (mi355_bls_pairing_check_each, mi355_bls_pairing_products, mi355_bls_batch_pairing_check):
+// k groups of (P, Q) pairs in CSR form.  A group is a group of the per-group path above WITHOUT a signature pair: the slices are
+// aggveach_cut's over `cap` pairs (a slice's pairs are all the pair slots it uses), the tables aggveach_groups / aggveach_measure /
+// aggveach_fill(with_sig = false), the carry of a group longer than a slice the same one.
+//   The blinded form multiplies every pair's P by its group's scalar and forms ONE product over all pairs: the call's pairs are one group of
+//   the per-group path (pairprod_blind_cut: parts of `cap` pairs, carried from part to part), and the setup lane of a pair needs the REAL
+//   group it belongs to for its scalar (pairprod_real_groups: the call's groups cut at the part's ends, as aggveach_groups gives them).
+//   The blinded form's tail is always the Fp12 engine: a slice has one Horner chain and one final exponentiation, which one lane of
+//   k_aggveach_tail would walk alone while the chip waits (the engine's workgroup does not depend on the context's mode).  NOT MEASURED.
+constexpr uint32_t PAIRPROD_VALIDATE = 1;                // the calls' flag bit (MI355_BLS_PAIR_VALIDATE)
+struct pairprod_plan {
+    uint32_t setup_grid;               // a lane per pair slot
+    lines_plan lines;
+    bool pkmul_spread;                 // the blinded form's [r]P: k_pkmul_spread | k_pkmul
+    bool tail_engine;
+    uint32_t tail_grid;
+};
+inline pairprod_plan pairprod_for(uint32_t slots, bool coop, uint32_t pairs, uint32_t ng, bool blinded) {
+    pairprod_plan p{};
+    const aggveach_plan a = aggveach_for(slots, coop, pairs, 0, ng);
+    p.setup_grid = a.setup_grid, p.lines = a.lines;
+    p.pkmul_spread = pkmul_spread_for(slots, coop, pairs);
+    p.tail_engine = blinded ? true : a.tail_engine;
+    p.tail_grid = blinded ? 1 : a.tail_grid;
+    return p;
+}
+// the slice of the blinded form that starts at position pos of n pairs: one group, cut in parts of cap pairs
+inline aggv_slice pairprod_blind_cut(size_t n, size_t pos, size_t cap) {
+    const size_t one[2] = {0, n};
+    return aggveach_cut(one, 1, 0, pos, cap);
+}
+// the call's groups that have pairs in positions [pos0, pos1), pos0 < pos1 <= offsets[k], as a slice aggveach_groups takes
+inline aggv_slice pairprod_real_groups(const size_t* offsets, size_t k, size_t pos0, size_t pos1) {
+    aggv_slice s{};
+    size_t g = 0;
+    while (g < k && offsets[g + 1] <= pos0) g++;
+    s.g0 = g, s.pos0 = pos0, s.pos1 = pos1;
+    s.open_in = g < k && pos0 > offsets[g];
+    for (; g < k && offsets[g] < pos1; g++)
+        if (offsets[g + 1] > offsets[g]) s.ng++, s.g1 = g + 1, s.open_out = offsets[g + 1] > pos1;
+    if (s.ng == 0) s.g1 = s.g0;
+    return s;
+}
+// the call's buffers in bytes: a status byte per pair, a bad word per group (one for the blinded form), the k scalars of the blinded form
+struct pairprod_sizes {
+    size_t status, flags, scalars;
+};
+inline pairprod_sizes pairprod_sizes_for(size_t n, size_t k, bool blinded) { return {n ? n : 1, (blinded ? 1 : k) * 4, blinded ? k * 8 : 0}; }
+// a slice's table in 16-byte entries: groups | items | (the blinded form) the real groups
+inline size_t pairprod_tab_entries(uint32_t ng, size_t items, uint32_t real_groups) { return (size_t)ng + items + real_groups; }
 
 // Per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): k batches of counts[b] sets, laid end to end.  Batch b is one
 // GROUP of the per-group path above: its pairs are ([r_i]PK_i, H(m_i)) for its sets, its signature pair (-G1, sum [r_i]S_i), so the group
