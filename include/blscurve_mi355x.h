@@ -662,6 +662,54 @@ int mi355_bls_p1s_mult_pippenger_many(mi355_bls_ctx* ctx, uint8_t* ret, const vo
 int mi355_bls_p1s_mult_pippenger_many_device(mi355_bls_ctx* ctx, uint8_t* ret, void* d_out, const void* d_points, size_t npoints, const void* d_scalars,
                                              const size_t* offsets, size_t k, size_t nbits, void* stream);
 
+/* k G2 MSMs in one device pass (blst_p2s_mult_pippenger, blst_abi.nim:358-362, k at once): the G2 counterpart of
+ * mi355_bls_p1s_mult_pippenger_many, with the same two addressing forms (ragged with k + 1 host offsets; shared base with offsets == NULL and
+ * k x npoints scalars), the same argument rules and the same error rules.  Points are 192-byte blst_p2_affine images (all-zero = infinity;
+ * subgroup membership is not assumed), scalars 32-byte little-endian images of which the low nbits count, nbits in 1..256; ret[j] / d_out[j] is
+ * the blst_p2 image (Jacobian, 288 B) of MSM j, an infinite result made by a pass 288 zero bytes; compare results as points, or normalise them
+ * with mi355_bls_p2s_to_affine.  What it is for: the k tiny linear combinations [tau - z_g]G2 of k openings, or one recovery with host
+ * coefficients per group - each of them a floor of a device call when made through mi355_bls_p2s_mult_pippenger_device.  The stages are the
+ * G1 call's over 384-byte points (csrc/plan.hpp MSM_MANY_G2_*: half the buckets per pass, one lane per segment), and ONE Horner walk per MSM at
+ * the end (k_pip_tail_many_g2: nbits doublings per MSM in all, one workgroup per MSM).
+ *   _many          host arrays (contiguous, not pointer lists), results to ret (k x 288 B)
+ *   _many_device   arrays in device memory; results to ret (host, may be NULL) and / or d_out (device, k x 288 B, 4-byte aligned, may be NULL),
+ *                  every pass enqueued on `stream` alone, and waited for before the call returns
+ * k == 0 returns 0 and touches nothing; k == 1, and a member of more than 2^20 pairs, take the single G2 path unchanged.  No call is refused
+ * for its size - only a single MSM of more than 2^28 points is.  MI355_BLS_ERR_ARG, before anything is launched: a NULL context (before any
+ * other rule), NULL arrays with work to do, bad offsets, nbits outside 1..256, no output, a d_out that is not 4-byte aligned, an MSM of more
+ * than 2^28 points.  Variable time, like every MSM here.  The window width is the G1 rule (pip_for) and was not measured for G2.
+ * COST (one MI355X, device-resident, 255 bits, median of 5 blocking calls; nim-blscurve_amd/tools/bench_msm_g2_many.py, a PARTIAL run: the rows
+ * named in profiles/msm_g2_many_bench.json): 64 MSMs of 4 096 points 10.8 - 10.9 ms, shared or ragged, against 395 - 398 ms for 64 single
+ * calls and 8.3 ms for one MSM over all pairs; 4 096 MSMs of 2 points 232 ms: 82 x faster than single calls (measured on 64, scaled) but 37 x
+ * one MSM over the same 8 192 pairs - SLOW for tiny members (52 five-bit windows each).  Other rows not measured yet: run the tool. */
+int mi355_bls_p2s_mult_pippenger_many(mi355_bls_ctx* ctx, uint8_t* ret, const void* points, size_t npoints, const void* scalars, const size_t* offsets,
+                                      size_t k, size_t nbits);
+int mi355_bls_p2s_mult_pippenger_many_device(mi355_bls_ctx* ctx, uint8_t* ret, void* d_out, const void* d_points, size_t npoints, const void* d_scalars,
+                                             const size_t* offsets, size_t k, size_t nbits, void* stream);
+
+/* blst_p1s_to_affine / blst_p2s_to_affine (blst_abi.nim:323, :345) for n CONTIGUOUS Jacobian images (not pointer lists: the device forms
+ * cannot take those): n x 144 B blst_p1 -> n x 96 B blst_p1_affine, n x 288 B blst_p2 -> n x 192 B blst_p2_affine.  Every MSM call here
+ * returns Jacobian images and every consumer takes affine ones; with these calls the results need not visit the host in between: the d_out
+ * of a _device form is, as it stands, the d_p1s96 / d_q2s192 argument of the pairing calls, the d_keys argument of the table-addressed calls
+ * and the input of mi355_bls_compress_public_keys_device / mi355_bls_compress_signatures_device.
+ *   Z == 0 gives the all-zero image: the library's affine infinity, what the pairing calls skip.  Output bytes are canonical Montgomery
+ *   images.  Input and output must NOT overlap (a lane reads its points twice).  A lane takes a run of consecutive points and shares one
+ *   inversion among them (csrc/toaffine.hpp; the run length is csrc/plan.hpp to_affine_for's: neither the rule nor its cap of 8 is measured).
+ *   _device: both arrays in device memory, 4-byte aligned; every launch is enqueued on `stream`, which is waited for once.  Any n: beyond one
+ *   launch's reach the library loops over chunks.
+ * n == 0 returns 0 and touches nothing.  MI355_BLS_ERR_ARG for a NULL context (first), NULL arrays with work to do, or a device pointer that
+ * is not 4-byte aligned.  Variable time (public points).
+ * COST (the same partial run, n = 4 096): 0.089 ms (G1) and 0.112 ms (G2) per blocking call, against 0.072 and 0.175 ms for the two copies
+ * of the same bytes (an earlier run of the same rows: 0.088 and 0.140) - on G1 the call is SLOWER than the copies it replaces, on G2 faster.
+ * Blocking calls this short are mostly launch and synchronise latency: what the caller saves is the host arithmetic between the copies, which
+ * these rows do not time.  n = 64 and 65 536 not measured yet: run nim-blscurve_amd/tools/bench_msm_g2_many.py.
+ * debug_to_affine_set_run: TEST HOOK, the points per lane of the following to_affine calls on this context (capped at 8; 0: the plan's own). */
+int mi355_bls_p1s_to_affine(mi355_bls_ctx* ctx, const uint8_t* in144, size_t n, uint8_t* out96);
+int mi355_bls_p1s_to_affine_device(mi355_bls_ctx* ctx, const void* d_in144, size_t n, void* d_out96, void* stream);
+int mi355_bls_p2s_to_affine(mi355_bls_ctx* ctx, const uint8_t* in288, size_t n, uint8_t* out192);
+int mi355_bls_p2s_to_affine_device(mi355_bls_ctx* ctx, const void* d_in288, size_t n, void* d_out192, void* stream);
+int mi355_bls_debug_to_affine_set_run(mi355_bls_ctx* ctx, uint32_t run);
+
 /* Fixed-base G1 MSM over a precomputed window table: blst_p1s_mult_wbits_precompute(_sizeof) and blst_p1s_mult_wbits (blst_abi.nim:327-335)
  * for callers whose point set does not change - k commitments over one SRS or Lagrange table.  A table is a library-owned handle that keeps, in
  * device memory, the rows [2^(w wbits)] P_i for w = 0 .. W - 1, W = ceil((nbits + 1) / wbits), W x npoints x 128 bytes

@@ -165,6 +165,13 @@ def lib():
         L.mi355_bls_p1s_mult_pippenger_device.argtypes = [vp, ctypes.c_char_p, vp, sz, vp, sz, vp]
         L.mi355_bls_p1s_mult_pippenger_many.argtypes = [vp, vp, vp, sz, vp, psz, sz, sz]
         L.mi355_bls_p1s_mult_pippenger_many_device.argtypes = [vp, vp, vp, vp, sz, vp, psz, sz, sz, vp]
+        L.mi355_bls_p2s_mult_pippenger_many.argtypes = [vp, vp, vp, sz, vp, psz, sz, sz]
+        L.mi355_bls_p2s_mult_pippenger_many_device.argtypes = [vp, vp, vp, vp, sz, vp, psz, sz, sz, vp]
+        L.mi355_bls_p1s_to_affine.argtypes = [vp, vp, sz, vp]
+        L.mi355_bls_p1s_to_affine_device.argtypes = [vp, vp, sz, vp, vp]
+        L.mi355_bls_p2s_to_affine.argtypes = [vp, vp, sz, vp]
+        L.mi355_bls_p2s_to_affine_device.argtypes = [vp, vp, sz, vp, vp]
+        L.mi355_bls_debug_to_affine_set_run.argtypes = [vp, u32]
         L.mi355_bls_p1s_table_sizeof.argtypes = [sz, sz, sz]
         L.mi355_bls_p1s_table_sizeof.restype = sz
         L.mi355_bls_p1s_table_create.argtypes = [vp, vp, vp, sz, sz, sz]
@@ -1687,6 +1694,83 @@ def p1s_mult_pippenger_many_device(cache, d_points, npoints, d_scalars, offsets,
     out = ctypes.create_string_buffer(144 * k)
     _check(lib().mi355_bls_p1s_mult_pippenger_many_device(cache._h, out, d_out, d_points, npoints, d_scalars, arr, k, nbits, stream))
     return [out.raw[144 * j:144 * j + 144] for j in range(k)]
+
+
+def p2s_mult_pippenger_many(cache, points, scalars, offsets=None, nbits=255):
+    """k G2 MSMs in one device pass -> a list of k 288-byte blst_p2 (Jacobian) results: p1s_mult_pippenger_many over 192-byte
+    blst_p2_affine images, the same two addressing forms."""
+    if len(points) % 192 or len(scalars) % 32:
+        raise ValueError("points: n x 192 bytes, scalars: 32 bytes each")
+    n, ns = len(points) // 192, len(scalars) // 32
+    if offsets is None:
+        if n == 0 or ns % n:
+            if ns:
+                raise ValueError("shared points: scalars must be k x n x 32 bytes")
+            return []
+        k, arr = ns // n, None
+    else:
+        offs = _many_offsets(offsets, n)
+        if ns != n:
+            raise ValueError("ragged: one 32-byte scalar per point")
+        k, arr = len(offs) - 1, (ctypes.c_size_t * len(offs))(*offs)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(288 * k)
+    _check(lib().mi355_bls_p2s_mult_pippenger_many(cache._h, out, bytes(points), n, bytes(scalars), arr, k, nbits))
+    return [out.raw[288 * j:288 * j + 288] for j in range(k)]
+
+
+def p2s_mult_pippenger_many_device(cache, d_points, npoints, d_scalars, offsets, k, nbits=255, d_out=None, stream=0, ret=True):
+    """The same with both arrays in device memory (pointers as integers); offsets as above or None.  The results come back as a list
+    (ret=False: nothing is copied to the host and None is returned) and, when d_out (a device pointer to k x 288 bytes) is given, are left
+    there as well."""
+    if k == 0:
+        return []
+    arr = None
+    if offsets is not None:
+        offs = _many_offsets(offsets, npoints)
+        if len(offs) != k + 1:
+            raise ValueError("offsets: k + 1 values")
+        arr = (ctypes.c_size_t * len(offs))(*offs)
+    out = ctypes.create_string_buffer(288 * k) if ret else None
+    _check(lib().mi355_bls_p2s_mult_pippenger_many_device(cache._h, out, d_out, d_points, npoints, d_scalars, arr, k, nbits, stream))
+    return [out.raw[288 * j:288 * j + 288] for j in range(k)] if ret else None
+
+
+def _to_affine(cache, name, jacb, images):
+    if len(images) % jacb:
+        raise ValueError("Jacobian images: n x %d bytes" % jacb)
+    n = len(images) // jacb
+    if n == 0:
+        return b""
+    out = ctypes.create_string_buffer(jacb // 3 * 2 * n)
+    _check(getattr(lib(), name)(cache._h, bytes(images), n, out))
+    return out.raw
+
+
+def p1s_to_affine(cache, images):
+    """n x 144 bytes of blst_p1 (Jacobian) images -> n x 96 bytes of blst_p1_affine images; Z == 0 gives 96 zero bytes."""
+    return _to_affine(cache, "mi355_bls_p1s_to_affine", 144, images)
+
+
+def p2s_to_affine(cache, images):
+    """n x 288 bytes of blst_p2 (Jacobian) images -> n x 192 bytes of blst_p2_affine images; Z == 0 gives 192 zero bytes."""
+    return _to_affine(cache, "mi355_bls_p2s_to_affine", 288, images)
+
+
+def p1s_to_affine_device(cache, d_in, n, d_out, stream=0):
+    """The same between device buffers (pointers as integers, 4-byte aligned, not overlapping): d_out takes n x 96 bytes."""
+    _check(lib().mi355_bls_p1s_to_affine_device(cache._h, d_in or None, n, d_out or None, stream))
+
+
+def p2s_to_affine_device(cache, d_in, n, d_out, stream=0):
+    """The same between device buffers: d_out takes n x 192 bytes."""
+    _check(lib().mi355_bls_p2s_to_affine_device(cache._h, d_in or None, n, d_out or None, stream))
+
+
+def debug_to_affine_set_run(cache, run=0):
+    """TEST HOOK: the points a lane of the following to_affine calls takes (capped at 8; 0: the plan's own)."""
+    _check(lib().mi355_bls_debug_to_affine_set_run(cache._h, run))
 
 
 class P1sTable:

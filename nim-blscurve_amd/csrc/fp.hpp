@@ -828,7 +828,8 @@ __device__ __forceinline__ bls_u32x32 fp2_pack(const fp& c0, const fp& c1) {
 // Second operand of fp2_mul_regs: 28 words per lane handed over through LDS (7 x 16 bytes, [group][lane] so a
 // wave's accesses are conflict-free).  Registers carry only 32 argument words; the rest would travel on the
 // stack, i.e. through scratch memory, which at 1024 waves x 13 products per line was ~6 GB of HBM writes per
-// k_lineprod launch.  Every kernel of this library runs one wave per workgroup, so the slot is wave-private.
+// k_lineprod launch.  The slot is ONE per workgroup: it is wave-private because every kernel that multiplies in Fp2 does so in one wave of
+// a workgroup at a time - one-wave workgroups, or (k_pip_tail_many_g2, four waves) wave 0 alone.  A kernel that breaks this corrupts products.
 // bls_xchg is the hand-over slot of fp2_mul; a kernel may park operands it uses repeatedly in LDS slots of its own
 // (k_lineprod: the line coefficients, which then occupy no registers at all) and multiply by them with
 // fp2_mul_lds.  A slot is 7 groups of 64 lanes x 16 bytes.

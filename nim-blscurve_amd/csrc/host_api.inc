@@ -197,6 +197,10 @@ struct mi355_bls_ctx {
     int bm_groups = -1;              // k of the last by-message slice (mi355_bls_last_message_groups)
     // k MSMs in one pass (mi355_bls_p1s_mult_pippenger_many): made at the first such call
     msm_many_ws msm_many;
+    msm_many_ws msm_many2;           // ... and the G2 form's (mi355_bls_p2s_mult_pippenger_many): the same buffers over 384-byte points
+    // Jacobian images to affine (mi355_bls_p1s_to_affine / mi355_bls_p2s_to_affine): the host forms' staging, and the test hook's run length
+    dev_buf<uint8_t> d_toaff_in, d_toaff_out;
+    uint32_t toaff_run = 0;          // mi355_bls_debug_to_affine_set_run; 0: the plan's own
     std::vector<uint32_t> many_offs; // the ragged passes' offsets of the call in flight: the async copies read them
     ptab_ws ptab;                    // MSMs over a fixed-base window table: made at the first such call
     // per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): sized by the largest slice of a call; it runs in the per-set path's
@@ -3712,7 +3716,9 @@ extern "C" int mi355_bls_p2s_mult_pippenger(mi355_bls_ctx* c, uint8_t ret_p2[288
 }
 
 // ------------------------------------------------------------------------------------------
-// k G1 MSMs in one device pass (mi355_bls_p1s_mult_pippenger_many): a walk over plan::msm_many_for / msm_many_next
+// k G1 MSMs in one device pass (mi355_bls_p1s_mult_pippenger_many), and k G2 MSMs (mi355_bls_p2s_mult_pippenger_many): a walk over
+// plan::msm_many_for / msm_many_next.  One driver over the field: F = fp is the G1 call's launch sequence as it was before the G2 form
+// existed; F = fp2 differs where the plan says so (384-byte points, k_pip_segred<fp2> alone, k_pip_tail_many_g2).
 // ------------------------------------------------------------------------------------------
 // The argument rules of both entries, made without looking into the context: 0 go on, 1 nothing to do (k == 0), or the error.
 static int msm_many_check(const mi355_bls_ctx* c, const void* ret, const void* d_out, const void* points, size_t npoints, const void* scalars, const size_t* offsets,
@@ -3731,17 +3737,20 @@ static int msm_many_check(const mi355_bls_ctx* c, const void* ret, const void* d
     return 0;
 }
 // Arguments checked (msm_many_check returned 0).  Every pass is enqueued on `st`; the results land in d_out (or the workspace's own k x 144
-// bytes), are copied to ret, and the stream is waited for, as the single call does.
+// (G2: 288) bytes), are copied to ret, and the stream is waited for, as the single call does.
+template <class F>
 static int msm_many_run(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const void* d_points, size_t npoints, const void* d_scalars, const size_t* offsets, size_t k,
                         size_t nbits, hipStream_t st) {
-    msm_many_ws* m = &c->msm_many;
-    const plan::msm_many_plan P = plan::msm_many_for(k, npoints, offsets == nullptr, nbits);
+    constexpr bool G2 = sizeof(F) != sizeof(fp);
+    constexpr size_t AFFB = G2 ? 192 : 96, JACB = AFFB / 2 * 3, JACW = JACB / 4;
+    msm_many_ws* m = G2 ? &c->msm_many2 : &c->msm_many;
+    const plan::msm_many_plan P = plan::msm_many_for(k, npoints, offsets == nullptr, nbits, G2);
     const plan::msm_many_sizes sz = plan::msm_many_sizes_for(P, offsets, npoints, k);
     int rc = 0;
     const auto grow = [&rc](auto& buf, size_t bytes) { rc = rc ? rc : buf.reserve(bytes, 0); };
     grow(m->pts_int, sz.pts_int), grow(m->offs_dev, sz.offs_dev), grow(m->hist, sz.hist), grow(m->offs, sz.hist), grow(m->cursor, sz.hist), grow(m->order, sz.hist);
     grow(m->chist, sz.chist), grow(m->sorted, sz.sorted), grow(m->buckets, sz.buckets), grow(m->segout, sz.segout), grow(m->part, sz.part);
-    if (!d_out) grow(m->out, k * 144);
+    if (!d_out) grow(m->out, k * JACB);
     if (rc) return rc;
     uint32_t* dst = d_out ? (uint32_t*)d_out : m->out.p;
     const uint8_t* pts = (const uint8_t*)d_points;
@@ -3762,21 +3771,21 @@ static int msm_many_run(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const void*
     for (size_t j = 0; j < k;) {
         const plan::msm_many_pass s = plan::msm_many_next(P, offsets, npoints, k, j);
         j = s.j1;
-        uint32_t* out = dst + s.j0 * 36;
+        uint32_t* out = dst + s.j0 * JACW;
         if (s.single) {
             const size_t n = offsets ? offsets[s.j0 + 1] - offsets[s.j0] : npoints;
             if (n == 0) {
-                HIPCHK(hipMemsetAsync(out, 0, 144, st));
+                HIPCHK(hipMemsetAsync(out, 0, JACB, st));
                 continue;
             }
-            rc = msm_enqueue<fp>(c, &c->msm, pts + (offsets ? s.pair0 * 96 : 0), n, sc + s.pair0 * 32, 32, nbits, st, false, true);
+            rc = msm_enqueue<F>(c, &c->msm, pts + (offsets ? s.pair0 * AFFB : 0), n, sc + s.pair0 * 32, 32, nbits, st, false, true);
             if (rc) return rc;
-            HIPCHK(hipMemcpyAsync(out, c->msm.out, 144, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(out, c->msm.out, JACB, hipMemcpyDeviceToDevice, st));
             continue;
         }
         const uint32_t kp = (uint32_t)(s.j1 - s.j0);
         if (s.pairs == 0) {
-            HIPCHK(hipMemsetAsync(out, 0, (size_t)kp * 144, st));
+            HIPCHK(hipMemsetAsync(out, 0, (size_t)kp * JACB, st));
             continue;
         }
         const many_addr A{s.pairs, kp, offsets ? 0u : (uint32_t)npoints, nw, W.cbk};
@@ -3792,8 +3801,8 @@ static int msm_many_run(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const void*
         const bool t = !timed;
         timed = true;
         if (t) HIPCHK(hipEventRecord(c->ev[0], st));
-        if (offsets) k_pip_convert<fp><<<plan::waves_for(s.points), WAVE, 0, st>>>(pts + s.pair0 * 96, s.points, m->pts_int);
-        else if (!converted) k_pip_convert<fp><<<plan::waves_for(s.points), WAVE, 0, st>>>(pts, s.points, m->pts_int);      // the shared points: once per call
+        if (offsets) k_pip_convert<F><<<plan::waves_for(s.points), WAVE, 0, st>>>(pts + s.pair0 * AFFB, s.points, m->pts_int);
+        else if (!converted) k_pip_convert<F><<<plan::waves_for(s.points), WAVE, 0, st>>>(pts, s.points, m->pts_int);      // the shared points: once per call
         converted = true;
         k_pipm_hist<<<dim3(s.pair_grid, nw), WAVE, 0, st>>>(psc, A, m->offs_dev, W, m->hist);
         k_pipm_scan<<<s.nv, WAVE, 0, st>>>(m->hist, A, m->offs_dev, m->offs, m->cursor);
@@ -3803,18 +3812,19 @@ static int msm_many_run(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const void*
         k_msm_order_scatter<<<s.order_grid, WAVE, 0, st>>>(m->hist, s.total, m->chist, m->order);
         if (t) HIPCHK(hipEventRecord(c->ev[1], st));
         // offs holds positions in `sorted` itself (k_pipm_scan): n = 0 takes k_pip_bucket's own window x n out
-        k_pip_bucket<fp><<<s.bucket_grid, WAVE, 0, st>>>(m->pts_int, m->sorted, m->offs, m->hist, m->order, 0, W.cbk, s.total, 0, s.total, m->buckets);
+        k_pip_bucket<F><<<s.bucket_grid, WAVE, 0, st>>>(m->pts_int, m->sorted, m->offs, m->hist, m->order, 0, W.cbk, s.total, 0, s.total, m->buckets);
         if (t) HIPCHK(hipEventRecord(c->ev[2], st));
-        if (s.team == 4) k_pip_segred_team<4><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
-        else if (s.team == 2) k_pip_segred_team<2><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
-        else k_pip_segred<fp><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
-        k_pip_winpart<fp><<<dim3(s.nv, P.nsplit), WAVE, 0, st>>>(m->segout, s.nseg, P.segs_per_win, 0, m->part);
+        if (!G2 && s.team == 4) k_pip_segred_team<4><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        else if (!G2 && s.team == 2) k_pip_segred_team<2><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        else k_pip_segred<F><<<s.segred_grid, WAVE, 0, st>>>(m->buckets, s.total, W.cbk, plan::MSM_SEG, s.nseg, 0, s.nseg, m->segout);
+        k_pip_winpart<F><<<dim3(s.nv, P.nsplit), WAVE, 0, st>>>(m->segout, s.nseg, P.segs_per_win, 0, m->part);
         if (t) HIPCHK(hipEventRecord(c->ev[3], st));
-        k_pip_rowtail_many<<<kp, P.tail_lanes, 0, st>>>(m->part, P.nsplit, W, out);
+        if constexpr (G2) k_pip_tail_many_g2<<<kp, P.tail_lanes, 0, st>>>(m->part, P.nsplit, W, out);      // one Horner walk per MSM, the G2 way
+        else k_pip_rowtail_many<<<kp, P.tail_lanes, 0, st>>>(m->part, P.nsplit, W, out);
         if (t) HIPCHK(hipEventRecord(c->ev[4], st));
         HIPCHK(hipGetLastError());
     }
-    if (ret) HIPCHK(hipMemcpyAsync(ret, dst, k * 144, hipMemcpyDeviceToHost, st));
+    if (ret) HIPCHK(hipMemcpyAsync(ret, dst, k * JACB, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (timed) return collect_timings(c, 4);       // the first pass's stages: [0] sort and order, [1] bucket accumulation, [2] reductions, [3] the tails
     for (float& t : c->timings) t = 0;             // every step took the single path (untimed here): no stale stages of an earlier call
@@ -3825,26 +3835,100 @@ extern "C" int mi355_bls_p1s_mult_pippenger_many_device(mi355_bls_ctx* c, uint8_
     const int chk = msm_many_check(c, ret, d_out, d_points, npoints, d_scalars, offsets, k, nbits);
     if (chk) return chk < 0 ? chk : 0;
     HIPCHK(hipSetDevice(c->device));
-    return msm_many_run(c, ret, d_out, d_points, npoints, d_scalars, offsets, k, nbits, (hipStream_t)stream);
+    return msm_many_run<fp>(c, ret, d_out, d_points, npoints, d_scalars, offsets, k, nbits, (hipStream_t)stream);
 }
 // host arrays -> staging -> msm_many_run on the null stream
-extern "C" int mi355_bls_p1s_mult_pippenger_many(mi355_bls_ctx* c, uint8_t* ret, const void* points, size_t npoints, const void* scalars, const size_t* offsets,
-                                                 size_t k, size_t nbits) {
+template <class F>
+static int msm_many_host(mi355_bls_ctx* c, uint8_t* ret, const void* points, size_t npoints, const void* scalars, const size_t* offsets, size_t k, size_t nbits) {
+    constexpr bool G2 = sizeof(F) != sizeof(fp);
+    constexpr size_t AFFB = G2 ? 192 : 96, JACB = AFFB / 2 * 3;
     const int chk = msm_many_check(c, ret, ret, points, npoints, scalars, offsets, k, nbits);
     if (chk) return chk < 0 ? chk : 0;
     if (npoints == 0) {
-        memset(ret, 0, k * 144);
+        memset(ret, 0, k * JACB);
         return 0;
     }
     HIPCHK(hipSetDevice(c->device));
-    msm_many_ws* m = &c->msm_many;
+    msm_many_ws* m = G2 ? &c->msm_many2 : &c->msm_many;
     const size_t nsc = offsets ? npoints : npoints * k;
-    int rc = m->d_pts.reserve(npoints * 96, 0);
+    int rc = m->d_pts.reserve(npoints * AFFB, 0);
     rc = rc ? rc : m->d_sc.reserve(nsc * 32, 0);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(m->d_pts, points, npoints * 96, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(m->d_pts, points, npoints * AFFB, hipMemcpyHostToDevice, nullptr));
     HIPCHK(hipMemcpyAsync(m->d_sc, scalars, nsc * 32, hipMemcpyHostToDevice, nullptr));
-    return msm_many_run(c, ret, nullptr, m->d_pts, npoints, m->d_sc, offsets, k, nbits, nullptr);
+    return msm_many_run<F>(c, ret, nullptr, m->d_pts, npoints, m->d_sc, offsets, k, nbits, nullptr);
+}
+extern "C" int mi355_bls_p1s_mult_pippenger_many(mi355_bls_ctx* c, uint8_t* ret, const void* points, size_t npoints, const void* scalars, const size_t* offsets,
+                                                 size_t k, size_t nbits) {
+    return msm_many_host<fp>(c, ret, points, npoints, scalars, offsets, k, nbits);
+}
+// the G2 form: 192-byte blst_p2_affine images in, blst_p2 images (288 B) out; a d_out that is not 4-byte aligned is refused with the other rules
+extern "C" int mi355_bls_p2s_mult_pippenger_many_device(mi355_bls_ctx* c, uint8_t* ret, void* d_out, const void* d_points, size_t npoints, const void* d_scalars,
+                                                        const size_t* offsets, size_t k, size_t nbits, void* stream) {
+    const int chk = msm_many_check(c, ret, d_out, d_points, npoints, d_scalars, offsets, k, nbits);
+    if (chk) return chk < 0 ? chk : 0;
+    if ((uintptr_t)d_out & 3) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    return msm_many_run<fp2>(c, ret, d_out, d_points, npoints, d_scalars, offsets, k, nbits, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_p2s_mult_pippenger_many(mi355_bls_ctx* c, uint8_t* ret, const void* points, size_t npoints, const void* scalars, const size_t* offsets,
+                                                 size_t k, size_t nbits) {
+    return msm_many_host<fp2>(c, ret, points, npoints, scalars, offsets, k, nbits);
+}
+
+// ------------------------------------------------------------------------------------------
+// Jacobian images to affine images, n at once (blst_p1s_to_affine / blst_p2s_to_affine, blst_abi.nim:323, :345): a walk over
+// plan::to_affine_for / to_affine_next, one k_to_affine launch per chunk, all on `st`, waited for once.
+// ------------------------------------------------------------------------------------------
+template <class F>
+static int to_affine_run_dev(mi355_bls_ctx* c, const void* d_in, size_t n, void* d_out, hipStream_t st) {
+    constexpr size_t AFFB = sizeof(F) == sizeof(fp) ? 96 : 192, JACB = AFFB / 2 * 3;
+    const plan::to_affine_plan p = plan::to_affine_for(n, c->toaff_run);
+    for (size_t first = 0; first < n;) {
+        const plan::to_affine_launch l = plan::to_affine_next(p, n, first);
+        k_to_affine<F><<<l.grid, WAVE, 0, st>>>((const uint32_t*)((const uint8_t*)d_in + first * JACB), l.n, p.run, (uint32_t*)((uint8_t*)d_out + first * AFFB));
+        first += l.n;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+template <class F>
+static int to_affine_device(mi355_bls_ctx* c, const void* d_in, size_t n, void* d_out, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!d_in || !d_out || (((uintptr_t)d_in | (uintptr_t)d_out) & 3)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    return to_affine_run_dev<F>(c, d_in, n, d_out, (hipStream_t)stream);
+}
+template <class F>
+static int to_affine_host(mi355_bls_ctx* c, const uint8_t* in, size_t n, uint8_t* out) {
+    constexpr size_t AFFB = sizeof(F) == sizeof(fp) ? 96 : 192, JACB = AFFB / 2 * 3;
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (n == 0) return 0;
+    if (!in || !out) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->d_toaff_in.reserve(n * JACB, 0);
+    rc = rc ? rc : c->d_toaff_out.reserve(n * AFFB, 0);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(c->d_toaff_in, in, n * JACB, hipMemcpyHostToDevice, nullptr));
+    rc = to_affine_run_dev<F>(c, c->d_toaff_in, n, c->d_toaff_out, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(out, c->d_toaff_out, n * AFFB, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int mi355_bls_p1s_to_affine(mi355_bls_ctx* c, const uint8_t* in144, size_t n, uint8_t* out96) { return to_affine_host<fp>(c, in144, n, out96); }
+extern "C" int mi355_bls_p2s_to_affine(mi355_bls_ctx* c, const uint8_t* in288, size_t n, uint8_t* out192) { return to_affine_host<fp2>(c, in288, n, out192); }
+extern "C" int mi355_bls_p1s_to_affine_device(mi355_bls_ctx* c, const void* d_in144, size_t n, void* d_out96, void* stream) {
+    return to_affine_device<fp>(c, d_in144, n, d_out96, stream);
+}
+extern "C" int mi355_bls_p2s_to_affine_device(mi355_bls_ctx* c, const void* d_in288, size_t n, void* d_out192, void* stream) {
+    return to_affine_device<fp2>(c, d_in288, n, d_out192, stream);
+}
+extern "C" int mi355_bls_debug_to_affine_set_run(mi355_bls_ctx* c, uint32_t run) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    c->toaff_run = run;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -46,6 +46,7 @@
 #include "keytable.hpp"
 #include "msmmany.hpp"
 #include "msmtable.hpp"
+#include "toaffine.hpp"
 #include "c12.hpp"
 #include "teamvm.hpp"
 #include "rowfp.hpp"
@@ -2218,6 +2219,60 @@ __global__ void __launch_bounds__(1024) k_pip_rowtail_many(const uint32_t* __res
         }
     }
 }
+// The G2 form's tail (mi355_bls_p2s_mult_pippenger_many) for MSM j = blockIdx.x of a pass: the MSM's window sums go into LDS (a Jacobian G2
+// point is G2W = 96 words: 64 windows are 24 KB) - copied by all waves when a window has one part, added by wave 0 alone when it has nsplit
+// > 1 (no two waves of a workgroup may multiply in Fp2 at once, see there) - then wave 0 makes ONE Horner walk from the top
+// window down (msmmany.hpp many_tail_walk: nbits doublings in all, where k_pip_winsum + k_pip_final double pip_off(W, w) times per window and
+// take one more launch) and writes the blst_p2 image at out + 72 j words; an infinite result is 288 zero bytes.  Every lane of wave 0 holds the
+// same point, as in k_pip_winsum: the doublings are the 8-lane cooperative ones, the additions the complete out-of-line ones.
+struct g2_tail_ops {
+    using point = g2_jac;
+    const uint32_t* sums;
+    __device__ __forceinline__ g2_jac inf() const { return jac_inf<fp2>(); }
+    // every lane holds the same point: the answer as a wave-uniform value, so that the walk's branches are scalar ones around the lane exchanges of dbl
+    __device__ __forceinline__ bool is_inf(const g2_jac& p) const { return __builtin_amdgcn_readfirstlane(jac_is_inf(p) ? 1 : 0) != 0; }
+    __device__ __forceinline__ g2_jac window(uint32_t w) const { return ld_g2_int(sums + (size_t)w * G2W); }
+    __device__ __forceinline__ g2_jac dbl(const g2_jac& p) const { return dbl_coop(p); }
+    __device__ __forceinline__ g2_jac add(const g2_jac& a, const g2_jac& b) const { return padd(a, b); }
+};
+__global__ void __launch_bounds__(plan::MSM_MANY_G2_TAIL_WAVES * WAVE) k_pip_tail_many_g2(const uint32_t* __restrict__ part, uint32_t nsplit, pip_win W, uint32_t* __restrict__ out) {
+    __shared__ uint32_t sums[plan::MSM_WINDOWS_MAX * G2W];
+    const uint32_t wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, lane = threadIdx.x & 63u, nwin = W.nwin;
+    part += (size_t)blockIdx.x * nwin * nsplit * G2W;
+    out += (size_t)blockIdx.x * 72;
+    const uint32_t nw = nwin < plan::MSM_WINDOWS_MAX ? nwin : plan::MSM_WINDOWS_MAX;
+    if (nsplit == 1) {
+        // a window's one part IS its sum: all waves copy, nobody multiplies
+        for (uint32_t i = threadIdx.x; i < nw * G2W; i += blockDim.x) sums[i] = part[i];
+    } else if (wave == 0) {
+        // fp2_mul hands its second operand over through ONE LDS slot per workgroup (fp.hpp bls_xchg): field products may run in one wave of a
+        // workgroup at a time, so wave 0 alone adds the parts, window after window, its lanes taking a part each
+#pragma clang loop unroll(disable)
+        for (uint32_t w = 0; w < nw; w++) {
+            g2_jac acc = jac_inf<fp2>();
+            for (uint32_t j = lane; j < nsplit; j += WAVE) acc = padd(acc, ld_g2_int(part + ((size_t)w * nsplit + j) * G2W));
+            int top = 32;
+            while (top >= 1 && (uint32_t)top >= nsplit) top >>= 1;          // lanes >= nsplit hold the neutral element
+            for (int d = top; d >= 1; d >>= 1) {
+                g2_jac o = shfl_down_struct(acc, d);
+                acc = padd(acc, o);
+            }
+            if (lane == 0) st_g2_int(sums + (size_t)w * G2W, acc);
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+#if defined(__HIP_DEVICE_COMPILE__)      // g2_tail_ops is device-only (lane exchanges): the host pass of this file never instantiates the walk with it
+    const g2_jac r = many_tail_walk(W, g2_tail_ops{sums});
+    if (threadIdx.x == 0) {
+        if (jac_is_inf(r)) {
+            for (int i = 0; i < 72; i++) out[i] = 0;
+        } else {
+            st_jac_blst(out, r);
+        }
+    }
+#endif
+}
 
 // ------------------------------------------------------------------------------------------
 // Fixed-base G1 MSM over a precomputed window table (mi355_bls_p1s_table_* / mi355_bls_p1s_mult_table*; csrc/msmtable.hpp, plan.hpp fixed_for).
@@ -2428,6 +2483,29 @@ __global__ void k_finish_affine(const uint32_t* __restrict__ p1, const uint32_t*
         fp2 x = fp2_mul(b.x, zi2), y = fp2_mul(b.y, fp2_mul(zi2, zi));
         st_fp_blst(out_sig, x.c0); st_fp_blst(out_sig + 12, x.c1); st_fp_blst(out_sig + 24, y.c0); st_fp_blst(out_sig + 36, y.c1);
     }
+}
+
+// blst_p1s_to_affine / blst_p2s_to_affine (blst_abi.nim:323, :345) for n contiguous Jacobian images (mi355_bls_p1s_to_affine / _p2s_): a lane
+// takes `run` consecutive points and inverts once for all of them (csrc/toaffine.hpp to_affine_run; plan.hpp to_affine_for chooses run).
+// in: n x 36 (72) words, out: n x 24 (48) words, not overlapping; Z == 0 -> the all-zero image.
+__device__ __forceinline__ void st_aff_blst(uint32_t* w, const g1_aff& a) { st_fp_blst(w, a.x); st_fp_blst(w + 12, a.y); }
+__device__ __forceinline__ void st_aff_blst(uint32_t* w, const g2_aff& a) {
+    st_fp_blst(w, a.x.c0); st_fp_blst(w + 12, a.x.c1); st_fp_blst(w + 24, a.y.c0); st_fp_blst(w + 36, a.y.c1);
+}
+template <class F>
+__global__ void __launch_bounds__(WAVE) k_to_affine(const uint32_t* __restrict__ in, uint32_t n, uint32_t run, uint32_t* __restrict__ out) {
+    constexpr uint32_t AFFW = fld<F>::AFFB / 4, JACW = AFFW / 2 * 3;
+    const uint32_t lane = blockIdx.x * WAVE + threadIdx.x;
+    if (run == 0 || run > plan::TOAFF_RUN_MAX || lane >= (n + run - 1) / run) return;
+    const uint32_t first = lane * run, count = n - first < run ? n - first : run;
+    in += (size_t)first * JACW;
+    out += (size_t)first * AFFW;
+    to_affine_run<F>(
+        count, [&](uint32_t i) { return ld_jac_blst(in + (size_t)i * JACW, (const jac<F>*)nullptr); },
+        [&](uint32_t i, const aff<F>& a) { st_aff_blst(out + (size_t)i * AFFW, a); },
+        [&](uint32_t i) {
+            for (uint32_t t = 0; t < AFFW; t++) out[(size_t)i * AFFW + t] = 0;
+        });
 }
 
 // ------------------------------------------------------------------------------------------

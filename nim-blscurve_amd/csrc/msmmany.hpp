@@ -68,4 +68,34 @@ BLS_HD int32_t many_digit(const uint32_t k[8], const plan::pip_win& W, uint32_t 
     return w + 1 == W.nwin ? raw : raw - (int32_t)(1u << (len - 1));
 }
 
+// The per-MSM tail of the G2 form (k_pip_tail_many_g2): ONE Horner walk over an MSM's window sums R_w from the top window down,
+// acc = 2^(width of window w) acc + R_w - nbits doublings in all, whatever the number of windows.  The schedule only: which window, how many
+// doublings, and whether the accumulator has started (empty top windows cost no doubling: the walk starts at the first window whose sum
+// is not infinity, and an MSM of empty windows only returns infinity without one).  The point operations are the caller's:
+//   Ops::point                     the accumulator's type
+//   inf(), is_inf(p), window(w)    the neutral element, the test for it, R_w
+//   dbl(p), add(p, q)              add must be COMPLETE: 2^width acc == +-R_w happens (tests/test_msm_many_g2_emu.py), and acc may turn infinite midway
+// The device passes the 8-lane cooperative doubling and the out-of-line complete addition, the host emulation jac_dbl and jac_add.
+template <class Ops>
+BLS_HD typename Ops::point many_tail_walk(const plan::pip_win& W, const Ops& ops) {
+    typename Ops::point acc = ops.inf();
+    bool started = false;
+#pragma clang loop unroll(disable)
+    for (uint32_t w = W.nwin; w-- > 0;) {
+        if (started) {
+            const uint32_t sh = many_win_off(W, w + 1) - many_win_off(W, w);
+#pragma clang loop unroll(disable)
+            for (uint32_t i = 0; i < sh; i++) acc = ops.dbl(acc);
+        }
+        const typename Ops::point R = ops.window(w);
+        if (started) {
+            acc = ops.add(acc, R);
+        } else if (!ops.is_inf(R)) {
+            acc = R;
+            started = true;
+        }
+    }
+    return acc;
+}
+
 }  // namespace bls

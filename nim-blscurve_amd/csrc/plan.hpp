@@ -973,7 +973,8 @@ inline msm_sizes msm_extents(const msm_plan& p, bool g2) {
 }
 
 // ------------------------------------------------------------------------------------------
-// k G1 MSMs in one device pass (mi355_bls_p1s_mult_pippenger_many): what msm_many_run follows, and what it reserves.
+// k G1 MSMs in one device pass (mi355_bls_p1s_mult_pippenger_many; the G2 form mi355_bls_p2s_mult_pippenger_many: see MSM_MANY_G2_* below):
+// what msm_many_run follows, and what it reserves.
 // Every stage of the bucket method works on VIRTUAL windows v = j x nwin + w (MSM j of the pass, its window w): the counting sort gives each
 // virtual window its buckets' point lists, and from there k_msm_order_*, k_pip_bucket, k_pip_segred(_team) and k_pip_winpart see one MSM of
 // k x nwin windows; k_pip_rowtail_many then walks each MSM's own nwin window parts, one workgroup per MSM.
@@ -995,6 +996,19 @@ constexpr uint32_t MSM_MANY_BUCKETS_MAX = 1u << 21;
 constexpr uint32_t MSM_MANY_PAIRS_MAX = 1u << 20;
 static_assert((uint64_t)MSM_MANY_PAIRS_MAX * MSM_WINDOWS_MAX < (1ull << 31), "a list position (pairs x windows) and a point index beside its sign bit fit a word");
 static_assert((uint64_t)MSM_MANY_BUCKETS_MAX * 16 < (1ull << 32), "k_pip_bucket's 16-byte bucket offsets");
+// The G2 form (mi355_bls_p2s_mult_pippenger_many): the same plan over 384-byte SoA points.  A pass takes HALF the buckets, so its bucket store
+// is no larger than a G1 pass's; the reduction is k_pip_segred<fp2> alone (team = 1: the lane teams are G1 code); the per-MSM tail is
+// k_pip_tail_many_g2, whose workgroup keeps an MSM's window sums in LDS (MSM_WINDOWS_MAX Jacobian points of G2_WORDS words: 24 KB) and is
+// MSM_MANY_G2_TAIL_WAVES waves wide - one wave per SIMD of a CU, so that the walking wave has the whole register file; that wave count is a
+// first choice, NOT MEASURED against others.  Its price: at ~340 registers a wave the workgroup needs all four SIMDs of a CU, three of which
+// idle through wave 0's walk, so a CU runs ONE walk at a time; the waves beside wave 0 only copy window sums (nsplit == 1) or do nothing
+// (nsplit > 1: Fp2 products may run in one wave of a workgroup at a time, fp.hpp bls_xchg).  A one-wave tail is the variant to measure next.  The window width stays pip_for's rule, made for G1 and NOT MEASURED for G2 (a G2 bucket
+// addition costs about three G1 ones, which argues for narrower windows on small members; nobody has tried).
+constexpr uint32_t MSM_MANY_G2_BUCKETS_MAX = MSM_MANY_BUCKETS_MAX / 2;
+constexpr uint32_t MSM_MANY_G2_TAIL_WAVES = 4;
+static_assert((uint64_t)MSM_MANY_G2_BUCKETS_MAX * G2_WORDS == (uint64_t)MSM_MANY_BUCKETS_MAX * G1_WORDS, "a G2 pass's bucket store is a G1 pass's");
+static_assert((((256 + 1 + 15) / 16) << 15) <= MSM_MANY_G2_BUCKETS_MAX, "one MSM always fits a G2 pass: pip_for's widest plan is 17 windows of 2^15 buckets");
+static_assert((size_t)MSM_WINDOWS_MAX * G2_WORDS * 4 <= 32 * 1024, "k_pip_tail_many_g2's window sums in LDS");
 struct msm_many_plan {
     pip_win W;
     bool shared;                       // every MSM over all npoints points | MSM j over [offsets[j], offsets[j + 1])
@@ -1003,20 +1017,23 @@ struct msm_many_plan {
     uint32_t segs_per_win, nsplit;     // as msm_plan's
     uint32_t tail_waves, tail_lanes;   // k_pip_rowtail_many's workgroup (one per MSM): a wave per window up to MSM_TAIL_WAVES_MAX
     uint32_t msms_max;                 // MSMs a pass takes at the most (virtual windows, buckets)
+    bool g2;                           // the G2 form: what msm_many_next / msm_many_extents / msm_many_sizes_for read the field from
 };
-inline msm_many_plan msm_many_for(size_t k, size_t npoints, bool shared, size_t nbits) {
+inline msm_many_plan msm_many_for(size_t k, size_t npoints, bool shared, size_t nbits, bool g2 = false) {
     msm_many_plan P{};
     P.shared = shared;
+    P.g2 = g2;
     const size_t mean = shared || k == 0 ? npoints : (npoints + k - 1) / k;
     P.n_ref = (uint32_t)(mean < 1 ? 1 : (mean > MSM_MANY_PAIRS_MAX ? MSM_MANY_PAIRS_MAX : mean));
     P.W = pip_for(P.n_ref, nbits);
     P.buckets_per_msm = P.W.nwin << P.W.cbk;
     P.segs_per_win = (1u << P.W.cbk) / MSM_SEG;
     P.nsplit = P.segs_per_win >= 1024 ? 16 : (P.segs_per_win >= 128 ? 4 : 1);
-    P.tail_waves = P.W.nwin < MSM_TAIL_WAVES_MAX ? P.W.nwin : MSM_TAIL_WAVES_MAX;
+    const uint32_t waves_max = g2 ? MSM_MANY_G2_TAIL_WAVES : MSM_TAIL_WAVES_MAX;
+    P.tail_waves = P.W.nwin < waves_max ? P.W.nwin : waves_max;
     P.tail_lanes = P.tail_waves * WAVE;
-    const uint32_t by_vwin = MSM_MANY_VWIN_MAX / P.W.nwin, by_buckets = MSM_MANY_BUCKETS_MAX / P.buckets_per_msm;
-    P.msms_max = by_vwin < by_buckets ? by_vwin : by_buckets;      // >= 1: 64 windows of 2^15 buckets are 2^21
+    const uint32_t by_vwin = MSM_MANY_VWIN_MAX / P.W.nwin, by_buckets = (g2 ? MSM_MANY_G2_BUCKETS_MAX : MSM_MANY_BUCKETS_MAX) / P.buckets_per_msm;
+    P.msms_max = by_vwin < by_buckets ? by_vwin : by_buckets;      // >= 1: 64 windows of 2^15 buckets are 2^21 (G2: pip_for's widest, 17 windows of 2^15, is below 2^20)
     return P;
 }
 // One step of a call: MSMs [j0, j1).  single: the one MSM j0 goes through msm_enqueue (the call has one MSM, or the member exceeds
@@ -1053,7 +1070,7 @@ inline msm_many_pass msm_many_next(const msm_many_plan& P, const size_t* offsets
     s.pair_grid = waves_for(s.pairs);
     s.order_grid = (s.total + WAVE * MSM_ORD_PER - 1) / (WAVE * MSM_ORD_PER);
     s.bucket_grid = waves_for(s.total);
-    s.team = (size_t)s.nseg * 4 <= MSM_TEAM_LANES_MAX ? 4 : ((size_t)s.nseg * 2 <= MSM_TEAM_LANES_MAX ? 2 : 1);
+    s.team = P.g2 ? 1 : ((size_t)s.nseg * 4 <= MSM_TEAM_LANES_MAX ? 4 : ((size_t)s.nseg * 2 <= MSM_TEAM_LANES_MAX ? 2 : 1));
     s.segred_grid = waves_for(s.nseg * s.team);
     return s;
 }
@@ -1061,25 +1078,26 @@ inline msm_many_pass msm_many_next(const msm_many_plan& P, const size_t* offsets
 // msm_many_sizes_for: what msm_many_run grows the workspace to before a call - the largest extent over the call's passes
 // (tests/test_msm_many_plan.py holds every pass to that).
 struct msm_many_sizes {
-    size_t pts_int;                    // k_pip_convert: point i at word i x 2 x FP_WORDS
+    size_t pts_int;                    // k_pip_convert: point i at word i x 2 x FP_WORDS (G2: x 4)
     size_t offs_dev;                   // ragged: the pass's k + 1 offsets, relative to its first pair
     size_t hist;                       // one word per bucket: hist, offs, cursor, order alike
     size_t chist;                      // k_msm_order_*: 256 bins
     size_t sorted;                     // virtual window v's list from word msmmany.hpp many_list_start(v): pairs x nwin words in all
-    size_t buckets, segout;            // SoA Jacobian G1 points: rows of `total` / `nseg`
+    size_t buckets, segout;            // SoA Jacobian points of G1_WORDS (G2: G2_WORDS) words: rows of `total` / `nseg`
     size_t part;                       // k_pip_winpart: a Jacobian point at (virtual window x nsplit + part)
 };
 inline msm_many_sizes msm_many_extents(const msm_many_plan& P, const msm_many_pass& s) {
     msm_many_sizes z{};
     if (s.single || s.pairs == 0) return z;
-    z.pts_int = (size_t)s.points * 2 * FP_WORDS * 4;
+    const size_t jac = P.g2 ? G2_WORDS : G1_WORDS;
+    z.pts_int = (size_t)s.points * (jac / 3 * 2) * 4;
     z.offs_dev = P.shared ? 0 : (s.j1 - s.j0 + 1) * 4;
     z.hist = (size_t)s.total * 4;
     z.chist = 256 * 4;
     z.sorted = (size_t)s.pairs * P.W.nwin * 4;
-    z.buckets = (size_t)s.total * G1_WORDS * 4;
-    z.segout = (size_t)s.nseg * G1_WORDS * 4;
-    z.part = (size_t)s.nv * P.nsplit * G1_WORDS * 4;
+    z.buckets = (size_t)s.total * jac * 4;
+    z.segout = (size_t)s.nseg * jac * 4;
+    z.part = (size_t)s.nv * P.nsplit * jac * 4;
     return z;
 }
 inline msm_many_sizes msm_many_sizes_for(const msm_many_plan& P, const size_t* offsets, size_t npoints, size_t k) {
@@ -1093,6 +1111,45 @@ inline msm_many_sizes msm_many_sizes_for(const msm_many_plan& P, const size_t* o
         j = s.j1;
     }
     return m;
+}
+
+// ------------------------------------------------------------------------------------------
+// Jacobian images to affine images (mi355_bls_p1s_to_affine / mi355_bls_p2s_to_affine): what to_affine_run follows.  A lane of k_to_affine
+// takes a RUN of `run` consecutive points and inverts once for all of them (csrc/toaffine.hpp): three products per point beside the one
+// inversion, where a lane per point pays an inversion each.
+//   run            one point per lane while the device has idle lanes (TOAFF_DEVICE_LANES: 256 CUs x 4 SIMDs x one wave of 64), then as many
+//                  as spread the call over those lanes, capped at TOAFF_RUN_MAX (the lane keeps the run's prefix products in private
+//                  memory).  Neither the rule nor the cap is MEASURED: a first choice.  force_run (the test hook
+//                  mi355_bls_debug_to_affine_set_run) replaces the rule, capped all the same; 0: the rule.
+//   one launch     at most TOAFF_CHUNK_POINTS points (point indices stay 32-bit words); a larger call is consecutive launches.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t TOAFF_DEVICE_LANES = 256 * 4 * WAVE;
+constexpr uint32_t TOAFF_RUN_MAX = 8;
+constexpr uint32_t TOAFF_CHUNK_POINTS = 1u << 24;
+static_assert((uint64_t)TOAFF_CHUNK_POINTS * 288 < (1ull << 33) && TOAFF_CHUNK_POINTS % TOAFF_RUN_MAX == 0, "a chunk's byte offsets are size_t; whole runs per chunk");
+struct to_affine_plan {
+    uint32_t run;                      // points per lane
+    uint32_t chunk;                    // points per launch
+};
+struct to_affine_launch {
+    size_t first;                      // the launch's first point in the call
+    uint32_t n;                        // its points
+    uint32_t lanes, grid;              // ceil(n / run) lanes in waves of WAVE
+};
+inline to_affine_plan to_affine_for(size_t n, uint32_t force_run = 0) {
+    to_affine_plan p{};
+    size_t run = force_run ? force_run : (n + TOAFF_DEVICE_LANES - 1) / TOAFF_DEVICE_LANES;
+    p.run = (uint32_t)(run < 1 ? 1 : (run > TOAFF_RUN_MAX ? TOAFF_RUN_MAX : run));
+    p.chunk = TOAFF_CHUNK_POINTS;
+    return p;
+}
+inline to_affine_launch to_affine_next(const to_affine_plan& p, size_t n, size_t first) {
+    to_affine_launch l{};
+    l.first = first;
+    l.n = (uint32_t)(n - first < p.chunk ? n - first : p.chunk);
+    l.lanes = (l.n + p.run - 1) / p.run;
+    l.grid = waves_for(l.lanes);
+    return l;
 }
 
 // ------------------------------------------------------------------------------------------
