@@ -710,6 +710,54 @@ int mi355_bls_p2s_to_affine(mi355_bls_ctx* ctx, const uint8_t* in288, size_t n, 
 int mi355_bls_p2s_to_affine_device(mi355_bls_ctx* ctx, const void* d_in288, size_t n, void* d_out192, void* stream);
 int mi355_bls_debug_to_affine_set_run(mi355_bls_ctx* ctx, uint32_t run);
 
+/* Short linear combinations for k groups in one device pass, with the CALLER's scalars: out[g] = sum_p [s_p mod 2^nbits] P_(t(p)) over the
+ * positions p of group g, as the canonical affine image (96-byte blst_p1_affine / 192-byte blst_p2_affine, Montgomery form; all zero =
+ * infinity) - what the pairing calls, the compress calls and the table-addressed calls take, with no to_affine call in between.  One lane
+ * per term multiplies (signed 4-bit windows, walked from window ceil(nbits / 4): 64-bit scalars pay 64 doublings), a segmented sum adds the
+ * products of a group, one inversion per group finishes.  This is the call for MANY SHORT groups - k openings [tau - z_g]G2, recoveries with
+ * host coefficients; mi355_bls_p?s_mult_pippenger_many stays the call for members of hundreds of points and more (its bucket method needs
+ * them to pay for 52 windows per member).
+ *   points, n_table, idx, offsets   the addressing of mi355_bls_aggregate_sets: a table of n_table affine images, an optional index array
+ *                  (repeats allowed: a fixed base such as the G2 generator is a one-row table with idx all 0), k + 1 host offsets, non-decreasing
+ *                  (group g = positions [offsets[g], offsets[g+1]) of the sequence)
+ *   scalars32      32 little-endian bytes per SEQUENCE POSITION, never taken through idx; offsets[k] x 32 bytes in all
+ *   nbits          1..256: only the low nbits bits of a scalar count
+ *   flags          0: subgroup membership is NOT assumed, the scalar acts as an integer (as in the MSM calls).
+ *                  MI355_BLS_LINCOMB_SUBGROUP (p2s only): the caller vouches that every point is in G2.  The scalar is then reduced mod r and
+ *                  written in base |x| (four digits below 2^64); psi acts on G2 as [x], so one four-way walk of 64 doublings replaces the
+ *                  256 of the plain route.  For a point outside G2 the result of this route is NOT the integer multiple.
+ *   out            k x 96 / k x 192 bytes, packed by group
+ *   status         k bytes, host memory: 3 an index was >= n_table (never dereferenced; wins over 1 and 2); 1 empty group; 2 the sum is the
+ *                  point at infinity (the all-zero image is its valid image); 0 ok.  Any status but 0 gives the all-zero image.
+ * An all-zero point and a zero scalar contribute nothing.  Device pointers are 4-byte aligned.
+ * Returns 1 when every status is 0, else 0; k == 0: 0, nothing written.  MI355_BLS_ERR_ARG: a NULL context (before any other rule), NULL
+ * arrays, decreasing offsets, offsets[k] > n_table without idx, a device pointer that is not 4-byte aligned, a busy context, nbits outside
+ * 1..256, an unknown flag bit, MI355_BLS_LINCOMB_SUBGROUP on the p1s call.  No call is refused for its size: it runs in chunks of whole
+ * groups (csrc/plan.hpp LINCOMB_TERMS_CHUNK), the workspace is sized by a chunk, nothing is bounded by max_sets.  The _device form enqueues
+ * on `stream` and synchronises it once per chunk, for the status bytes.
+ * VARIABLE TIME: public scalars only.
+ * COST (one MI355X, device-resident, median of 5 blocking calls; profiles/lincomb_bench.json, nim-blscurve_amd/tools/bench_lincomb.py; plain /
+ * MI355_BLS_LINCOMB_SUBGROUP / mi355_bls_p?s_mult_pippenger_many_device + mi355_bls_p?s_to_affine_device over the same terms):
+ *   G2, 255 bits: 4 096 x 2 over a one-row table (openings) 7.37 / 5.17 / 172 ms; 256 x 3: 7.25 / 5.04 / 12.3 ms (recover_signature_sets_device
+ *   over the same shares: 7.74 ms); 65 536 x 1: 11.3 / 8.66 / 2 662 ms; 4 096 x 16: 8.55 / 6.16 / 173 ms.  G2, 64 bits, 4 096 x 2: 2.28 / 2.45 /
+ *   41.5 ms.  G1: 4 096 x 2 at 255 bits 3.23 ms against 58.2, at 64 bits 1.13 against 33.6; 65 536 x 1: 6.18 ms against 8 770.
+ * WHICH CALL: this one for groups of up to some tens of terms - it won every measured row, 1.7 x to 1 400 x; larger members were not measured
+ * against mi355_bls_p?s_mult_pippenger_many, whose bucket method is made for them.  WHICH ROUTE on G2: MI355_BLS_LINCOMB_SUBGROUP for scalars
+ * wider than 64 bits when every point is known to be in G2 (1.3 - 1.4 x faster at 255 bits); flags 0 otherwise - at nbits = 64 the subgroup
+ * route is the SLOWER one (0.93 x).  The floor of a call is one lane's walk: 7.2 ms for 256 doublings, 5.0 ms for the subgroup route, 2.3 ms
+ * at 64 bits.
+ * debug_lincomb_set_chunk: TEST HOOK, the terms per chunk of the following lincomb_many calls on this context (0: the plan's own). */
+#define MI355_BLS_LINCOMB_SUBGROUP 1u
+int mi355_bls_p1s_lincomb_many(mi355_bls_ctx* ctx, const void* points96, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                               const void* scalars32, size_t nbits, uint32_t flags, void* out96, uint8_t* status);
+int mi355_bls_p1s_lincomb_many_device(mi355_bls_ctx* ctx, const void* d_points96, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                      size_t k, const void* d_scalars32, size_t nbits, uint32_t flags, void* d_out96, uint8_t* status, void* stream);
+int mi355_bls_p2s_lincomb_many(mi355_bls_ctx* ctx, const void* points192, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                               const void* scalars32, size_t nbits, uint32_t flags, void* out192, uint8_t* status);
+int mi355_bls_p2s_lincomb_many_device(mi355_bls_ctx* ctx, const void* d_points192, size_t n_table, const uint32_t* d_idx, const size_t* offsets,
+                                      size_t k, const void* d_scalars32, size_t nbits, uint32_t flags, void* d_out192, uint8_t* status, void* stream);
+int mi355_bls_debug_lincomb_set_chunk(mi355_bls_ctx* ctx, size_t members);
+
 /* Fixed-base G1 MSM over a precomputed window table: blst_p1s_mult_wbits_precompute(_sizeof) and blst_p1s_mult_wbits (blst_abi.nim:327-335)
  * for callers whose point set does not change - k commitments over one SRS or Lagrange table.  A table is a library-owned handle that keeps, in
  * device memory, the rows [2^(w wbits)] P_i for w = 0 .. W - 1, W = ceil((nbits + 1) / wbits), W x npoints x 128 bytes

@@ -172,6 +172,10 @@ def lib():
         L.mi355_bls_p2s_to_affine.argtypes = [vp, vp, sz, vp]
         L.mi355_bls_p2s_to_affine_device.argtypes = [vp, vp, sz, vp, vp]
         L.mi355_bls_debug_to_affine_set_run.argtypes = [vp, u32]
+        for name in ("mi355_bls_p1s_lincomb_many", "mi355_bls_p2s_lincomb_many"):
+            getattr(L, name).argtypes = [vp, vp, sz, pu32, psz, sz, vp, sz, u32, vp, vp]
+            getattr(L, name + "_device").argtypes = [vp, vp, sz, vp, psz, sz, vp, sz, u32, vp, vp, vp]
+        L.mi355_bls_debug_lincomb_set_chunk.argtypes = [vp, sz]
         L.mi355_bls_p1s_table_sizeof.argtypes = [sz, sz, sz]
         L.mi355_bls_p1s_table_sizeof.restype = sz
         L.mi355_bls_p1s_table_create.argtypes = [vp, vp, vp, sz, sz, sz]
@@ -1276,13 +1280,14 @@ def batchPairingCheckLocate_device(cache, d_p1s, d_q2s, offsets, secureRandomByt
     return ok, [x == 1 for x in out.raw]
 
 
-def _signature_lists(signatures):
+def _signature_lists(signatures, row=192, what="signature"):
     """The signature lists of aggregateSignatureSets -> (table bytes, n_table, idx array or None, offsets array, k).  signatures: a list of
     signature lists (each a list of 192-byte blst_p2_affine images, or their concatenation) - they are laid end to end and no index array is
-    sent - or a tuple (table, idx, offsets) as aggregateSets takes it for keys."""
+    sent - or a tuple (table, idx, offsets) as aggregateSets takes it for keys.  row, what: the same for other rows (the points of the
+    lincomb calls)."""
     if isinstance(signatures, tuple):
         table, idx, offsets = signatures
-        table = _join(table, 192, "signature table")
+        table = _join(table, row, what + " table")
         offsets = [int(x) for x in offsets]
         if idx is not None:
             idx = [int(x) for x in idx]
@@ -1291,15 +1296,15 @@ def _signature_lists(signatures):
             if offsets and offsets[-1] != len(idx):
                 raise ValueError("offsets[k] is the length of the index array")
     else:
-        lists = [_join(x, 192, "signatures") for x in signatures]
+        lists = [_join(x, row, what + "s") for x in signatures]
         table, idx, offsets = b"".join(lists), None, [0]
         for x in lists:
-            offsets.append(offsets[-1] + len(x) // 192)
+            offsets.append(offsets[-1] + len(x) // row)
     if not offsets or any(x < 0 for x in offsets):
         raise ValueError("offsets: k + 1 non-negative positions")
     k = len(offsets) - 1
     iarr = (ctypes.c_uint32 * max(len(idx), 1))(*idx) if idx is not None else None
-    return table, len(table) // 192, iarr, (ctypes.c_size_t * (k + 1))(*offsets), k
+    return table, len(table) // row, iarr, (ctypes.c_size_t * (k + 1))(*offsets), k
 
 
 def aggregateSignatureSets(cache, signatures, want192=True, want96=True):
@@ -1391,6 +1396,90 @@ def recoverSignatureSets_device(cache, d_sigs, n_table, d_idx, offsets, d_ids, d
     ok = _check(lib().mi355_bls_recover_signature_sets_device(cache._h, d_sigs, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k, d_ids,
                                                               d_out192 or None, d_out96 or None, st, stream))
     return bool(ok), st.raw
+
+
+LINCOMB_SUBGROUP = 1                   # flag of p2sLincombMany: the caller vouches that every point is in G2
+
+
+def _scalars_by_position(scalars, n_terms):
+    """scalars: a list of lists (one per group) of 32-byte little-endian images or of integers below 2^256, or their concatenation by
+    position -> n_terms x 32 bytes"""
+    if isinstance(scalars, (bytes, bytearray, memoryview)):
+        b = bytes(scalars)
+    else:
+        flat = []
+        for x in scalars:
+            flat += [x] if isinstance(x, (int, bytes, bytearray, memoryview)) else list(x)
+        flat = [int(e).to_bytes(32, "little") if isinstance(e, int) else bytes(e) for e in flat]      # OverflowError is a ValueError's kin: let it out
+        if any(len(e) != 32 for e in flat):
+            raise ValueError("scalars: 32 bytes each")
+        b = b"".join(flat)
+    if len(b) != 32 * n_terms:
+        raise ValueError("one 32-byte scalar per term: %d bytes for %d terms" % (len(b), n_terms))
+    return b
+
+
+def _lincomb_args(nbits, flags, g2):
+    if not 1 <= int(nbits) <= 256:
+        raise ValueError("nbits is 1..256")
+    if int(flags) & ~(LINCOMB_SUBGROUP if g2 else 0):
+        raise ValueError("flags: LINCOMB_SUBGROUP on the G2 call, nothing else")
+
+
+def _lincomb_many(cache, g2, points, scalars, nbits, flags):
+    _lincomb_args(nbits, flags, g2)
+    row = 192 if g2 else 96
+    table, n_table, idx, offs, k = _signature_lists(points, row, "point")
+    sc = _scalars_by_position(scalars, offs[k] if k else 0)
+    if k == 0:
+        return False, b"", b""
+    out, st = ctypes.create_string_buffer(row * k), ctypes.create_string_buffer(k)
+    fn = lib().mi355_bls_p2s_lincomb_many if g2 else lib().mi355_bls_p1s_lincomb_many
+    ok = _check(fn(cache._h, table or b"\0", n_table, idx, offs, k, sc or b"\0", int(nbits), int(flags), out, st))
+    return bool(ok), out.raw, st.raw
+
+
+def _lincomb_many_device(cache, g2, d_points, n_table, d_idx, offsets, d_scalars, d_out, nbits, flags, stream):
+    _lincomb_args(nbits, flags, g2)
+    k = len(offsets) - 1
+    if k <= 0:
+        return False, b""
+    st = ctypes.create_string_buffer(k)
+    fn = lib().mi355_bls_p2s_lincomb_many_device if g2 else lib().mi355_bls_p1s_lincomb_many_device
+    ok = _check(fn(cache._h, d_points, n_table, d_idx or None, (ctypes.c_size_t * (k + 1))(*offsets), k, d_scalars, int(nbits), int(flags), d_out or None, st, stream))
+    return bool(ok), st.raw
+
+
+def p1sLincombMany(cache, points, scalars, nbits=255, flags=0):
+    """out[g] = sum_p [s_p mod 2^nbits] P_p for every group of (point, scalar) terms in one device pass (mi355_bls_p1s_lincomb_many): the call
+    for many SHORT groups.  points: a list of point lists (96-byte blst_p1_affine images, or their concatenation), or a tuple (table, idx,
+    offsets) as aggregateSets takes it; scalars: one per sequence position (_scalars_by_position), never taken through idx.
+    -> (all_ok, k x 96-byte affine images, k status bytes: 0 ok, 1 empty group, 2 the sum is infinity, 3 index out of range; any status but 0
+    gives the all-zero image).  VARIABLE TIME: public scalars only."""
+    return _lincomb_many(cache, False, points, scalars, nbits, flags)
+
+
+def p2sLincombMany(cache, points, scalars, nbits=255, flags=0):
+    """The same on G2 (192-byte blst_p2_affine images; mi355_bls_p2s_lincomb_many).  flags = LINCOMB_SUBGROUP: the caller vouches that every
+    point is in G2, and the multiplication walks 64 doublings through the psi endomorphism instead of nbits; with flags = 0 the scalar acts
+    as an integer and nothing is assumed about the points."""
+    return _lincomb_many(cache, True, points, scalars, nbits, flags)
+
+
+def p1sLincombMany_device(cache, d_points, n_table, d_idx, offsets, d_scalars, d_out, nbits=255, flags=0, stream=0):
+    """Same with the point table, the indices (0 / None: none), the scalars (32 bytes per sequence position) and the output (k x 96 bytes) in
+    device memory (raw pointers); offsets stay on the host.  -> (all_ok, status bytes)."""
+    return _lincomb_many_device(cache, False, d_points, n_table, d_idx, offsets, d_scalars, d_out, nbits, flags, stream)
+
+
+def p2sLincombMany_device(cache, d_points, n_table, d_idx, offsets, d_scalars, d_out, nbits=255, flags=0, stream=0):
+    """The G2 form (k x 192 bytes out): d_out is, as it stands, the d_q2s argument of pairingCheckEach_device."""
+    return _lincomb_many_device(cache, True, d_points, n_table, d_idx, offsets, d_scalars, d_out, nbits, flags, stream)
+
+
+def debug_lincomb_set_chunk(cache, terms=0):
+    """TEST HOOK (mi355_bls_debug_lincomb_set_chunk): the terms per chunk of the following lincomb calls on this context; 0: the plan's own."""
+    _check(lib().mi355_bls_debug_lincomb_set_chunk(cache._h, int(terms)))
 
 
 def compressSignatures(cache, signatures):

@@ -42,15 +42,17 @@ struct ptab_ws {
 //                               has tables of its own and takes the flag words alone
 //   d_status, status_h          all but by_message and aggregate_verify_each
 //   d_g1_part                   aggregate_sets, aggregate_sets_bits, combine_sets (key side), by_message
-//   d_g2_prod                   combine_sets ([s_j]S_j), recover_signature_sets ([l_j]S_j)
-//   d_g2_part                   combine_sets (signature side), aggregate_signature_sets, recover_signature_sets
+//   d_g1_prod                   p1s_lincomb_many ([s_p]P_p; its partials are in d_g1_part)
+//   d_g2_prod                   combine_sets ([s_j]S_j), recover_signature_sets ([l_j]S_j), p2s_lincomb_many ([s_p]Q_p)
+//   d_g2_part                   combine_sets (signature side), aggregate_signature_sets, recover_signature_sets, p2s_lincomb_many
 //   d_rec                       aggregate_sets, aggregate_sets_bits, combine_sets: the forms that verify their records, and the host forms
 //   d_in                        the host forms of all but by_message
-//   d_g2_out                    the host forms of aggregate_signature_sets and recover_signature_sets
+//   d_g2_out                    the host forms of aggregate_signature_sets, recover_signature_sets and the two lincomb_many calls
 struct grouped_ws {
     std::vector<uint32_t> items;     // the item table of the call in flight (the feature's words behind it): the async copy reads it
     dev_buf<uint32_t> d_items;       // ... on the device
     dev_buf<uint32_t> d_g1_part;     // the plan's G1 partials, G1W words each
+    dev_buf<uint32_t> d_g1_prod;     // a G1 product per term, G1W words each
     dev_buf<uint32_t> d_g2_prod;     // a G2 product per member, G2W words each
     dev_buf<uint32_t> d_g2_part;     // the plan's G2 partials, G2W words each
     dev_buf<uint32_t> d_flag;        // per group: an index was out of range (or what else the feature's kernels raise)
@@ -202,6 +204,7 @@ struct mi355_bls_ctx {
     dev_buf<uint8_t> d_toaff_in, d_toaff_out;
     uint32_t toaff_run = 0;          // mi355_bls_debug_to_affine_set_run; 0: the plan's own
     std::vector<uint32_t> many_offs; // the ragged passes' offsets of the call in flight: the async copies read them
+    size_t lincomb_chunk = 0;        // mi355_bls_debug_lincomb_set_chunk: terms per chunk of the lincomb_many calls; 0: the plan's own
     ptab_ws ptab;                    // MSMs over a fixed-base window table: made at the first such call
     // per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): sized by the largest slice of a call; it runs in the per-set path's
     // pair store with the per-group path's tables, partials and step values (d_aggv_*) and combine_sets' G2 products and tables (grp, d_comb_*)
@@ -2350,6 +2353,134 @@ extern "C" int mi355_bls_recover_signature_sets(mi355_bls_ctx* c, const void* si
     if (int rc = stage_inputs(c, {{sigs192, n_table * 192}, {ids32, offsets[k] * 32}, {idx, offsets[k] * 4}}, nullptr, d)) return rc;
     return recover_run(c, d[0], n_table, reinterpret_cast<const uint32_t*>(d[2]), offsets, k, d[1], nullptr, nullptr, (uint8_t*)out_sigs192, (uint8_t*)out_sigs96, status,
                        nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Short linear combinations per group with the caller's scalars (mi355_bls_p1s_lincomb_many / mi355_bls_p2s_lincomb_many): the recovery's
+// walk - chunks of whole groups (plan.hpp lincomb_chunk_end), per chunk a lane per term (k_lincomb_mul<F>, or k_lincomb_mul_psi under
+// MI355_BLS_LINCOMB_SUBGROUP), the segmented sum over the products and k_lincomb_finish<F>, all on the caller's stream, then the chunk's
+// status bytes come back (its synchronisation: the host table of the next chunk reuses the vector).
+// ------------------------------------------------------------------------------------------
+template <class F>
+static bool lincomb_args_ok(size_t nbits, uint32_t flags) {
+    const uint32_t known = sizeof(F) != sizeof(fp) ? (uint32_t)MI355_BLS_LINCOMB_SUBGROUP : 0u;
+    if (nbits >= 1 && nbits <= 256 && !(flags & ~known)) return true;
+    g_err = "lincomb_many: nbits is 1..256; the only flag is MI355_BLS_LINCOMB_SUBGROUP, on the p2s call";
+    return false;
+}
+// h_out: the host form - the device output is then the chunk's own (grp.d_g2_out) and copied out chunk by chunk
+template <class F>
+static int lincomb_run(mi355_bls_ctx* c, const uint8_t* d_pts, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k, const uint8_t* d_sc,
+                       size_t nbits, uint32_t flags, uint8_t* d_out, uint8_t* h_out, uint8_t* status, hipStream_t st) {
+    constexpr bool G2 = sizeof(F) != sizeof(fp);
+    constexpr size_t AFFB = G2 ? 192 : 96;
+    if (!d_pts || !offsets || !d_sc || !status || (!h_out && !d_out) || !lincomb_args_ok<F>(nbits, flags)) return MI355_BLS_ERR_ARG;
+    if (((uintptr_t)d_pts | (uintptr_t)d_idx | (uintptr_t)d_sc | (uintptr_t)d_out) & 3) {
+        g_err = "lincomb_many: points, indices, scalars and outputs must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const plan::recover_plan rp = plan::lincomb_measure(offsets, k, c->lincomb_chunk);
+    if (!rp.ok) {
+        g_err = "lincomb_many: offsets decrease, or 2^32 - 1 positions or groups, or more";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (!table_holds(d_idx, offsets, k, n_table, "lincomb_many: offsets[k] exceeds the number of points")) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    if (h_out) {
+        if (int rc = c->grp.d_g2_out.reserve(rp.max_groups * AFFB, rp.max_groups * AFFB / 4)) return rc;
+    }
+    const bool psi = G2 && (flags & MI355_BLS_LINCOMB_SUBGROUP);
+    dev_buf<uint32_t>& prod_buf = G2 ? c->grp.d_g2_prod : c->grp.d_g1_prod;
+    dev_buf<uint32_t>& part_buf = G2 ? c->grp.d_g2_part : c->grp.d_g1_part;
+    std::vector<size_t> ro;
+    int all = 1;
+    for (size_t g0 = 0; g0 < k;) {
+        const size_t g1 = plan::lincomb_chunk_end(offsets, k, g0, c->lincomb_chunk), kc = g1 - g0, base = offsets[g0], m = offsets[g1] - base;
+        ro.resize(kc + 1);
+        for (size_t i = 0; i <= kc; i++) ro[i] = offsets[g0 + i] - base;
+        const plan::aggsets_plan p = plan::aggsets_measure(ro.data(), kc);
+        if (!p.ok) return MI355_BLS_ERR_ARG;           // cannot happen below 2^32 - 1 positions
+        const plan::lincomb_sizes sz = plan::lincomb_sizes_for(p, m, kc, G2);
+        c->grp.items.resize(sz.tab / 4);
+        uint32_t* tab = c->grp.items.data();
+        const size_t t_items = m * 4, t_final = t_items + p.items * 4, t_len = t_final + kc;
+        plan::recover_fill(offsets, g0, g1, reinterpret_cast<plan::rec_item*>(tab));
+        plan::aggsets_fill(p, ro.data(), kc, reinterpret_cast<plan::agg_item*>(tab + t_items), tab + t_final);
+        for (size_t i = 0; i < kc; i++) tab[t_len + i] = (uint32_t)(ro[i + 1] - ro[i]);
+        // never beyond what the largest chunk needs; the previous chunk has drained the stream
+        int rc = prod_buf.reserve(sz.prod, sz.prod / 4);
+        if (!rc) rc = part_buf.reserve(sz.part, sz.part / 4);
+        if (!rc) rc = grouped_upload(c, sz.tab, sz.flags, sz.status, st);
+        if (rc) return rc;
+        const uint4* items = reinterpret_cast<const uint4*>(c->grp.d_items.p);
+        const uint32_t *pts = reinterpret_cast<const uint32_t*>(d_pts), *sc = reinterpret_cast<const uint32_t*>(d_sc);
+        uint32_t *prod = prod_buf, *part = part_buf;
+        if (m) {
+            if constexpr (G2) {
+                if (psi) k_lincomb_mul_psi<<<plan::waves_for((uint32_t)m), WAVE, 0, st>>>(items, (uint32_t)m, pts, n_table, d_idx, sc, (uint32_t)nbits, (uint32_t)base, prod, c->grp.d_flag);
+                else k_lincomb_mul<fp2><<<plan::waves_for((uint32_t)m), WAVE, 0, st>>>(items, (uint32_t)m, pts, n_table, d_idx, sc, (uint32_t)nbits, (uint32_t)base, prod, c->grp.d_flag);
+            } else {
+                k_lincomb_mul<fp><<<plan::waves_for((uint32_t)m), WAVE, 0, st>>>(items, (uint32_t)m, pts, n_table, d_idx, sc, (uint32_t)nbits, (uint32_t)base, prod, c->grp.d_flag);
+            }
+        }
+        const auto sum = [&](const uint4* it, uint32_t cnt, const uint32_t* src) {      // one kernel at every level: level 0 sums the products, the levels above it the partials
+            if constexpr (G2) k_combsets_g2_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, src, part);
+            else k_lincomb_g1_sum<<<plan::waves_for(cnt), WAVE, 0, st>>>(it, cnt, src, part);
+        };
+        launch_levels(p, items + m, [&](const uint4* it, uint32_t cnt) { sum(it, cnt, prod); }, [&](const uint4* it, uint32_t cnt) { sum(it, cnt, part); });
+        uint8_t* o = h_out ? c->grp.d_g2_out.p : d_out + g0 * AFFB;
+        k_lincomb_finish<F><<<plan::waves_for((uint32_t)kc), WAVE, 0, st>>>(c->grp.d_items + t_final, c->grp.d_items + t_len, (uint32_t)kc, part, c->grp.d_flag,
+                                                                           reinterpret_cast<uint32_t*>(o), c->grp.d_status);
+        HIPCHK(hipGetLastError());
+        if (h_out) HIPCHK(hipMemcpyAsync(h_out + g0 * AFFB, o, kc * AFFB, hipMemcpyDeviceToHost, st));
+        const int ok = grouped_status(c, kc, status + g0, st);
+        if (ok < 0) return ok;
+        all &= ok;
+        g0 = g1;
+    }
+    return all;
+}
+template <class F>
+static int lincomb_device(mi355_bls_ctx* c, const void* d_pts, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k, const void* d_sc, size_t nbits,
+                          uint32_t flags, void* d_out, uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing computed, nothing written
+    return lincomb_run<F>(c, (const uint8_t*)d_pts, n_table, d_idx, offsets, k, (const uint8_t*)d_sc, nbits, flags, (uint8_t*)d_out, nullptr, status, (hipStream_t)stream);
+}
+template <class F>
+static int lincomb_host(mi355_bls_ctx* c, const void* pts, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k, const void* sc, size_t nbits,
+                        uint32_t flags, void* out, uint8_t* status) {
+    constexpr size_t AFFB = sizeof(F) == sizeof(fp) ? 96 : 192;
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!pts || !offsets || !sc || !status || !out || !agg_offsets_ok(offsets, k) || !lincomb_args_ok<F>(nbits, flags)) return MI355_BLS_ERR_ARG;
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const uint8_t* d[3];      // points | scalars | indices
+    if (int rc = stage_inputs(c, {{pts, n_table * AFFB}, {sc, offsets[k] * 32}, {idx, offsets[k] * 4}}, nullptr, d)) return rc;
+    return lincomb_run<F>(c, d[0], n_table, reinterpret_cast<const uint32_t*>(d[2]), offsets, k, d[1], nbits, flags, nullptr, (uint8_t*)out, status, nullptr);
+}
+extern "C" int mi355_bls_p1s_lincomb_many(mi355_bls_ctx* c, const void* points96, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                          const void* scalars32, size_t nbits, uint32_t flags, void* out96, uint8_t* status) {
+    return lincomb_host<fp>(c, points96, n_table, idx, offsets, k, scalars32, nbits, flags, out96, status);
+}
+extern "C" int mi355_bls_p1s_lincomb_many_device(mi355_bls_ctx* c, const void* d_points96, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                                 const void* d_scalars32, size_t nbits, uint32_t flags, void* d_out96, uint8_t* status, void* stream) {
+    return lincomb_device<fp>(c, d_points96, n_table, d_idx, offsets, k, d_scalars32, nbits, flags, d_out96, status, stream);
+}
+extern "C" int mi355_bls_p2s_lincomb_many(mi355_bls_ctx* c, const void* points192, size_t n_table, const uint32_t* idx, const size_t* offsets, size_t k,
+                                          const void* scalars32, size_t nbits, uint32_t flags, void* out192, uint8_t* status) {
+    return lincomb_host<fp2>(c, points192, n_table, idx, offsets, k, scalars32, nbits, flags, out192, status);
+}
+extern "C" int mi355_bls_p2s_lincomb_many_device(mi355_bls_ctx* c, const void* d_points192, size_t n_table, const uint32_t* d_idx, const size_t* offsets, size_t k,
+                                                 const void* d_scalars32, size_t nbits, uint32_t flags, void* d_out192, uint8_t* status, void* stream) {
+    return lincomb_device<fp2>(c, d_points192, n_table, d_idx, offsets, k, d_scalars32, nbits, flags, d_out192, status, stream);
+}
+// TEST HOOK: the terms per chunk of the following lincomb_many calls on this context (0: the plan's own)
+extern "C" int mi355_bls_debug_lincomb_set_chunk(mi355_bls_ctx* c, size_t members) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    c->lincomb_chunk = members;
+    return 0;
 }
 
 // The two decoders, k_deser's halves: Signature.fromBytes (bls_sig_io.nim:42-58) for n signatures without key or message, PublicKey.fromBytes (:81-121)

@@ -43,6 +43,7 @@
 #include "bymsg.hpp"
 #include "aggsigs.hpp"
 #include "recover.hpp"
+#include "lincomb.hpp"
 #include "keytable.hpp"
 #include "msmmany.hpp"
 #include "msmtable.hpp"
@@ -3113,6 +3114,66 @@ __global__ void __launch_bounds__(WAVE) k_recover_finish(const uint32_t* __restr
         for (int i = 0; i < 48; i++) out192[(size_t)g * 48 + i] = e.sig[i];
     if (out96)
         for (int i = 0; i < 24; i++) out96[(size_t)g * 24 + i] = e.wire[i];
+    status[g] = e.status;
+}
+
+// ------------------------------------------------------------------------------------------
+// Short linear combinations of many groups with the caller's scalars (mi355_bls_p1s_lincomb_many / mi355_bls_p2s_lincomb_many).  The
+// arithmetic is csrc/lincomb.hpp; the term items are plan.hpp recover_fill's (pos, seg_first, seg_len, seg: one 16-byte load).  Per term:
+// k_lincomb_mul<F>, or k_lincomb_mul_psi for G2 points the caller vouches for.  Per group: the segmented sum over plan.hpp aggsets_fill's
+// tables - G2: k_combsets_g2_sum as it stands, G1: k_lincomb_g1_sum, level 0 reading the products by position - and k_lincomb_finish<F>.
+// One-wave workgroups throughout (fp.hpp bls_xchg).  The window table of either multiplication is the lane's own, as in k_recover_mul.
+// ------------------------------------------------------------------------------------------
+// one lane per term of a chunk: [s mod 2^nbits] P for its point P (a blst_p1_affine / blst_p2_affine image; through idx into a table of
+// n_table points when idx != nullptr) and the scalar at its position (sc: 8 little-endian words per position of the call) -> product number
+// pos - base of `prod` (internal Jacobian image).  An index that is not below n_table is not dereferenced: the lane sets its group's word.
+template <class F>
+__global__ void __launch_bounds__(WAVE) k_lincomb_mul(const uint4* __restrict__ items, uint32_t n_items, const uint32_t* __restrict__ pts, size_t n_table,
+                                                      const uint32_t* __restrict__ idx, const uint32_t* __restrict__ sc, uint32_t nbits, uint32_t base,
+                                                      uint32_t* __restrict__ prod, uint32_t* __restrict__ seg_flags) {
+    constexpr uint32_t AFFW = fld<F>::AFFB / 4, JACW = 3 * fld<F>::W;
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    uint32_t fl = 0;
+    const jac<F> r = lincomb_mul_item<F>(it.x, idx, n_table, nbits, [&](size_t t) { return ld_aff_blst(pts + t * AFFW, (const aff<F>*)nullptr); },
+                                         [&](uint32_t pos, int w) { return sc[(size_t)pos * 8 + w]; }, fl);
+    if (fl) atomicOr(seg_flags + it.w, fl);
+    st_jac_int(prod + (size_t)(it.x - base) * JACW, r);
+}
+// the same for G2 points in the prime-order subgroup: the scalar mod r through the psi endomorphism (lincomb.hpp lincomb_mul_psi_body)
+__global__ void __launch_bounds__(WAVE) k_lincomb_mul_psi(const uint4* __restrict__ items, uint32_t n_items, const uint32_t* __restrict__ pts, size_t n_table,
+                                                          const uint32_t* __restrict__ idx, const uint32_t* __restrict__ sc, uint32_t nbits, uint32_t base,
+                                                          uint32_t* __restrict__ prod, uint32_t* __restrict__ seg_flags) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    uint32_t fl = 0;
+    const g2_jac r = lincomb_mul_psi_item(it.x, idx, n_table, nbits, [&](size_t t) { return ld_g2a_blst(pts + t * 48); },
+                                          [&](uint32_t pos, int w) { return sc[(size_t)pos * 8 + w]; }, fl);
+    if (fl) atomicOr(seg_flags + it.w, fl);
+    st_g2_int(prod + (size_t)(it.x - base) * G2W, r);
+}
+// the G1 sum, one lane per item: up to AGG_C internal G1 images of `src` (level 0: the per-term products; above: the partials) -> partial
+// it.z of `dst` (k_combsets_g2_sum's item body on fp)
+__global__ void __launch_bounds__(WAVE) k_lincomb_g1_sum(const uint4* __restrict__ items, uint32_t n_items, const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const uint4 it = items[i];
+    st_g1_int(dst + (size_t)it.z * G1W, combsets_sum_item<fp>(it.x, it.y, [&](uint32_t j) { return ld_g1_int(src + (size_t)j * G1W); }));
+}
+// one lane per group of a chunk: its last partial (final_of[g]; 0xffffffff: no term at all) to affine with one inversion; the 96-byte /
+// 192-byte image, packed by group, and the status byte (lincomb_finish_item)
+template <class F>
+__global__ void __launch_bounds__(WAVE) k_lincomb_finish(const uint32_t* __restrict__ final_of, const uint32_t* __restrict__ seg_len, uint32_t k,
+                                                         const uint32_t* __restrict__ part, const uint32_t* __restrict__ seg_flags, uint32_t* __restrict__ out,
+                                                         uint8_t* __restrict__ status) {
+    constexpr uint32_t AFFW = fld<F>::AFFB / 4, JACW = 3 * fld<F>::W;
+    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= k) return;
+    const uint32_t f = final_of[g];
+    const lincomb_end<F> e = lincomb_finish_item<F>(seg_len[g], seg_flags[g], f == 0xffffffffu ? jac_inf<F>() : ld_jac_int(part + (size_t)f * JACW, (const jac<F>*)nullptr));
+    for (uint32_t i = 0; i < AFFW; i++) out[(size_t)g * AFFW + i] = e.img[i];
     status[g] = e.status;
 }
 

@@ -578,6 +578,29 @@ inline recover_sizes recover_sizes_for(const aggsets_plan& p, size_t members, si
             groups * 4, groups, groups * 192, groups * 96};
 }
 
+// Short linear combinations per group (mi355_bls_p1s_lincomb_many / mi355_bls_p2s_lincomb_many): the recovery's shape with the caller's
+// scalars - one lane per term multiplies (k_lincomb_mul<F>, k_lincomb_mul_psi: waves_for(terms) workgroups of WAVE lanes), the segmented sum
+// of aggsets_measure / aggsets_fill over the renumbered offsets adds the products per group (level 0 reads them by position), a lane per
+// group finishes (k_lincomb_finish<F>).  The term items are recover_fill's rec_item; the call runs in chunks of whole groups by
+// recover_chunk_end's rule, and the workspace holds one chunk.
+//   LINCOMB_TERMS_CHUNK is the recovery's MEMORY bound: 65 536 products are 24 MiB on G2 and 12 MiB on G1, and as many lanes are one wave
+//   per SIMD of the chip.  Not tuned.  `forced` is the test hook's (mi355_bls_debug_lincomb_set_chunk; 0: the constant).
+//   Refused: offsets that decrease, and what the 32-bit tables cannot address (2^32 - 1 positions or groups, or more).  Nothing for its size.
+constexpr size_t LINCOMB_TERMS_CHUNK = REC_MEMBERS_CHUNK;
+inline size_t lincomb_chunk(size_t forced) { return forced ? forced : LINCOMB_TERMS_CHUNK; }
+inline recover_plan lincomb_measure(const size_t* offsets, size_t k, size_t forced = 0) { return recover_measure(offsets, k, lincomb_chunk(forced)); }
+inline size_t lincomb_chunk_end(const size_t* offsets, size_t k, size_t g0, size_t forced = 0) { return recover_chunk_end(offsets, k, g0, lincomb_chunk(forced)); }
+// The workspace of one chunk of `terms` terms in `groups` groups whose segmented sum is `p`, in bytes; g2: 384-byte Jacobian points and 192-byte
+// images, else 192 and 96.  The products, the sum's partials (one at least), the tables (term items | sum items | final_of | group lengths), a
+// flag word and a status byte per group, and the host form's output array.
+struct lincomb_sizes {
+    size_t prod, part, tab, flags, status, out;
+};
+inline lincomb_sizes lincomb_sizes_for(const aggsets_plan& p, size_t terms, size_t groups, bool g2) {
+    const size_t jac = (size_t)(g2 ? G2_WORDS : G1_WORDS) * 4;
+    return {(terms ? terms : 1) * jac, (p.items ? p.items : 1) * jac, ((terms + p.items) * 4 + 2 * groups) * 4, groups * 4, groups, groups * (g2 ? 192 : 96)};
+}
+
 // Per-group aggregateVerify (mi355_bls_aggregate_verify_each): k groups of (key, message) pairs in CSR form, one aggregate signature each.
 // The call runs in SLICES of at most `cap` pairs of the per-set path's pair store (2 cap slots: the pairs, then one (-G1, sig) pair per
 // group that ends in the slice - never more than the pairs, a group in a slice has a pair there).
