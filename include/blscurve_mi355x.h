@@ -758,6 +758,47 @@ int mi355_bls_p2s_lincomb_many_device(mi355_bls_ctx* ctx, const void* d_points19
                                       size_t k, const void* d_scalars32, size_t nbits, uint32_t flags, void* d_out192, uint8_t* status, void* stream);
 int mi355_bls_debug_lincomb_set_chunk(mi355_bls_ctx* ctx, size_t members);
 
+/* Openings of k polynomials over the scalar field Fr in one device pass: for polynomial g of n scalars and its point z_g, the value
+ * y_g = p_g(z_g) and the quotient q_g(X) = (p_g(X) - y_g) / (X - z_g), written as canonical 32-byte little-endian images in the scalar layout
+ * the MSM calls read - a proof is mi355_bls_fr_open_many_device followed by mi355_bls_p1s_mult_table_many_device, or by
+ * mi355_bls_p1s_mult_pippenger_many_device, over the quotients, with no scalar visiting the host.
+ *   polys32        k x n 32-byte little-endian images; polynomial g is images [g n, (g + 1) n)
+ *   zs32           k images
+ *                  ANY 256-bit image is accepted and acts as its value mod r.
+ *   out_ys32       k images in [0, r)
+ *   out_quot32     k x n images in [0, r), laid out like polys32
+ *   status         k bytes, HOST memory, may be NULL.  Both bits are informational - the outputs are valid whenever the call returns >= 0:
+ *                  bit 0 (1): z lies in the domain (evaluation form only); bit 1 (2): an image of this polynomial, or its z, was >= r and
+ *                  was reduced.
+ *   Each output may be NULL on its own (it is then not computed or not stored); all three NULL is MI355_BLS_ERR_ARG, and so is the host form
+ *   without out_ys32 and out_quot32.  Outputs must not overlap inputs.  Device pointers are 4-byte aligned (16-byte aligned ones are read
+ *   and written 16 bytes at a time).
+ * flags == 0, COEFFICIENT form: p_g = sum c_i X^i, domain32 must be NULL.  Quotient slot i holds q_i for i < n - 1 (q_(i-1) = c_i + z q_i);
+ *   slot n - 1 holds 0, the PADDING SLOT: the n-point table that committed to p_g serves q_g as it stands.
+ * MI355_BLS_FR_OPEN_EVAL, EVALUATION form: domain32 is required, n images x_i shared by all k polynomials - the n distinct n-th roots of unity
+ *   of Fr, in the caller's order (natural, bit-reversed, any).  THAT THE DOMAIN IS THIS SET IS A PRECONDITION AND IS NOT CHECKED; with another
+ *   set the outputs mean nothing (no fault).  n must be a power of two, at most 2^32: checked.  polys32 holds f_i = p_g(x_i).  For z outside
+ *   the domain y = (z^n - 1) / n * sum f_i x_i / (z - x_i) and q_i = (f_i - y) / (x_i - z); for z = x_j: y = f_j, the other slots as before,
+ *   q_j = sum over i != j of (f_i - y) x_i / (z (z - x_i)).
+ * Returns the number of polynomials with status bit 1 set (0: none), k == 0: 0, nothing touched.  MI355_BLS_ERR_ARG, before anything is
+ * launched: a NULL context (before the k == 0 rule), NULL inputs, n == 0, a flag other than MI355_BLS_FR_OPEN_EVAL, a domain without the flag or
+ * the flag without a domain, n that is no power of two (or above 2^32) in evaluation form, a misaligned device pointer, a busy context.
+ * Nothing else is refused for its size: k x n beyond one pass is cut into passes of whole polynomials (csrc/plan.hpp fropen_sizes_for); the
+ * _device form enqueues on `stream` and synchronises it once per pass, for the status bytes.
+ * One workgroup of 256 lanes owns one polynomial (csrc/fropen.hpp: two products per element in coefficient form, six in evaluation form
+ * with ONE field inversion per polynomial).  A SINGLE very long polynomial (k = 1, n = 2^20) therefore runs on one workgroup: correct, slow;
+ * a form that spreads one polynomial over several workgroups is not built.
+ * VARIABLE TIME: public polynomials only.
+ * COST: profiles/fr_open_bench.json (nim-blscurve_amd/tools/bench_fr_open.py), reported row by row in README.md.
+ * debug_fropen_set_pass: TEST HOOK, the polynomials per pass of the following fr_open_many calls on this context (0: the plan's own; it
+ * can only shorten a pass). */
+#define MI355_BLS_FR_OPEN_EVAL 1u
+int mi355_bls_fr_open_many(mi355_bls_ctx* ctx, const void* polys32, size_t n, const void* zs32, size_t k, uint32_t flags, const void* domain32,
+                           uint8_t* out_ys32, uint8_t* out_quot32, uint8_t* status);
+int mi355_bls_fr_open_many_device(mi355_bls_ctx* ctx, const void* d_polys32, size_t n, const void* d_zs32, size_t k, uint32_t flags,
+                                  const void* d_domain32, void* d_out_ys32, void* d_out_quot32, uint8_t* status, void* stream);
+int mi355_bls_debug_fropen_set_pass(mi355_bls_ctx* ctx, size_t polys_per_pass);
+
 /* Fixed-base G1 MSM over a precomputed window table: blst_p1s_mult_wbits_precompute(_sizeof) and blst_p1s_mult_wbits (blst_abi.nim:327-335)
  * for callers whose point set does not change - k commitments over one SRS or Lagrange table.  A table is a library-owned handle that keeps, in
  * device memory, the rows [2^(w wbits)] P_i for w = 0 .. W - 1, W = ceil((nbits + 1) / wbits), W x npoints x 128 bytes

@@ -176,6 +176,9 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, sz, pu32, psz, sz, vp, sz, u32, vp, vp]
             getattr(L, name + "_device").argtypes = [vp, vp, sz, vp, psz, sz, vp, sz, u32, vp, vp, vp]
         L.mi355_bls_debug_lincomb_set_chunk.argtypes = [vp, sz]
+        L.mi355_bls_fr_open_many.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, vp]
+        L.mi355_bls_fr_open_many_device.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, vp, vp]
+        L.mi355_bls_debug_fropen_set_pass.argtypes = [vp, sz]
         L.mi355_bls_p1s_table_sizeof.argtypes = [sz, sz, sz]
         L.mi355_bls_p1s_table_sizeof.restype = sz
         L.mi355_bls_p1s_table_create.argtypes = [vp, vp, vp, sz, sz, sz]
@@ -1480,6 +1483,75 @@ def p2sLincombMany_device(cache, d_points, n_table, d_idx, offsets, d_scalars, d
 def debug_lincomb_set_chunk(cache, terms=0):
     """TEST HOOK (mi355_bls_debug_lincomb_set_chunk): the terms per chunk of the following lincomb calls on this context; 0: the plan's own."""
     _check(lib().mi355_bls_debug_lincomb_set_chunk(cache._h, int(terms)))
+
+
+FR_OPEN_EVAL = 1                       # flag of frOpenMany: the polynomials are given by their values over a domain of n-th roots of unity
+
+
+def _fr_open_args(n, flags, have_domain):
+    n, flags = int(n), int(flags)
+    if n < 1:
+        raise ValueError("n is at least 1")
+    if flags & ~FR_OPEN_EVAL:
+        raise ValueError("flags: FR_OPEN_EVAL, nothing else")
+    if bool(flags & FR_OPEN_EVAL) != bool(have_domain):
+        raise ValueError("the domain goes with FR_OPEN_EVAL: not one without the other")
+    if flags and (n & (n - 1) or n > 1 << 32):
+        raise ValueError("evaluation form: n is a power of two, at most 2^32")
+    return n, flags
+
+
+def frOpenMany(cache, polys, n, zs, flags=0, domain=None, want_ys=True, want_quot=True):
+    """k polynomials of n scalars over Fr opened at k points in one device pass (mi355_bls_fr_open_many): y_g = p_g(z_g) and the quotient
+    (p_g(X) - y_g) / (X - z_g).  polys: k x n 32-byte little-endian images, polynomial g at [g n, (g + 1) n); zs: k images; any 256-bit image
+    acts as its value mod r.  flags = 0: coefficients, and quotient slot n - 1 is 0 (the padding slot: the table that committed to p serves q).
+    flags = FR_OPEN_EVAL: values over `domain`, n images of the n distinct n-th roots of unity in the caller's order, n a power of two - that
+    the domain is this set is NOT checked.
+    -> (polynomials with status bit 2, k x 32 bytes of y or None, k x n x 32 bytes of quotients or None, k status bytes: 1 z is in the
+    domain, 2 an image was >= r and was reduced; both informational).  VARIABLE TIME: public polynomials only.  One workgroup per polynomial:
+    a single very long polynomial is correct but slow."""
+    n, flags = _fr_open_args(n, flags, domain is not None)
+    polys, zs = bytes(polys), bytes(zs)
+    if len(zs) % 32:
+        raise ValueError("zs: 32 bytes each")
+    k = len(zs) // 32
+    if len(polys) != k * n * 32:
+        raise ValueError("polys: k x n x 32 bytes (%d for k = %d, n = %d)" % (len(polys), k, n))
+    if domain is not None and len(domain) != n * 32:
+        raise ValueError("domain: n x 32 bytes")
+    if not (want_ys or want_quot):
+        raise ValueError("values or quotients: ask for one at least")
+    if k == 0:
+        return 0, b"" if want_ys else None, b"" if want_quot else None, b""
+    ys = ctypes.create_string_buffer(32 * k) if want_ys else None
+    quot = ctypes.create_string_buffer(32 * k * n) if want_quot else None
+    st = ctypes.create_string_buffer(k)
+    rc = _check(lib().mi355_bls_fr_open_many(cache._h, polys, n, zs, k, flags, bytes(domain) if domain is not None else None, ys, quot, st))
+    return rc, ys.raw if want_ys else None, quot.raw if want_quot else None, st.raw
+
+
+def frOpenMany_device(cache, d_polys, n, d_zs, k, flags=0, d_domain=None, d_out_ys=None, d_out_quot=None, stream=0, want_status=True):
+    """The same with polynomials, points, domain and outputs in device memory (raw pointers; an output of 0 / None is not wanted):
+    d_out_quot is, as it stands, the d_scalars argument of p1s_mult_table_many_device and p1s_mult_pippenger_many_device.
+    -> (polynomials with status bit 2, status bytes or None)."""
+    n, flags = _fr_open_args(n, flags, bool(d_domain))
+    k = int(k)
+    if k < 0:
+        raise ValueError("k is a count")
+    if not (d_out_ys or d_out_quot or want_status):
+        raise ValueError("every output is None")
+    if k == 0:
+        return 0, b"" if want_status else None
+    if not d_polys or not d_zs:
+        raise ValueError("polynomials and points: device pointers")
+    st = ctypes.create_string_buffer(k) if want_status else None
+    rc = _check(lib().mi355_bls_fr_open_many_device(cache._h, d_polys, n, d_zs, k, flags, d_domain or None, d_out_ys or None, d_out_quot or None, st, stream))
+    return rc, st.raw if want_status else None
+
+
+def debug_fropen_set_pass(cache, polys_per_pass=0):
+    """TEST HOOK (mi355_bls_debug_fropen_set_pass): the polynomials per pass of the following frOpenMany calls on this context; 0: the plan's own."""
+    _check(lib().mi355_bls_debug_fropen_set_pass(cache._h, int(polys_per_pass)))
 
 
 def compressSignatures(cache, signatures):

@@ -148,4 +148,36 @@ BLS_HDN fr fr_inv(fr a) {
     return acc;
 }
 
+// ---- what the vectors of csrc/fropen.hpp need beside the above (which stays as it is: the recovery depends on it bit for bit)
+BLS_HD fr fr_neg(const fr& a) { return fr_sub(fr{}, a); }
+BLS_HD fr fr_sqr(const fr& a) { return fr_mont_mul(a, a); }
+// ANY 256-bit value -> the value in [0, r), in the SAME form (no Montgomery factor comes or goes): 2^256 < 3 r, so two conditional
+// subtractions.  reduced: the value was >= r.
+BLS_HD fr fr_canon_words(const uint32_t (&w)[8], bool& reduced) {
+    const fr a = fr_cond_sub(w, 0);
+    const fr b = fr_cond_sub(a.l, 0);
+    uint32_t diff = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) diff |= b.l[i] ^ w[i];
+    reduced = diff != 0;
+    return b;
+}
+// a value in [0, r) to Montgomery form and back: a chunk converts once.  A product of a plain value and a Montgomery one is plain.
+BLS_HD fr fr_to_mont(const fr& a) { return fr_from_words(a.l); }
+BLS_HD fr fr_from_mont(const fr& a) {
+    fr o;
+    fr_to_words(o.l, a);
+    return o;
+}
+// a^e for a in Montgomery form, e >= 0 (a^0 = 1); square and multiply from the low bit
+BLS_HD fr fr_pow_u64(fr a, uint64_t e) {
+    fr acc = fr_one();
+#pragma clang loop unroll(disable)
+    for (; e; e >>= 1) {
+        if (e & 1) acc = fr_mont_mul(acc, a);
+        a = fr_mont_mul(a, a);
+    }
+    return acc;
+}
+
 }  // namespace bls

@@ -205,6 +205,9 @@ struct mi355_bls_ctx {
     uint32_t toaff_run = 0;          // mi355_bls_debug_to_affine_set_run; 0: the plan's own
     std::vector<uint32_t> many_offs; // the ragged passes' offsets of the call in flight: the async copies read them
     size_t lincomb_chunk = 0;        // mi355_bls_debug_lincomb_set_chunk: terms per chunk of the lincomb_many calls; 0: the plan's own
+    // openings over Fr (mi355_bls_fr_open_many): the domain in Montgomery form | the scan workspace of a pass; the host form's outputs of a pass
+    dev_buf<uint32_t> d_fro_ws, d_fro_out;
+    size_t fropen_pass = 0;          // mi355_bls_debug_fropen_set_pass: polynomials per pass of the fr_open_many calls; 0: the plan's own
     ptab_ws ptab;                    // MSMs over a fixed-base window table: made at the first such call
     // per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): sized by the largest slice of a call; it runs in the per-set path's
     // pair store with the per-group path's tables, partials and step values (d_aggv_*) and combine_sets' G2 products and tables (grp, d_comb_*)
@@ -2480,6 +2483,98 @@ extern "C" int mi355_bls_p2s_lincomb_many_device(mi355_bls_ctx* c, const void* d
 extern "C" int mi355_bls_debug_lincomb_set_chunk(mi355_bls_ctx* c, size_t members) {
     if (!c) return MI355_BLS_ERR_ARG;
     c->lincomb_chunk = members;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Openings of k polynomials over Fr (mi355_bls_fr_open_many): passes of whole polynomials (plan.hpp fropen_sizes_for), per pass one workgroup
+// per polynomial (k_fropen_coef, or k_fropen_eval over the domain k_fropen_domain has brought to Montgomery form once), all on the caller's
+// stream, then the pass's status bytes come back (its synchronisation).  h_ys / h_quot: the host form - the device outputs are then the
+// pass's own (d_fro_out: the values, then the quotients) and copied out pass by pass.  -> the polynomials with FROPEN_ST_REDUCED set.
+// ------------------------------------------------------------------------------------------
+static int fropen_run(mi355_bls_ctx* c, const uint8_t* d_polys, size_t n, const uint8_t* d_zs, size_t k, uint32_t flags, const uint8_t* d_domain, uint8_t* d_ys,
+                      uint8_t* d_quot, uint8_t* h_ys, uint8_t* h_quot, uint8_t* status, hipStream_t st) {
+    const bool eval = flags & MI355_BLS_FR_OPEN_EVAL;
+    const plan::fropen_sizes sz = plan::fropen_sizes_for(n, k, eval, c->fropen_pass);
+    if (!sz.ok) {
+        g_err = "fr_open_many: n is at least 1; in evaluation form a power of two, at most 2^32";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (((uintptr_t)d_polys | (uintptr_t)d_zs | (uintptr_t)d_domain | (uintptr_t)d_ys | (uintptr_t)d_quot) & 3) {
+        g_err = "fr_open_many: polynomials, points, domain and outputs must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const bool host = h_ys || h_quot;
+    int rc = c->grp.d_status.reserve(sz.status, sz.status / 4);
+    if (!rc && eval) rc = c->d_fro_ws.reserve(sz.domain + sz.scan, 0);
+    if (!rc && host) rc = c->d_fro_out.reserve(sz.out_ys + (h_quot ? sz.out_quot : 0), 0);
+    if (rc) return rc;
+    const uint32_t *polys = reinterpret_cast<const uint32_t*>(d_polys), *zs = reinterpret_cast<const uint32_t*>(d_zs);
+    uint32_t *ws_dom = c->d_fro_ws, *ws_scan = eval ? c->d_fro_ws + n * 8 : nullptr;
+    fr ninv{};
+    if (eval) {
+        const uint32_t nw[8] = {(uint32_t)n, (uint32_t)((uint64_t)n >> 32), 0, 0, 0, 0, 0, 0};
+        ninv = fr_inv(fr_from_words(nw));
+        k_fropen_domain<<<(unsigned)((n + FROPEN_LANES - 1) / FROPEN_LANES), FROPEN_LANES, 0, st>>>(reinterpret_cast<const uint32_t*>(d_domain), n, ws_dom);
+    }
+    std::vector<uint8_t> st_own;
+    if (!status) st_own.resize(sz.per_pass);
+    int reduced = 0;
+    for (size_t p = 0; p < sz.passes; p++) {
+        size_t g0, kc;
+        plan::fropen_pass(sz, k, p, g0, kc);
+        uint32_t* ys = host ? (h_ys ? c->d_fro_out.p : nullptr) : d_ys ? reinterpret_cast<uint32_t*>(d_ys) + g0 * 8 : nullptr;
+        uint32_t* quot = host ? (h_quot ? c->d_fro_out.p + sz.out_ys / 4 : nullptr) : d_quot ? reinterpret_cast<uint32_t*>(d_quot) + g0 * n * 8 : nullptr;
+        if (eval) k_fropen_eval<<<(unsigned)kc, FROPEN_LANES, 0, st>>>(polys + g0 * n * 8, n, sz.log2n, ws_dom, zs + g0 * 8, ninv, ws_scan, ys, quot, c->grp.d_status);
+        else k_fropen_coef<<<(unsigned)kc, FROPEN_LANES, 0, st>>>(polys + g0 * n * 8, n, zs + g0 * 8, ys, quot, c->grp.d_status);
+        HIPCHK(hipGetLastError());
+        if (h_ys) HIPCHK(hipMemcpyAsync(h_ys + g0 * 32, ys, kc * 32, hipMemcpyDeviceToHost, st));
+        if (h_quot) HIPCHK(hipMemcpyAsync(h_quot + g0 * n * 32, quot, kc * n * 32, hipMemcpyDeviceToHost, st));
+        uint8_t* sb = status ? status + g0 : st_own.data();
+        HIPCHK(hipMemcpyAsync(sb, c->grp.d_status, kc, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < kc; i++) reduced += (sb[i] & FROPEN_ST_REDUCED) != 0;
+    }
+    return reduced;
+}
+static bool fropen_args_ok(const void* polys, size_t n, const void* zs, uint32_t flags, const void* domain, const void* ys, const void* quot, const uint8_t* status) {
+    if (polys && zs && n && !(flags & ~(uint32_t)MI355_BLS_FR_OPEN_EVAL) && ((flags & MI355_BLS_FR_OPEN_EVAL) != 0) == (domain != nullptr) && (ys || quot || status))
+        return true;
+    g_err = "fr_open_many: NULL inputs, n == 0, every output NULL, a flag other than MI355_BLS_FR_OPEN_EVAL, or a domain without that flag (the flag without a domain)";
+    return false;
+}
+extern "C" int mi355_bls_fr_open_many_device(mi355_bls_ctx* c, const void* d_polys32, size_t n, const void* d_zs32, size_t k, uint32_t flags, const void* d_domain32,
+                                             void* d_out_ys32, void* d_out_quot32, uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing computed, nothing written
+    if (!fropen_args_ok(d_polys32, n, d_zs32, flags, d_domain32, d_out_ys32, d_out_quot32, status)) return MI355_BLS_ERR_ARG;
+    return fropen_run(c, (const uint8_t*)d_polys32, n, (const uint8_t*)d_zs32, k, flags, (const uint8_t*)d_domain32, (uint8_t*)d_out_ys32, (uint8_t*)d_out_quot32, nullptr,
+                      nullptr, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_fr_open_many(mi355_bls_ctx* c, const void* polys32, size_t n, const void* zs32, size_t k, uint32_t flags, const void* domain32, uint8_t* out_ys32,
+                                      uint8_t* out_quot32, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!fropen_args_ok(polys32, n, zs32, flags, domain32, out_ys32, out_quot32, status)) return MI355_BLS_ERR_ARG;
+    if (!plan::fropen_sizes_for(n, k, flags & MI355_BLS_FR_OPEN_EVAL).ok) {
+        g_err = "fr_open_many: in evaluation form n is a power of two, at most 2^32";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (!out_ys32 && !out_quot32) {
+        g_err = "fr_open_many: the host form computes values or quotients";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const uint8_t* d[3];      // polynomials | points | domain
+    if (int rc = stage_inputs(c, {{polys32, k * n * 32}, {zs32, k * 32}, {domain32, n * 32}}, nullptr, d)) return rc;
+    return fropen_run(c, d[0], n, d[1], k, flags, d[2], nullptr, nullptr, out_ys32, out_quot32, status, nullptr);
+}
+// TEST HOOK: the polynomials per pass of the following fr_open_many calls on this context (0: the plan's own; it can only shorten a pass)
+extern "C" int mi355_bls_debug_fropen_set_pass(mi355_bls_ctx* c, size_t polys_per_pass) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    c->fropen_pass = polys_per_pass;
     return 0;
 }
 

@@ -44,6 +44,7 @@
 #include "aggsigs.hpp"
 #include "recover.hpp"
 #include "lincomb.hpp"
+#include "fropen.hpp"
 #include "keytable.hpp"
 #include "msmmany.hpp"
 #include "msmtable.hpp"
@@ -3175,6 +3176,108 @@ __global__ void __launch_bounds__(WAVE) k_lincomb_finish(const uint32_t* __restr
     const lincomb_end<F> e = lincomb_finish_item<F>(seg_len[g], seg_flags[g], f == 0xffffffffu ? jac_inf<F>() : ld_jac_int(part + (size_t)f * JACW, (const jac<F>*)nullptr));
     for (uint32_t i = 0; i < AFFW; i++) out[(size_t)g * AFFW + i] = e.img[i];
     status[g] = e.status;
+}
+
+// ------------------------------------------------------------------------------------------
+// Openings of many polynomials over Fr (mi355_bls_fr_open_many).  The arithmetic and the scheme are csrc/fropen.hpp's; here a workgroup of
+// FROPEN_LANES lanes per polynomial (blockIdx.x: the polynomial's number in the pass) walks its phases with the workgroup's values in LDS
+// (two arrays of 256 Fr: 16 KiB).  ys / quot null: that output is not wanted.  status: a byte per polynomial of the pass.
+// ------------------------------------------------------------------------------------------
+// the tree sum of the lanes' `mine` -> every lane gets the total
+static __device__ __forceinline__ fr fropen_wg_sum(fr* sh, uint32_t t, const fr& mine) {
+    __syncthreads();
+    sh[t] = mine;
+    __syncthreads();
+#pragma clang loop unroll(disable)
+    for (uint32_t dist = FROPEN_LANES / 2; dist; dist >>= 1) {
+        fropen_sum_step(sh, t, dist);
+        __syncthreads();
+    }
+    return sh[0];
+}
+__global__ void __launch_bounds__(FROPEN_LANES) k_fropen_coef(const uint32_t* __restrict__ polys, size_t n, const uint32_t* __restrict__ zs, uint32_t* __restrict__ ys,
+                                                              uint32_t* __restrict__ quot, uint8_t* __restrict__ status) {
+    __shared__ fr sh[FROPEN_LANES];
+    __shared__ uint32_t sh_flags;
+    const uint32_t t = threadIdx.x;
+    const size_t g = blockIdx.x;
+    const uint32_t* poly = polys + g * n * 8;
+    if (t == 0) sh_flags = 0;
+    uint32_t fl = 0;
+    const fr zm = fr_to_mont(fropen_image(zs, g, fl));
+    const fropen_span c = fropen_chunk(t, n);
+    sh[t] = fropen_coef_horner(poly, c, zm, fl);
+    __syncthreads();
+    if (fl) atomicOr(&sh_flags, fl);
+    fr pw = fr_pow_u64(zm, fropen_chunk_len(n));
+#pragma clang loop unroll(disable)
+    for (uint32_t s = 0; s < FROPEN_SCAN_STEPS; s++) {
+        const fr v = fropen_coef_scan_step(sh, t, s, pw);
+        __syncthreads();
+        sh[t] = v;
+        __syncthreads();
+        pw = fr_sqr(pw);
+    }
+    if (quot) fropen_coef_emit(poly, c, zm, t + 1 < FROPEN_LANES ? sh[t + 1] : fr{}, quot + g * n * 8);
+    if (t == 0) {
+        if (ys) fropen_st(ys + g * 8, sh[0]);
+        status[g] = (uint8_t)sh_flags;
+    }
+}
+// a lane per domain element: the caller's image below r and in Montgomery form, once for all k polynomials
+__global__ void __launch_bounds__(FROPEN_LANES) k_fropen_domain(const uint32_t* __restrict__ domain, size_t n, uint32_t* __restrict__ ws_dom) {
+    const size_t i = (size_t)blockIdx.x * FROPEN_LANES + threadIdx.x;
+    if (i < n) fropen_domain_item(domain, i, ws_dom);
+}
+// log2n: n = 2^log2n.  ninv: 1 / n in Montgomery form (the host's fr_inv).  scan: n Fr of workspace per polynomial of the pass.
+__global__ void __launch_bounds__(FROPEN_LANES) k_fropen_eval(const uint32_t* __restrict__ polys, size_t n, uint32_t log2n, const uint32_t* __restrict__ ws_dom,
+                                                              const uint32_t* __restrict__ zs, fr ninv, uint32_t* __restrict__ scan_ws, uint32_t* __restrict__ ys,
+                                                              uint32_t* __restrict__ quot_all, uint8_t* __restrict__ status) {
+    __shared__ fr before[FROPEN_LANES], behind[FROPEN_LANES];
+    __shared__ uint32_t sh_flags;
+    __shared__ unsigned long long sh_j;
+    const uint32_t t = threadIdx.x;
+    const size_t g = blockIdx.x;
+    const uint32_t* poly = polys + g * n * 8;
+    uint32_t* scan = scan_ws + g * n * 8;
+    uint32_t* quot = quot_all ? quot_all + g * n * 8 : nullptr;
+    if (t == 0) sh_flags = 0, sh_j = FROPEN_NO_J;
+    __syncthreads();
+    uint32_t fl = 0;
+    const fr zm = fr_to_mont(fropen_image(zs, g, fl));
+    const fropen_span c = fropen_chunk(t, n);
+    uint64_t j = FROPEN_NO_J;
+    before[t] = behind[t] = fropen_eval_products(ws_dom, c, zm, scan, j);
+    if (j != FROPEN_NO_J) sh_j = j;
+    __syncthreads();
+    const auto mul = [](const fr& a, const fr& b) { return fr_mont_mul(a, b); };
+#pragma clang loop unroll(disable)
+    for (uint32_t s = 0; s < FROPEN_SCAN_STEPS; s++) {
+        const fr a = fropen_scan_step(before, t, 1u << s, false, mul), b = fropen_scan_step(behind, t, 1u << s, true, mul);
+        __syncthreads();
+        before[t] = a, behind[t] = b;
+        __syncthreads();
+    }
+    j = sh_j;
+    __shared__ fr sh_inv;
+    if (t == 0) sh_inv = fr_inv(behind[0]);          // ONE inversion per polynomial: the product of all n differences
+    __syncthreads();
+    const fr run = fropen_eval_lane_inverse(sh_inv, before, behind, t);
+    const fr part = fropen_eval_invert(poly, ws_dom, c, zm, run, j, scan, fl);
+    if (fl) atomicOr(&sh_flags, fl);
+    const fr sum = fropen_wg_sum(before, t, part);
+    const fropen_zpow zp = fropen_z_powers(zm, log2n);
+    const fr y = fropen_eval_value(poly, sum, zp.zn, ninv, j);
+    const fr part_j = fropen_eval_emit(poly, ws_dom, c, y, j, scan, quot);
+    if (j != FROPEN_NO_J && quot) {                   // uniform: every lane read the same j
+        const fr sum_j = fropen_wg_sum(behind, t, part_j);
+        if (t == 0) fropen_st(quot + (size_t)j * 8, fropen_eval_slot_j(sum_j, zp.zn1));
+    }
+    __syncthreads();
+    if (t == 0) {
+        if (ys) fropen_st(ys + g * 8, y);
+        status[g] = (uint8_t)(sh_flags | (j != FROPEN_NO_J ? FROPEN_ST_IN_DOMAIN : 0u));
+    }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -601,6 +601,52 @@ inline lincomb_sizes lincomb_sizes_for(const aggsets_plan& p, size_t terms, size
     return {(terms ? terms : 1) * jac, (p.items ? p.items : 1) * jac, ((terms + p.items) * 4 + 2 * groups) * 4, groups * 4, groups, groups * (g2 ? 192 : 96)};
 }
 
+// Openings of k polynomials of n scalars over Fr (mi355_bls_fr_open_many; csrc/fropen.hpp): one workgroup of 256 lanes per polynomial, in
+// PASSES of whole polynomials, polynomials [first, first + count) each.  What bounds a pass:
+//   FROPEN_POLYS_PASS   workgroups of one launch, 65 536: a status byte each, and a grid far inside what a launch takes.  Not tuned.
+//   FROPEN_SCAN_BYTES   n x 32 bytes per polynomial of the pass, 256 MiB in all (2 048 polynomials of 4 096 a pass): the evaluation form's
+//                       scan workspace (the running products of the differences, then their inverses), and in either form the host call's
+//                       quotients on their way out.  One polynomial always fits a pass, whatever its length - a polynomial of 2^26 scalars
+//                       asks for 2 GiB, and gets them or the allocation's error.  Not tuned.
+//   `forced` is the test hook's (mi355_bls_debug_fropen_set_pass; 0: the rule above; it can only shorten a pass).
+// The workspace: `domain`, the n domain elements in Montgomery form (evaluation form; once per call), `scan` as above, a status byte per
+// polynomial of a pass; out_ys / out_quot: the host form's device outputs of one pass.  Refused (ok == false): n == 0, and in evaluation
+// form n that is no power of two or above 2^32.  Nothing for its size: n up to 2^26 with k up to 2^20 stays far inside 64 bits.
+constexpr size_t FROPEN_POLYS_PASS = 65536, FROPEN_SCAN_BYTES = (size_t)256 << 20;
+struct fropen_sizes {
+    bool ok;
+    size_t per_pass, passes;                 // polynomials per pass (the last one may hold fewer), passes of the call
+    uint32_t log2n;                          // evaluation form: n = 2^log2n
+    size_t domain, scan, status, out_ys, out_quot;
+};
+inline fropen_sizes fropen_sizes_for(size_t n, size_t k, bool eval, size_t forced = 0) {
+    fropen_sizes s{};
+    if (n == 0 || n > ((size_t)1 << 58)) return s;                 // n x 32 bytes is a size_t
+    if (eval) {
+        if ((n & (n - 1)) || n > ((size_t)1 << 32)) return s;
+        while (((size_t)1 << s.log2n) < n) s.log2n++;
+    }
+    size_t per = FROPEN_POLYS_PASS;
+    if (FROPEN_SCAN_BYTES / (n * 32) < per) per = FROPEN_SCAN_BYTES / (n * 32);
+    if (per == 0) per = 1;
+    if (forced && forced < per) per = forced;
+    if (per > k && k) per = k;
+    s.ok = true;
+    s.per_pass = per;
+    s.passes = (k + per - 1) / per;
+    s.domain = eval ? n * 32 : 0;
+    s.scan = eval ? per * n * 32 : 0;
+    s.status = per;
+    s.out_ys = per * 32;
+    s.out_quot = per * n * 32;
+    return s;
+}
+// pass p of the call: polynomials [first, first + count)
+inline void fropen_pass(const fropen_sizes& s, size_t k, size_t p, size_t& first, size_t& count) {
+    first = p * s.per_pass;
+    count = k - first < s.per_pass ? k - first : s.per_pass;
+}
+
 // Per-group aggregateVerify (mi355_bls_aggregate_verify_each): k groups of (key, message) pairs in CSR form, one aggregate signature each.
 // The call runs in SLICES of at most `cap` pairs of the per-set path's pair store (2 cap slots: the pairs, then one (-G1, sig) pair per
 // group that ends in the slice - never more than the pairs, a group in a slice has a pair there).
