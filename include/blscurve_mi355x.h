@@ -799,6 +799,44 @@ int mi355_bls_fr_open_many_device(mi355_bls_ctx* ctx, const void* d_polys32, siz
                                   const void* d_domain32, void* d_out_ys32, void* d_out_quot32, uint8_t* status, void* stream);
 int mi355_bls_debug_fropen_set_pass(mi355_bls_ctx* ctx, size_t polys_per_pass);
 
+/* Number-theoretic transforms of k vectors over the scalar field Fr in one device pass, and the domain they and mi355_bls_fr_open_many's
+ * evaluation form speak of: the link between that call's two forms, with no scalar visiting the host.
+ *   r the group order, omega_n = 7^((r - 1) / n) mod r for n = 2^m, 0 <= m <= 32 (7 generates Fr*); rev_m(i) is i with its m low bits reversed.
+ *   FORWARD  out[i] = sum_j in[j] (g omega_n^i)^j: coefficients in, values over the domain (g = 1) or over the coset g x domain out.
+ *   MI355_BLS_FR_NTT_INVERSE  the exact inverse map: values in, coefficients out, the factor 1 / n and g^-j included.
+ *   MI355_BLS_FR_NTT_BITREV   the EVALUATION side (the forward output, the inverse input) is in bit-reversed order: slot i holds the value at
+ *                  omega_n^rev_m(i).  The coefficient side is always in natural order.  With the flag no permutation is made (forward:
+ *                  decimation in frequency, inverse: decimation in time); without it the last store permutes.
+ *   in32 / out32   k x n 32-byte little-endian images; vector g is images [g n, (g + 1) n) - the layout fr_open_many and the MSM calls read.
+ *                  ANY 256-bit input image acts as its value mod r; every output image is in [0, r).
+ *   shift32        ONE image in HOST memory in both forms, shared by the k vectors, acting as its value mod r; NULL: g = 1.
+ *   status         k bytes, HOST memory, may be NULL: bit 1 (2) an image of this vector was >= r and was reduced (informational; the shift sets
+ *                  no bit).  Returns the number of such vectors; k == 0: 0, nothing touched.  n == 1 is the identity up to reduction.
+ *   IN PLACE       d_out32 == d_in32 exactly is allowed in the _device form; any other overlap is a precondition violation.
+ * MI355_BLS_ERR_ARG, before anything is launched: a NULL context (before the k == 0 rule), NULL in or out, n == 0, n that is no power of two or
+ * above 2^32, an unknown flag bit, a shift that is 0 mod r, a misaligned device pointer (4-byte aligned; 16-byte aligned ones are read and
+ * written 16 bytes at a time), a busy context.  Nothing else is refused for its size: k x n beyond one slice is cut into slices of whole
+ * vectors (csrc/plan.hpp frntt_sizes_for); the _device form enqueues on `stream` and synchronises it once per slice, for the status bytes.
+ * A transform whose last store permutes and that is longer than a tile uses a library buffer of one slice.
+ * The m radix-2 stages run in passes of at most `tile` stages with their elements in LDS (csrc/frntt.hpp; one twiddle table per call).
+ * fr_domain writes omega_n^i, or omega_n^rev_m(i) with MI355_BLS_FR_NTT_BITREV (no other flag), as n canonical images: a valid domain32
+ * argument of mi355_bls_fr_open_many.  Both forms return when the images are written.
+ * VARIABLE TIME: public vectors only.
+ * COST: profiles/fr_ntt_bench.json (nim-blscurve_amd/tools/bench_fr_ntt.py), reported row by row in README.md.
+ * debug_frntt_set_tile: TEST HOOK, log2 of the tile of the following fr_ntt_many calls on this context (0: the plan's own; it can only shrink
+ * the tile below the largest one a workgroup's LDS holds, 2^12 elements).  debug_frntt_set_pass: the vectors per slice (0: the plan's own; it
+ * can only shorten a slice). */
+#define MI355_BLS_FR_NTT_INVERSE 1u
+#define MI355_BLS_FR_NTT_BITREV 2u
+int mi355_bls_fr_ntt_many(mi355_bls_ctx* ctx, const void* in32, size_t n, size_t k, uint32_t flags, const uint8_t* shift32, uint8_t* out32,
+                          uint8_t* status);
+int mi355_bls_fr_ntt_many_device(mi355_bls_ctx* ctx, const void* d_in32, size_t n, size_t k, uint32_t flags, const uint8_t* shift32,
+                                 void* d_out32, uint8_t* status, void* stream);
+int mi355_bls_fr_domain(mi355_bls_ctx* ctx, size_t n, uint32_t flags, uint8_t* out32);
+int mi355_bls_fr_domain_device(mi355_bls_ctx* ctx, size_t n, uint32_t flags, void* d_out32, void* stream);
+int mi355_bls_debug_frntt_set_tile(mi355_bls_ctx* ctx, uint32_t log2_tile);
+int mi355_bls_debug_frntt_set_pass(mi355_bls_ctx* ctx, size_t vectors_per_pass);
+
 /* Fixed-base G1 MSM over a precomputed window table: blst_p1s_mult_wbits_precompute(_sizeof) and blst_p1s_mult_wbits (blst_abi.nim:327-335)
  * for callers whose point set does not change - k commitments over one SRS or Lagrange table.  A table is a library-owned handle that keeps, in
  * device memory, the rows [2^(w wbits)] P_i for w = 0 .. W - 1, W = ceil((nbits + 1) / wbits), W x npoints x 128 bytes

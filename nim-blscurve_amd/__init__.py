@@ -179,6 +179,12 @@ def lib():
         L.mi355_bls_fr_open_many.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, vp]
         L.mi355_bls_fr_open_many_device.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, vp, vp]
         L.mi355_bls_debug_fropen_set_pass.argtypes = [vp, sz]
+        L.mi355_bls_fr_ntt_many.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp]
+        L.mi355_bls_fr_ntt_many_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, vp]
+        L.mi355_bls_fr_domain.argtypes = [vp, sz, u32, vp]
+        L.mi355_bls_fr_domain_device.argtypes = [vp, sz, u32, vp, vp]
+        L.mi355_bls_debug_frntt_set_tile.argtypes = [vp, u32]
+        L.mi355_bls_debug_frntt_set_pass.argtypes = [vp, sz]
         L.mi355_bls_p1s_table_sizeof.argtypes = [sz, sz, sz]
         L.mi355_bls_p1s_table_sizeof.restype = sz
         L.mi355_bls_p1s_table_create.argtypes = [vp, vp, vp, sz, sz, sz]
@@ -1552,6 +1558,87 @@ def frOpenMany_device(cache, d_polys, n, d_zs, k, flags=0, d_domain=None, d_out_
 def debug_fropen_set_pass(cache, polys_per_pass=0):
     """TEST HOOK (mi355_bls_debug_fropen_set_pass): the polynomials per pass of the following frOpenMany calls on this context; 0: the plan's own."""
     _check(lib().mi355_bls_debug_fropen_set_pass(cache._h, int(polys_per_pass)))
+
+
+FR_NTT_INVERSE = 1                     # flags of frNttMany: values in, coefficients out (the exact inverse map, 1 / n included)
+FR_NTT_BITREV = 2                      # the evaluation side is in bit-reversed order: slot i holds the value at omega_n^rev(i)
+_FR_R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+
+
+def _fr_ntt_args(n, flags, shift, allowed=FR_NTT_INVERSE | FR_NTT_BITREV):
+    n, flags = int(n), int(flags)
+    if n < 1 or n & (n - 1) or n > 1 << 32:
+        raise ValueError("n is a power of two, 1 .. 2^32")
+    if flags & ~allowed:
+        raise ValueError("flags: an unknown bit")
+    if shift is not None:
+        shift = bytes(shift)
+        if len(shift) != 32:
+            raise ValueError("shift: one 32-byte image")
+        if int.from_bytes(shift, "little") % _FR_R == 0:
+            raise ValueError("shift: 0 mod r")
+    return n, flags, shift
+
+
+def frNttMany(cache, vectors, n, flags=0, shift=None):
+    """The forward or inverse number-theoretic transform of k vectors of n = 2^m scalars over Fr in one device pass (mi355_bls_fr_ntt_many).
+    vectors: k x n 32-byte little-endian images, vector g at [g n, (g + 1) n); any 256-bit image acts as its value mod r.  Forward:
+    out[i] = sum_j in[j] (g omega_n^i)^j with omega_n = 7^((r - 1) / n) and g = shift (host bytes; None: 1).  FR_NTT_INVERSE: the exact inverse.
+    FR_NTT_BITREV: the evaluation side is bit-reversed.  -> (vectors with status bit 2, k x n x 32 bytes in [0, r), k status bytes: 2 an
+    image was >= r and was reduced).  VARIABLE TIME: public vectors only."""
+    n, flags, shift = _fr_ntt_args(n, flags, shift)
+    vectors = bytes(vectors)
+    if len(vectors) % (n * 32):
+        raise ValueError("vectors: k x n x 32 bytes (%d for n = %d)" % (len(vectors), n))
+    k = len(vectors) // (n * 32)
+    if k == 0:
+        return 0, b"", b""
+    out, st = ctypes.create_string_buffer(len(vectors)), ctypes.create_string_buffer(k)
+    rc = _check(lib().mi355_bls_fr_ntt_many(cache._h, vectors, n, k, flags, shift, out, st))
+    return rc, out.raw, st.raw
+
+
+def frNttMany_device(cache, d_in, n, k, flags=0, shift=None, d_out=None, stream=0, want_status=True):
+    """The same with the vectors and the output in device memory (raw pointers; d_out None: in place, d_out == d_in); the shift stays host
+    bytes.  d_out is, as it stands, the d_polys argument of frOpenMany_device.  -> (vectors with status bit 2, status bytes or None)."""
+    n, flags, shift = _fr_ntt_args(n, flags, shift)
+    k = int(k)
+    if k < 0:
+        raise ValueError("k is a count")
+    if k == 0:
+        return 0, b"" if want_status else None
+    if not d_in:
+        raise ValueError("vectors: a device pointer")
+    st = ctypes.create_string_buffer(k) if want_status else None
+    rc = _check(lib().mi355_bls_fr_ntt_many_device(cache._h, d_in, n, k, flags, shift, d_out or d_in, st, stream))
+    return rc, st.raw if want_status else None
+
+
+def frDomain(cache, n, flags=0):
+    """The domain frNttMany and frOpenMany's evaluation form speak of (mi355_bls_fr_domain): omega_n^i, or omega_n^rev(i) with FR_NTT_BITREV,
+    as n canonical 32-byte images."""
+    n, flags, _ = _fr_ntt_args(n, flags, None, FR_NTT_BITREV)
+    out = ctypes.create_string_buffer(n * 32)
+    _check(lib().mi355_bls_fr_domain(cache._h, n, flags, out))
+    return out.raw
+
+
+def frDomain_device(cache, n, d_out, flags=0, stream=0):
+    """The same into device memory (n x 32 bytes at d_out): as it stands the d_domain argument of frOpenMany_device."""
+    n, flags, _ = _fr_ntt_args(n, flags, None, FR_NTT_BITREV)
+    if not d_out:
+        raise ValueError("the output: a device pointer")
+    _check(lib().mi355_bls_fr_domain_device(cache._h, n, flags, d_out, stream))
+
+
+def debug_frntt_set_tile(cache, log2_tile=0):
+    """TEST HOOK (mi355_bls_debug_frntt_set_tile): log2 of the tile of the following frNttMany calls on this context; 0: the plan's own."""
+    _check(lib().mi355_bls_debug_frntt_set_tile(cache._h, int(log2_tile)))
+
+
+def debug_frntt_set_pass(cache, vectors_per_pass=0):
+    """TEST HOOK (mi355_bls_debug_frntt_set_pass): the vectors per slice of the following frNttMany calls on this context; 0: the plan's own."""
+    _check(lib().mi355_bls_debug_frntt_set_pass(cache._h, int(vectors_per_pass)))
 
 
 def compressSignatures(cache, signatures):

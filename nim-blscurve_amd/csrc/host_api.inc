@@ -208,6 +208,11 @@ struct mi355_bls_ctx {
     // openings over Fr (mi355_bls_fr_open_many): the domain in Montgomery form | the scan workspace of a pass; the host form's outputs of a pass
     dev_buf<uint32_t> d_fro_ws, d_fro_out;
     size_t fropen_pass = 0;          // mi355_bls_debug_fropen_set_pass: polynomials per pass of the fr_open_many calls; 0: the plan's own
+    // transforms over Fr (mi355_bls_fr_ntt_many): the twiddle table of the call | a slice's elements (the host form's staging; the second buffer
+    // of a transform whose last store permutes) | a status word per vector of a slice
+    dev_buf<uint32_t> d_ntt_tw, d_ntt_io, d_ntt_st;
+    uint32_t frntt_tile = 0;         // mi355_bls_debug_frntt_set_tile: log2 of the tile of the fr_ntt_many calls; 0: the plan's own
+    size_t frntt_vecs = 0;           // mi355_bls_debug_frntt_set_pass: vectors per slice of the fr_ntt_many calls; 0: the plan's own
     ptab_ws ptab;                    // MSMs over a fixed-base window table: made at the first such call
     // per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): sized by the largest slice of a call; it runs in the per-set path's
     // pair store with the per-group path's tables, partials and step values (d_aggv_*) and combine_sets' G2 products and tables (grp, d_comb_*)
@@ -2575,6 +2580,178 @@ extern "C" int mi355_bls_fr_open_many(mi355_bls_ctx* c, const void* polys32, siz
 extern "C" int mi355_bls_debug_fropen_set_pass(mi355_bls_ctx* c, size_t polys_per_pass) {
     if (!c) return MI355_BLS_ERR_ARG;
     c->fropen_pass = polys_per_pass;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Transforms of k vectors over Fr (mi355_bls_fr_ntt_many): slices of whole vectors (plan.hpp frntt_sizes_for); per call the twiddle table
+// (k_frntt_twiddle), per slice the passes (k_frntt_pass<DIT>) with the elementwise kernel in front of them (forward: the shift powers, or
+// the copy of n = 1) or behind them (inverse: g^-j / n), all on the caller's stream, then the slice's status words come back (its
+// synchronisation).  Which transform runs: frntt.hpp.  A transform whose last store permutes and that has more than one pass runs its
+// earlier passes in a second buffer (d_ntt_io), so that the permuting pass never stores where another workgroup has yet to load.
+// h_in / h_out: the host form - a slice is staged in d_ntt_io, transformed there and copied out.  -> the vectors with FRNTT_ST_REDUCED set.
+// ------------------------------------------------------------------------------------------
+static bool frntt_args_ok(const void* in, size_t n, uint32_t flags, const void* out) {
+    if (in && out && n && !(n & (n - 1)) && n <= ((size_t)1 << 32) && !(flags & ~(uint32_t)(MI355_BLS_FR_NTT_INVERSE | MI355_BLS_FR_NTT_BITREV))) return true;
+    g_err = "fr_ntt_many: NULL input or output, n that is no power of two in 1 .. 2^32, or a flag other than MI355_BLS_FR_NTT_INVERSE and MI355_BLS_FR_NTT_BITREV";
+    return false;
+}
+template <bool DIT>
+static int frntt_launch_pass(const frntt_geo& g, const uint32_t* src, bool raw, const uint32_t* tw, bool permute, uint32_t* dst, uint32_t* status, hipStream_t st) {
+    const uint64_t wgs = frntt_workgroups(g);
+    const size_t lds = (size_t)32 << g.L;
+    if (wgs > 0x7fffffffu) {
+        g_err = "fr_ntt_many: a pass of more than 2^31 - 1 workgroups";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (lds > (64u << 10)) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frntt_pass<DIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k_frntt_pass<DIT><<<(unsigned)wgs, FRNTT_LANES, lds, st>>>(g, src, raw, tw, permute, dst, status);
+    return 0;
+}
+static int frntt_run(mi355_bls_ctx* c, const uint8_t* d_in, const uint8_t* h_in, size_t n, size_t k, uint32_t flags, const uint8_t* shift32, uint8_t* d_out, uint8_t* h_out,
+                     uint8_t* status, hipStream_t st) {
+    const plan::frntt_sizes sz = plan::frntt_sizes_for(n, k, c->frntt_tile, c->frntt_vecs);
+    if (!sz.ok) {
+        g_err = "fr_ntt_many: n is a power of two, 1 .. 2^32";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 3) {
+        g_err = "fr_ntt_many: input and output must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    fr gm{};
+    if (shift32) {
+        uint32_t w[8];
+        for (int i = 0; i < 8; i++) w[i] = (uint32_t)shift32[4 * i] | ((uint32_t)shift32[4 * i + 1] << 8) | ((uint32_t)shift32[4 * i + 2] << 16) | ((uint32_t)shift32[4 * i + 3] << 24);
+        bool reduced;
+        gm = fr_to_mont(fr_canon_words(w, reduced));
+        if (fr_is_zero(gm)) {
+            g_err = "fr_ntt_many: the shift is 0 mod r";
+            return MI355_BLS_ERR_ARG;
+        }
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const bool inverse = flags & MI355_BLS_FR_NTT_INVERSE, bitrev = flags & MI355_BLS_FR_NTT_BITREV, host = h_out != nullptr;
+    const uint32_t m = sz.log2n;
+    const bool dit = inverse && bitrev, permute = !bitrev, second = permute && sz.passes > 1;
+    int rc = c->d_ntt_tw.reserve(sz.twiddles, 0);
+    if (!rc) rc = c->d_ntt_st.reserve(sz.status, sz.status / 4);
+    if (!rc) rc = c->d_ntt_io.reserve((host ? sz.staging : 0) + (second ? sz.staging : 0), 0);
+    if (rc) return rc;
+    fr root = frntt_omega(m);
+    if (inverse) root = fr_inv(root);
+    if (n > 1) {
+        const uint64_t runs = (n / 2 + FRNTT_RUN - 1) / FRNTT_RUN;
+        k_frntt_twiddle<<<(unsigned)((runs + FRNTT_LANES - 1) / FRNTT_LANES), FRNTT_LANES, 0, st>>>(root, n / 2, c->d_ntt_tw);
+    }
+    frntt_scale_args sa{};
+    sa.m = m;
+    if (inverse) {
+        const uint32_t nw[8] = {(uint32_t)n, (uint32_t)((uint64_t)n >> 32), 0, 0, 0, 0, 0, 0};
+        sa.base = fr_inv(fr_from_words(nw));
+        sa.ratio = shift32 ? fr_inv(gm) : fr_one();
+        sa.mult = true, sa.use_ratio = shift32 != nullptr;
+    } else {
+        sa.base = fr_one(), sa.ratio = gm;
+        sa.mult = sa.use_ratio = shift32 != nullptr;
+    }
+    const bool scale_first = !inverse && (shift32 || sz.passes == 0), scale_last = inverse;
+    const uint64_t runs_per_vec = (n + FRNTT_RUN - 1) / FRNTT_RUN;
+    std::vector<uint32_t> words(sz.vecs);
+    int reduced = 0;
+    for (size_t i = 0; i < sz.slices; i++) {
+        size_t g0, kc;
+        plan::frntt_slice(sz, k, i, g0, kc);
+        uint32_t* io = c->d_ntt_io;
+        const uint32_t* src = host ? io : reinterpret_cast<const uint32_t*>(d_in) + g0 * n * 8;
+        uint32_t* out = host ? io : reinterpret_cast<uint32_t*>(d_out) + g0 * n * 8;
+        uint32_t* mid = second ? io + (host ? sz.staging / 4 : 0) : out;
+        if (host) HIPCHK(hipMemcpyAsync(io, h_in + g0 * n * 32, kc * n * 32, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(c->d_ntt_st, 0, kc * 4, st));
+        const unsigned scale_grid = (unsigned)((kc * runs_per_vec + FRNTT_LANES - 1) / FRNTT_LANES);
+        sa.k = kc;
+        bool raw = true;
+        if (scale_first) {
+            sa.raw = true;
+            k_frntt_scale<<<scale_grid, FRNTT_LANES, 0, st>>>(sa, src, mid, c->d_ntt_st);
+            src = mid, raw = false;
+        }
+        uint32_t done = 0;
+        for (uint32_t p = 0; p < sz.passes; p++) {
+            const uint32_t tp = sz.stages[p], sigma = dit ? done : m - done - tp;
+            const plan::frntt_shape sh = plan::frntt_geo_for(m, sz.tile, sigma, tp, kc);
+            const frntt_geo g{m, sigma, tp, sh.clo, sh.chi, sh.L, kc};
+            const bool last = p + 1 == sz.passes;
+            uint32_t* dst = last ? out : mid;
+            rc = dit ? frntt_launch_pass<true>(g, src, raw, c->d_ntt_tw, false, dst, c->d_ntt_st, st)
+                     : frntt_launch_pass<false>(g, src, raw, c->d_ntt_tw, permute && last, dst, c->d_ntt_st, st);
+            if (rc) return rc;
+            src = dst, raw = false, done += tp;
+        }
+        if (scale_last) {
+            sa.raw = raw;
+            k_frntt_scale<<<scale_grid, FRNTT_LANES, 0, st>>>(sa, src, out, c->d_ntt_st);
+        }
+        HIPCHK(hipGetLastError());
+        if (host) HIPCHK(hipMemcpyAsync(h_out + g0 * n * 32, out, kc * n * 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(words.data(), c->d_ntt_st, kc * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t v = 0; v < kc; v++) {
+            if (status) status[g0 + v] = (uint8_t)words[v];
+            reduced += (words[v] & FRNTT_ST_REDUCED) != 0;
+        }
+    }
+    return reduced;
+}
+extern "C" int mi355_bls_fr_ntt_many_device(mi355_bls_ctx* c, const void* d_in32, size_t n, size_t k, uint32_t flags, const uint8_t* shift32, void* d_out32,
+                                            uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing computed, nothing written
+    if (!frntt_args_ok(d_in32, n, flags, d_out32)) return MI355_BLS_ERR_ARG;
+    return frntt_run(c, (const uint8_t*)d_in32, nullptr, n, k, flags, shift32, (uint8_t*)d_out32, nullptr, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_fr_ntt_many(mi355_bls_ctx* c, const void* in32, size_t n, size_t k, uint32_t flags, const uint8_t* shift32, uint8_t* out32, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    if (!frntt_args_ok(in32, n, flags, out32)) return MI355_BLS_ERR_ARG;
+    return frntt_run(c, nullptr, (const uint8_t*)in32, n, k, flags, shift32, nullptr, out32, status, nullptr);
+}
+// The domain both calls speak of: omega_n^i, or omega_n^rev_m(i) with BITREV, as n canonical images (k_frntt_domain); h_out: the host form,
+// through d_ntt_io.  Both forms return after the stream has drained.
+static int frntt_domain(mi355_bls_ctx* c, size_t n, uint32_t flags, uint8_t* d_out, uint8_t* h_out, hipStream_t st) {
+    if (!c || !(d_out || h_out) || n == 0 || (n & (n - 1)) || n > ((size_t)1 << 32) || (flags & ~(uint32_t)MI355_BLS_FR_NTT_BITREV) || ((uintptr_t)d_out & 3)) {
+        g_err = "fr_domain: a NULL context or output, n that is no power of two in 1 .. 2^32, a flag other than MI355_BLS_FR_NTT_BITREV, or a misaligned device pointer";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    if (h_out)
+        if (int rc = c->d_ntt_io.reserve(n * 32, 0)) return rc;
+    uint32_t* out = h_out ? c->d_ntt_io.p : reinterpret_cast<uint32_t*>(d_out);
+    uint32_t m = 0;
+    while (((size_t)1 << m) < n) m++;
+    const uint64_t runs = (n + FRNTT_RUN - 1) / FRNTT_RUN;
+    k_frntt_domain<<<(unsigned)((runs + FRNTT_LANES - 1) / FRNTT_LANES), FRNTT_LANES, 0, st>>>(frntt_omega(m), m, (flags & MI355_BLS_FR_NTT_BITREV) != 0, out);
+    HIPCHK(hipGetLastError());
+    if (h_out) HIPCHK(hipMemcpyAsync(h_out, out, n * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int mi355_bls_fr_domain(mi355_bls_ctx* c, size_t n, uint32_t flags, uint8_t* out32) { return frntt_domain(c, n, flags, nullptr, out32, nullptr); }
+extern "C" int mi355_bls_fr_domain_device(mi355_bls_ctx* c, size_t n, uint32_t flags, void* d_out32, void* stream) {
+    return frntt_domain(c, n, flags, (uint8_t*)d_out32, nullptr, (hipStream_t)stream);
+}
+// TEST HOOKS: log2 of the tile (0: the plan's own; at most plan::FRNTT_TILE_MAX_LOG2) and the vectors per slice (0: the plan's own; it can
+// only shorten a slice) of the following fr_ntt_many calls on this context
+extern "C" int mi355_bls_debug_frntt_set_tile(mi355_bls_ctx* c, uint32_t log2_tile) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    c->frntt_tile = log2_tile;
+    return 0;
+}
+extern "C" int mi355_bls_debug_frntt_set_pass(mi355_bls_ctx* c, size_t vectors_per_pass) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    c->frntt_vecs = vectors_per_pass;
     return 0;
 }
 

@@ -45,6 +45,7 @@
 #include "recover.hpp"
 #include "lincomb.hpp"
 #include "fropen.hpp"
+#include "frntt.hpp"
 #include "keytable.hpp"
 #include "msmmany.hpp"
 #include "msmtable.hpp"
@@ -3278,6 +3279,50 @@ __global__ void __launch_bounds__(FROPEN_LANES) k_fropen_eval(const uint32_t* __
         if (ys) fropen_st(ys + g * 8, y);
         status[g] = (uint8_t)(sh_flags | (j != FROPEN_NO_J ? FROPEN_ST_IN_DOMAIN : 0u));
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Transforms of many vectors over Fr (mi355_bls_fr_ntt_many, mi355_bls_fr_domain).  The arithmetic and the scheme are csrc/frntt.hpp's; here
+// the lanes of a workgroup walk its bodies.  status: a WORD per vector of the slice, cleared by the host call (several workgroups may hold
+// elements of one vector, and one workgroup elements of several).
+// ------------------------------------------------------------------------------------------
+// a lane per run of FRNTT_RUN table entries: root^j in Montgomery form, j < count
+__global__ void __launch_bounds__(FRNTT_LANES) k_frntt_twiddle(fr root, uint64_t count, uint32_t* __restrict__ tw) {
+    frntt_twiddle_run(root, (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x, count, tw);
+}
+// a lane per run of domain elements
+__global__ void __launch_bounds__(FRNTT_LANES) k_frntt_domain(fr omega, uint32_t m, bool bitrev, uint32_t* __restrict__ out) {
+    frntt_domain_run(omega, (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x, m, bitrev, out);
+}
+// a lane per run of elements: the shift powers and 1 / n, or the copy of a call without stages.  src == dst is allowed: a lane reads an
+// element before it writes it, and no other lane touches it.
+__global__ void __launch_bounds__(FRNTT_LANES) k_frntt_scale(frntt_scale_args a, const uint32_t* src, uint32_t* dst, uint32_t* __restrict__ status) {
+    uint64_t vec;
+    if (frntt_scale_run(a, (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x, src, dst, vec)) atomicOr(&status[vec], FRNTT_ST_REDUCED);
+}
+// One pass: the workgroup's 2^L elements into LDS (8 words x 2^L, limb-major: the launch's dynamic LDS), g.tp stages with a barrier behind
+// each, and out again.  src == dst is allowed where the store does not permute: a workgroup stores where it loaded, after its last load.
+extern __shared__ uint32_t frntt_lds[];
+template <bool DIT>
+__global__ void __launch_bounds__(FRNTT_LANES) k_frntt_pass(frntt_geo g, const uint32_t* src, bool raw, const uint32_t* __restrict__ tw, bool permute, uint32_t* dst,
+                                                             uint32_t* __restrict__ status) {
+    const uint32_t t = threadIdx.x, slots = 1u << g.L;
+    const uint64_t w = blockIdx.x;
+#pragma clang loop unroll(disable)
+    for (uint32_t l = t; l < slots; l += FRNTT_LANES) {
+        uint64_t vec;
+        if (frntt_load_item(g, w, l, src, raw, frntt_lds, vec)) atomicOr(&status[vec], FRNTT_ST_REDUCED);
+    }
+    __syncthreads();
+#pragma clang loop unroll(disable)
+    for (uint32_t s = 0; s < g.tp; s++) {
+        const uint32_t pos = g.clo + (DIT ? s : g.tp - 1 - s);
+#pragma clang loop unroll(disable)
+        for (uint32_t bf = t; bf < slots / 2; bf += FRNTT_LANES) frntt_butterfly<DIT>(g, w, bf, pos, tw, frntt_lds);
+        __syncthreads();
+    }
+#pragma clang loop unroll(disable)
+    for (uint32_t l = t; l < slots; l += FRNTT_LANES) frntt_store_item(g, w, l, frntt_lds, permute, dst);
 }
 
 // ------------------------------------------------------------------------------------------

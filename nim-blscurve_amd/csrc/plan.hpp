@@ -647,6 +647,73 @@ inline void fropen_pass(const fropen_sizes& s, size_t k, size_t p, size_t& first
     count = k - first < s.per_pass ? k - first : s.per_pass;
 }
 
+// Transforms of k vectors of n = 2^m scalars over Fr (mi355_bls_fr_ntt_many; csrc/frntt.hpp): m radix-2 stages in PASSES over global memory,
+// each pass the next <= tile stages with the elements they connect in LDS, and the call in SLICES of whole vectors, vectors
+// [first, first + count) each.
+//   FRNTT_TILE_LOG2     the default tile, 2^10 elements = 32 KiB of LDS: four workgroups (sixteen waves) fit a CU's 160 KiB, and other
+//                       waves cover the dependent chain of a lane's Montgomery product.  2^12 elements (FRNTT_TILE_MAX_LOG2, 128 KiB: one
+//                       workgroup, four waves per CU) halve the passes of a long vector instead.  tools/bench_fr_ntt.py measures both
+//                       through the hook; the default is the one that was faster at 64 x 4 096 (profiles/fr_ntt_bench.json, README.md).
+//   passes              ceil(m / tile) of them, the stages spread evenly (the first ones take the odd stage): m = 16 at tile 10 is 8 + 8,
+//                       not 10 + 6, so that BOTH passes leave LDS room for adjacent columns (frntt_geo_for) - a pass that fills the tile
+//                       with its own stages reads single 32-byte elements a stride apart.
+//   FRNTT_SLICE_BYTES   n x 32 bytes per vector of a slice, 256 MiB in all: the host form's staging, and the second buffer of a transform
+//                       whose last store permutes (more than one pass, no BITREV).  One vector always fits.  FRNTT_SLICE_VECS: the status
+//                       words of a slice, 2^20.  Not tuned.
+//   forced_tile is the test hook's log2 (mi355_bls_debug_frntt_set_tile; 0: the default; it cannot exceed FRNTT_TILE_MAX_LOG2, the LDS a
+//   workgroup may ask for), forced_vecs that of mi355_bls_debug_frntt_set_pass (0: the rule above; it can only shorten a slice).
+// Refused (ok == false): n == 0, n that is no power of two or above 2^32.  Nothing for its size: n = 2^32 with k = 2^20 stays inside 64 bits.
+constexpr uint32_t FRNTT_TILE_LOG2 = 10, FRNTT_TILE_MAX_LOG2 = 12, FRNTT_MAX_PASSES = 32;
+constexpr size_t FRNTT_SLICE_VECS = (size_t)1 << 20, FRNTT_SLICE_BYTES = (size_t)256 << 20;
+struct frntt_sizes {
+    bool ok;
+    uint32_t log2n, tile, passes;            // n = 2^log2n; log2 of the tile; the passes of one transform
+    uint8_t stages[FRNTT_MAX_PASSES];        // the stages of each pass, in the order they run: they sum to log2n
+    size_t vecs, slices;                     // vectors per slice (the last one may hold fewer), slices of the call
+    size_t twiddles, status, staging;        // bytes: the n / 2 table entries, a status word per vector of a slice, a slice's elements
+};
+inline frntt_sizes frntt_sizes_for(size_t n, size_t k, uint32_t forced_tile = 0, size_t forced_vecs = 0) {
+    frntt_sizes s{};
+    if (n == 0 || (n & (n - 1)) || n > ((size_t)1 << 32)) return s;
+    while (((size_t)1 << s.log2n) < n) s.log2n++;
+    s.tile = forced_tile ? (forced_tile < FRNTT_TILE_MAX_LOG2 ? forced_tile : FRNTT_TILE_MAX_LOG2) : FRNTT_TILE_LOG2;
+    s.passes = (s.log2n + s.tile - 1) / s.tile;
+    for (uint32_t p = 0; p < s.passes; p++) s.stages[p] = (uint8_t)(s.log2n / s.passes + (p < s.log2n % s.passes));
+    size_t per = FRNTT_SLICE_VECS;
+    if (FRNTT_SLICE_BYTES / (n * 32) < per) per = FRNTT_SLICE_BYTES / (n * 32);
+    if (per == 0) per = 1;
+    if (forced_vecs && forced_vecs < per) per = forced_vecs;
+    if (per > k && k) per = k;
+    s.ok = true;
+    s.vecs = per;
+    s.slices = (k + per - 1) / per;
+    s.twiddles = n / 2 * 32;
+    s.status = per * 4;
+    s.staging = per * n * 32;
+    return s;
+}
+// slice i of the call: vectors [first, first + count)
+inline void frntt_slice(const frntt_sizes& s, size_t k, size_t i, size_t& first, size_t& count) {
+    first = i * s.vecs;
+    count = k - first < s.vecs ? k - first : s.vecs;
+}
+// The shape of a pass over `vecs` vectors that takes `tp` stages from index bit `sigma` up (frntt.hpp frntt_geo): what is left of the tile
+// goes to adjacent columns first (clo <= sigma), then to adjacent blocks (chi, no more than the pass has blocks).
+struct frntt_shape {
+    uint32_t clo, chi, L;
+};
+inline frntt_shape frntt_geo_for(uint32_t log2n, uint32_t tile, uint32_t sigma, uint32_t tp, size_t vecs) {
+    frntt_shape g{};
+    const uint32_t room = tile - tp;
+    g.clo = room < sigma ? room : sigma;
+    const uint64_t blocks = (uint64_t)vecs << (log2n - sigma - tp);
+    uint32_t need = 0;
+    while (need < 63 && ((uint64_t)1 << need) < blocks) need++;
+    g.chi = room - g.clo < need ? room - g.clo : need;
+    g.L = g.clo + tp + g.chi;
+    return g;
+}
+
 // Per-group aggregateVerify (mi355_bls_aggregate_verify_each): k groups of (key, message) pairs in CSR form, one aggregate signature each.
 // The call runs in SLICES of at most `cap` pairs of the per-set path's pair store (2 cap slots: the pairs, then one (-G1, sig) pair per
 // group that ends in the slice - never more than the pairs, a group in a slice has a pair there).
