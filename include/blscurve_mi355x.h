@@ -837,6 +837,36 @@ int mi355_bls_fr_domain_device(mi355_bls_ctx* ctx, size_t n, uint32_t flags, voi
 int mi355_bls_debug_frntt_set_tile(mi355_bls_ctx* ctx, uint32_t log2_tile);
 int mi355_bls_debug_frntt_set_pass(mi355_bls_ctx* ctx, size_t vectors_per_pass);
 
+/* Number-theoretic transforms of k vectors of G1 POINTS in one device pass: what mi355_bls_fr_ntt_many does to scalars, done to points.  The
+ * inverse transform of the monomial table [tau^j]G is the Lagrange table that commits to values (mi355_bls_fr_open_many's evaluation form);
+ * the forward transform is the last step of an all-openings (FK20-style) computation.
+ *   omega_n, rev_m and both flags are mi355_bls_fr_ntt_many's: n = 2^m, 0 <= m <= 32, omega_n = 7^((r - 1) / n) mod r.
+ *   FORWARD  out[i] = sum_j [omega_n^(i j)] P_j.
+ *   MI355_BLS_P1S_NTT_INVERSE  the exact inverse map: [1 / n] sum_i [omega_n^(-i j)] P_i.
+ *   MI355_BLS_P1S_NTT_BITREV   the EVALUATION side (the forward output, the inverse input) is in bit-reversed order; with the flag no
+ *                  permutation is made, without it the last store permutes.
+ *   So for P_j = [a_j]G the result is [fr_ntt(a)_i]G under the same flags.  There is no coset shift.
+ *   points96       k x n 96-byte blst_p1_affine images; vector g is images [g n, (g + 1) n); the all-zero image is infinity.  The points
+ *                  must be in G1, the prime-order subgroup: this is NOT checked - with other points the outputs mean nothing, but nothing faults.
+ *   out96          k x n canonical affine images in the same form, all zero: infinity - what p1s_lincomb_many writes and every consumer reads.
+ *   IN PLACE       d_out96 == d_points96 exactly is allowed in the _device form; any other overlap is a precondition violation.
+ * Returns 0; k == 0: 0, nothing touched.  n == 1 is the canonicalising copy.
+ * MI355_BLS_ERR_ARG, before anything is launched: a NULL context (before the k == 0 rule), NULL points or output, n == 0, n that is no power
+ * of two or above 2^32, an unknown flag bit, a misaligned device pointer (4-byte aligned), a busy context.  Nothing else is refused for its
+ * size: k x n beyond one slice is cut into slices of whole vectors, and one vector always forms a slice (csrc/plan.hpp p1ntt_sizes_for; the
+ * workspace is the library's own: 192 bytes per point of a slice).  The _device form enqueues on `stream` and waits for it once at the end.
+ * The m radix-2 stages run over global memory, one lane per butterfly (csrc/p1ntt.hpp): a butterfly is a 255-bit scalar multiplication by
+ * signed 4-bit windows, except where its twiddle is 1; the inverse's 1 / n is folded into one stage.
+ * VARIABLE TIME: public points only.
+ * COST: profiles/p1s_ntt_bench.json (nim-blscurve_amd/tools/bench_p1s_ntt.py), reported row by row in README.md.
+ * debug_p1ntt_set_pass: TEST HOOK, the vectors per slice of the following p1s_ntt_many calls on this context (0: the plan's own; it can only
+ * shorten a slice). */
+#define MI355_BLS_P1S_NTT_INVERSE 1u
+#define MI355_BLS_P1S_NTT_BITREV 2u
+int mi355_bls_p1s_ntt_many(mi355_bls_ctx* ctx, const void* points96, size_t n, size_t k, uint32_t flags, void* out96);
+int mi355_bls_p1s_ntt_many_device(mi355_bls_ctx* ctx, const void* d_points96, size_t n, size_t k, uint32_t flags, void* d_out96, void* stream);
+int mi355_bls_debug_p1ntt_set_pass(mi355_bls_ctx* ctx, size_t vectors_per_pass);
+
 /* Fixed-base G1 MSM over a precomputed window table: blst_p1s_mult_wbits_precompute(_sizeof) and blst_p1s_mult_wbits (blst_abi.nim:327-335)
  * for callers whose point set does not change - k commitments over one SRS or Lagrange table.  A table is a library-owned handle that keeps, in
  * device memory, the rows [2^(w wbits)] P_i for w = 0 .. W - 1, W = ceil((nbits + 1) / wbits), W x npoints x 128 bytes

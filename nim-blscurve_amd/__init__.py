@@ -185,6 +185,9 @@ def lib():
         L.mi355_bls_fr_domain_device.argtypes = [vp, sz, u32, vp, vp]
         L.mi355_bls_debug_frntt_set_tile.argtypes = [vp, u32]
         L.mi355_bls_debug_frntt_set_pass.argtypes = [vp, sz]
+        L.mi355_bls_p1s_ntt_many.argtypes = [vp, vp, sz, sz, u32, vp]
+        L.mi355_bls_p1s_ntt_many_device.argtypes = [vp, vp, sz, sz, u32, vp, vp]
+        L.mi355_bls_debug_p1ntt_set_pass.argtypes = [vp, sz]
         L.mi355_bls_p1s_table_sizeof.argtypes = [sz, sz, sz]
         L.mi355_bls_p1s_table_sizeof.restype = sz
         L.mi355_bls_p1s_table_create.argtypes = [vp, vp, vp, sz, sz, sz]
@@ -1639,6 +1642,47 @@ def debug_frntt_set_tile(cache, log2_tile=0):
 def debug_frntt_set_pass(cache, vectors_per_pass=0):
     """TEST HOOK (mi355_bls_debug_frntt_set_pass): the vectors per slice of the following frNttMany calls on this context; 0: the plan's own."""
     _check(lib().mi355_bls_debug_frntt_set_pass(cache._h, int(vectors_per_pass)))
+
+
+P1S_NTT_INVERSE = 1                    # flags of p1sNttMany: the exact inverse map, [1 / n] included
+P1S_NTT_BITREV = 2                     # the evaluation side (the forward output, the inverse input) is in bit-reversed order
+
+
+def p1sNttMany(cache, points, n, flags=0):
+    """The forward or inverse number-theoretic transform of k vectors of n = 2^m G1 points in one device pass (mi355_bls_p1s_ntt_many).
+    points: k x n 96-byte blst_p1_affine images, vector g at [g n, (g + 1) n); all zero: infinity; the points must be in G1 (not checked).
+    Forward: out[i] = sum_j [omega_n^(i j)] P_j with omega_n = 7^((r - 1) / n); P1S_NTT_INVERSE: the exact inverse; P1S_NTT_BITREV: the
+    evaluation side is bit-reversed - frNttMany's conventions, so [a_j]G goes to [frNttMany(a)_i]G.  -> k x n canonical affine images.
+    VARIABLE TIME: public points only."""
+    n, flags, _ = _fr_ntt_args(n, flags, None, P1S_NTT_INVERSE | P1S_NTT_BITREV)
+    points = bytes(points)
+    if len(points) % (n * 96):
+        raise ValueError("points: k x n x 96 bytes (%d for n = %d)" % (len(points), n))
+    k = len(points) // (n * 96)
+    if k == 0:
+        return b""
+    out = ctypes.create_string_buffer(len(points))
+    _check(lib().mi355_bls_p1s_ntt_many(cache._h, points, n, k, flags, out))
+    return out.raw
+
+
+def p1sNttMany_device(cache, d_in, n, k, flags=0, d_out=None, stream=0):
+    """The same with the points and the output in device memory (raw pointers, k x n x 96 bytes each; d_out None: in place, d_out == d_in).
+    d_out is, as it stands, a points argument of the MSM and lincomb calls."""
+    n, flags, _ = _fr_ntt_args(n, flags, None, P1S_NTT_INVERSE | P1S_NTT_BITREV)
+    k = int(k)
+    if k < 0:
+        raise ValueError("k is a count")
+    if k == 0:
+        return
+    if not d_in:
+        raise ValueError("points: a device pointer")
+    _check(lib().mi355_bls_p1s_ntt_many_device(cache._h, d_in, n, k, flags, d_out or d_in, stream))
+
+
+def debug_p1ntt_set_pass(cache, vectors_per_pass=0):
+    """TEST HOOK (mi355_bls_debug_p1ntt_set_pass): the vectors per slice of the following p1sNttMany calls on this context; 0: the plan's own."""
+    _check(lib().mi355_bls_debug_p1ntt_set_pass(cache._h, int(vectors_per_pass)))
 
 
 def compressSignatures(cache, signatures):

@@ -213,6 +213,10 @@ struct mi355_bls_ctx {
     dev_buf<uint32_t> d_ntt_tw, d_ntt_io, d_ntt_st;
     uint32_t frntt_tile = 0;         // mi355_bls_debug_frntt_set_tile: log2 of the tile of the fr_ntt_many calls; 0: the plan's own
     size_t frntt_vecs = 0;           // mi355_bls_debug_frntt_set_pass: vectors per slice of the fr_ntt_many calls; 0: the plan's own
+    // transforms over G1 (mi355_bls_p1s_ntt_many): the twiddle table of the call | a slice's internal Jacobian images | the host form's
+    // staging of a slice's affine images
+    dev_buf<uint32_t> d_p1n_tw, d_p1n_ws, d_p1n_io;
+    size_t p1ntt_vecs = 0;           // mi355_bls_debug_p1ntt_set_pass: vectors per slice of the p1s_ntt_many calls; 0: the plan's own
     ptab_ws ptab;                    // MSMs over a fixed-base window table: made at the first such call
     // per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): sized by the largest slice of a call; it runs in the per-set path's
     // pair store with the per-group path's tables, partials and step values (d_aggv_*) and combine_sets' G2 products and tables (grp, d_comb_*)
@@ -2752,6 +2756,86 @@ extern "C" int mi355_bls_debug_frntt_set_tile(mi355_bls_ctx* c, uint32_t log2_ti
 extern "C" int mi355_bls_debug_frntt_set_pass(mi355_bls_ctx* c, size_t vectors_per_pass) {
     if (!c) return MI355_BLS_ERR_ARG;
     c->frntt_vecs = vectors_per_pass;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Transforms of k vectors of G1 points (mi355_bls_p1s_ntt_many): slices of whole vectors (plan.hpp p1ntt_sizes_for); per call the twiddle
+// table (k_p1ntt_twiddle), per slice the m stages (k_p1ntt_stage<DIT>, the first reading the caller's images, all writing d_p1n_ws) and the
+// finish (k_p1ntt_finish), all on the caller's stream, which is waited for once at the end.  Which transform runs: p1ntt.hpp.
+// h_in / h_out: the host form - a slice is staged in d_p1n_io, transformed there and copied out, slice by slice.
+// ------------------------------------------------------------------------------------------
+static int p1ntt_run(mi355_bls_ctx* c, const uint8_t* d_in, const uint8_t* h_in, size_t n, size_t k, uint32_t flags, uint8_t* d_out, uint8_t* h_out, hipStream_t st) {
+    const plan::p1ntt_sizes sz = plan::p1ntt_sizes_for(n, k, c->p1ntt_vecs);
+    if (!(d_in || h_in) || !(d_out || h_out) || !sz.ok || (flags & ~(uint32_t)(MI355_BLS_P1S_NTT_INVERSE | MI355_BLS_P1S_NTT_BITREV))) {
+        g_err = "p1s_ntt_many: NULL points or output, n that is no power of two in 1 .. 2^32, or a flag other than MI355_BLS_P1S_NTT_INVERSE and MI355_BLS_P1S_NTT_BITREV";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 3) {
+        g_err = "p1s_ntt_many: points and output must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const bool inverse = flags & MI355_BLS_P1S_NTT_INVERSE, bitrev = flags & MI355_BLS_P1S_NTT_BITREV, host = h_out != nullptr;
+    const uint32_t m = sz.log2n;
+    const bool dit = inverse && bitrev, permute = !bitrev;
+    int rc = c->d_p1n_tw.reserve(sz.twiddles, 0);
+    if (!rc && m) rc = c->d_p1n_ws.reserve(sz.ws, 0);
+    if (!rc && host) rc = c->d_p1n_io.reserve(sz.staging, 0);
+    if (rc) return rc;
+    p1ntt_stage g{};
+    g.m = m;
+    if (m) {
+        fr root = frntt_omega(m);
+        if (inverse) root = fr_inv(root);
+        const uint64_t runs = (n / 2 + FRNTT_RUN - 1) / FRNTT_RUN;
+        k_p1ntt_twiddle<<<(unsigned)((runs + FRNTT_LANES - 1) / FRNTT_LANES), FRNTT_LANES, 0, st>>>(root, n / 2, c->d_p1n_tw);
+    }
+    if (inverse) {
+        const uint32_t nw[8] = {(uint32_t)n, (uint32_t)((uint64_t)n >> 32), 0, 0, 0, 0, 0, 0};
+        g.s_mont = fr_inv(fr_from_words(nw));
+        fr_to_words(g.s, g.s_mont);
+    }
+    for (size_t i = 0; i < sz.slices; i++) {
+        size_t g0, kc;
+        plan::p1ntt_slice(sz, k, i, g0, kc);
+        const plan::p1ntt_launch l = plan::p1ntt_launch_for(sz, kc);
+        const uint32_t* src = host ? c->d_p1n_io.p : reinterpret_cast<const uint32_t*>(d_in + g0 * n * 96);
+        uint32_t* out = host ? c->d_p1n_io.p : reinterpret_cast<uint32_t*>(d_out + g0 * n * 96);
+        if (host) HIPCHK(hipMemcpyAsync(c->d_p1n_io, h_in + g0 * n * 96, kc * n * 96, hipMemcpyHostToDevice, st));
+        g.k = kc;
+        for (uint32_t s = 0; s < m; s++) {
+            g.b = dit ? s : m - 1 - s;
+            g.scaled = inverse && g.b == m - 1;
+            const uint32_t* in_aff = s == 0 ? src : nullptr;
+            if (dit) k_p1ntt_stage<true><<<l.stage_grid, WAVE, 0, st>>>(g, in_aff, c->d_p1n_ws, c->d_p1n_tw);
+            else k_p1ntt_stage<false><<<l.stage_grid, WAVE, 0, st>>>(g, in_aff, c->d_p1n_ws, c->d_p1n_tw);
+        }
+        k_p1ntt_finish<<<l.finish_grid, WAVE, 0, st>>>(m ? c->d_p1n_ws.p : src, m == 0, (uint64_t)kc << m, m, permute, l.run, out);
+        HIPCHK(hipGetLastError());
+        if (host) {
+            HIPCHK(hipMemcpyAsync(h_out + g0 * n * 96, out, kc * n * 96, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
+    if (!host) HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int mi355_bls_p1s_ntt_many_device(mi355_bls_ctx* c, const void* d_points96, size_t n, size_t k, uint32_t flags, void* d_out96, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing computed, nothing written
+    return p1ntt_run(c, (const uint8_t*)d_points96, nullptr, n, k, flags, (uint8_t*)d_out96, nullptr, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_p1s_ntt_many(mi355_bls_ctx* c, const void* points96, size_t n, size_t k, uint32_t flags, void* out96) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    return p1ntt_run(c, nullptr, (const uint8_t*)points96, n, k, flags, nullptr, (uint8_t*)out96, nullptr);
+}
+// TEST HOOK: the vectors per slice of the following p1s_ntt_many calls on this context (0: the plan's own; it can only shorten a slice)
+extern "C" int mi355_bls_debug_p1ntt_set_pass(mi355_bls_ctx* c, size_t vectors_per_pass) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    c->p1ntt_vecs = vectors_per_pass;
     return 0;
 }
 

@@ -46,6 +46,7 @@
 #include "lincomb.hpp"
 #include "fropen.hpp"
 #include "frntt.hpp"
+#include "p1ntt.hpp"
 #include "keytable.hpp"
 #include "msmmany.hpp"
 #include "msmtable.hpp"
@@ -3323,6 +3324,38 @@ __global__ void __launch_bounds__(FRNTT_LANES) k_frntt_pass(frntt_geo g, const u
     }
 #pragma clang loop unroll(disable)
     for (uint32_t l = t; l < slots; l += FRNTT_LANES) frntt_store_item(g, w, l, frntt_lds, permute, dst);
+}
+
+// ------------------------------------------------------------------------------------------
+// Transforms of many vectors of G1 points (mi355_bls_p1s_ntt_many).  The arithmetic and the scheme are csrc/p1ntt.hpp's; here a lane walks
+// its bodies.  One-wave workgroups, like every one-lane-per-item kernel of the curve arithmetic.  ws: the slice's k x n internal Jacobian
+// images (G1W words each).
+// ------------------------------------------------------------------------------------------
+// a lane per run of FRNTT_RUN table entries: root^j as a canonical plain scalar, j < count
+__global__ void __launch_bounds__(FRNTT_LANES) k_p1ntt_twiddle(fr root, uint64_t count, uint32_t* __restrict__ tw) {
+    p1ntt_twiddle_run(root, (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x, count, tw);
+}
+// One stage, a lane per butterfly in twiddle-major order.  in_aff != nullptr: the first stage, whose elements are the caller's 96-byte
+// affine images (all zero: infinity); every stage stores into ws, where the later ones load.  No two lanes share an element.
+template <bool DIT>
+__global__ void __launch_bounds__(WAVE) k_p1ntt_stage(p1ntt_stage g, const uint32_t* in_aff, uint32_t* ws, const uint32_t* __restrict__ tw) {
+    const uint64_t lane = (uint64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (lane >= p1ntt_lanes(g)) return;
+    p1ntt_butterfly<DIT, fp>(
+        g, lane, [&](uint64_t e) { return in_aff ? jac_from_aff(ld_g1a_blst(in_aff + (size_t)e * 24)) : ld_g1_int(ws + (size_t)e * G1W); },
+        [&](uint64_t e, const g1_jac& a) { st_g1_int(ws + (size_t)e * G1W, a); }, [&](uint64_t t) { return fropen_own(tw, (size_t)t); });
+}
+// The finish, a lane per run of `run` consecutive elements of the slice's total = k n: canonical affine images with one inversion per
+// run, element e at slot e of out or, with permute, at the bit-reversed place in its vector.  src_aff: src holds the caller's affine
+// images (n == 1, a call without stages; src == out is allowed then: a lane loads and stores nothing but its own run, and permutes nothing).
+__global__ void __launch_bounds__(WAVE) k_p1ntt_finish(const uint32_t* src, bool src_aff, uint64_t total, uint32_t m, bool permute, uint32_t run, uint32_t* out) {
+    p1ntt_finish_run<fp>(
+        total, m, permute, run, (uint64_t)blockIdx.x * WAVE + threadIdx.x,
+        [&](uint64_t e) { return src_aff ? jac_from_aff(ld_g1a_blst(src + (size_t)e * 24)) : ld_g1_int(src + (size_t)e * G1W); },
+        [&](uint64_t slot, const g1_aff& a) { st_aff_blst(out + (size_t)slot * 24, a); },
+        [&](uint64_t slot) {
+            for (uint32_t t = 0; t < 24; t++) out[(size_t)slot * 24 + t] = 0;
+        });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1288,6 +1288,58 @@ inline to_affine_launch to_affine_next(const to_affine_plan& p, size_t n, size_t
     return l;
 }
 
+// Transforms of k vectors of n = 2^m G1 points (mi355_bls_p1s_ntt_many; csrc/p1ntt.hpp): m radix-2 stages over a workspace of internal
+// Jacobian images in global memory, one lane per butterfly, then the finish to affine images; the call in SLICES of whole vectors, vectors
+// [first, first + count) each.
+//   P1NTT_SLICE_BYTES   n x G1_WORDS x 4 = n x 192 bytes per vector of a slice, 256 MiB in all: FRNTT_SLICE_BYTES' reasoning - a workspace
+//                       the library can always ask for, far beyond the 2^16 lanes that fill the device - and like it NOT TUNED.  One
+//                       vector always forms a slice, whatever its size.  The host form stages a slice's 96-byte images beside it.
+//   forced_vecs         the test hook's vectors per slice (mi355_bls_debug_p1ntt_set_pass; 0: the rule above; it can only shorten a slice).
+//   a stage             count x n / 2 lanes in workgroups of WAVE (p1ntt_launch_for): one vector of 2^32 points is 2^25 workgroups, and a
+//                       slice of several vectors holds fewer elements than 2^21.
+//   the finish          to_affine_for's run over the slice's count x n elements, a lane per run.
+// Refused (ok == false): n == 0, n that is no power of two or above 2^32.  Nothing for its size.
+constexpr size_t P1NTT_SLICE_BYTES = (size_t)256 << 20;
+struct p1ntt_sizes {
+    bool ok;
+    uint32_t log2n;                          // n = 2^log2n: the stages of one transform
+    size_t vecs, slices;                     // vectors per slice (the last one may hold fewer), slices of the call
+    size_t twiddles, ws, staging;            // bytes: the n / 2 table entries, a slice's Jacobian images, a slice's affine images
+};
+inline p1ntt_sizes p1ntt_sizes_for(size_t n, size_t k, size_t forced_vecs = 0) {
+    p1ntt_sizes s{};
+    if (n == 0 || (n & (n - 1)) || n > ((size_t)1 << 32)) return s;
+    while (((size_t)1 << s.log2n) < n) s.log2n++;
+    size_t per = P1NTT_SLICE_BYTES / (n * G1_WORDS * 4);
+    if (per == 0) per = 1;
+    if (forced_vecs && forced_vecs < per) per = forced_vecs;
+    if (per > k && k) per = k;
+    s.ok = true;
+    s.vecs = per;
+    s.slices = (k + per - 1) / per;
+    s.twiddles = n / 2 * 32;
+    s.ws = per * n * G1_WORDS * 4;
+    s.staging = per * n * 96;
+    return s;
+}
+// slice i of the call: vectors [first, first + count)
+inline void p1ntt_slice(const p1ntt_sizes& s, size_t k, size_t i, size_t& first, size_t& count) {
+    first = i * s.vecs;
+    count = k - first < s.vecs ? k - first : s.vecs;
+}
+// the launches of a slice of `count` vectors: workgroups of WAVE lanes of a stage, points per lane and workgroups of the finish
+struct p1ntt_launch {
+    uint32_t stage_grid, run, finish_grid;
+};
+inline p1ntt_launch p1ntt_launch_for(const p1ntt_sizes& s, size_t count) {
+    p1ntt_launch l{};
+    const uint64_t total = (uint64_t)count << s.log2n;
+    l.stage_grid = (uint32_t)((total / 2 + WAVE - 1) / WAVE);
+    l.run = to_affine_for((size_t)total).run;
+    l.finish_grid = (uint32_t)(((total + l.run - 1) / l.run + WAVE - 1) / WAVE);
+    return l;
+}
+
 // ------------------------------------------------------------------------------------------
 // Fixed-base G1 MSM over a precomputed window table (mi355_bls_p1s_table_* / mi355_bls_p1s_mult_table*): what ptab_run follows and reserves.
 // The table holds, for point i and window w, the affine row T[w][i] = [2^(w wbits)] P_i at entry w x npoints + i (k_pip_convert's record).
