@@ -867,6 +867,52 @@ int mi355_bls_p1s_ntt_many(mi355_bls_ctx* ctx, const void* points96, size_t n, s
 int mi355_bls_p1s_ntt_many_device(mi355_bls_ctx* ctx, const void* d_points96, size_t n, size_t k, uint32_t flags, void* d_out96, void* stream);
 int mi355_bls_debug_p1ntt_set_pass(mi355_bls_ctx* ctx, size_t vectors_per_pass);
 
+/* ALL n openings of each of k polynomials over the n-th roots of unity in one device pass (the Feist-Khovratovich route, "FK20", over G1):
+ * O(n log n) scalar multiplications per polynomial where mi355_bls_fr_open_many over the whole domain followed by n MSMs needs n^2.
+ *   DEFINITION, for ANY G1 points S_0 .. S_(n-1), n = 2^m, 0 <= m <= 31, coefficients c_0 .. c_(n-1) and mi355_bls_fr_ntt_many's omega_n:
+ *       h_t  = sum_{i=0}^{n-2-t} [c_(i+t+1)] S_i     t = 0 .. n-2,   h_(n-1) = infinity
+ *       pi_l = sum_{t=0}^{n-1} [omega_n^(l t)] h_t   l = 0 .. n-1
+ *   For an SRS S_j = [tau^j]G, pi_l is the commitment to (p(X) - p(omega_n^l)) / (X - omega_n^l): the KZG proof at z = omega_n^l, what
+ *   mi355_bls_fr_open_many followed by an MSM over the SRS gives for that z.
+ *   THE SETUP is a library-owned handle in device memory, 2n x 96 bytes (mi355_bls_fk20_setup_sizeof; 0 for an n that create refuses): the
+ *   transform of length 2n of the reversed, zero-extended setup points as affine images in bit-reversed order.  Creating it is one
+ *   mi355_bls_p1s_ntt_many-style transform of 2n points.  srs96: n 96-byte blst_p1_affine images, all zero: infinity; the points must be in
+ *   G1, which is NOT checked.  Ownership, device and lifetime are mi355_bls_p1s_table's: the handle belongs to its caller, not to the context
+ *   that made it, any context of the same device may use it, and mi355_bls_fk20_setup_destroy releases it (NULL: no-op).
+ *   polys32        k x n 32-byte little-endian coefficient images, polynomial g at [g n, (g + 1) n).  An image >= r acts as its value mod r
+ *                  and is reported as mi355_bls_fr_ntt_many reports it: status[g] bit 1 (value 2), and the return value counts such g.
+ *   out96          k x n canonical affine images; image g n + l is pi_l of polynomial g; all zero: infinity.
+ *   status         k bytes, or NULL.
+ *   MI355_BLS_FK20_BITREV   the proofs in bit-reversed order (slot l holds pi_rev_m(l)), MI355_BLS_P1S_NTT_BITREV's meaning: no permutation
+ *                  is made.
+ *   MI355_BLS_FK20_H        write h_0 .. h_(n-1) in natural order instead of the proofs, stopping before the last transform: for the caller
+ *                  who wants the proofs on a larger domain (transform h there).  MI355_BLS_FK20_BITREV changes nothing beside it.
+ * Returns the number of polynomials with status bit 1; k == 0: 0, nothing touched.  n == 1 is legal: every output is infinity.
+ * MI355_BLS_ERR_ARG, before anything is launched: a NULL context (before the k == 0 rule), a NULL setup, polynomials, output or (create)
+ * srs96 / handle pointer, n == 0, n that is no power of two or above 2^31 (the transform of 2n points must fit mi355_bls_p1s_ntt_many's
+ * bound), an unknown flag bit, a setup of another device, a misaligned device pointer (4-byte aligned), a busy context.  Nothing is refused
+ * for its size: k beyond one pass runs as passes of whole polynomials, and one polynomial always forms a pass (csrc/plan.hpp fk20_sizes_for:
+ * 448 n bytes of the library's workspace per polynomial of a pass, 256 MiB per pass, not tuned).  The _device forms enqueue on `stream`;
+ * open_all waits for it once per pass (the status words), create once at the end.
+ * The route (csrc/fk20.hpp): the coefficients laid out as a circulant's first column and scaled by 1 / (2n), one Fr transform of length 2n,
+ * a scalar multiplication per element of the setup, the inverse point transform of length 2n and the forward one of length n with no affine
+ * image in between: 2m + 2 dependent 255-bit multiplications deep, whatever k.
+ * VARIABLE TIME: public polynomials only.
+ * COST: profiles/fk20_bench.json (nim-blscurve_amd/tools/bench_fk20.py), reported row by row in README.md.
+ * debug_fk20_set_pass: TEST HOOK, the polynomials per pass of the following fk20_open_all_many calls on this context (0: the plan's own; it
+ * can only shorten a pass). */
+#define MI355_BLS_FK20_BITREV 2u
+#define MI355_BLS_FK20_H 4u
+typedef struct mi355_bls_fk20_setup mi355_bls_fk20_setup;
+size_t mi355_bls_fk20_setup_sizeof(size_t n);
+int mi355_bls_fk20_setup_create(mi355_bls_ctx* ctx, mi355_bls_fk20_setup** out, const void* srs96, size_t n);
+int mi355_bls_fk20_setup_create_device(mi355_bls_ctx* ctx, mi355_bls_fk20_setup** out, const void* d_srs96, size_t n, void* stream);
+void mi355_bls_fk20_setup_destroy(mi355_bls_fk20_setup* setup);
+int mi355_bls_fk20_open_all_many(mi355_bls_ctx* ctx, const mi355_bls_fk20_setup* setup, const void* polys32, size_t k, uint32_t flags, void* out96, uint8_t* status);
+int mi355_bls_fk20_open_all_many_device(mi355_bls_ctx* ctx, const mi355_bls_fk20_setup* setup, const void* d_polys32, size_t k, uint32_t flags, void* d_out96,
+                                        uint8_t* status, void* stream);
+int mi355_bls_debug_fk20_set_pass(mi355_bls_ctx* ctx, size_t polys_per_pass);
+
 /* Fixed-base G1 MSM over a precomputed window table: blst_p1s_mult_wbits_precompute(_sizeof) and blst_p1s_mult_wbits (blst_abi.nim:327-335)
  * for callers whose point set does not change - k commitments over one SRS or Lagrange table.  A table is a library-owned handle that keeps, in
  * device memory, the rows [2^(w wbits)] P_i for w = 0 .. W - 1, W = ceil((nbits + 1) / wbits), W x npoints x 128 bytes

@@ -188,6 +188,15 @@ def lib():
         L.mi355_bls_p1s_ntt_many.argtypes = [vp, vp, sz, sz, u32, vp]
         L.mi355_bls_p1s_ntt_many_device.argtypes = [vp, vp, sz, sz, u32, vp, vp]
         L.mi355_bls_debug_p1ntt_set_pass.argtypes = [vp, sz]
+        L.mi355_bls_fk20_setup_sizeof.argtypes = [sz]
+        L.mi355_bls_fk20_setup_sizeof.restype = sz
+        L.mi355_bls_fk20_setup_create.argtypes = [vp, vp, vp, sz]
+        L.mi355_bls_fk20_setup_create_device.argtypes = [vp, vp, vp, sz, vp]
+        L.mi355_bls_fk20_setup_destroy.argtypes = [vp]
+        L.mi355_bls_fk20_setup_destroy.restype = None
+        L.mi355_bls_fk20_open_all_many.argtypes = [vp, vp, vp, sz, u32, vp, vp]
+        L.mi355_bls_fk20_open_all_many_device.argtypes = [vp, vp, vp, sz, u32, vp, vp, vp]
+        L.mi355_bls_debug_fk20_set_pass.argtypes = [vp, sz]
         L.mi355_bls_p1s_table_sizeof.argtypes = [sz, sz, sz]
         L.mi355_bls_p1s_table_sizeof.restype = sz
         L.mi355_bls_p1s_table_create.argtypes = [vp, vp, vp, sz, sz, sz]
@@ -1683,6 +1692,98 @@ def p1sNttMany_device(cache, d_in, n, k, flags=0, d_out=None, stream=0):
 def debug_p1ntt_set_pass(cache, vectors_per_pass=0):
     """TEST HOOK (mi355_bls_debug_p1ntt_set_pass): the vectors per slice of the following p1sNttMany calls on this context; 0: the plan's own."""
     _check(lib().mi355_bls_debug_p1ntt_set_pass(cache._h, int(vectors_per_pass)))
+
+
+FK20_BITREV = 2                        # flags of fk20OpenAllMany: the proofs in bit-reversed order (P1S_NTT_BITREV's meaning)
+FK20_H = 4                             # h_0 .. h_(n-1) instead of the proofs, stopping before the last transform
+
+
+class Fk20Setup:
+    """The setup of the all-openings call (mi355_bls_fk20_setup_create): the handle and its n.  It outlives the cache that made it and serves
+    any cache of the same device; fk20_setup_destroy (or destroy()) releases it."""
+
+    def __init__(self, handle, n):
+        self._h, self.n = handle, n
+
+    def destroy(self):
+        if self._h:
+            lib().mi355_bls_fk20_setup_destroy(self._h)
+            self._h = None
+
+
+def fk20_setup_sizeof(n):
+    """device bytes a setup of n points takes (2n x 96); 0 for an n that fk20_setup_create refuses"""
+    return lib().mi355_bls_fk20_setup_sizeof(n)
+
+
+def fk20_setup_create(cache, srs):
+    """srs: n = 2^m 96-byte blst_p1_affine images S_j ([tau^j]G for a KZG setup; all zero: infinity; in G1, not checked) -> Fk20Setup"""
+    srs = bytes(srs)
+    if len(srs) % 96:
+        raise ValueError("srs: n x 96 bytes")
+    h = ctypes.c_void_p()
+    _check(lib().mi355_bls_fk20_setup_create(cache._h, ctypes.byref(h), srs, len(srs) // 96))
+    return Fk20Setup(h, len(srs) // 96)
+
+
+def fk20_setup_create_device(cache, d_srs, n, stream=0):
+    """the same with the points in device memory (a pointer as an integer)"""
+    h = ctypes.c_void_p()
+    _check(lib().mi355_bls_fk20_setup_create_device(cache._h, ctypes.byref(h), d_srs, n, stream))
+    return Fk20Setup(h, n)
+
+
+def fk20_setup_destroy(setup):
+    """releases a setup; None: no-op, like mi355_bls_fk20_setup_destroy(NULL)"""
+    if setup is None:
+        lib().mi355_bls_fk20_setup_destroy(None)
+    else:
+        setup.destroy()
+
+
+def _fk20_flags(flags):
+    flags = int(flags)
+    if flags & ~(FK20_BITREV | FK20_H):
+        raise ValueError("flags: FK20_BITREV and FK20_H")
+    return flags
+
+
+def fk20OpenAllMany(cache, setup, polys, flags=0):
+    """The KZG proofs of k polynomials at EVERY n-th root of unity in one device pass (mi355_bls_fk20_open_all_many, the Feist-Khovratovich
+    route).  polys: k x n 32-byte little-endian coefficient images, n = setup.n; an image >= r acts as its value mod r.  For setup points S_j
+    the call gives h_t = sum_{i <= n-2-t} [c_(i+t+1)] S_i and pi_l = sum_t [omega_n^(l t)] h_t; for S_j = [tau^j]G, pi_l is the proof at
+    omega_n^l.  FK20_BITREV: slot l holds pi_rev(l); FK20_H: the h_t instead.  -> (polynomials with status bit 2, k x n canonical 96-byte
+    affine images, k status bytes: 2 an image was >= r).  VARIABLE TIME: public polynomials only."""
+    flags, n = _fk20_flags(flags), setup.n
+    polys = bytes(polys)
+    if len(polys) % (n * 32):
+        raise ValueError("polys: k x n x 32 bytes (%d for n = %d)" % (len(polys), n))
+    k = len(polys) // (n * 32)
+    if k == 0:
+        return 0, b"", b""
+    out, st = ctypes.create_string_buffer(k * n * 96), ctypes.create_string_buffer(k)
+    rc = _check(lib().mi355_bls_fk20_open_all_many(cache._h, setup._h, polys, k, flags, out, st))
+    return rc, out.raw, st.raw
+
+
+def fk20OpenAllMany_device(cache, setup, d_polys, k, d_out, flags=0, stream=0, want_status=True):
+    """The same with the polynomials (k x n x 32 bytes) and the output (k x n x 96 bytes) in device memory, raw pointers.  d_out is, as it
+    stands, a points argument of the pairing, MSM and lincomb calls.  -> (polynomials with status bit 2, status bytes or None)."""
+    flags, k = _fk20_flags(flags), int(k)
+    if k < 0:
+        raise ValueError("k is a count")
+    if k == 0:
+        return 0, b"" if want_status else None
+    if not d_polys or not d_out:
+        raise ValueError("polys and the output: device pointers")
+    st = ctypes.create_string_buffer(k) if want_status else None
+    rc = _check(lib().mi355_bls_fk20_open_all_many_device(cache._h, setup._h, d_polys, k, flags, d_out, st, stream))
+    return rc, st.raw if want_status else None
+
+
+def debug_fk20_set_pass(cache, polys_per_pass=0):
+    """TEST HOOK (mi355_bls_debug_fk20_set_pass): the polynomials per pass of the following fk20OpenAllMany calls on this context; 0: the plan's own."""
+    _check(lib().mi355_bls_debug_fk20_set_pass(cache._h, int(polys_per_pass)))
 
 
 def compressSignatures(cache, signatures):

@@ -53,6 +53,17 @@ struct mi355_bls_p1s_table {
     }
 };
 
+// The setup of the all-openings call (mi355_bls_fk20_setup_create): NTT_2n(s^) of csrc/fk20.hpp in device memory.  p1s_table's ownership:
+// it belongs to its caller, mi355_bls_fk20_setup_destroy releases it, on its own device.
+struct mi355_bls_fk20_setup {
+    int device = 0;
+    size_t n = 0;
+    dev_buf<uint32_t> x;                         // 2n canonical affine images (24 words each), slot s: entry rev_(m+1)(s) of the transform
+    ~mi355_bls_fk20_setup() {
+        if (x) (void)hipSetDevice(device);
+    }
+};
+
 // H: the handle; Destroy: what releases it
 template <class H, hipError_t (*Destroy)(H)>
 struct dev_handle {

@@ -217,6 +217,9 @@ struct mi355_bls_ctx {
     // staging of a slice's affine images
     dev_buf<uint32_t> d_p1n_tw, d_p1n_ws, d_p1n_io;
     size_t p1ntt_vecs = 0;           // mi355_bls_debug_p1ntt_set_pass: vectors per slice of the p1s_ntt_many calls; 0: the plan's own
+    // all openings (mi355_bls_fk20_open_all_many) run in the two transforms' buffers: scalars and staged coefficients in d_ntt_io, the two
+    // point twiddle tables in d_p1n_tw, the Jacobian workspace in d_p1n_ws, the host form's outputs in d_p1n_io
+    size_t fk20_polys = 0;           // mi355_bls_debug_fk20_set_pass: polynomials per pass of the fk20 calls; 0: the plan's own
     ptab_ws ptab;                    // MSMs over a fixed-base window table: made at the first such call
     // per-batch verdicts for many batches (mi355_bls_batch_verify_many_each): sized by the largest slice of a call; it runs in the per-set path's
     // pair store with the per-group path's tables, partials and step values (d_aggv_*) and combine_sets' G2 products and tables (grp, d_comb_*)
@@ -2836,6 +2839,147 @@ extern "C" int mi355_bls_p1s_ntt_many(mi355_bls_ctx* c, const void* points96, si
 extern "C" int mi355_bls_debug_p1ntt_set_pass(mi355_bls_ctx* c, size_t vectors_per_pass) {
     if (!c) return MI355_BLS_ERR_ARG;
     c->p1ntt_vecs = vectors_per_pass;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// All openings of k polynomials over the n-th roots of unity (mi355_bls_fk20_open_all_many): csrc/fk20.hpp's route.  The setup handle is one
+// p1ntt_run of 2n points (forward, BITREV, in place in the handle's memory).  A call makes its three twiddle tables once, then per pass of
+// whole polynomials (plan.hpp fk20_sizes_for): the layout (k_fk20_circ), the Fr transform's forward passes in place (k_frntt_pass<false>,
+// frntt_sizes_for's tile and stages for 2n), the pointwise product (k_fk20_pointwise), the m + 1 DIT stages of the inverse
+// (k_p1ntt_stage<true>), the m DIF stages of the forward (k_fk20_stage) unless MI355_BLS_FK20_H, and the finish (k_fk20_finish), all on the
+// caller's stream; then the pass's status words come back (its synchronisation).  h_polys / h_out: the host form, staged pass by pass.
+// -> the polynomials with FK20_ST_REDUCED set.
+// ------------------------------------------------------------------------------------------
+static_assert(plan::FK20_CIRC_RUN == FRNTT_RUN && plan::FK20_CIRC_LANES == FRNTT_LANES, "fk20_launch_for counts k_fk20_circ's lanes");
+extern "C" size_t mi355_bls_fk20_setup_sizeof(size_t n) { return plan::fk20_setup_bytes(n); }
+extern "C" void mi355_bls_fk20_setup_destroy(mi355_bls_fk20_setup* s) { delete s; }
+extern "C" int mi355_bls_fk20_setup_create_device(mi355_bls_ctx* c, mi355_bls_fk20_setup** out, const void* d_srs96, size_t n, void* stream) {
+    if (!c || !out || !d_srs96 || !plan::fk20_sizes_for(n, 1).ok || ((uintptr_t)d_srs96 & 3)) {
+        g_err = "fk20_setup_create: a NULL argument, n that is no power of two in 1 .. 2^31, or a misaligned device pointer";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    std::unique_ptr<mi355_bls_fk20_setup> s(new mi355_bls_fk20_setup());
+    s->device = c->device, s->n = n;
+    if (int rc = s->x.alloc(plan::fk20_setup_bytes(n))) return rc;
+    k_fk20_setup_layout<<<(unsigned)((2 * n + FRNTT_LANES - 1) / FRNTT_LANES), FRNTT_LANES, 0, st>>>(reinterpret_cast<const uint32_t*>(d_srs96), n, s->x);
+    HIPCHK(hipGetLastError());
+    if (int rc = p1ntt_run(c, reinterpret_cast<const uint8_t*>(s->x.p), nullptr, 2 * n, 1, MI355_BLS_P1S_NTT_BITREV, reinterpret_cast<uint8_t*>(s->x.p), nullptr, st)) return rc;
+    *out = s.release();
+    return 0;
+}
+// host array -> staging -> create_device on the null stream
+extern "C" int mi355_bls_fk20_setup_create(mi355_bls_ctx* c, mi355_bls_fk20_setup** out, const void* srs96, size_t n) {
+    if (!c || !out || !srs96 || !plan::fk20_sizes_for(n, 1).ok) {
+        g_err = "fk20_setup_create: a NULL argument, or n that is no power of two in 1 .. 2^31";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const uint8_t* d[1];
+    if (int rc = stage_inputs(c, {{srs96, n * 96}}, nullptr, d)) return rc;
+    return mi355_bls_fk20_setup_create_device(c, out, d[0], n, nullptr);
+}
+static int fk20_run(mi355_bls_ctx* c, const mi355_bls_fk20_setup* setup, const uint8_t* d_polys, const uint8_t* h_polys, size_t k, uint32_t flags, uint8_t* d_out,
+                    uint8_t* h_out, uint8_t* status, hipStream_t st) {
+    if (!setup || !(d_polys || h_polys) || !(d_out || h_out) || (flags & ~(uint32_t)(MI355_BLS_FK20_BITREV | MI355_BLS_FK20_H)) || setup->device != c->device) {
+        g_err = "fk20_open_all_many: a NULL setup, polynomials or output, a flag other than MI355_BLS_FK20_BITREV and MI355_BLS_FK20_H, or a setup of another device";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (((uintptr_t)d_polys | (uintptr_t)d_out) & 3) {
+        g_err = "fk20_open_all_many: polynomials and output must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const size_t n = setup->n;
+    const plan::fk20_sizes sz = plan::fk20_sizes_for(n, k, c->fk20_polys);
+    const plan::frntt_sizes fsz = plan::frntt_sizes_for(2 * n, sz.per_pass, c->frntt_tile, 0);
+    if (!sz.ok || !fsz.ok) return MI355_BLS_ERR_ARG;           // a handle holds no such n
+    HIPCHK(hipSetDevice(c->device));
+    const bool want_h = flags & MI355_BLS_FK20_H, host = h_out != nullptr;
+    const bool permute = !want_h && !(flags & MI355_BLS_FK20_BITREV);
+    const uint32_t m = sz.log2n, M = m + 1;
+    int rc = c->d_ntt_tw.reserve(sz.tw_fr, 0);
+    if (!rc) rc = c->d_ntt_st.reserve(sz.status, sz.status / 4);
+    if (!rc) rc = c->d_ntt_io.reserve(sz.scalars + (host ? sz.polys : 0), 0);
+    if (!rc) rc = c->d_p1n_tw.reserve(sz.tw_inv + sz.tw_fwd, 0);
+    if (!rc) rc = c->d_p1n_ws.reserve(sz.ws, 0);
+    if (!rc && host) rc = c->d_p1n_io.reserve(sz.out, 0);
+    if (rc) return rc;
+    uint32_t* const tw_inv = c->d_p1n_tw;
+    uint32_t* const tw_fwd = tw_inv + sz.tw_inv / 4;
+    uint32_t* const scal = c->d_ntt_io;
+    uint32_t* const staged = scal + sz.scalars / 4;
+    {
+        const fr w2n = frntt_omega(M);
+        const unsigned grid = (unsigned)(((n + FRNTT_RUN - 1) / FRNTT_RUN + FRNTT_LANES - 1) / FRNTT_LANES);
+        k_frntt_twiddle<<<grid, FRNTT_LANES, 0, st>>>(w2n, n, c->d_ntt_tw);
+        k_p1ntt_twiddle<<<grid, FRNTT_LANES, 0, st>>>(fr_inv(w2n), n, tw_inv);
+        if (n > 1) k_p1ntt_twiddle<<<(unsigned)(((n / 2 + FRNTT_RUN - 1) / FRNTT_RUN + FRNTT_LANES - 1) / FRNTT_LANES), FRNTT_LANES, 0, st>>>(frntt_omega(m), n / 2, tw_fwd);
+    }
+    const uint32_t n2w[8] = {(uint32_t)(2 * (uint64_t)n), (uint32_t)((2 * (uint64_t)n) >> 32), 0, 0, 0, 0, 0, 0};
+    const fr inv2n = fr_inv(fr_from_words(n2w));
+    std::vector<uint32_t> words(sz.per_pass);
+    int reduced = 0;
+    for (size_t p = 0; p < sz.passes; p++) {
+        size_t g0, kc;
+        plan::fk20_pass(sz, k, p, g0, kc);
+        const plan::fk20_launch l = plan::fk20_launch_for(sz, kc);
+        const uint32_t* src = host ? staged : reinterpret_cast<const uint32_t*>(d_polys + g0 * n * 32);
+        uint32_t* out = host ? c->d_p1n_io.p : reinterpret_cast<uint32_t*>(d_out + g0 * n * 96);
+        if (host) HIPCHK(hipMemcpyAsync(staged, h_polys + g0 * n * 32, kc * n * 32, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(c->d_ntt_st, 0, kc * 4, st));
+        k_fk20_circ<<<l.circ_grid, FRNTT_LANES, 0, st>>>(m, kc, inv2n, src, scal, c->d_ntt_st);
+        uint32_t done = 0;
+        for (uint32_t q = 0; q < fsz.passes; q++) {
+            const uint32_t tp = fsz.stages[q], sigma = M - done - tp;
+            const plan::frntt_shape sh = plan::frntt_geo_for(M, fsz.tile, sigma, tp, kc);
+            const frntt_geo g{M, sigma, tp, sh.clo, sh.chi, sh.L, kc};
+            if ((rc = frntt_launch_pass<false>(g, scal, false, c->d_ntt_tw, false, scal, c->d_ntt_st, st))) return rc;
+            done += tp;
+        }
+        k_fk20_pointwise<<<l.point_grid, WAVE, 0, st>>>((uint64_t)kc << M, ((uint64_t)1 << M) - 1, scal, setup->x, c->d_p1n_ws);
+        p1ntt_stage g{};
+        g.k = kc, g.m = M;
+        for (uint32_t b = 0; b < M; b++) {
+            g.b = b;
+            k_p1ntt_stage<true><<<l.inv_grid, WAVE, 0, st>>>(g, nullptr, c->d_p1n_ws, tw_inv);
+        }
+        g.m = m;
+        for (uint32_t s = 0; s < m && !want_h; s++) {
+            g.b = m - 1 - s;
+            k_fk20_stage<<<l.fwd_grid, WAVE, 0, st>>>(g, c->d_p1n_ws, tw_fwd);
+        }
+        k_fk20_finish<<<l.finish_grid, WAVE, 0, st>>>(c->d_p1n_ws, (uint64_t)kc << m, m, permute, l.run, out);
+        HIPCHK(hipGetLastError());
+        if (host) HIPCHK(hipMemcpyAsync(h_out + g0 * n * 96, out, kc * n * 96, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(words.data(), c->d_ntt_st, kc * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t v = 0; v < kc; v++) {
+            if (status) status[g0 + v] = (uint8_t)words[v];
+            reduced += (words[v] & FK20_ST_REDUCED) != 0;
+        }
+    }
+    return reduced;
+}
+extern "C" int mi355_bls_fk20_open_all_many_device(mi355_bls_ctx* c, const mi355_bls_fk20_setup* setup, const void* d_polys32, size_t k, uint32_t flags, void* d_out96,
+                                                   uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing computed, nothing written
+    return fk20_run(c, setup, (const uint8_t*)d_polys32, nullptr, k, flags, (uint8_t*)d_out96, nullptr, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_fk20_open_all_many(mi355_bls_ctx* c, const mi355_bls_fk20_setup* setup, const void* polys32, size_t k, uint32_t flags, void* out96,
+                                            uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    return fk20_run(c, setup, nullptr, (const uint8_t*)polys32, k, flags, nullptr, (uint8_t*)out96, status, nullptr);
+}
+// TEST HOOK: the polynomials per pass of the following fk20 calls on this context (0: the plan's own; it can only shorten a pass)
+extern "C" int mi355_bls_debug_fk20_set_pass(mi355_bls_ctx* c, size_t polys_per_pass) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    c->fk20_polys = polys_per_pass;
     return 0;
 }
 

@@ -47,6 +47,7 @@
 #include "fropen.hpp"
 #include "frntt.hpp"
 #include "p1ntt.hpp"
+#include "fk20.hpp"
 #include "keytable.hpp"
 #include "msmmany.hpp"
 #include "msmtable.hpp"
@@ -3352,6 +3353,52 @@ __global__ void __launch_bounds__(WAVE) k_p1ntt_finish(const uint32_t* src, bool
     p1ntt_finish_run<fp>(
         total, m, permute, run, (uint64_t)blockIdx.x * WAVE + threadIdx.x,
         [&](uint64_t e) { return src_aff ? jac_from_aff(ld_g1a_blst(src + (size_t)e * 24)) : ld_g1_int(src + (size_t)e * G1W); },
+        [&](uint64_t slot, const g1_aff& a) { st_aff_blst(out + (size_t)slot * 24, a); },
+        [&](uint64_t slot) {
+            for (uint32_t t = 0; t < 24; t++) out[(size_t)slot * 24 + t] = 0;
+        });
+}
+
+// ------------------------------------------------------------------------------------------
+// All openings of many polynomials (mi355_bls_fk20_open_all_many).  The route and the bodies are csrc/fk20.hpp's; the inverse transform of
+// length 2n runs k_p1ntt_stage<true> as it is.  ws: the pass's k x 2n internal Jacobian images.
+// ------------------------------------------------------------------------------------------
+// the setup's input: a lane per slot u < 2n of s^, the caller's image of S_(n-2-u) or the all-zero one
+__global__ void __launch_bounds__(FRNTT_LANES) k_fk20_setup_layout(const uint32_t* __restrict__ srs, uint64_t n, uint32_t* __restrict__ out) {
+    const uint64_t u = (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x;
+    if (u >= 2 * n) return;
+    uint64_t j;
+    const bool has = fk20_setup_src(n, u, j);
+    for (uint32_t t = 0; t < 24; t++) out[(size_t)u * 24 + t] = has ? srs[(size_t)j * 24 + t] : 0u;
+}
+// step 1's layout, a lane per run of FRNTT_RUN slots: b / (2n) for k polynomials into the Fr transform's array.  status: a word per
+// polynomial of the pass, cleared by the host call.
+__global__ void __launch_bounds__(FRNTT_LANES) k_fk20_circ(uint32_t m, uint64_t k, fr inv2n, const uint32_t* __restrict__ polys, uint32_t* __restrict__ dst,
+                                                            uint32_t* __restrict__ status) {
+    uint64_t vec;
+    if (fk20_circ_run(m, k, inv2n, (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x, polys, dst, vec)) atomicOr(&status[vec], FK20_ST_REDUCED);
+}
+// step 2, a lane per slot e < total = k x 2n: [v_e] X_(e mod 2n) into ws.  mask = 2n - 1; setup: the handle's 2n affine images.
+__global__ void __launch_bounds__(WAVE) k_fk20_pointwise(uint64_t total, uint64_t mask, const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ setup,
+                                                          uint32_t* __restrict__ ws) {
+    const uint64_t e = (uint64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (e >= total) return;
+    st_g1_int(ws + (size_t)e * G1W, fk20_pointwise<fp>(ld_g1a_blst(setup + (size_t)(e & mask) * 24), fropen_own(scalars, (size_t)e)));
+}
+// step 4: one DIF stage of the transform of length n = 2^g.m over the first halves of the k vectors of 2n elements in ws, k_p1ntt_stage's
+// lanes with fk20_at's places
+__global__ void __launch_bounds__(WAVE) k_fk20_stage(p1ntt_stage g, uint32_t* ws, const uint32_t* __restrict__ tw) {
+    const uint64_t lane = (uint64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (lane >= p1ntt_lanes(g)) return;
+    p1ntt_butterfly<false, fp>(
+        g, lane, [&](uint64_t e) { return ld_g1_int(ws + (size_t)fk20_at(g.m, e) * G1W); }, [&](uint64_t e, const g1_jac& a) { st_g1_int(ws + (size_t)fk20_at(g.m, e) * G1W, a); },
+        [&](uint64_t t) { return fropen_own(tw, (size_t)t); });
+}
+// the finish over the same places: element e < total = k n of the first halves to slot e of out, or with permute to the bit-reversed place
+// in its vector
+__global__ void __launch_bounds__(WAVE) k_fk20_finish(const uint32_t* ws, uint64_t total, uint32_t m, bool permute, uint32_t run, uint32_t* __restrict__ out) {
+    p1ntt_finish_run<fp>(
+        total, m, permute, run, (uint64_t)blockIdx.x * WAVE + threadIdx.x, [&](uint64_t e) { return ld_g1_int(ws + (size_t)fk20_at(m, e) * G1W); },
         [&](uint64_t slot, const g1_aff& a) { st_aff_blst(out + (size_t)slot * 24, a); },
         [&](uint64_t slot) {
             for (uint32_t t = 0; t < 24; t++) out[(size_t)slot * 24 + t] = 0;

@@ -1340,6 +1340,74 @@ inline p1ntt_launch p1ntt_launch_for(const p1ntt_sizes& s, size_t count) {
     return l;
 }
 
+// All openings of k polynomials of n = 2^m coefficients (mi355_bls_fk20_open_all_many; csrc/fk20.hpp): the call in PASSES of whole
+// polynomials, polynomials [first, first + count) each.
+//   FK20_PASS_BYTES     the workspace a pass may ask for, 256 MiB in all: per polynomial 2n internal Jacobian images (G1_WORDS x 4 = 192
+//                       bytes each) and 2n scalars (32 bytes each), 448 n bytes.  P1NTT_SLICE_BYTES' reasoning, and like it NOT TUNED.  One
+//                       polynomial always forms a pass, whatever its size: nothing is refused for its size.  The host form stages a pass's
+//                       n coefficient images and n affine outputs per polynomial beside it.
+//   forced              the test hook's polynomials per pass (mi355_bls_debug_fk20_set_pass; 0: the rule above; it can only shorten a pass).
+//   the launches        (fk20_launch_for) the layout: a lane per run of FRNTT_RUN slots of the count x 2n array, FRNTT_LANES per workgroup;
+//                       the pointwise product: a lane per slot; a stage of the inverse: count x n butterflies; a stage of the forward:
+//                       count x n / 2; the finish: to_affine_for's run over count x n elements.  One polynomial of 2^31 coefficients is
+//                       2^26 workgroups of WAVE lanes in the widest launch.
+// Refused (ok == false): n == 0, n that is no power of two or above 2^31 - the transform of 2n points must fit p1ntt_sizes_for's bound.
+constexpr size_t FK20_PASS_BYTES = (size_t)256 << 20;
+constexpr size_t FK20_POLY_BYTES_PER_COEFF = 2 * (G1_WORDS * 4 + 32);
+constexpr uint32_t FK20_CIRC_RUN = 16, FK20_CIRC_LANES = 256;            // frntt.hpp's FRNTT_RUN and FRNTT_LANES (asserted where both are seen)
+struct fk20_sizes {
+    bool ok;
+    uint32_t log2n;                          // n = 2^log2n
+    size_t per_pass, passes;                 // polynomials per pass (the last one may hold fewer), passes of the call
+    size_t ws, scalars;                      // bytes: a pass's 2n Jacobian images and 2n scalars per polynomial
+    size_t polys, out, status;               // bytes: a pass's coefficient images, its affine outputs, a status word per polynomial
+    size_t tw_fr, tw_inv, tw_fwd;            // bytes: the tables of omega_2n (n entries), 1 / omega_2n (n entries) and omega_n (n / 2 entries)
+};
+inline fk20_sizes fk20_sizes_for(size_t n, size_t k, size_t forced = 0) {
+    fk20_sizes s{};
+    if (n == 0 || (n & (n - 1)) || n > ((size_t)1 << 31)) return s;
+    while (((size_t)1 << s.log2n) < n) s.log2n++;
+    size_t per = FK20_PASS_BYTES / (n * FK20_POLY_BYTES_PER_COEFF);
+    if (per == 0) per = 1;
+    if (forced && forced < per) per = forced;
+    if (per > k && k) per = k;
+    s.ok = true;
+    s.per_pass = per;
+    s.passes = (k + per - 1) / per;
+    s.ws = per * 2 * n * G1_WORDS * 4;
+    s.scalars = per * 2 * n * 32;
+    s.polys = per * n * 32;
+    s.out = per * n * 96;
+    s.status = per * 4;
+    s.tw_fr = n * 32;
+    s.tw_inv = n * 32;
+    s.tw_fwd = n / 2 * 32;
+    return s;
+}
+// pass p of the call: polynomials [first, first + count)
+inline void fk20_pass(const fk20_sizes& s, size_t k, size_t p, size_t& first, size_t& count) {
+    first = p * s.per_pass;
+    count = k - first < s.per_pass ? k - first : s.per_pass;
+}
+// the bytes of a setup handle's device memory: NTT_2n(s^) as 2n affine images; 0 where n is refused
+inline size_t fk20_setup_bytes(size_t n) { return fk20_sizes_for(n, 1).ok ? 2 * n * 96 : 0; }
+// the launches of a pass of `count` polynomials
+struct fk20_launch {
+    uint32_t circ_grid, point_grid, inv_grid, fwd_grid, run, finish_grid;
+};
+inline fk20_launch fk20_launch_for(const fk20_sizes& s, size_t count) {
+    fk20_launch l{};
+    const uint64_t half = (uint64_t)count << s.log2n, total = half << 1;
+    const uint64_t runs_per_poly = ((total / count) + FK20_CIRC_RUN - 1) / FK20_CIRC_RUN;
+    l.circ_grid = (uint32_t)((count * runs_per_poly + FK20_CIRC_LANES - 1) / FK20_CIRC_LANES);
+    l.point_grid = (uint32_t)((total + WAVE - 1) / WAVE);
+    l.inv_grid = (uint32_t)((half + WAVE - 1) / WAVE);
+    l.fwd_grid = (uint32_t)((half / 2 + WAVE - 1) / WAVE);
+    l.run = to_affine_for((size_t)half).run;
+    l.finish_grid = (uint32_t)(((half + l.run - 1) / l.run + WAVE - 1) / WAVE);
+    return l;
+}
+
 // ------------------------------------------------------------------------------------------
 // Fixed-base G1 MSM over a precomputed window table (mi355_bls_p1s_table_* / mi355_bls_p1s_mult_table*): what ptab_run follows and reserves.
 // The table holds, for point i and window w, the affine row T[w][i] = [2^(w wbits)] P_i at entry w x npoints + i (k_pip_convert's record).
