@@ -913,6 +913,51 @@ int mi355_bls_fk20_open_all_many_device(mi355_bls_ctx* ctx, const mi355_bls_fk20
                                         uint8_t* status, void* stream);
 int mi355_bls_debug_fk20_set_pass(mi355_bls_ctx* ctx, size_t polys_per_pass);
 
+/* The proofs of ALL CELLS of each of k polynomials in one device pass (the Feist-Khovratovich route over cosets): a cell is a coset of
+ * l = `cell` evaluation points of a domain that may be larger than the polynomial - PeerDAS: n = 4 096 coefficients, cell = 64, ext_log2 = 1,
+ * 128 cells on the domain of 8 192.  One proof per cell where the definition route divides by X^l - a on the host and runs an MSM of about n
+ * points per cell.
+ *   DEFINITION, for ANY G1 points S_0 .. S_(n-1), n = 2^m, 0 <= m <= 31, coefficients c_0 .. c_(n-1), l = 2^c with 1 <= l <= n, q = n / l,
+ *   N = q 2^ext_log2 cells with n 2^ext_log2 <= 2^32, and mi355_bls_fr_ntt_many's omega_N:
+ *       h_s  = sum_{i=0}^{n-1-l(s+1)} [c_(i + l(s+1))] S_i     s = 0 .. q-2,   h_(q-1) = infinity
+ *       pi_j = sum_{s=0}^{q-1} [omega_N^(j s)] h_s              j = 0 .. N-1
+ *   For an SRS S_i = [tau^i]G, pi_j is the commitment to the polynomial quotient p(X) div (X^l - omega_N^j): the KZG multi-proof for the
+ *   coset {x : x^l = omega_N^j} = {omega_(l N)^(j + N u), u < l} of the domain of n 2^ext_log2 points.  cell == 1 and ext_log2 == 0 is
+ *   mi355_bls_fk20_open_all_many's definition, and the outputs are the same bytes.
+ *   THE SETUP is the same handle type, made by mi355_bls_fk20_setup_create_cells for ONE cell size: the l transforms of length 2q of the
+ *   reversed, zero-extended sub-setups S_(l u + v), 2n x 96 bytes as before (mi355_bls_fk20_setup_sizeof), the l images of a slot adjacent.
+ *   Creating a handle with cell > 1 takes a second 2n x 96 bytes of device memory, released before create returns: twice the handle at peak.
+ *   cell == 1 gives mi355_bls_fk20_setup_create's handle, byte for byte.  Ownership, device, lifetime and destroy are unchanged.  A handle
+ *   made with cell > 1 serves mi355_bls_fk20_open_cells_many only: mi355_bls_fk20_open_all_many refuses it.  The points must be in G1, which
+ *   is NOT checked.
+ *   polys32        k x n 32-byte little-endian coefficient images; an image >= r acts as its value mod r: status[g] bit 1 (value 2), and
+ *                  the return value counts such g, as in mi355_bls_fk20_open_all_many.
+ *   out96          k x N canonical affine images; image g N + j is pi_j of polynomial g; all zero: infinity.
+ *   MI355_BLS_FK20_BITREV   slot j holds pi_rev(j), rev over log2 N bits; no permutation is made.  For n = 4 096, cell = 64, ext_log2 = 1 this
+ *                  is PeerDAS' cell order: cell i of the bit-reversed extended evaluation is the coset x^64 = omega_128^rev7(i).
+ *   MI355_BLS_FK20_H        out96 is k x q images h_0 .. h_(q-1) in natural order, stopping before the last transform; ext_log2 is still
+ *                  validated.  MI355_BLS_FK20_BITREV changes nothing beside it.
+ * Returns the number of polynomials with status bit 1; k == 0: 0, nothing touched.  cell == n is legal (q = 1: every output is infinity), and
+ * so is n == 1.
+ * MI355_BLS_ERR_ARG, before anything is launched: what mi355_bls_fk20_open_all_many refuses (a NULL context before the k == 0 rule, a NULL
+ * setup, polynomials, output or (create) srs96 / handle pointer, n == 0, n that is no power of two or above 2^31, an unknown flag bit, a
+ * setup of another device, a misaligned device pointer, a busy context); (create) a cell that is 0, no power of two or above n; ext_log2
+ * with n 2^ext_log2 > 2^32.  Nothing is refused for its size: passes of whole polynomials under the same bound (csrc/plan.hpp
+ * fk20_cells_sizes_for: 448 n + 192 max(2q, N) bytes of the library's workspace per polynomial), one polynomial always forms a pass, and
+ * mi355_bls_debug_fk20_set_pass shortens these passes too.  The _device forms enqueue on `stream`; open_cells waits for it once per pass,
+ * create at the end.
+ * The route (csrc/fk20cells.hpp): l Fr transforms of length 2q per polynomial, a scalar multiplication per element of the setup (2n), an
+ * l-fold sum per slot, ONE inverse point transform of length 2q and the forward one of length N: log2(2q) + log2 N + 1 dependent 255-bit
+ * multiplications deep, whatever k and l.
+ * VARIABLE TIME: public polynomials only.
+ * COST: profiles/fk20_cells_bench.json (nim-blscurve_amd/tools/bench_fk20_cells.py), reported row by row in README.md. */
+int mi355_bls_fk20_setup_create_cells(mi355_bls_ctx* ctx, mi355_bls_fk20_setup** out, const void* srs96, size_t n, size_t cell);
+int mi355_bls_fk20_setup_create_cells_device(mi355_bls_ctx* ctx, mi355_bls_fk20_setup** out, const void* d_srs96, size_t n, size_t cell, void* stream);
+int mi355_bls_fk20_open_cells_many(mi355_bls_ctx* ctx, const mi355_bls_fk20_setup* setup, const void* polys32, size_t k, size_t ext_log2, uint32_t flags, void* out96,
+                                   uint8_t* status);
+int mi355_bls_fk20_open_cells_many_device(mi355_bls_ctx* ctx, const mi355_bls_fk20_setup* setup, const void* d_polys32, size_t k, size_t ext_log2, uint32_t flags,
+                                          void* d_out96, uint8_t* status, void* stream);
+
 /* Fixed-base G1 MSM over a precomputed window table: blst_p1s_mult_wbits_precompute(_sizeof) and blst_p1s_mult_wbits (blst_abi.nim:327-335)
  * for callers whose point set does not change - k commitments over one SRS or Lagrange table.  A table is a library-owned handle that keeps, in
  * device memory, the rows [2^(w wbits)] P_i for w = 0 .. W - 1, W = ceil((nbits + 1) / wbits), W x npoints x 128 bytes

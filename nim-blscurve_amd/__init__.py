@@ -197,6 +197,10 @@ def lib():
         L.mi355_bls_fk20_open_all_many.argtypes = [vp, vp, vp, sz, u32, vp, vp]
         L.mi355_bls_fk20_open_all_many_device.argtypes = [vp, vp, vp, sz, u32, vp, vp, vp]
         L.mi355_bls_debug_fk20_set_pass.argtypes = [vp, sz]
+        L.mi355_bls_fk20_setup_create_cells.argtypes = [vp, vp, vp, sz, sz]
+        L.mi355_bls_fk20_setup_create_cells_device.argtypes = [vp, vp, vp, sz, sz, vp]
+        L.mi355_bls_fk20_open_cells_many.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp]
+        L.mi355_bls_fk20_open_cells_many_device.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp]
         L.mi355_bls_p1s_table_sizeof.argtypes = [sz, sz, sz]
         L.mi355_bls_p1s_table_sizeof.restype = sz
         L.mi355_bls_p1s_table_create.argtypes = [vp, vp, vp, sz, sz, sz]
@@ -1702,8 +1706,8 @@ class Fk20Setup:
     """The setup of the all-openings call (mi355_bls_fk20_setup_create): the handle and its n.  It outlives the cache that made it and serves
     any cache of the same device; fk20_setup_destroy (or destroy()) releases it."""
 
-    def __init__(self, handle, n):
-        self._h, self.n = handle, n
+    def __init__(self, handle, n, cell=1):
+        self._h, self.n, self.cell = handle, n, cell
 
     def destroy(self):
         if self._h:
@@ -1784,6 +1788,69 @@ def fk20OpenAllMany_device(cache, setup, d_polys, k, d_out, flags=0, stream=0, w
 def debug_fk20_set_pass(cache, polys_per_pass=0):
     """TEST HOOK (mi355_bls_debug_fk20_set_pass): the polynomials per pass of the following fk20OpenAllMany calls on this context; 0: the plan's own."""
     _check(lib().mi355_bls_debug_fk20_set_pass(cache._h, int(polys_per_pass)))
+
+
+def fk20_setup_create_cells(cache, srs, cell):
+    """The setup of fk20OpenCellsMany for cells of `cell` = 2^c points (mi355_bls_fk20_setup_create_cells).  srs: n = 2^m 96-byte
+    blst_p1_affine images S_i, 1 <= cell <= n; cell == 1 is fk20_setup_create.  -> Fk20Setup; with cell > 1 it serves fk20OpenCellsMany only."""
+    srs = bytes(srs)
+    if len(srs) % 96:
+        raise ValueError("srs: n x 96 bytes")
+    h = ctypes.c_void_p()
+    _check(lib().mi355_bls_fk20_setup_create_cells(cache._h, ctypes.byref(h), srs, len(srs) // 96, int(cell)))
+    return Fk20Setup(h, len(srs) // 96, int(cell))
+
+
+def fk20_setup_create_cells_device(cache, d_srs, n, cell, stream=0):
+    """the same with the points in device memory (a pointer as an integer)"""
+    h = ctypes.c_void_p()
+    _check(lib().mi355_bls_fk20_setup_create_cells_device(cache._h, ctypes.byref(h), d_srs, n, int(cell), stream))
+    return Fk20Setup(h, n, int(cell))
+
+
+def fk20_cells_rows(setup, ext_log2, flags=0):
+    """the images one polynomial gives: N = (n / cell) 2^ext_log2 proofs, or n / cell with FK20_H"""
+    q = setup.n // setup.cell
+    return q if flags & FK20_H else q << int(ext_log2)
+
+
+def fk20OpenCellsMany(cache, setup, polys, ext_log2=0, flags=0):
+    """The KZG proofs of ALL cells of k polynomials in one device pass (mi355_bls_fk20_open_cells_many, the Feist-Khovratovich route over
+    cosets).  setup: fk20_setup_create_cells' handle for cells of l = setup.cell points; q = n / l, N = q 2^ext_log2 cells.  polys: k x n
+    32-byte little-endian coefficient images; an image >= r acts as its value mod r.  For setup points S_i the call gives
+    h_s = sum_{i <= n-1-l(s+1)} [c_(i + l(s+1))] S_i and pi_j = sum_s [omega_N^(j s)] h_s; for S_i = [tau^i]G, pi_j commits to
+    p(X) div (X^l - omega_N^j), the multi-proof of the coset x^l = omega_N^j.  FK20_BITREV: slot j holds pi_rev(j) (n = 4096, l = 64,
+    ext_log2 = 1: PeerDAS' cell order); FK20_H: the q images h_s instead.  -> (polynomials with status bit 2, k x N (or k x q) canonical
+    96-byte affine images, k status bytes: 2 an image was >= r).  VARIABLE TIME: public polynomials only."""
+    flags, n, ext_log2 = _fk20_flags(flags), setup.n, int(ext_log2)
+    if ext_log2 < 0:
+        raise ValueError("ext_log2 is a count")
+    polys = bytes(polys)
+    if len(polys) % (n * 32):
+        raise ValueError("polys: k x n x 32 bytes (%d for n = %d)" % (len(polys), n))
+    k = len(polys) // (n * 32)
+    if k == 0:
+        return 0, b"", b""
+    if (n << ext_log2) > 1 << 32:
+        raise ValueError("ext_log2: n 2^ext_log2 <= 2^32")
+    out, st = ctypes.create_string_buffer(k * fk20_cells_rows(setup, ext_log2, flags) * 96), ctypes.create_string_buffer(k)
+    rc = _check(lib().mi355_bls_fk20_open_cells_many(cache._h, setup._h, polys, k, ext_log2, flags, out, st))
+    return rc, out.raw, st.raw
+
+
+def fk20OpenCellsMany_device(cache, setup, d_polys, k, d_out, ext_log2=0, flags=0, stream=0, want_status=True):
+    """The same with the polynomials (k x n x 32 bytes) and the output (k x fk20_cells_rows x 96 bytes) in device memory, raw pointers.
+    -> (polynomials with status bit 2, status bytes or None)."""
+    flags, k, ext_log2 = _fk20_flags(flags), int(k), int(ext_log2)
+    if k < 0 or ext_log2 < 0:
+        raise ValueError("k and ext_log2 are counts")
+    if k == 0:
+        return 0, b"" if want_status else None
+    if not d_polys or not d_out:
+        raise ValueError("polys and the output: device pointers")
+    st = ctypes.create_string_buffer(k) if want_status else None
+    rc = _check(lib().mi355_bls_fk20_open_cells_many_device(cache._h, setup._h, d_polys, k, ext_log2, flags, d_out, st, stream))
+    return rc, st.raw if want_status else None
 
 
 def compressSignatures(cache, signatures):

@@ -58,7 +58,9 @@ struct mi355_bls_p1s_table {
 struct mi355_bls_fk20_setup {
     int device = 0;
     size_t n = 0;
-    dev_buf<uint32_t> x;                         // 2n canonical affine images (24 words each), slot s: entry rev_(m+1)(s) of the transform
+    size_t cell = 1;                             // the cell size l the handle was made for (mi355_bls_fk20_setup_create_cells); 1: all openings
+    dev_buf<uint32_t> x;                         // 2n canonical affine images (24 words each), slot s: entry rev_(m+1)(s) of the transform;
+                                                 // cell > 1: image slot l + v is entry rev(slot) of NTT_2q(s^(v)) (csrc/fk20cells.hpp)
     ~mi355_bls_fk20_setup() {
         if (x) (void)hipSetDevice(device);
     }

@@ -2892,6 +2892,10 @@ static int fk20_run(mi355_bls_ctx* c, const mi355_bls_fk20_setup* setup, const u
         g_err = "fk20_open_all_many: polynomials and output must be 4-byte aligned";
         return MI355_BLS_ERR_ARG;
     }
+    if (setup->cell != 1) {
+        g_err = "fk20_open_all_many: the setup was made for cells (mi355_bls_fk20_setup_create_cells with cell > 1)";
+        return MI355_BLS_ERR_ARG;
+    }
     if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
     const size_t n = setup->n;
     const plan::fk20_sizes sz = plan::fk20_sizes_for(n, k, c->fk20_polys);
@@ -2976,7 +2980,174 @@ extern "C" int mi355_bls_fk20_open_all_many(mi355_bls_ctx* c, const mi355_bls_fk
     if (k == 0) return 0;
     return fk20_run(c, setup, nullptr, (const uint8_t*)polys32, k, flags, nullptr, (uint8_t*)out96, status, nullptr);
 }
-// TEST HOOK: the polynomials per pass of the following fk20 calls on this context (0: the plan's own; it can only shorten a pass)
+// ------------------------------------------------------------------------------------------
+// The proofs of all cells of k polynomials (mi355_bls_fk20_open_cells_many): csrc/fk20cells.hpp's route.  The setup handle for cells of l
+// points: the l vectors s^(v) laid out one after the other in the point transform's staging (k_fk20c_setup_layout), one p1ntt_run of l
+// vectors of 2q points (forward, BITREV, in place), and k_fk20c_setup_place into the handle; l == 1 is fk20_setup_create's own path.  A
+// call makes its three twiddle tables once, then per pass of whole polynomials (plan.hpp fk20_cells_sizes_for): the layout (k_fk20c_circ),
+// the Fr transform's forward passes of 2q over count x l vectors in place, the products (k_fk20c_pointwise), the levels of the sum
+// (k_fk20c_sum), the inverse's stages (k_p1ntt_stage<true> where a vector is 2q images wide, k_fk20c_stage<true> where it is wider), and
+// unless MI355_BLS_FK20_H the padding (k_fk20c_pad) and the forward's stages (k_fk20c_stage<false>); then the finish (k_fk20c_finish), all
+// on the caller's stream; then the pass's status words come back (its synchronisation).  -> the polynomials with FK20_ST_REDUCED set.
+// ------------------------------------------------------------------------------------------
+static_assert(plan::FK20_CELLS_FAN_LOG2 == FK20C_FAN_LOG2, "fk20_cells_sum_lanes counts k_fk20c_sum's lanes");
+extern "C" int mi355_bls_fk20_setup_create_cells_device(mi355_bls_ctx* c, mi355_bls_fk20_setup** out, const void* d_srs96, size_t n, size_t cell, void* stream) {
+    const plan::fk20_cells_sizes sz = plan::fk20_cells_sizes_for(n, cell, 0, 1);
+    if (!c || !out || !d_srs96 || !sz.ok || ((uintptr_t)d_srs96 & 3)) {
+        g_err = "fk20_setup_create_cells: a NULL argument, n that is no power of two in 1 .. 2^31, a cell that is no power of two in 1 .. n, or a misaligned device pointer";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (cell == 1) return mi355_bls_fk20_setup_create_device(c, out, d_srs96, n, stream);
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    std::unique_ptr<mi355_bls_fk20_setup> s(new mi355_bls_fk20_setup());
+    s->device = c->device, s->n = n, s->cell = cell;
+    if (int rc = s->x.alloc(plan::fk20_setup_bytes(n))) return rc;
+    dev_buf<uint32_t> tmp;                               // the l vectors before and after the transform, a second 2n x 96 bytes until create
+                                                         // returns; p1ntt_run waits for the stream
+    if (int rc = tmp.alloc(plan::fk20_setup_bytes(n))) return rc;
+    const unsigned grid = (unsigned)((2 * n + FRNTT_LANES - 1) / FRNTT_LANES);
+    k_fk20c_setup_layout<<<grid, FRNTT_LANES, 0, st>>>(reinterpret_cast<const uint32_t*>(d_srs96), 2 * (uint64_t)n, sz.log2q, sz.log2cell, tmp);
+    HIPCHK(hipGetLastError());
+    if (int rc = p1ntt_run(c, reinterpret_cast<const uint8_t*>(tmp.p), nullptr, 2 * (n / cell), cell, MI355_BLS_P1S_NTT_BITREV, reinterpret_cast<uint8_t*>(tmp.p), nullptr, st)) return rc;
+    k_fk20c_setup_place<<<grid, FRNTT_LANES, 0, st>>>(tmp, 2 * (uint64_t)n, sz.log2q, sz.log2cell, s->x);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    *out = s.release();
+    return 0;
+}
+// host array -> staging -> create_cells_device on the null stream
+extern "C" int mi355_bls_fk20_setup_create_cells(mi355_bls_ctx* c, mi355_bls_fk20_setup** out, const void* srs96, size_t n, size_t cell) {
+    if (!c || !out || !srs96 || !plan::fk20_cells_sizes_for(n, cell, 0, 1).ok) {
+        g_err = "fk20_setup_create_cells: a NULL argument, n that is no power of two in 1 .. 2^31, or a cell that is no power of two in 1 .. n";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const uint8_t* d[1];
+    if (int rc = stage_inputs(c, {{srs96, n * 96}}, nullptr, d)) return rc;
+    return mi355_bls_fk20_setup_create_cells_device(c, out, d[0], n, cell, nullptr);
+}
+static int fk20_cells_run(mi355_bls_ctx* c, const mi355_bls_fk20_setup* setup, const uint8_t* d_polys, const uint8_t* h_polys, size_t k, size_t ext_log2, uint32_t flags,
+                          uint8_t* d_out, uint8_t* h_out, uint8_t* status, hipStream_t st) {
+    if (!setup || !(d_polys || h_polys) || !(d_out || h_out) || (flags & ~(uint32_t)(MI355_BLS_FK20_BITREV | MI355_BLS_FK20_H)) || setup->device != c->device) {
+        g_err = "fk20_open_cells_many: a NULL setup, polynomials or output, a flag other than MI355_BLS_FK20_BITREV and MI355_BLS_FK20_H, or a setup of another device";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (((uintptr_t)d_polys | (uintptr_t)d_out) & 3) {
+        g_err = "fk20_open_cells_many: polynomials and output must be 4-byte aligned";
+        return MI355_BLS_ERR_ARG;
+    }
+    const size_t n = setup->n;
+    const plan::fk20_cells_sizes sz = plan::fk20_cells_sizes_for(n, setup->cell, ext_log2, k, c->fk20_polys);
+    if (!sz.ok) {
+        g_err = "fk20_open_cells_many: ext_log2 with n 2^ext_log2 above 2^32";
+        return MI355_BLS_ERR_ARG;
+    }
+    if (ctx_busy(c)) return MI355_BLS_ERR_ARG;
+    const uint32_t mq = sz.log2q, cl = sz.log2cell, M = mq + 1, a = sz.log2cells, w = sz.log2w;
+    const size_t q = (size_t)1 << mq, cells = (size_t)1 << a;
+    const plan::frntt_sizes fsz = plan::frntt_sizes_for(2 * q, sz.per_pass << cl, c->frntt_tile, 0);
+    if (!fsz.ok) {                                               // a handle holds no such n
+        g_err = "fk20_open_cells_many: the Fr transform refuses the length 2n / cell";
+        return MI355_BLS_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const bool want_h = flags & MI355_BLS_FK20_H, host = h_out != nullptr;
+    const bool permute = !want_h && !(flags & MI355_BLS_FK20_BITREV);
+    const size_t rows = want_h ? q : cells;                      // the images a polynomial gives
+    int rc = c->d_ntt_tw.reserve(sz.tw_fr, 0);
+    if (!rc) rc = c->d_ntt_st.reserve(sz.status, sz.status / 4);
+    if (!rc) rc = c->d_ntt_io.reserve(sz.scalars + (host ? sz.polys : 0), 0);
+    if (!rc) rc = c->d_p1n_tw.reserve(sz.tw_inv + sz.tw_fwd, 0);
+    if (!rc) rc = c->d_p1n_ws.reserve(sz.ws + sz.prod, 0);
+    if (!rc && host) rc = c->d_p1n_io.reserve(sz.out, 0);
+    if (rc) return rc;
+    uint32_t* const tw_inv = c->d_p1n_tw;
+    uint32_t* const tw_fwd = tw_inv + sz.tw_inv / 4;
+    uint32_t* const scal = c->d_ntt_io;
+    uint32_t* const staged = scal + sz.scalars / 4;
+    uint32_t* const ws = c->d_p1n_ws;
+    uint32_t* const prod = ws + sz.ws / 4;
+    {
+        const fr w2q = frntt_omega(M);
+        const unsigned grid = (unsigned)(((q + FRNTT_RUN - 1) / FRNTT_RUN + FRNTT_LANES - 1) / FRNTT_LANES);
+        k_frntt_twiddle<<<grid, FRNTT_LANES, 0, st>>>(w2q, q, c->d_ntt_tw);
+        k_p1ntt_twiddle<<<grid, FRNTT_LANES, 0, st>>>(fr_inv(w2q), q, tw_inv);
+        if (cells > 1 && !want_h)
+            k_p1ntt_twiddle<<<(unsigned)(((cells / 2 + FRNTT_RUN - 1) / FRNTT_RUN + FRNTT_LANES - 1) / FRNTT_LANES), FRNTT_LANES, 0, st>>>(frntt_omega(a), cells / 2, tw_fwd);
+    }
+    const uint32_t q2w[8] = {(uint32_t)(2 * (uint64_t)q), (uint32_t)((2 * (uint64_t)q) >> 32), 0, 0, 0, 0, 0, 0};
+    const fr inv2q = fr_inv(fr_from_words(q2w));
+    const uint32_t levels = plan::fk20_cells_sum_levels(sz);
+    std::vector<uint32_t> words(sz.per_pass);
+    int reduced = 0;
+    for (size_t p = 0; p < sz.passes; p++) {
+        size_t g0, kc;
+        plan::fk20_cells_pass(sz, k, p, g0, kc);
+        const plan::fk20_cells_launch l = plan::fk20_cells_launch_for(sz, kc);
+        const uint32_t* src = host ? staged : reinterpret_cast<const uint32_t*>(d_polys + g0 * n * 32);
+        uint32_t* out = host ? c->d_p1n_io.p : reinterpret_cast<uint32_t*>(d_out + g0 * rows * 96);
+        if (host) HIPCHK(hipMemcpyAsync(staged, h_polys + g0 * n * 32, kc * n * 32, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(c->d_ntt_st, 0, kc * 4, st));
+        k_fk20c_circ<<<l.circ_grid, FRNTT_LANES, 0, st>>>(mq, cl, kc, inv2q, src, scal, c->d_ntt_st);
+        const size_t vecs = kc << cl;
+        uint32_t done = 0;
+        for (uint32_t i = 0; i < fsz.passes; i++) {
+            const uint32_t tp = fsz.stages[i], sigma = M - done - tp;
+            const plan::frntt_shape sh = plan::frntt_geo_for(M, fsz.tile, sigma, tp, vecs);
+            const frntt_geo g{M, sigma, tp, sh.clo, sh.chi, sh.L, vecs};
+            if ((rc = frntt_launch_pass<false>(g, scal, false, c->d_ntt_tw, false, scal, c->d_ntt_st, st))) return rc;
+            done += tp;
+        }
+        k_fk20c_pointwise<<<l.point_grid, WAVE, 0, st>>>((uint64_t)kc << (sz.log2n + 1), mq, cl, scal, setup->x, prod);
+        for (uint32_t t = 0; t < levels; t++) {
+            const uint64_t lanes = plan::fk20_cells_sum_lanes(sz, kc, t);
+            k_fk20c_sum<<<(unsigned)((lanes + WAVE - 1) / WAVE), WAVE, 0, st>>>(lanes, t * FK20C_FAN_LOG2, fk20c_level_bits(cl, t), prod, t + 1 == levels, M, w, ws);
+        }
+        p1ntt_stage g{};
+        g.k = kc, g.m = M;
+        for (uint32_t b = 0; b < M; b++) {
+            g.b = b;
+            if (w == M) k_p1ntt_stage<true><<<l.inv_grid, WAVE, 0, st>>>(g, nullptr, ws, tw_inv);
+            else k_fk20c_stage<true><<<l.inv_grid, WAVE, 0, st>>>(g, w, ws, tw_inv);
+        }
+        if (!want_h) {
+            if (l.pad_grid) k_fk20c_pad<<<l.pad_grid, WAVE, 0, st>>>((uint64_t)kc << a, mq, a, w, ws);
+            g.m = a;
+            for (uint32_t s = 0; s < a; s++) {
+                g.b = a - 1 - s;
+                k_fk20c_stage<false><<<l.fwd_grid, WAVE, 0, st>>>(g, w, ws, tw_fwd);
+            }
+            k_fk20c_finish<<<l.finish_grid, WAVE, 0, st>>>(ws, (uint64_t)kc << a, a, w, permute, l.run, out);
+        } else {
+            k_fk20c_finish<<<l.finish_h_grid, WAVE, 0, st>>>(ws, (uint64_t)kc << mq, mq, w, false, l.run_h, out);
+        }
+        HIPCHK(hipGetLastError());
+        if (host) HIPCHK(hipMemcpyAsync(h_out + g0 * rows * 96, out, kc * rows * 96, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(words.data(), c->d_ntt_st, kc * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t v = 0; v < kc; v++) {
+            if (status) status[g0 + v] = (uint8_t)words[v];
+            reduced += (words[v] & FK20_ST_REDUCED) != 0;
+        }
+    }
+    return reduced;
+}
+extern "C" int mi355_bls_fk20_open_cells_many_device(mi355_bls_ctx* c, const mi355_bls_fk20_setup* setup, const void* d_polys32, size_t k, size_t ext_log2,
+                                                     uint32_t flags, void* d_out96, uint8_t* status, void* stream) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;                      // nothing computed, nothing written
+    return fk20_cells_run(c, setup, (const uint8_t*)d_polys32, nullptr, k, ext_log2, flags, (uint8_t*)d_out96, nullptr, status, (hipStream_t)stream);
+}
+extern "C" int mi355_bls_fk20_open_cells_many(mi355_bls_ctx* c, const mi355_bls_fk20_setup* setup, const void* polys32, size_t k, size_t ext_log2, uint32_t flags,
+                                              void* out96, uint8_t* status) {
+    if (!c) return MI355_BLS_ERR_ARG;
+    if (k == 0) return 0;
+    return fk20_cells_run(c, setup, nullptr, (const uint8_t*)polys32, k, ext_log2, flags, nullptr, (uint8_t*)out96, status, nullptr);
+}
+// TEST HOOK: the polynomials per pass of the following fk20 calls - all openings and cells - on this context (0: the plan's own; it can only
+// shorten a pass)
 extern "C" int mi355_bls_debug_fk20_set_pass(mi355_bls_ctx* c, size_t polys_per_pass) {
     if (!c) return MI355_BLS_ERR_ARG;
     c->fk20_polys = polys_per_pass;

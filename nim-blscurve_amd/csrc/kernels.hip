@@ -48,6 +48,7 @@
 #include "frntt.hpp"
 #include "p1ntt.hpp"
 #include "fk20.hpp"
+#include "fk20cells.hpp"
 #include "keytable.hpp"
 #include "msmmany.hpp"
 #include "msmtable.hpp"
@@ -3400,6 +3401,74 @@ __global__ void __launch_bounds__(WAVE) k_fk20_finish(const uint32_t* ws, uint64
     p1ntt_finish_run<fp>(
         total, m, permute, run, (uint64_t)blockIdx.x * WAVE + threadIdx.x, [&](uint64_t e) { return ld_g1_int(ws + (size_t)fk20_at(m, e) * G1W); },
         [&](uint64_t slot, const g1_aff& a) { st_aff_blst(out + (size_t)slot * 24, a); },
+        [&](uint64_t slot) {
+            for (uint32_t t = 0; t < 24; t++) out[(size_t)slot * 24 + t] = 0;
+        });
+}
+
+// ------------------------------------------------------------------------------------------
+// The proofs of all cells of many polynomials (mi355_bls_fk20_open_cells_many).  The route and the bodies are csrc/fk20cells.hpp's; the Fr
+// passes, the twiddle tables and - where a polynomial's vector is 2q images wide - the inverse stages are the existing kernels.  mq, c:
+// q = 2^mq, l = 2^c; prod: the pass's k x 2n product images, term (g 2q + slot) l + v; ws: its k x 2^w workspace images.
+// ------------------------------------------------------------------------------------------
+// the setup's input, a lane per entry t < n2 = 2n of the l vectors s^(v) one after the other
+__global__ void __launch_bounds__(FRNTT_LANES) k_fk20c_setup_layout(const uint32_t* __restrict__ srs, uint64_t n2, uint32_t mq, uint32_t c, uint32_t* __restrict__ out) {
+    const uint64_t t = (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x;
+    if (t >= n2) return;
+    uint64_t i;
+    const bool has = fk20c_setup_src(mq, c, t, i);
+    for (uint32_t x = 0; x < 24; x++) out[(size_t)t * 24 + x] = has ? srs[(size_t)i * 24 + x] : 0u;
+}
+// the transformed vectors into the handle, a lane per entry: slot-major, v minor
+__global__ void __launch_bounds__(FRNTT_LANES) k_fk20c_setup_place(const uint32_t* __restrict__ src, uint64_t n2, uint32_t mq, uint32_t c, uint32_t* __restrict__ out) {
+    const uint64_t t = (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x;
+    if (t >= n2) return;
+    const uint64_t at = fk20c_setup_at(mq, c, t);
+    for (uint32_t x = 0; x < 24; x++) out[(size_t)at * 24 + x] = src[(size_t)t * 24 + x];
+}
+// step 1's layout, a lane per run of FRNTT_RUN slots of the (k l) x 2q array.  status: a word per polynomial of the pass, cleared by the host.
+__global__ void __launch_bounds__(FRNTT_LANES) k_fk20c_circ(uint32_t mq, uint32_t c, uint64_t k, fr inv2q, const uint32_t* __restrict__ polys,
+                                                             uint32_t* __restrict__ dst, uint32_t* __restrict__ status) {
+    uint64_t poly;
+    if (fk20c_circ_run(mq, c, k, inv2q, (uint64_t)blockIdx.x * FRNTT_LANES + threadIdx.x, polys, dst, poly)) atomicOr(&status[poly], FK20_ST_REDUCED);
+}
+// step 2's products, a lane per term e < total = k x 2n
+__global__ void __launch_bounds__(WAVE) k_fk20c_pointwise(uint64_t total, uint32_t mq, uint32_t c, const uint32_t* __restrict__ scalars,
+                                                           const uint32_t* __restrict__ setup, uint32_t* __restrict__ prod) {
+    const uint64_t e = (uint64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (e >= total) return;
+    const fk20c_term_at t = fk20c_term(mq, c, e);
+    st_g1_int(prod + (size_t)e * G1W, fk20_pointwise<fp>(ld_g1a_blst(setup + (size_t)t.setup * 24), fropen_own(scalars, (size_t)t.scalar)));
+}
+// one level of step 2's sum, a lane per group o < lanes of 2^bits images 2^shift apart: the result to the group's first image, or with
+// `last` (o is then the slot of the k x 2q array) to its place in ws.  No two lanes share an image.
+__global__ void __launch_bounds__(WAVE) k_fk20c_sum(uint64_t lanes, uint32_t shift, uint32_t bits, uint32_t* prod, bool last, uint32_t M, uint32_t w, uint32_t* ws) {
+    const uint64_t o = (uint64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (o >= lanes) return;
+    const uint64_t first = o << (shift + bits);
+    const g1_jac r = fk20c_sum_item<fp>(first, (uint64_t)1 << shift, 1u << bits, [&](uint64_t j) { return ld_g1_int(prod + (size_t)j * G1W); });
+    st_g1_int(last ? ws + (size_t)fk20c_at(M, w, o) * G1W : prod + (size_t)first * G1W, r);
+}
+// one stage over the k vectors of 2^g.m elements that lie 2^w images apart in ws: k_p1ntt_stage's lanes with fk20c_at's places
+template <bool DIT>
+__global__ void __launch_bounds__(WAVE) k_fk20c_stage(p1ntt_stage g, uint32_t w, uint32_t* ws, const uint32_t* __restrict__ tw) {
+    const uint64_t lane = (uint64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (lane >= p1ntt_lanes(g)) return;
+    p1ntt_butterfly<DIT, fp>(
+        g, lane, [&](uint64_t e) { return ld_g1_int(ws + (size_t)fk20c_at(g.m, w, e) * G1W); },
+        [&](uint64_t e, const g1_jac& a) { st_g1_int(ws + (size_t)fk20c_at(g.m, w, e) * G1W, a); }, [&](uint64_t t) { return fropen_own(tw, (size_t)t); });
+}
+// step 4's padding, a lane per element e < total = k N, N = 2^a: entries q .. N-1 of each vector become infinity
+__global__ void __launch_bounds__(WAVE) k_fk20c_pad(uint64_t total, uint32_t mq, uint32_t a, uint32_t w, uint32_t* __restrict__ ws) {
+    const uint64_t e = (uint64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (e >= total || !fk20c_pad(mq, a, e)) return;
+    st_g1_int(ws + (size_t)fk20c_at(a, w, e) * G1W, jac_inf<fp>());
+}
+// the finish over the same places: element e < total = k 2^a to slot e of out, or with permute to the bit-reversed place in its vector
+__global__ void __launch_bounds__(WAVE) k_fk20c_finish(const uint32_t* ws, uint64_t total, uint32_t a, uint32_t w, bool permute, uint32_t run, uint32_t* __restrict__ out) {
+    p1ntt_finish_run<fp>(
+        total, a, permute, run, (uint64_t)blockIdx.x * WAVE + threadIdx.x, [&](uint64_t e) { return ld_g1_int(ws + (size_t)fk20c_at(a, w, e) * G1W); },
+        [&](uint64_t slot, const g1_aff& p) { st_aff_blst(out + (size_t)slot * 24, p); },
         [&](uint64_t slot) {
             for (uint32_t t = 0; t < 24; t++) out[(size_t)slot * 24 + t] = 0;
         });

@@ -1408,6 +1408,85 @@ inline fk20_launch fk20_launch_for(const fk20_sizes& s, size_t count) {
     return l;
 }
 
+// The proofs of all cells of k polynomials (mi355_bls_fk20_open_cells_many; csrc/fk20cells.hpp): n = 2^m coefficients, cells of
+// `cell` = l = 2^c points, q = n / l, N = q 2^ext cells; PASSES of whole polynomials under the same FK20_PASS_BYTES.  Per polynomial a pass
+// holds 2n scalars (the l transforms of 2q), 2n product images and W = max(2q, N) workspace images: 448 n + 192 W bytes.  One polynomial
+// always forms a pass, nothing is refused for its size, and `forced` (mi355_bls_debug_fk20_set_pass) only shortens a pass.
+//   the launches        (fk20_cells_launch_for) the layout: a lane per run of FRNTT_RUN slots of the (count l) x 2q array; the product: a
+//                       lane per term, count x 2n; level t of the sum (fk20_cells_sum_lanes): a lane per group of up to FK20_CELLS_FAN
+//                       images, the last level count x 2q lanes; a stage of the inverse: count x q butterflies; the padding: a lane per
+//                       element of count x N (none for N == q); a stage of the forward: count x N / 2; the finish: to_affine_for's run
+//                       over count x N elements, with MI355_BLS_FK20_H over count x q.
+// Refused (ok == false): what fk20_sizes_for refuses, a cell that is 0, no power of two or above n, ext_log2 with n 2^ext > 2^32 (so N and
+// the transform of 2q both fit p1ntt_sizes_for's bound).
+constexpr uint32_t FK20_CELLS_FAN_LOG2 = 3;                              // fk20cells.hpp's FK20C_FAN_LOG2 (asserted where both are seen)
+struct fk20_cells_sizes {
+    bool ok;
+    uint32_t log2n, log2cell, log2q, log2cells, log2w;   // n, l, q = n / l, N = q 2^ext, W = max(2q, N)
+    size_t per_pass, passes;                 // polynomials per pass (the last one may hold fewer), passes of the call
+    size_t scalars, prod, ws;                // bytes: a pass's 2n scalars, 2n product images and W workspace images per polynomial
+    size_t polys, out, status;               // bytes: a pass's coefficient images, its N affine outputs per polynomial, a status word each
+    size_t tw_fr, tw_inv, tw_fwd;            // bytes: the tables of omega_2q (q entries), 1 / omega_2q (q entries) and omega_N (N / 2 entries)
+};
+inline fk20_cells_sizes fk20_cells_sizes_for(size_t n, size_t cell, size_t ext_log2, size_t k, size_t forced = 0) {
+    fk20_cells_sizes s{};
+    if (!fk20_sizes_for(n, 1).ok || cell == 0 || (cell & (cell - 1)) || cell > n) return s;
+    while (((size_t)1 << s.log2n) < n) s.log2n++;
+    if (ext_log2 > 32 || s.log2n + ext_log2 > 32) return s;
+    while (((size_t)1 << s.log2cell) < cell) s.log2cell++;
+    s.log2q = s.log2n - s.log2cell;
+    s.log2cells = s.log2q + (uint32_t)ext_log2;
+    s.log2w = s.log2cells > s.log2q + 1 ? s.log2cells : s.log2q + 1;
+    const size_t w = (size_t)1 << s.log2w, cells = (size_t)1 << s.log2cells, q = (size_t)1 << s.log2q;
+    size_t per = FK20_PASS_BYTES / (n * FK20_POLY_BYTES_PER_COEFF + w * G1_WORDS * 4);
+    if (per == 0) per = 1;
+    if (forced && forced < per) per = forced;
+    if (per > k && k) per = k;
+    s.ok = true;
+    s.per_pass = per;
+    s.passes = (k + per - 1) / per;
+    s.scalars = per * 2 * n * 32;
+    s.prod = per * 2 * n * G1_WORDS * 4;
+    s.ws = per * w * G1_WORDS * 4;
+    s.polys = per * n * 32;
+    s.out = per * cells * 96;
+    s.status = per * 4;
+    s.tw_fr = q * 32;
+    s.tw_inv = q * 32;
+    s.tw_fwd = cells / 2 * 32;
+    return s;
+}
+// pass p of the call: polynomials [first, first + count)
+inline void fk20_cells_pass(const fk20_cells_sizes& s, size_t k, size_t p, size_t& first, size_t& count) {
+    first = p * s.per_pass;
+    count = k - first < s.per_pass ? k - first : s.per_pass;
+}
+// the levels of the sum over l = 2^log2cell terms, and the lanes of level t for `count` polynomials: level t adds groups of
+// 2^min(FK20_CELLS_FAN_LOG2, what is left) images; l == 1 is one level, the copy
+inline uint32_t fk20_cells_sum_levels(const fk20_cells_sizes& s) { return s.log2cell == 0 ? 1 : (s.log2cell + FK20_CELLS_FAN_LOG2 - 1) / FK20_CELLS_FAN_LOG2; }
+inline uint64_t fk20_cells_sum_lanes(const fk20_cells_sizes& s, size_t count, uint32_t t) {
+    const uint32_t done = (t + 1) * FK20_CELLS_FAN_LOG2 < s.log2cell ? (t + 1) * FK20_CELLS_FAN_LOG2 : s.log2cell;
+    return (uint64_t)count << (s.log2q + 1 + s.log2cell - done);
+}
+struct fk20_cells_launch {
+    uint32_t circ_grid, point_grid, inv_grid, pad_grid, fwd_grid, run, finish_grid, run_h, finish_h_grid;
+};
+inline fk20_cells_launch fk20_cells_launch_for(const fk20_cells_sizes& s, size_t count) {
+    fk20_cells_launch l{};
+    const uint64_t terms = (uint64_t)count << (s.log2n + 1), hs = (uint64_t)count << s.log2q, cells = (uint64_t)count << s.log2cells;
+    const uint64_t runs_per_vec = (((uint64_t)2 << s.log2q) + FK20_CIRC_RUN - 1) / FK20_CIRC_RUN;
+    l.circ_grid = (uint32_t)((((uint64_t)count << s.log2cell) * runs_per_vec + FK20_CIRC_LANES - 1) / FK20_CIRC_LANES);
+    l.point_grid = (uint32_t)((terms + WAVE - 1) / WAVE);
+    l.inv_grid = (uint32_t)((hs + WAVE - 1) / WAVE);
+    l.pad_grid = s.log2cells > s.log2q ? (uint32_t)((cells + WAVE - 1) / WAVE) : 0;
+    l.fwd_grid = (uint32_t)((cells / 2 + WAVE - 1) / WAVE);
+    l.run = to_affine_for((size_t)cells).run;
+    l.finish_grid = (uint32_t)(((cells + l.run - 1) / l.run + WAVE - 1) / WAVE);
+    l.run_h = to_affine_for((size_t)hs).run;
+    l.finish_h_grid = (uint32_t)(((hs + l.run_h - 1) / l.run_h + WAVE - 1) / WAVE);
+    return l;
+}
+
 // ------------------------------------------------------------------------------------------
 // Fixed-base G1 MSM over a precomputed window table (mi355_bls_p1s_table_* / mi355_bls_p1s_mult_table*): what ptab_run follows and reserves.
 // The table holds, for point i and window w, the affine row T[w][i] = [2^(w wbits)] P_i at entry w x npoints + i (k_pip_convert's record).
