@@ -79,11 +79,13 @@ extern "C" {
 // srs96: n setup images; polys32: k x n coefficient images -> out96 (k x n x 96), status (k).  Returns the polynomials with FK20_ST_REDUCED;
 // -1: the plan refuses n.  flags: 2 BITREV, 4 H.  passes_run, if wanted: the passes walked.  h_last_z_zero, if wanted: 1 when entry n - 1
 // of EVERY polynomial's inverse transform lies in the workspace as a Jacobian point with Z == 0 - infinity out of the additions themselves.
-int emu_fk20(const uint8_t* srs96, size_t n, const uint8_t* polys32, size_t k, uint32_t flags, size_t forced, uint8_t* out96, uint8_t* status, size_t* passes_run,
-             int* h_last_z_zero) {
+// forced_tile: mi355_bls_debug_frntt_set_tile's log2 as fk20_run hands it to frntt_sizes_for (0: the plan's own); fr_passes, if wanted: the
+// passes of the Fr transform it gave.
+int emu_fk20(const uint8_t* srs96, size_t n, const uint8_t* polys32, size_t k, uint32_t flags, size_t forced, uint32_t forced_tile, uint8_t* out96, uint8_t* status,
+             size_t* passes_run, int* h_last_z_zero, size_t* fr_passes) {
     const plan::fk20_sizes sz = plan::fk20_sizes_for(n, k, forced);
     if (!sz.ok) return -1;
-    const plan::frntt_sizes fsz = plan::frntt_sizes_for(2 * n, sz.per_pass, 0, 0);
+    const plan::frntt_sizes fsz = plan::frntt_sizes_for(2 * n, sz.per_pass, forced_tile, 0);
     const bool want_h = flags & 4, permute = !want_h && !(flags & 2);
     const uint32_t m = sz.log2n, M = m + 1;
     std::vector<uint8_t> x;
@@ -153,6 +155,7 @@ int emu_fk20(const uint8_t* srs96, size_t n, const uint8_t* polys32, size_t k, u
     }
     if (passes_run) *passes_run = sz.passes;
     if (h_last_z_zero) *h_last_z_zero = z_zero;
+    if (fr_passes) *fr_passes = fsz.passes;
     return reduced;
 }
 // the 2n scalars step 1's layout writes for ONE polynomial, before the transform, with inv2n = 1 (Montgomery one): b itself, canonical

@@ -129,13 +129,15 @@ int emu_fk20c_setup(const uint8_t* srs96, size_t n, size_t cell, int plain, uint
 // srs96: n setup images; polys32: k x n coefficient images -> out96 (k x N x 96, with H k x q x 96), status (k).  Returns the polynomials
 // with FK20_ST_REDUCED; -1: the plan refuses.  flags: 2 BITREV, 4 H.  passes_run, if wanted: the passes walked.  The workspace and the
 // product array are filled with a pattern that is no point of the curve before every pass: an image read before it is written shows.
-int emu_fk20c(const uint8_t* srs96, size_t n, size_t cell, size_t ext, const uint8_t* polys32, size_t k, uint32_t flags, size_t forced, uint8_t* out96, uint8_t* status,
-              size_t* passes_run) {
+// forced_tile: mi355_bls_debug_frntt_set_tile's log2 as fk20_cells_run hands it to frntt_sizes_for (0: the plan's own); fr_passes, if wanted:
+// the passes of the Fr transform it gave.
+int emu_fk20c(const uint8_t* srs96, size_t n, size_t cell, size_t ext, const uint8_t* polys32, size_t k, uint32_t flags, size_t forced, uint32_t forced_tile, uint8_t* out96,
+              uint8_t* status, size_t* passes_run, size_t* fr_passes) {
     const plan::fk20_cells_sizes sz = plan::fk20_cells_sizes_for(n, cell, ext, k, forced);
     if (!sz.ok) return -1;
     const uint32_t mq = sz.log2q, cl = sz.log2cell, M = mq + 1, a = sz.log2cells, w = sz.log2w;
     const size_t q = (size_t)1 << mq, cells = (size_t)1 << a;
-    const plan::frntt_sizes fsz = plan::frntt_sizes_for(2 * q, sz.per_pass << cl, 0, 0);
+    const plan::frntt_sizes fsz = plan::frntt_sizes_for(2 * q, sz.per_pass << cl, forced_tile, 0);
     const bool want_h = flags & 4, permute = !want_h && !(flags & 2);
     const size_t rows = want_h ? q : cells;
     std::vector<uint8_t> x;
@@ -233,6 +235,7 @@ int emu_fk20c(const uint8_t* srs96, size_t n, size_t cell, size_t ext, const uin
         }
     }
     if (passes_run) *passes_run = sz.passes;
+    if (fr_passes) *fr_passes = fsz.passes;
     return reduced;
 }
 }

@@ -1,7 +1,9 @@
 """The cell-proof call executed on the CPU under the bounds tracker (tests/host_emu/fk20cells.cpp walks csrc/fk20cells.hpp's lane bodies, with
 those of fk20.hpp, frntt.hpp and p1ntt.hpp between them, in the host call's order, the setup included): every case of
 tests/golden/fk20_cells.json byte for byte, forced passes, the cell == 1 handle against fk20_setup_create's, the slot-major order of the
-handle, and what the fixture itself must hold."""
+handle, and what the fixture itself must hold.  Beyond the fixture (tests/fk20_levels_cases.py, expected images from the C oracle's [a]G of
+tests/fk20_scalars.py's scalars): cells of 16 to 512 points, where the sum runs two and three levels, sums_n64 with equal, opposite and
+infinite level-0 results, and the Fr transform forced into two passes."""
 import ctypes
 import os
 import subprocess
@@ -10,7 +12,9 @@ import pytest
 
 import fk20_cases as k1
 import fk20_cells_cases as kc
+import fk20_levels_cases as lc
 import frntt_cases as fc
+import g1_images as gi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 R = kc.R
@@ -23,19 +27,24 @@ def lib():
     subprocess.check_call([os.path.join(HERE, "host_emu", "build_fk20cells.sh")])
     L = ctypes.CDLL(os.path.join(HERE, "host_emu", "_build", "libfk20cells.so"))
     cp = ctypes.c_char_p
-    L.emu_fk20c.argtypes = [cp, SZ, SZ, SZ, cp, SZ, U32, SZ, cp, cp, ctypes.POINTER(SZ)]
+    L.emu_fk20c.argtypes = [cp, SZ, SZ, SZ, cp, SZ, U32, SZ, U32, cp, cp, ctypes.POINTER(SZ), ctypes.POINTER(SZ)]
     L.emu_fk20c_setup.argtypes = [cp, SZ, SZ, ctypes.c_int, cp]
     return L
 
 
-def run(lib, setup, n, cell, ext, polys, flags, forced=0):
+def run_tiled(lib, setup, n, cell, ext, polys, flags, forced=0, tile=0):
+    """tile: the log2 mi355_bls_debug_frntt_set_tile would set (0: the plan's own) -> (..., the passes the Fr transform took)"""
     k = len(polys) // (n * 32)
     q = n // cell
     per = q if flags & kc.H else q << ext
     out, st = ctypes.create_string_buffer(k * per * 96), ctypes.create_string_buffer(k)
-    passes = SZ()
-    rc = lib.emu_fk20c(setup, n, cell, ext, polys, k, flags, forced, out, st, ctypes.byref(passes))
-    return rc, out.raw, st.raw, passes.value
+    passes, fr_passes = SZ(), SZ()
+    rc = lib.emu_fk20c(setup, n, cell, ext, polys, k, flags, forced, tile, out, st, ctypes.byref(passes), ctypes.byref(fr_passes))
+    return rc, out.raw, st.raw, passes.value, fr_passes.value
+
+
+def run(lib, setup, n, cell, ext, polys, flags, forced=0):
+    return run_tiled(lib, setup, n, cell, ext, polys, flags, forced)[:4]
 
 
 def handle(lib, srs, n, cell, plain=0):
@@ -124,16 +133,17 @@ def test_cell_1_handle_is_the_all_openings_handle(lib):
 
 
 def test_handle_is_slot_major_over_the_sub_setups(lib):
-    """the handle for cells of l points holds, at slot l + v, slot `slot` of the all-openings handle of the sub-setup S_(l u + v)"""
-    c = kc.case("n16_l4_x1")
-    srs = kc.rows(bytes.fromhex(c["setup"]))
-    n, cell = 16, 4
-    q = n // cell
-    got = kc.rows(handle(lib, b"".join(srs), n, cell))
-    for v in range(cell):
-        sub = kc.rows(handle(lib, b"".join(srs[v::cell]), q, 1, plain=1))
-        assert [got[slot * cell + v] for slot in range(2 * q)] == sub, v
-    assert len(set(got)) > n                                                  # and it is no trivial array
+    """the handle for cells of l points holds, at slot l + v, slot `slot` of the all-openings handle of the sub-setup S_(l u + v); l = 64 is
+    the cell whose terms the sum adds in two full levels"""
+    for n, cell in ((16, 4), (128, 64)):
+        srs = kc.rows(bytes.fromhex(kc.case("n16_l4_x1")["setup"])) if n == 16 else kc.rows(gi.multiples_of_g_cpu(lc.srs_scalars(n)))
+        q = n // cell
+        got = kc.rows(handle(lib, b"".join(srs), n, cell))
+        for v in range(cell):
+            sub = kc.rows(handle(lib, b"".join(srs[v::cell]), q, 1, plain=1))
+            assert [got[slot * cell + v] for slot in range(2 * q)] == sub, (n, v)
+        # and it is no trivial array (q = 2: s^ of a sub-setup is its one point S_v, the transform four copies of it - l distinct images)
+        assert len(set(got)) > n if q > 2 else len(set(got)) == cell and kc.INF not in got
 
 
 def test_refused_by_the_plan(lib):
@@ -141,4 +151,71 @@ def test_refused_by_the_plan(lib):
     srs, polys = bytes.fromhex(c["setup"]), bytes.fromhex(c["polys"])
     out, st = ctypes.create_string_buffer(3 * 16 * 4 * 96), ctypes.create_string_buffer(3)
     for cell, ext in ((0, 0), (3, 0), (32, 0), (4, 29)):
-        assert lib.emu_fk20c(srs, 16, cell, ext, polys, 3, 0, 0, out, st, None) == -1, (cell, ext)
+        assert lib.emu_fk20c(srs, 16, cell, ext, polys, 3, 0, 0, 0, out, st, None, None) == -1, (cell, ext)
+
+
+def expect(got, want_scalars, what):
+    """the rows of `got` against [a]G of the expected scalars, row by row"""
+    want = gi.multiples_of_g_cpu(list(want_scalars))
+    assert len(got) == len(want), what
+    for i, (a, b) in enumerate(zip(kc.rows(got), kc.rows(want))):
+        assert a == b, (what, i)
+
+
+@pytest.mark.parametrize("n,cell,ext,k,flag_values", lc.SHAPES, ids=["n%d_l%d_x%d" % c[:3] for c in lc.SHAPES])
+def test_sums_of_two_and_three_levels(lib, n, cell, ext, k, flag_values):
+    """l >= 16: the levels at strides 8 and 64 store in place in the product array, the last one into the workspace"""
+    srs = gi.multiples_of_g_cpu(lc.srs_scalars(n))
+    rows, status = lc.polynomials(n, cell, ext, k)
+    for flags in flag_values:
+        rc, got, st, passes = run(lib, srs, n, cell, ext, lc.pack(rows), flags)
+        assert (rc, st, passes) == (1, status, 1), flags
+        expect(got, lc.expected(n, cell, ext, k, flags), (n, cell, ext, flags))
+
+
+def test_forced_passes_and_a_forced_tile_behind_a_two_level_sum(lib):
+    n, cell, ext, k = lc.FORCED
+    srs = gi.multiples_of_g_cpu(lc.srs_scalars(n))
+    rows, status = lc.polynomials(n, cell, ext, k)
+    for flags in lc.ALL:
+        whole = run(lib, srs, n, cell, ext, lc.pack(rows), flags)
+        expect(whole[1], lc.expected(n, cell, ext, k, flags), flags)
+        for forced in (1, 2):
+            assert run(lib, srs, n, cell, ext, lc.pack(rows), flags, forced) == whole[:3] + (-(-k // forced),), (flags, forced)
+        assert run_tiled(lib, srs, n, cell, ext, lc.pack(rows), flags, tile=2) == whole + (2,), flags          # 2q = 8 scalars in tiles of four
+
+
+def test_fr_transform_in_two_passes_gives_the_same_bytes(lib):
+    """a tile of four elements: the 2q = 8 or 16 scalars of a vector take two passes, in place in the scalar array as fk20_cells_run drives
+    them; by default every fixture case takes one"""
+    seen = set()
+    for name, n, k, cell, ext, flags, setup, polys, want, status in kc.cases():
+        if name in ("n16_l4_x1", "wide_n16", "n64_l8_x1", "special_n16"):
+            assert run_tiled(lib, setup, n, cell, ext, polys, flags)[4] == 1
+            rc, got, st, passes, fr_passes = run_tiled(lib, setup, n, cell, ext, polys, flags, tile=2)
+            assert fr_passes == 2 and passes == 1 and st == status and rc == sum(1 for b in status if b), (name, flags)
+            assert len(got) == len(want)
+            for i, (a, b) in enumerate(zip(kc.rows(got), kc.rows(want))):
+                assert a == b, (name, flags, i)
+            seen.add((name, flags))
+    assert len(seen) == 3 + 2 + 2 + 2
+
+
+@pytest.mark.parametrize("name", sorted(lc.sums_n64()))
+def test_sums_n64(lib, name):
+    """n = 64, l = 16, no SRS: the second level adds two equal results (a doubling), two opposite ones, a result and infinity, and two
+    infinities - each in every slot (tests/fk20_levels_cases.py sums_n64)"""
+    n, cell, ext = lc.SUMS
+    s, polys, kinds = lc.sums_n64()[name]
+    setup = gi.multiples_of_g_cpu(s)
+    for flags in lc.ALL:
+        want = lc.sums_expected(name, flags)
+        rc, got, st, passes = run(lib, setup, n, cell, ext, lc.pack(polys), flags)
+        assert (rc, st, passes) == (0, bytes(len(polys)), 1), flags
+        expect(got, want, (name, flags))
+        per = len(want) // len(polys)
+        for g, kind in enumerate(kinds):                                      # the structure, on the images that came out
+            mine = kc.rows(got)[g * per:(g + 1) * per]
+            assert (set(mine) == {kc.INF}) == (kind == "infinity"), (name, flags, g)
+            if kind == "finite":
+                assert [i for i, r in enumerate(mine) if r == kc.INF] == ([per - 1] if flags & kc.H else []), (name, flags, g)

@@ -1,6 +1,6 @@
 """The all-openings call executed on the CPU under the bounds tracker (tests/host_emu/fk20.cpp walks csrc/fk20.hpp's lane bodies, with those
 of frntt.hpp and p1ntt.hpp between them, in the host call's order, the setup included): every case of tests/golden/fk20.json up to n = 16
-byte for byte, forced passes, the circulant layout against a Python list, the reversed setup, and h_(n-1) as an infinity that the complete
+byte for byte, forced passes, the Fr transform forced into two and three passes, the circulant layout against a Python list, the reversed setup, and h_(n-1) as an infinity that the complete
 additions produce."""
 import ctypes
 import os
@@ -22,7 +22,7 @@ def lib():
     subprocess.check_call([os.path.join(HERE, "host_emu", "build_fk20.sh")])
     L = ctypes.CDLL(os.path.join(HERE, "host_emu", "_build", "libfk20.so"))
     cp = ctypes.c_char_p
-    L.emu_fk20.argtypes = [cp, SZ, cp, SZ, U32, SZ, cp, cp, ctypes.POINTER(SZ), ctypes.POINTER(ctypes.c_int)]
+    L.emu_fk20.argtypes = [cp, SZ, cp, SZ, U32, SZ, U32, cp, cp, ctypes.POINTER(SZ), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(SZ)]
     L.emu_fk20_circ.argtypes = [cp, SZ, cp]
     L.emu_fk20_circ.restype = None
     L.emu_fk20_setup_src.argtypes = [U64, U64]
@@ -32,12 +32,17 @@ def lib():
     return L
 
 
-def run(lib, setup, n, polys, flags, forced=0):
+def run_tiled(lib, setup, n, polys, flags, forced=0, tile=0):
+    """tile: the log2 mi355_bls_debug_frntt_set_tile would set (0: the plan's own) -> (..., the passes the Fr transform took)"""
     k = len(polys) // (n * 32)
     out, st = ctypes.create_string_buffer(k * n * 96), ctypes.create_string_buffer(k)
-    passes, z = SZ(), ctypes.c_int()
-    rc = lib.emu_fk20(setup, n, polys, k, flags, forced, out, st, ctypes.byref(passes), ctypes.byref(z))
-    return rc, out.raw, st.raw, passes.value, z.value
+    passes, z, fr_passes = SZ(), ctypes.c_int(), SZ()
+    rc = lib.emu_fk20(setup, n, polys, k, flags, forced, tile, out, st, ctypes.byref(passes), ctypes.byref(z), ctypes.byref(fr_passes))
+    return rc, out.raw, st.raw, passes.value, z.value, fr_passes.value
+
+
+def run(lib, setup, n, polys, flags, forced=0):
+    return run_tiled(lib, setup, n, polys, flags, forced)[:5]
 
 
 def test_fixture_holds_what_the_tests_speak_of():
@@ -84,6 +89,22 @@ def test_forced_passes_give_the_same_bytes(lib):
             for forced in (1, 2):
                 rc, got, st, passes, _ = run(lib, setup, n, polys, flags, forced)
                 assert got == want and st == status and passes == -(-k // forced), (name, flags, forced)
+
+
+def test_fr_transform_in_more_than_one_pass_gives_the_same_bytes(lib):
+    """a tile of four elements: the 2n scalars of a polynomial take two passes at n = 8 and three at n = 16, in place in the scalar array as
+    fk20_run drives them; by default every fixture case takes one"""
+    seen = set()
+    for name, n, k, flags, setup, polys, want, status in kc.cases():
+        if name in ("n8_k3", "n16_k3", "special_n8"):
+            assert run_tiled(lib, setup, n, polys, flags)[5] == 1
+            rc, got, st, passes, z, fr_passes = run_tiled(lib, setup, n, polys, flags, tile=2)
+            assert fr_passes == -(-(n.bit_length()) // 2) >= 2 and passes == 1, (name, flags)
+            assert st == status and rc == sum(1 for b in status if b) and z == 1, (name, flags)
+            for i, (a, b) in enumerate(zip(kc.rows(got), kc.rows(want))):
+                assert a == b, (name, flags, i)
+            seen.add((name, flags))
+    assert len(seen) == 3 + 3 + 2
 
 
 def test_h_last_is_infinity_out_of_the_complete_addition(lib):

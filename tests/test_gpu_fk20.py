@@ -1,12 +1,18 @@
 """All openings of k polynomials on the device (mi355_bls_fk20_open_all_many, host and device form): every case of tests/golden/fk20.json
 byte for byte with its status bytes and return count, forced passes, a setup made through one context and used through another, k = 0,
-destroy of NULL, and the argument errors of the C entry points.  The CPU half is tests/test_fk20_emu.py."""
+destroy of NULL, and the argument errors of the C entry points.  Beyond the fixture (expected images are [a]G of tests/fk20_scalars.py's
+scalars through p1sLincombMany_device): the Fr transform in more than one pass - a forced tile of four, and the default tile at n = 1024 -
+and a finish over more than TOAFF_DEVICE_LANES elements, where neighbours share an inversion.  The CPU half is tests/test_fk20_emu.py."""
 import ctypes
 import functools
 
 import pytest
 
 import fk20_cases as kc
+import fk20_levels_cases as lc
+import fk20_scalars as ks
+import frntt_cases as fc
+import g1_images as gi
 
 pytestmark = pytest.mark.gpu
 ROW = kc.ROW
@@ -192,3 +198,79 @@ def test_a_busy_context_is_refused(m, setups):
         assert L.mi355_bls_fk20_open_all_many(c._h, s._h, bytes(4 * 32), 1, 0, out, None) == 0 and out.raw == bytes(4 * ROW)
     finally:
         c.close()
+
+
+# ---- beyond the fixture: expected images from scalars
+def test_fr_transform_in_more_than_one_pass_gives_the_same_bytes(m, cache, setups):
+    """a tile of four elements: the 2n scalars of a polynomial take two passes at n = 8 and three at n = 16, in place in the scalar array"""
+    seen = set()
+    try:
+        m.debug_frntt_set_tile(cache, 2)
+        for name, n, k, flags, setup, polys, want, status in kc.cases():
+            if name in ("n8_k3", "n16_k3", "special_n8"):
+                rc, got, st = both_forms(m, cache, setups(setup), polys, flags)
+                assert st == status and rc == sum(1 for b in status if b), (name, flags)
+                for i, (a, b) in enumerate(zip(kc.rows(got), kc.rows(want))):
+                    assert a == b, (name, flags, i)
+                seen.add((name, flags))
+    finally:
+        m.debug_frntt_set_tile(cache, 0)
+    assert len(seen) == 3 + 3 + 2
+
+
+@pytest.fixture(scope="module")
+def srs_setup(m, cache):
+    """-> (handle over [tau^i]G, i < n; the SRS made on the device and handed over there), one per n; released at the end"""
+    made = {}
+
+    def get(n):
+        if n not in made:
+            d_srs = gi.dev(gi.multiples_of_g(m, cache, list(lc.srs_scalars(n))))
+            made[n] = m.fk20_setup_create_device(cache, d_srs.data_ptr(), n)
+        return made[n]
+    yield get
+    for s in made.values():
+        m.fk20_setup_destroy(s)
+
+
+@pytest.mark.parametrize("flags", [0, kc.BITREV, kc.H])
+def test_fr_transform_in_two_passes_at_the_default_tile(m, cache, srs_setup, flags):
+    """n = 1024: 2048 scalars per polynomial, twice the default tile; k = 3 and its first polynomial alone"""
+    n = 1024
+    assert 2 * n > lc.fr_tile()
+    rows = [list(v) for v in fc.random_vectors(1024, 3, n)]
+    rows[1][n - 1] += kc.R                                                    # status byte 2 at polynomial 1; c_(n-1) is the one the circulant wraps
+    want = gi.multiples_of_g(m, cache, [a for row in ks.expected_srs(kc.TAU, rows, 1, 0, flags) for a in row])
+    assert want.count(0) < 3 * n * 8
+    assert both_forms(m, cache, srs_setup(n), fc.pack(rows), flags) == (1, want, bytes([0, 2, 0]))
+    assert both_forms(m, cache, srs_setup(n), fc.pack(rows[:1]), flags) == (0, want[:n * ROW], bytes(1))
+
+
+def with_a_root_at(n, j, tau, seed):
+    """(X - omega_n^j)(X - tau) d(X) + const, d random of degree n - 3: the quotient by X - omega_n^j has the root tau, pi_j is infinity"""
+    d = list(fc.random_vectors(seed, 1, n - 1)[0])
+    p, const = d[:n - 2], d[n - 2]
+    for root in (pow(fc.omega(n), j, kc.R), tau):
+        p = [((p[i - 1] if i else 0) - root * (p[i] if i < len(p) else 0)) % kc.R for i in range(len(p) + 1)]
+    p[0] = (p[0] + const) % kc.R
+    return p
+
+
+@pytest.mark.parametrize("flags", [kc.H, 0])
+def test_finish_with_a_shared_inversion(m, cache, srs_setup, flags):
+    """k = 1025 polynomials of 64 coefficients, three distinct ones cycled: 65 600 outputs, more than TOAFF_DEVICE_LANES, so a lane of
+    k_fk20_finish inverts once for two neighbours.  With H every vector ends in h_62 beside the infinity h_63; without, one polynomial
+    in three has the infinity pi_6 beside pi_7, stored at their bit-reversed places"""
+    n, k, j = 64, 1025, 6
+    assert k * n > lc.toaff_device_lanes() and k * n <= 2 * lc.toaff_device_lanes()
+    rows = [list(v) for v in fc.random_vectors(65, 2, n)] + [with_a_root_at(n, j, kc.TAU, 66)]
+    scalars = ks.expected_srs(kc.TAU, rows, 1, 0, flags)
+    if flags & kc.H:
+        assert all(row[n - 1] == 0 and all(row[:n - 1]) for row in scalars)
+    else:
+        assert all(all(row) for row in scalars[:2]) and [i for i, a in enumerate(scalars[2]) if a == 0] == [j] and scalars[2][j + 1]
+    want = kc.rows(gi.multiples_of_g(m, cache, [a for row in scalars for a in row]))
+    want = lc.cycled([b"".join(want[g * n:(g + 1) * n]) for g in range(3)], k)
+    rc, got, st = both_forms(m, cache, srs_setup(n), lc.cycled([fc.pack([row]) for row in rows], k), flags)
+    assert (rc, st) == (0, bytes(k))
+    assert got == want, [i for i, (a, b) in enumerate(zip(kc.rows(got), kc.rows(want))) if a != b][:8]

@@ -8,6 +8,8 @@ import functools
 import pytest
 
 import fk20_cells_cases as kc
+import fk20_levels_cases as lc
+import g1_images as gi
 
 pytestmark = pytest.mark.gpu
 ROW = kc.ROW
@@ -241,3 +243,129 @@ def test_a_busy_context_is_refused(m, setups):
         assert L.mi355_bls_fk20_open_cells_many(c._h, s._h, bytes(16 * 32), 1, 1, 0, out, None) == 0 and out.raw == bytes(8 * ROW)
     finally:
         c.close()
+
+
+# ---- beyond the fixture: expected images from scalars
+@pytest.fixture(scope="module")
+def images(m, cache):
+    """[a]G for a tuple of scalars, each tuple once"""
+    @functools.lru_cache(maxsize=None)
+    def get(scalars):
+        return gi.multiples_of_g(m, cache, list(scalars))
+    return get
+
+
+@pytest.fixture(scope="module")
+def srs_setups(m, cache, images):
+    """a cells handle over [tau^i]G, the SRS made on the device and handed over there; released at the end"""
+    made = {}
+
+    def get(n, cell):
+        if (n, cell) not in made:
+            d_srs = dev(images(lc.srs_scalars(n)))
+            made[n, cell] = m.fk20_setup_create_cells_device(cache, d_srs.data_ptr(), n, cell)
+        return made[n, cell]
+    yield get
+    for s in made.values():
+        m.fk20_setup_destroy(s)
+
+
+def expect(got, want, what):
+    assert len(got) == len(want), what
+    for i, (a, b) in enumerate(zip(kc.rows(got), kc.rows(want))):
+        assert a == b, (what, i)
+
+
+@pytest.mark.parametrize("n,cell,ext,k,flag_values", lc.SHAPES, ids=["n%d_l%d_x%d" % c[:3] for c in lc.SHAPES])
+def test_sums_of_two_and_three_levels(m, cache, images, srs_setups, n, cell, ext, k, flag_values):
+    """l >= 16: the levels at strides 8 and 64 store in place in the product array, the last one into the workspace"""
+    rows, status = lc.polynomials(n, cell, ext, k)
+    for flags in flag_values:
+        rc, got, st = both_forms(m, cache, srs_setups(n, cell), lc.pack(rows), ext, flags)
+        assert (rc, st) == (1, status), flags
+        expect(got, images(lc.expected(n, cell, ext, k, flags)), (n, cell, ext, flags))
+
+
+def test_forced_passes_and_a_forced_tile_behind_a_two_level_sum(m, cache, images, srs_setups):
+    n, cell, ext, k = lc.FORCED
+    rows, status = lc.polynomials(n, cell, ext, k)
+    s = srs_setups(n, cell)
+    for flags in lc.ALL:
+        want = (1, images(lc.expected(n, cell, ext, k, flags)), status)
+        for forced in (1, 2):
+            try:
+                m.debug_fk20_set_pass(cache, forced)
+                assert both_forms(m, cache, s, lc.pack(rows), ext, flags) == want, (flags, forced)
+            finally:
+                m.debug_fk20_set_pass(cache, 0)
+        try:
+            m.debug_frntt_set_tile(cache, 2)                                  # 2q = 8 scalars in tiles of four: two passes
+            assert both_forms(m, cache, s, lc.pack(rows), ext, flags) == want, flags
+        finally:
+            m.debug_frntt_set_tile(cache, 0)
+
+
+def test_fr_transform_in_two_passes_gives_the_same_bytes(m, cache, setups):
+    """a tile of four elements: the 2q = 8 or 16 scalars of a vector take two passes, in place in the scalar array"""
+    seen = set()
+    try:
+        m.debug_frntt_set_tile(cache, 2)
+        for name, n, k, cell, ext, flags, setup, polys, want, status in kc.cases():
+            if name in ("n16_l4_x1", "wide_n16", "n64_l8_x1", "special_n16"):
+                rc, got, st = both_forms(m, cache, setups(setup, cell), polys, ext, flags)
+                assert st == status and rc == sum(1 for b in status if b), (name, flags)
+                expect(got, want, (name, flags))
+                seen.add((name, flags))
+    finally:
+        m.debug_frntt_set_tile(cache, 0)
+    assert len(seen) == 3 + 2 + 2 + 2
+
+
+def test_fr_transform_in_two_passes_at_the_default_tile(m, cache, images, srs_setups):
+    """n = 2048 in cells of 2 points: 2q = 2048 scalars per vector, two vectors per polynomial"""
+    n, cell, ext = 2048, 2, 0
+    assert 2 * (n // cell) > lc.fr_tile()
+    rows, status = lc.polynomials(n, cell, ext, 1)
+    for flags in (kc.BITREV, kc.H):
+        rc, got, st = both_forms(m, cache, srs_setups(n, cell), lc.pack(rows), ext, flags)
+        assert (rc, st) == (1, status), flags
+        expect(got, images(lc.expected(n, cell, ext, 1, flags)), flags)
+
+
+@pytest.mark.parametrize("name", sorted(lc.sums_n64()))
+def test_sums_n64(m, cache, images, name):
+    """n = 64, l = 16, no SRS: the second level adds two equal results (a doubling), two opposite ones, a result and infinity, and two
+    infinities - each in every slot (tests/fk20_levels_cases.py sums_n64)"""
+    n, cell, ext = lc.SUMS
+    s, polys, kinds = lc.sums_n64()[name]
+    setup = m.fk20_setup_create_cells(cache, images(tuple(s)), cell)
+    try:
+        for flags in lc.ALL:
+            want = images(lc.sums_expected(name, flags))
+            rc, got, st = both_forms(m, cache, setup, lc.pack(polys), ext, flags)
+            assert (rc, st) == (0, bytes(len(polys))), flags
+            expect(got, want, (name, flags))
+            per = len(want) // ROW // len(polys)
+            for g, kind in enumerate(kinds):                                  # the structure, on the images that came out
+                mine = kc.rows(got)[g * per:(g + 1) * per]
+                assert (set(mine) == {kc.INF}) == (kind == "infinity"), (name, flags, g)
+                if kind == "finite":
+                    assert [i for i, r in enumerate(mine) if r == kc.INF] == ([per - 1] if flags & kc.H else []), (name, flags, g)
+    finally:
+        m.fk20_setup_destroy(setup)
+
+
+def test_finish_with_a_shared_inversion(m, cache, setups):
+    """k = 4097 polynomials of n64_l8_x1, its two cycled: 65 552 cells, more than TOAFF_DEVICE_LANES, so a lane of k_fk20c_finish inverts
+    once for two neighbouring cells"""
+    c = kc.case("n64_l8_x1")
+    k, per = 4097, kc.per_poly(c, kc.BITREV)
+    assert k * per > lc.toaff_device_lanes() and k * per <= 2 * lc.toaff_device_lanes()
+    size = c["n"] * 32
+    polys = [bytes.fromhex(c["polys"])[g * size:(g + 1) * size] for g in range(2)]
+    out = [bytes.fromhex(c["out"]["2"])[g * per * ROW:(g + 1) * per * ROW] for g in range(2)]
+    assert kc.INF not in kc.rows(out[0] + out[1]) and out[0] != out[1]
+    rc, got, st = both_forms(m, cache, setups(bytes.fromhex(c["setup"]), 8), lc.cycled(polys, k), 1, kc.BITREV)
+    assert (rc, st) == (0, bytes(k))
+    want = lc.cycled(out, k)
+    assert got == want, [i for i, (a, b) in enumerate(zip(kc.rows(got), kc.rows(want))) if a != b][:8]

@@ -1,13 +1,16 @@
 """Transforms of k vectors of G1 points on the device (mi355_bls_p1s_ntt_many, host and device form): every case of tests/golden/p1ntt.json
 in place and not in place, larger sizes through the defining property - the transform of [a_j]G is [fr_ntt(a)_i]G, both sides made by
 p1sLincombMany_device over a one-row table of G - the round trip, many short vectors, forced slices, one context through changing lengths,
-and the argument errors of the C entry points.  The CPU half is tests/test_p1ntt_emu.py."""
+a finish over more than TOAFF_DEVICE_LANES elements (neighbours share an inversion), and the argument errors of the C entry points.  The
+CPU half is tests/test_p1ntt_emu.py."""
 import functools
 
 import pytest
 
+import fk20_levels_cases as lc
 import frntt_cases as fc
 import p1ntt_cases as pc
+from g1_images import multiples_of_g
 
 pytestmark = pytest.mark.gpu
 R = pc.R
@@ -58,18 +61,6 @@ def both_forms(m, cache, images, n, flags=0, in_place=False):
     return out
 
 
-def multiples_of_g(m, cache, scalars):
-    """[a]G for each scalar, as affine images, through p1sLincombMany_device over the one-row table of G (a == 0: the all-zero image)"""
-    import torch
-    count = len(scalars)
-    d_tab, d_idx = dev(pc.G_IMAGE), torch.zeros(count, dtype=torch.int32, device="cuda")
-    d_sc = dev(b"".join(fc.le(a) for a in scalars))
-    d_out = torch.empty((count * ROW,), dtype=torch.uint8, device="cuda")
-    _, st = m.p1sLincombMany_device(cache, d_tab.data_ptr(), 1, d_idx.data_ptr(), list(range(count + 1)), d_sc.data_ptr(), d_out.data_ptr())
-    assert all(s == (2 if a == 0 else 0) for s, a in zip(st, scalars))
-    return host(d_out)
-
-
 @functools.lru_cache(maxsize=None)
 def _property_inputs(n, k):
     return fc.random_vectors(7000 + n + k, k, n)
@@ -108,6 +99,22 @@ def test_many_short_vectors(m, cache, n):
     for flags in (0, pc.INVERSE | pc.BITREV):
         want = multiples_of_g(m, cache, [a for v in pc.expected_scalars(vectors, flags) for a in v])
         assert both_forms(m, cache, images, n, flags) == want, flags
+
+
+@pytest.mark.parametrize("flags", [0, pc.INVERSE | pc.BITREV])
+def test_finish_with_a_shared_inversion(m, cache, flags):
+    """k = 1025 vectors of 64 points, three distinct ones cycled: 65 600 elements, more than TOAFF_DEVICE_LANES, so a lane of
+    k_p1ntt_finish inverts once for two neighbours - all finite (a random vector), a finite one beside infinity and infinities alone (a
+    constant vector: one output is no infinity), and infinities on the input side (a vector of one entry)"""
+    n, k = 64, 1025
+    assert k * n > lc.toaff_device_lanes() and k * n <= 2 * lc.toaff_device_lanes()
+    vectors = [list(fc.random_vectors(6464, 1, n)[0]), [fc.random_vectors(6465, 1, 1)[0][0]] * n, [0] * 5 + [fc.random_vectors(6466, 1, 1)[0][0]] + [0] * (n - 6)]
+    want = pc.expected_scalars(vectors, flags)
+    assert all(want[0]) and sum(1 for a in want[1] if a) == 1 and all(want[2])
+    rows = lambda scalars: [b"".join(pc.rows(multiples_of_g(m, cache, v))) for v in scalars]      # noqa: E731
+    got = both_forms(m, cache, lc.cycled(rows(vectors), k), n, flags)
+    expected = lc.cycled(rows(want), k)
+    assert got == expected, [i for i, (a, b) in enumerate(zip(pc.rows(got), pc.rows(expected))) if a != b][:8]
 
 
 def test_forced_slices_give_the_one_slice_bytes(m, cache):
